@@ -16,9 +16,13 @@ runs the same workload on its own problem instance (seed + rank), no data-path c
 (independent problems shard: SURVEY.md section 8e) -> weak scaling; one tiny RCCL all-reduce
 of the timing at the end.
 
-Usage:  python bench.py --gpus N --steps K --warmup W
+Usage:  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
         (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and reports them (metric, value,
+ms_per_step, the structure in config).  --full adds the other passes on the same handle (eager constant-RHS solves,
+the instrumented per-phase pass and its roofline objects, level B, host vectors), the scale modes and the CPU
+baseline.  --dump-outputs DIR writes what the last timed step returned to its caller (rank 0's step direction and
+(dtau, dkappa) pairs) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -381,7 +385,17 @@ def main():
     ap.add_argument("--concurrent", action="store_true",
                     help="--configs 4: one stream and host thread per handle (their latency-bound steps side by side); --mode problems does "
                          "so by default")
+    ap.add_argument("--full", action="store_true",
+                    help="iter mode: after the timed steps, also run the passes that only explain them (eager constant-RHS solves, the "
+                         "instrumented per-phase pass with its roofline objects, level B, host vectors), the scale modes and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="iter mode: write what the last timed step returned (rank 0: step direction x, s, z and the affine / combined "
+                         "(dtau, dkappa)) as DIR/<name>.npy, float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.configs or args.mode != "iter" or args.dry_run):
+        ap.error("--dump-outputs: the headline run only (--mode iter, no --configs, no --dry-run)")
     if args.configs:
         return run_configs(args)
     if args.mode == "problems" and not args.sequential_handles:
@@ -512,15 +526,18 @@ def main():
         """One interior-point iteration's reduced-system work as solver.jl:278-319 issues it: kkt_update!, then
         kkt_solve!(:affine), then kkt_solve!(:combined) -- three separate calls, each returning its own status (and
         (dtau, dkappa)) to the host.  In lazy mode the first leaves its constant-RHS solve to the second, which sends
-        both right-hand sides through the sweeps together; 3 solves with refinement per step either way."""
+        both right-hand sides through the sweeps together; 3 solves with refinement per step either way.  Returns the
+        (dtau, dkappa) of the affine and of the combined solve."""
         update, solve_affine, solve_combined = st["calls"]
         if not update():
             raise RuntimeError("kkt_update! failed")
-        for solve in (solve_affine, solve_combined):
-            ok, dtau, dkappa = solve()
-            if not ok:
-                raise RuntimeError("kkt_solve! failed")
-        return dtau
+        ok, dtau_a, dkappa_a = solve_affine()
+        if not ok:
+            raise RuntimeError("kkt_solve! failed")
+        ok, dtau, dkappa = solve_combined()
+        if not ok:
+            raise RuntimeError("kkt_solve! failed")
+        return dtau_a, dkappa_a, dtau, dkappa
 
     base = {"n_gpus": world, "steps": args.steps, "warmup": args.warmup, "higher_is_better": True, "vs_baseline": None,
             "dtype": "f64", "data": "synthetic"}
@@ -689,12 +706,12 @@ def main():
 
     if dry:
         elapsed = timed(lambda: None)
-        sm = scale_modes()
+        extra = dict(scale_modes=scale_modes()) if args.full else {}
         if rank == 0:
             print(json.dumps(dict(base, metric="KKT factorize+solve/sec (fp64) per IPM iter, 100k-var SOCP",
                                   value=world * args.steps / max(elapsed, 1e-9), unit="KKT factorize+solve/s",
                                   ms_per_step=elapsed / args.steps * 1e3, scaling="weak",
-                                  config={"workload": "dry run (no GPU work)"}, scale_modes=sm)), flush=True)
+                                  config={"workload": "dry run (no GPU work)"}, **extra)), flush=True)
         if world > 1:
             dist.destroy_process_group()
         return
@@ -702,7 +719,7 @@ def main():
     t0 = time.perf_counter()
     ks, system, stc = make_system(pb, np.random.default_rng(0), lazy=not args.sequential_solves)
     setup_s = time.perf_counter() - t0
-    st = resident(pb, np.random.default_rng(0))
+    st = resident(pb, np.random.default_rng(0)) if args.full else None       # the level-B passes' vectors (--full)
     # (set-up has freed large host arrays; let the unmapping settle before any timed GPU work: see the note at gc.disable)
     gc.collect()
     torch.cuda.synchronize(dev)
@@ -715,12 +732,47 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        unit_c(system, stc)
+        last = unit_c(system, stc)
     barrier()
     elapsed = reduce_max(time.perf_counter() - t0, device=dev)
     fb1 = ks.fallbacks
     if fb1 != fb0:
         raise RuntimeError("a fallback was taken inside the timed region (overlap, top) %s -> %s" % (fb0, fb1))
+    if args.dump_outputs and rank == 0:
+        # what the caller holds after the last timed step: the step direction (x, s, z) of kkt_solve!(:combined), which
+        # overwrote the affine one in the same buffers, and both solves' (dtau, dkappa)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("step_x", stc["keep"][2][0]), ("step_s", stc["keep"][2][1]), ("step_z", stc["keep"][2][2]),
+                        ("dtau_dkappa_affine_combined", torch.tensor(last, dtype=torch.float64))):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a.cpu().numpy().astype(np.float64))
+    info = ks.info
+    headline = {
+        "metric": "KKT factorize+solve/sec (fp64) per IPM iter, 100k-var SOCP",
+        "value": world * args.steps / elapsed,
+        "unit": "KKT factorize+solve/s",
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "scaling": "weak",
+        "config": {"workload": "cfg2: random sparse SOCP n=%d m=%d NN(%d)+%dxSOC(100), P=diag, A 4 nnz/row local "
+                               "window; 1 update + 1 LDL' refactor + 3 solves with IR per step" %
+                               (pb.n, pb.m, pb.n, pb.n // 100),
+                   "N": info["N"], "nnzK": info["nnzK"], "nnzL": info["nnzL"], "nnzL_stored": info["nnzL_stored"],
+                   "fill_ratio": info["nnzL"] / info["nnzK"], "etree_height": info["etree_height"],
+                   "nsuper": info["nsuper"], "levels": info["nlevels"], "max_front": info["max_front"],
+                   "factor_flops": info["factor_flops"], "ordering": args.ordering,
+                   "setup_s": setup_s, "parallelism": "independent problems per GPU",
+                   "calls": "level C (hipkkt_kkt_system_*): kkt_update!, kkt_solve!(:affine), kkt_solve!(:combined) as "
+                            "three separate calls per step (solver.jl:278-319), each returning its status and "
+                            "(dtau, dkappa) to the host; right-hand-side construction and step recovery included; "
+                            + ("eager constant-RHS solve" if args.sequential_solves else
+                               "lazy mode: kkt_update! leaves the constant-RHS solve to the affine kkt_solve! (one 2-column solve)"),
+                   "csrc_sha16": traffic_summary()[2]},
+    }
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(dict(base, **headline)), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # ---- the same step with the constant-RHS solve issued by kkt_update! itself (eager: three single-column solves)
     system.set_lazy(False)
     unit_c(system, stc)
@@ -797,7 +849,6 @@ def main():
     sm = scale_modes()
 
     if rank == 0:
-        info = ks.info
         B = algorithmic_bytes(info)
         phases = {}
         for name, ms_key, n_key, byt in (("factor", "factor_ms", "n_factor", B["factor"]),
@@ -852,27 +903,8 @@ def main():
                 rt["frac_vs_amd_fill"] = None
                 rt["amd_note"] = str(e)
         phase_sum = sum(phases[k]["total_ms"] for k in phases) / max(args.steps, 1)
-        out = dict(base, **{
-            "metric": "KKT factorize+solve/sec (fp64) per IPM iter, 100k-var SOCP",
-            "value": world * args.steps / elapsed,
-            "unit": "KKT factorize+solve/s",
-            "ms_per_step": elapsed / args.steps * 1e3,
-            "scaling": "weak",
-            "config": {"workload": "cfg2: random sparse SOCP n=%d m=%d NN(%d)+%dxSOC(100), P=diag, A 4 nnz/row local "
-                                   "window; 1 update + 1 LDL' refactor + 3 solves with IR per step" %
-                                   (pb.n, pb.m, pb.n, pb.n // 100),
-                       "N": info["N"], "nnzK": info["nnzK"], "nnzL": info["nnzL"], "nnzL_stored": info["nnzL_stored"],
-                       "fill_ratio": info["nnzL"] / info["nnzK"], "etree_height": info["etree_height"],
-                       "nsuper": info["nsuper"], "levels": info["nlevels"], "max_front": info["max_front"],
-                       "factor_flops": info["factor_flops"], "ordering": args.ordering,
-                       "ir_rounds_per_step": prof["ir_iterations"] / max(args.steps, 1),
-                       "setup_s": setup_s, "parallelism": "independent problems per GPU",
-                       "calls": "level C (hipkkt_kkt_system_*): kkt_update!, kkt_solve!(:affine), kkt_solve!(:combined) as "
-                                "three separate calls per step (solver.jl:278-319), each returning its status and "
-                                "(dtau, dkappa) to the host; right-hand-side construction and step recovery included; "
-                                + ("eager constant-RHS solve" if args.sequential_solves else
-                                   "lazy mode: kkt_update! leaves the constant-RHS solve to the affine kkt_solve! (one 2-column solve)"),
-                       "csrc_sha16": traffic_summary()[2]},
+        headline["config"]["ir_rounds_per_step"] = prof["ir_iterations"] / max(args.steps, 1)
+        out = dict(base, **headline, **{
             "roofline": roofline,
             "roofline_trisolve": rt,      # the north-star's named roofline target
             "phases": phases,

@@ -6,7 +6,7 @@ OUT=gpurun_out/ab_winv
 mkdir -p $OUT
 run() {
   tag=$1; shift
-  env "$@" python3 bench.py --no-cpu-baseline --no-scale-modes > $OUT/$tag.json 2> $OUT/$tag.err
+  env "$@" python3 bench.py --full --no-cpu-baseline --no-scale-modes > $OUT/$tag.json 2> $OUT/$tag.err
   python3 - "$tag" "$OUT/$tag.json" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

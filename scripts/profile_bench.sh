@@ -1,10 +1,10 @@
 #!/bin/bash
 # Profiles a command on the GPU box with rocprofv3, four separate passes (never --pmc together with a trace).
 # Usage (through gpurun):  scripts/profile_bench.sh <tag> [bench|cfg3|cfg5]
-#   bench (default): python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --sequential-solves   (cfg2, the headline
+#   bench (default): python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --sequential-solves   (cfg2, the headline
 #                    workload, every sweep single-column so that per-solve traffic is well defined)
 #   cfgN:            python3 scripts/bench_one_config.py N 5
-# Produces under gpurun_out/profile_<tag>/:
+# Produces under $PROFILE_OUT/profile_<tag>/ (PROFILE_OUT: default profile_out):
 #   stats/      --kernel-trace --stats (per-kernel durations)
 #   pmc_fetch/  --pmc FETCH_SIZE   (own pass: TCC has 4 slots, FETCH_SIZE takes 3)
 #   pmc_write/  --pmc WRITE_SIZE
@@ -13,11 +13,12 @@
 set -e
 TAG=${1:-r02}
 WHAT=${2:-bench}
-OUT=gpurun_out/profile_$TAG
+PROFILE_OUT=${PROFILE_OUT:-profile_out}
+OUT=$PROFILE_OUT/profile_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 if [ "$WHAT" = "bench" ]; then
-  ARGS="bench.py --steps 5 --warmup 2 --no-cpu-baseline --sequential-solves --no-scale-modes"
+  ARGS="bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --sequential-solves --no-scale-modes"
   python3 $ARGS > $OUT/bench.json 2> $OUT/bench.err
 else
   ARGS="scripts/bench_one_config.py ${WHAT#cfg} 5"
