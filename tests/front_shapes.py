@@ -1,0 +1,358 @@
+"""Matrices whose supernodal fronts have CHOSEN shapes, for the level-A (hipkkt_ldl_*) boundary tests.
+
+A case is a forest of supernodes listed children first: ``(nc, nb, parent)`` is a front of ``nc`` dense columns whose
+``nb`` rows below are the first ``nb`` positions of its parent's front (the parent's columns, then the parent's own
+rows).  The columns are numbered in that order, so ORDER_NATURAL's elimination order is the listed one.
+
+Two parts of the symbolic phase (csrc/symbolic.cpp) change shapes on their own:
+
+* Relaxed amalgamation merges a child into its parent when the merged front has few explicit zeros: any merged front
+  of <= 32 columns always, wider ones when the zero fraction stays under 0.3 (<= 128 columns) or 0.1 (the allowances of
+  the tallest child, which is tried first; the others get half of them).  Two constructions keep a designed front
+  T = (nc, nb) apart:
+  - ``designed``: T hangs below a narrow, tall STICK P = (rp, sp) that T's rows fill only in part; P itself is
+    absorbed by the root G = (sp + 1, 0) above it afterwards, but a child's decision is never revisited, so T stays.
+    ``stick`` finds the smallest such P.  This needs nc >= ~10 (T's zero fraction is at most ~nc / (nc + rp)).
+  - ``beside_sibling``, for narrow fronts: P = (1, R) first absorbs a wider sibling S = (20, 1) (the widest child is
+    tried first, with the larger allowance).  P then carries S's explicit zeros, and the merge test counts them: T,
+    tried second with the plain allowance, would make P's front mostly zeros and stays out -- (1, 38), (2, 6) ...
+* Sibling bundles act on more than 200 one-wave children of one parent: the many-front cases are forests of roots.
+
+Values: off-diagonal entries are uniform in (-s, s) with s = 1 / sqrt(rows), the diagonal is sign * (1 + |row|_1)
+with a random sign per column.  K is then strictly diagonally dominant, hence quasi-definite in every order (no pivot
+changes sign), and no eigenvalue lies in (-m, m) for the smallest dominance margin m (K - mu I stays dominant), which
+gives cond_2(K) <= |K|_inf / m a priori.
+"""
+import dataclasses
+
+import numpy as np
+import scipy.sparse as sp
+
+U = np.finfo(np.float64).eps / 2          # unit round-off
+
+# csrc/symbolic.hpp SymbolicOptions: relax_cols {8, 32, 128}, relax_zeros {1.0, 0.5, 0.15, 0.05}, relax_tall 2.0
+_RELAX_COLS = (8, 32, 128)
+_RELAX_ZEROS = (1.0, 0.5, 0.15, 0.05)
+_RELAX_TALL = 2.0
+
+# shapes of the issue's table that no matrix produces, with the reason
+UNREACHABLE = {
+    "nb = 0 at a non-root":
+        "a supernode's parent is the one that holds its first row below (elimination tree): with no rows below it is a "
+        "root.  The cases place (nc, 0) roots in a level beside non-roots instead",
+}
+
+
+def _trap(nc, nb):
+    return nc * (nc + 1) / 2 + nc * nb
+
+
+def _allowance(width, tall=True):
+    z = _RELAX_ZEROS[3]
+    for c, zz in zip(_RELAX_COLS, _RELAX_ZEROS):
+        if width <= c:
+            z = zz
+            break
+    return z * (_RELAX_TALL if tall else 1.0)
+
+
+def stays_separate(nc, nb, rp, sp):
+    """Would a dense (nc, nb) child stay out of its only parent (rp, sp)?  (symbolic.cpp step 5)"""
+    if nb >= rp + sp:
+        return False                      # fundamental supernode with its parent
+    frac = nc * (rp + sp - nb) / _trap(nc + rp, sp)
+    return frac > _allowance(nc + rp)
+
+
+def stick(nc, nb):
+    """Smallest stick (rp, sp) above which a designed (nc, nb) front survives amalgamation, or None (a narrow front:
+    use beside_sibling)."""
+    best = None
+    for rp in range(1, 130):
+        for sp in range(max(nb - rp + 1, 1), 1200):
+            if stays_separate(nc, nb, rp, sp):
+                if best is None or rp + sp < sum(best):
+                    best = (rp, sp)
+                break
+    return best
+
+
+def designed(nc, nb, copies=1, st=None):
+    """Spec of `copies` independent trees, each: the (nc, nb) front, a stick P = st (default: stick(nc, nb)) above it
+    and the root G above P.  nb = 0: `copies` independent (nc, 0) roots."""
+    spec = []
+    for _ in range(copies):
+        if nb == 0:
+            spec.append((nc, 0, -1))
+            continue
+        st = st or stick(nc, nb)
+        if st is None or not stays_separate(nc, nb, *st):
+            raise ValueError(f"({nc}, {nb}) cannot be placed (see UNREACHABLE)")
+        rp, sp = st
+        b = len(spec)
+        spec += [(nc, nb, b + 1), (rp, sp, b + 2), (sp + 1, 0, -1)]
+    return spec
+
+
+def beside_sibling(nc, nb, R=40):
+    """Spec of one tree for a narrow (nc, nb) front: T and a wider sibling S = (20, 1) below P = (1, R), below the root
+    G = (R + 1, 0).  S merges into P first; T stays out (see the module docstring).  nb <= R."""
+    if not 0 < nb <= R:
+        raise ValueError("0 < nb <= R")
+    return [(nc, nb, 2), (20, 1, 2), (1, R, 3), (R + 1, 0, -1)]
+
+
+@dataclasses.dataclass
+class Case:
+    K: sp.csc_matrix                 # upper triangle, CSC, explicit zeros kept
+    dsigns: np.ndarray
+    ordering: int
+    x_true: np.ndarray
+    b: np.ndarray                    # K~ x_true accumulated in long double, rounded once
+    cond_bound: float
+    cols: list                       # per spec entry: its column indices
+    rows: list                       # per spec entry: its row indices below (absolute)
+    Kt: sp.csc_matrix = None         # K~: K with the regularised pivots replaced (== K when there are none)
+
+
+def layout(spec):
+    """Column and row index lists of every spec entry."""
+    cols, rows, c = [], [None] * len(spec), 0
+    for nc, _, _ in spec:
+        cols.append(list(range(c, c + nc)))
+        c += nc
+    # parents come after their children: fill rows top-down
+    for s in range(len(spec) - 1, -1, -1):
+        nc, nb, p = spec[s]
+        if p < 0:
+            if nb:
+                raise ValueError("a root has no rows below it")
+            rows[s] = []
+            continue
+        if p <= s:
+            raise ValueError("children must be listed before their parents")
+        front = cols[p] + rows[p]
+        if nb > len(front) - 1:
+            raise ValueError(f"entry {s}: nb {nb} exceeds its parent's front less one")
+        rows[s] = front[:nb]
+    return cols, rows, c
+
+
+def pattern(spec):
+    """(rows, cols) of the upper triangle (row <= col)."""
+    cols, rows, N = layout(spec)
+    I, J = [], []
+    for cs, rs in zip(cols, rows):
+        cs = np.asarray(cs, dtype=np.int64)
+        ii, jj = np.triu_indices(len(cs))
+        I.append(cs[ii]); J.append(cs[jj])
+        if rs:
+            a, r = np.meshgrid(cs, np.asarray(rs, dtype=np.int64), indexing="ij")
+            I.append(a.ravel()); J.append(r.ravel())
+    return np.concatenate(I), np.concatenate(J), N, cols, rows
+
+
+def symmetric_matvec_ld(K, x):
+    """K_full @ x in long double from the upper triangle K (CSC)."""
+    K = sp.coo_matrix(K)
+    xl = np.asarray(x, dtype=np.longdouble)
+    v = K.data.astype(np.longdouble)
+    y = np.zeros(K.shape[0], dtype=np.longdouble)
+    np.add.at(y, K.row, v * xl[K.col])
+    off = K.row != K.col
+    np.add.at(y, K.col[off], v[off] * xl[K.row[off]])
+    return y
+
+
+def norm_inf_sym(K):
+    K = sp.coo_matrix(K)
+    a = np.abs(K.data)
+    r = np.zeros(K.shape[0])
+    np.add.at(r, K.row, a)
+    off = K.row != K.col
+    np.add.at(r, K.col[off], a[off])
+    return r.max()
+
+
+def full(K):
+    """The symmetric matrix of the upper triangle K, as CSC (explicit zeros kept)."""
+    K = sp.csc_matrix(K)
+    return (K + sp.triu(K, 1, format="csc").T).tocsc()
+
+
+def make_case(spec, seed, ordering=None, signs=None):
+    """Matrix, signs, ordering, x_true, b and a condition bound for a spec (see the module docstring)."""
+    from cuclarabel_amd import _lib
+    rng = np.random.default_rng(seed)
+    I, J, N, cols, rows = pattern(spec)
+    cnt = np.zeros(N)
+    np.add.at(cnt, I, 1)
+    np.add.at(cnt, J, 1)
+    off = I != J
+    scale = 1.0 / np.sqrt(np.maximum(cnt, 1))
+    v = rng.uniform(-1.0, 1.0, I.size) * np.minimum(scale[I], scale[J])
+    rowsum = np.zeros(N)
+    np.add.at(rowsum, I[off], np.abs(v[off]))
+    np.add.at(rowsum, J[off], np.abs(v[off]))
+    dsigns = np.where(rng.random(N) < 0.5, -1, 1).astype(np.int64) if signs is None else np.asarray(signs, np.int64)
+    d = ~off
+    v[d] = dsigns[I[d]] * (1.0 + rowsum[I[d]] + rng.uniform(0.0, 0.5, d.sum()))
+    K = sp.csc_matrix((v, (I, J)), shape=(N, N))
+    K.sort_indices()
+    margin = (np.abs(K.diagonal()) - rowsum).min()
+    x_true = rng.standard_normal(N)
+    b = symmetric_matvec_ld(K, x_true).astype(np.float64)
+    return Case(K=K, dsigns=dsigns, ordering=_lib.ORDER_NATURAL if ordering is None else ordering, x_true=x_true, b=b,
+                cond_bound=norm_inf_sym(K) / margin, cols=cols, rows=rows, Kt=K)
+
+
+def set_pivots(case, pivots, eps, delta):
+    """Pivot-rule cases.  For each (column k, value, sign): row k becomes an explicit zero in every column eliminated
+    before k (ORDER_NATURAL on these matrices eliminates in index order), so that the pivot met at k is exactly the
+    value put on the diagonal; the sign goes into dsigns.  K~ is K with sign * delta on the diagonal where
+    value * sign < eps (the rule is a strict <).  b, K~ and the condition number (measured) are rebuilt."""
+    K = sp.coo_matrix(case.K)
+    I, J, v = K.row.astype(np.int64), K.col.astype(np.int64), K.data.copy()
+    vt = None
+    for k, val, sg in pivots:
+        v[(J == k) & (I < k)] = 0.0
+        v[(I == k) & (J == k)] = val
+        case.dsigns[k] = sg
+    vt = v.copy()
+    for k, val, sg in pivots:
+        if val * sg < eps:
+            vt[(I == k) & (J == k)] = sg * delta
+    N = case.K.shape[0]
+    case.K = sp.csc_matrix((v, (I, J)), shape=(N, N))
+    case.Kt = sp.csc_matrix((vt, (I, J)), shape=(N, N))
+    case.K.sort_indices()
+    case.Kt.sort_indices()
+    case.b = symmetric_matvec_ld(case.Kt, case.x_true).astype(np.float64)
+    case.cond_bound = float(np.linalg.cond(full(case.Kt).toarray()))
+    return case
+
+
+def errors(case, x):
+    """(forward error |x - x_true|_inf / |x_true|_inf, long-double backward error |b - K~ x| / (|K~||x| + |b|))."""
+    fwd = np.abs(x - case.x_true).max() / np.abs(case.x_true).max()
+    r = np.asarray(case.b, dtype=np.longdouble) - symmetric_matvec_ld(case.Kt, x)
+    bwd = float(np.abs(r).max() / (np.longdouble(norm_inf_sym(case.Kt)) * np.abs(np.asarray(x, np.longdouble)).max()
+                                   + np.abs(np.asarray(case.b, np.longdouble)).max()))
+    return float(fwd), bwd
+
+
+def reference_solve(case, K=None):
+    """scipy's sparse LU solve of K~ (or K) x = b in fp64."""
+    import scipy.sparse.linalg as spla
+    A = full(case.Kt if K is None else K)
+    return spla.splu(A.tocsc(), permc_spec="COLAMD").solve(case.b)
+
+
+def forward_bound(case, scipy_fwd):
+    return max(100.0 * case.cond_bound * U, 10.0 * scipy_fwd)
+
+
+BWD_BOUND = 64 * U
+
+
+# --------------------------------------------------------------------------- the shape table
+# name -> (spec, expected level 0 (count, fmax, ncmax, n_f<=8, n_f<=64), intended class of the designed front)
+# class: "tiny" (f <= 8), "wave" (one-wave: f <= 64 and f*nc + nb^2 <= 1536), "block" (panel kernel), "chain" (a
+# supernode wider than a panel, cut into links), "sliced" (row slices)
+def _one_wave(nc, nb):
+    f = nc + nb
+    return f <= 64 and f * nc + nb * nb <= 1536
+
+
+def _roots(nc, copies):
+    f = nc
+    return designed(nc, 0, copies), (copies, f, nc, copies * (f <= 8), copies * (f <= 64))
+
+
+def _child(nc, nb, copies=1):
+    f = nc + nb
+    return designed(nc, nb, copies), (copies, f, nc, copies * (f <= 8), copies * (f <= 64))
+
+
+def _narrow(nc, nb):
+    f = nc + nb
+    return beside_sibling(nc, nb), (1, f, nc, int(f <= 8), int(f <= 64))
+
+
+def _mixed(n_small, small=(39, 0), big=(96, 0)):
+    spec = [small + (-1,)] * n_small + [big + (-1,)]
+    return spec, (n_small + 1, big[0], big[0], 0, n_small)
+
+
+def shape_table():
+    T = {}
+    for nc in (1, 2, 8, 9):
+        T[f"f{nc}_root"] = _roots(nc, 3) + ("tiny" if nc <= 8 else "wave",)
+    # tiny and one-wave fronts WITH update rows (extend-add into a parent): f = 2, 8, 9, and the binding clause of the
+    # one-wave rule at one column, f * nc + nb^2 = 39 + 1444 <= 1536 < 40 + 1521
+    T["tiny_1_1"] = _narrow(1, 1) + ("tiny",)
+    T["tiny_2_6"] = _narrow(2, 6) + ("tiny",)
+    T["wave_1_8"] = _narrow(1, 8) + ("wave",)
+    T["wave_1_38"] = _narrow(1, 38) + ("wave",)
+    T["block_1_39"] = _narrow(1, 39) + ("block",)
+    T["wave_39_0"] = _roots(39, 2) + ("wave",)
+    T["block_40_0"] = _roots(40, 2) + ("block",)
+    T["wave_16_28"] = _child(16, 28) + ("wave",)
+    T["block_16_29"] = _child(16, 29) + ("block",)
+    T["merge_128"] = _mixed(128) + ("wave+block",)
+    T["merge_129"] = _mixed(129) + ("wave+block",)
+    for nc in (15, 16, 17, 31, 32, 33, 95, 96):
+        T[f"panel_nc{nc}"] = _child(nc, 40) + ("block",)
+    for nb in (1, 63, 64, 65, 127, 128, 129, 192, 193):
+        T[f"schur_nb{nb}"] = _child(40, nb) + ("block",)
+    for f in (128, 129, 192, 193):
+        T[f"bs_f{f}"] = _child(64, f - 64) + ("block",)
+    T["trap_96_151"] = _child(96, 151) + ("block",)
+    return T
+
+
+# fronts whose designed supernode is cut by the symbolic split (7b): name -> (spec, level-0 tuple, class)
+def chain_table():
+    T = {}
+    # 97 columns: two links, (49, 48 + 40) and (48, 40)
+    T["chain_nc97"] = (designed(97, 40), (1, 137, 49, 0, 0), "chain")
+    # one past the trapezoid cap (96 * 97 / 2 + 96 * 152 > 19 200): two links of 48 columns
+    T["trap_96_152"] = (designed(96, 152), (1, 248, 48, 0, 0), "chain")
+    return T
+
+
+def solve_bs_table():
+    # (the schedule summary does not report the sweep's workgroup size: these two cases show that both sides of the
+    #  solve_bs switch -- 1023 fronts on 256-thread, 1024 on 128-thread workgroups -- solve correctly, not which one
+    #  each took)
+    return {f"solve_bs_{n}": (designed(40, 0, n), (n, 40, 40, 0, n), "block") for n in (1023, 1024)}
+
+
+def klass(f, nc):
+    """Kernel class of a front of f rows and nc columns, as the schedule decides it (kernels.hpp: one-wave when
+    f <= 64 and f * nc + nb^2 <= 1536; tiny fronts are one-wave fronts with a solve kernel of their own)."""
+    nb = f - nc
+    return "tiny" if f <= 8 else "wave" if _one_wave(nc, nb) else "block"
+
+
+def all_cases():
+    T = {}
+    T.update(shape_table())
+    T.update(chain_table())
+    T.update(solve_bs_table())
+    return T
+
+
+def designed_front(case):
+    """Columns and rows of the designed front: the first spec entry."""
+    return case.cols[0], case.rows[0]
+
+
+def perturbed(case, rel=1e-7):
+    """K~ + E: one diagonal entry in the designed front's update region (its first row below; the front's last
+    column for a root) changed by `rel` relative -- a stand-in for a dropped or misplaced extend-add term."""
+    cols, rows = designed_front(case)
+    k = rows[0] if rows else cols[-1]
+    K = sp.csc_matrix(case.Kt, copy=True)
+    K[k, k] = K[k, k] * (1.0 + rel)
+    return K
