@@ -911,7 +911,7 @@ __global__ __launch_bounds__(256) void k_cone_psd(ConeDev C, ConeState S, const 
                     for (int o = 4; o > 0; o >>= 1) {
                         a += __shfl_xor(a, o, 8); b += __shfl_xor(b, o, 8); cc += __shfl_xor(cc, o, 8);
                     }
-                    const double ab = sqrt(a * b);
+                    const double ab = sqrt(a) * sqrt(b);       // (sqrt(a * b) overflows / flushes for entries beyond ~2^+-256)
                     if (!(fabs(cc) <= 1e-300 || fabs(cc) <= 1e-17 * ab)) {
                         myoff = fmax(myoff, fabs(cc) / ab);
                         const double zeta = (b - a) / (2.0 * cc);

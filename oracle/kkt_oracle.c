@@ -522,14 +522,15 @@ static void jacobi_svd(double *A, double *U, double *s, double *V, I n)
         double off = 0.0;
         for (i = 0; i < n - 1; i++)
             for (j = i + 1; j < n; j++) {
-                double a = 0, b = 0, c = 0, zeta, t, cs, sn;
+                double a = 0, b = 0, c = 0, ab, zeta, t, cs, sn;
                 for (q = 0; q < n; q++) {
                     a += A[q + i * n] * A[q + i * n];
                     b += A[q + j * n] * A[q + j * n];
                     c += A[q + i * n] * A[q + j * n];
                 }
-                if (fabs(c) <= 1e-300 || fabs(c) <= 1e-17 * sqrt(a * b)) continue;
-                off = fmax(off, fabs(c) / sqrt(a * b));
+                ab = sqrt(a) * sqrt(b);   /* sqrt(a * b) overflows / flushes for entries beyond ~2^+-256 */
+                if (fabs(c) <= 1e-300 || fabs(c) <= 1e-17 * ab) continue;
+                off = fmax(off, fabs(c) / ab);
                 zeta = (b - a) / (2.0 * c);
                 t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
                 cs = 1.0 / sqrt(1.0 + t * t); sn = cs * t;
@@ -798,6 +799,17 @@ void orc_cones_lambda(const orc_kkt *k, double *lam)
         for (i = 0; i < K->numel; i++) l[i] = 0.0;
         if (K->kind == ORC_NN || K->kind == ORC_SOC) for (i = 0; i < K->numel; i++) l[i] = K->lam[i];
         else if (K->kind == ORC_PSD) for (i = 0; i < K->dim; i++) l[i] = K->plam[i];
+    }
+}
+
+void orc_cones_scaling_w(const orc_kkt *k, double *w, double *eta)
+{
+    I c, i;
+    for (c = 0; c < k->ncones; c++) {
+        const cone_t *K = &k->cones[c];
+        double *wc = w + K->off;
+        for (i = 0; i < K->numel; i++) wc[i] = (K->kind == ORC_NN || K->kind == ORC_SOC) ? K->w[i] : 0.0;
+        eta[c] = K->kind == ORC_SOC ? K->eta : 0.0;
     }
 }
 

@@ -54,6 +54,7 @@ def _load():
     lib.orc_cones_mul_Hs.argtypes = [C.c_void_p, _f64p, _f64p]
     lib.orc_cones_soc_sparse.argtypes = [C.c_void_p, _f64p, _f64p, _f64p, _f64p]
     lib.orc_cones_lambda.argtypes = [C.c_void_p, _f64p]
+    lib.orc_cones_scaling_w.argtypes = [C.c_void_p, _f64p, _f64p]
     lib.orc_cones_psd_scaling.argtypes = [C.c_void_p, _f64p, _f64p]
     lib.orc_kkt_update.restype = C.c_int
     lib.orc_kkt_update.argtypes = [C.c_void_p]
@@ -200,6 +201,12 @@ class OracleKKT:
         out = np.zeros(max(self.m, 1))
         lib().orc_cones_lambda(self._h, out)
         return out[:self.m]
+
+    def scaling_w(self):
+        """(w (m), eta (per cone)) as the device's scaling_w() returns them"""
+        w, eta = np.zeros(max(self.m, 1)), np.zeros(max(len(self.cones), 1))
+        lib().orc_cones_scaling_w(self._h, w, eta)
+        return w[:self.m], eta[:len(self.cones)]
 
     def psd_scaling(self):
         """[(R, Rinv, lam)] per PSD cone, matrices k x k"""
