@@ -98,7 +98,7 @@ __device__ __forceinline__ void chain_fwd_block(const SolveArgs& A, const ChainA
     const int nks = (nc + 7) >> 3, nrb = (f + 63) >> 6, nitF = nrb * nks;
     const int cst = (1 + nks) * fpad;
     double* y = smem;
-    double* part = smem + fpad;
+    double* part = lds_part<NR>(smem, fpad);
 #define CH_STAMP(dir, slot) do { if (A.top_stamps && tid == 0) A.top_stamps[((int64_t)(dir) * C.nstamp + (pos - C.lo0)) * 8 + (slot)] = wall_clock64(); } while (0)
     if (A.top_stamps && tid == 0) A.top_stamps[((int64_t)0 * C.nstamp + (pos - C.lo0)) * 8 + 0] = t0;
     ItemRegs rf[PF];
@@ -129,7 +129,7 @@ __device__ __forceinline__ void chain_fwd_block(const SolveArgs& A, const ChainA
     if (tid < f) {
         gather_add<NR, true>(A, G, bmine);
 #pragma unroll
-        for (int c = 0; c < NR; ++c) y[c * cst + tid] = bmine[c];
+        for (int c = 0; c < NR; ++c) y[lds_ix<NR>(c, cst, tid)] = bmine[c];
     }
     for (int i = tid + BS; i < f; i += BS) {              // fronts taller than the workgroup
         int pj;
@@ -141,17 +141,14 @@ __device__ __forceinline__ void chain_fwd_block(const SolveArgs& A, const ChainA
         for (int c = 0; c < NR; ++c) v[c] = (i < nc) ? A.b[c * A.ld_b + pj] : 0.0;
         gather_add<NR, true>(A, Gi, v);
 #pragma unroll
-        for (int c = 0; c < NR; ++c) y[c * cst + i] = v[c];
+        for (int c = 0; c < NR; ++c) y[lds_ix<NR>(c, cst, i)] = v[c];
     }
     __syncthreads();
     CH_STAMP(0, 3);
 #pragma unroll
     for (int p = 0; p < PF; ++p) {
         const int it = wv + p * NW;
-        if (it < nitF) {
-#pragma unroll
-            for (int c = 0; c < NR; ++c) item_apply(rf[p], y + c * cst, f, nc, part + c * cst, fpad, it, nrb, lane);
-        }
+        if (it < nitF) item_apply_cols<NR>(rf[p], y, cst, f, nc, part, fpad, it, nrb, lane);
     }
     for (int it0 = wv + PF * NW; it0 < nitF; it0 += 2 * NW) {
         ItemRegs rr[2];
@@ -166,19 +163,17 @@ __device__ __forceinline__ void chain_fwd_block(const SolveArgs& A, const ChainA
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u)
-            if (it0 + u * NW < nitF) {
-#pragma unroll
-                for (int c = 0; c < NR; ++c) item_apply(rr[u], y + c * cst, f, nc, part + c * cst, fpad, it0 + u * NW, nrb, lane);
-            }
+            if (it0 + u * NW < nitF) item_apply_cols<NR>(rr[u], y, cst, f, nc, part, fpad, it0 + u * NW, nrb, lane);
     }
     __syncthreads();
     CH_STAMP(0, 4);
     for (int i = tid; i < f; i += BS) {
+        const double2 vp = lds_sum_pair<NR>(part, i, nks, fpad);
 #pragma unroll
         for (int c = 0; c < NR; ++c) {
-            const double v = lds_sum_strided(part + c * cst + i, nks, fpad);
+            const double v = lds_sum_col<NR>(vp, part, cst, c, i, nks, fpad);
             if (i < nc) ST_AGENT_F64(A.xp + (int64_t)(c0 + i) * NR + c, v);
-            else ST_AGENT_F64(A.uvec + (int64_t)(rp + i - nc) * NR + c, y[c * cst + i] - v);
+            else ST_AGENT_F64(A.uvec + (int64_t)(rp + i - nc) * NR + c, y[lds_ix<NR>(c, cst, i)] - v);
         }
     }
     drain_stores();
@@ -391,7 +386,7 @@ __device__ __forceinline__ void chain_bwd_block(const SolveArgs& A, const ChainA
     const int ncb = (nc + 63) >> 6, nrs = (f + 7) >> 3, nitB = ncb * nrs;
     const int cst = fpad + nrs * ncpad;
     double* z = smem;
-    double* part = smem + fpad;
+    double* part = lds_part<NR>(smem, fpad);
 #define CH_STAMP(dir, slot) do { if (A.top_stamps && tid == 0) A.top_stamps[((int64_t)(dir) * C.nstamp + (pos - C.lo0)) * 8 + (slot)] = wall_clock64(); } while (0)
     ItemRegs rbk[PB];
 #pragma unroll
@@ -424,26 +419,30 @@ __device__ __forceinline__ void chain_bwd_block(const SolveArgs& A, const ChainA
         }
 #pragma unroll
         for (int c = 0; c < NR; ++c)
-            if (tid < f) z[c * cst + tid] = (tid < nc) ? zv[c] * dinv : -zv[c];
+            if (tid < f) z[lds_ix<NR>(c, cst, tid)] = (tid < nc) ? zv[c] * dinv : -zv[c];
     }
 #pragma unroll
     for (int c = 0; c < NR; ++c) {
         const double* xc = A.xp + c;
         for (int i = tid + BS; i < f; i += BS)
-            z[c * cst + i] = (i < nc) ? LD_AGENT_F64(xc + (int64_t)(c0 + i) * NR) * A.Dinv[c0 + i]
+            z[lds_ix<NR>(c, cst, i)] = (i < nc) ? LD_AGENT_F64(xc + (int64_t)(c0 + i) * NR) * A.Dinv[c0 + i]
                                       : -LD_AGENT_F64(xc + (int64_t)(rec ? rec_idx(rec, i) : T.rows[rp + i - nc]) * NR);
     }
     __syncthreads();
     CH_STAMP(1, 3);
     auto apply = [&](const ItemRegs& R, int it) {
-        const int rs = it / ncb, cb = it - rs * ncb;
-        const int j = cb * 64 + lane, r0 = 8 * rs;
+        if constexpr (NR == 2) {
+            item_apply_cols<NR>(R, z, cst, nc, f, part, ncpad, it, ncb, lane);
+        } else {
+            const int rs = it / ncb, cb = it - rs * ncb;
+            const int j = cb * 64 + lane, r0 = 8 * rs;
 #pragma unroll
-        for (int c = 0; c < NR; ++c) {
-            double acc = 0.0;
+            for (int c = 0; c < NR; ++c) {
+                double acc = 0.0;
 #pragma unroll
-            for (int q = 0; q < 8; ++q) acc = fma(R.m[q], (r0 + q < f) ? z[c * cst + r0 + q] : 0.0, acc);
-            if (j < nc) part[c * cst + rs * ncpad + j] = acc;
+                for (int q = 0; q < 8; ++q) acc = fma(R.m[q], (r0 + q < f) ? z[c * cst + r0 + q] : 0.0, acc);
+                if (j < nc) part[c * cst + rs * ncpad + j] = acc;
+            }
         }
     };
 #pragma unroll
@@ -468,9 +467,10 @@ __device__ __forceinline__ void chain_bwd_block(const SolveArgs& A, const ChainA
     CH_STAMP(1, 4);
     for (int j = tid; j < nc; j += BS) {
         const int pi = j == tid ? ridx : (rec ? rec_idx(rec, j) : T.perm[c0 + j]);
+        const double2 vp = lds_sum_pair<NR>(part, j, nrs, ncpad);
 #pragma unroll
         for (int c = 0; c < NR; ++c) {
-            const double v = lds_sum_strided(part + c * cst + j, nrs, ncpad);
+            const double v = lds_sum_col<NR>(vp, part, cst, c, j, nrs, ncpad);
             ST_AGENT_F64(A.xp + (int64_t)(c0 + j) * NR + c, v);
             A.out[c * A.ld_out + pi] = v;
         }

@@ -105,6 +105,90 @@ __device__ inline void item_apply(const ItemRegs& R, const double* v, int Rn, in
     if (r < Rn) part[ks * ldp + r] = acc;
 }
 
+// LDS image of a block-class hop's work vectors (y or z, then the partial sums), NR columns of cst entries each.
+// NR = 2: the columns are interleaved like the global work vectors (entry e of column c at 2 e + c), so one 16-byte
+// access serves both columns of an entry -- the hop's products and sums then make ONE walk over a matrix item for the
+// two columns (item_apply2, lds_sum_strided2) instead of one per column: the walk's cost is its LDS traffic, not its
+// FMAs.  Other NR: column-planar (column c at c * cst) with a column loop around the one-column routines.
+template <int NR>
+__device__ __forceinline__ int lds_ix(int c, int cst, int e) { return NR == 2 ? 2 * e + c : c * cst + e; }
+// where the partial sums start: behind the n entries of y / z
+template <int NR>
+__device__ __forceinline__ double* lds_part(double* image, int n) { return image + (NR == 2 ? 2 * n : n); }
+
+// item_apply for two interleaved columns: every broadcast read of v feeds two FMAs against the one register-held
+// matrix entry; per column the order of the FMAs is item_apply's (bit-identical results)
+__device__ inline void item_apply2(const double (&m)[8], const double* v_, int Rn, int Kn, double* part_, int ldp, int it,
+                                   int nrb, int lane)
+{
+    const double2* v = reinterpret_cast<const double2*>(v_);          // (both 16-byte aligned: lds_part)
+    double2* part = reinterpret_cast<double2*>(part_);
+    const int ks = it / nrb, rb = it - ks * nrb;
+    const int r = rb * 64 + lane, k0 = 8 * ks;
+    double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+    for (int h = 0; h < 8; h += 4) {          // four 16-byte reads in flight: the registers of item_apply's eight 8-byte ones
+        double2 t[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) t[q] = (k0 + h + q < Kn) ? v[k0 + h + q] : make_double2(0.0, 0.0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            a0 = fma(m[h + q], t[q].x, a0);
+            a1 = fma(m[h + q], t[q].y, a1);
+        }
+    }
+    if (r < Rn) part[ks * ldp + r] = make_double2(a0, a1);
+}
+// lds_sum_strided for two interleaved columns: one 16-byte read per term, two accumulators, each in index order
+__device__ inline double2 lds_sum_strided2(const double* p_, int n, int stride)
+{
+    const double2* p = reinterpret_cast<const double2*>(p_);
+    double v0 = 0.0, v1 = 0.0;
+    int k = 0;
+    for (; k + 4 <= n; k += 4) {              // (four 16-byte reads at a time: lds_sum_strided's registers)
+        double2 t[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) t[q] = p[(k + q) * stride];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { v0 += t[q].x; v1 += t[q].y; }
+        __builtin_amdgcn_sched_barrier(0);    // (the next round's reads stay behind these sums: registers)
+    }
+    double2 t[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) t[q] = (k + q < n) ? p[(k + q) * stride] : make_double2(0.0, 0.0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) if (k + q < n) { v0 += t[q].x; v1 += t[q].y; }
+    return make_double2(v0, v1);
+}
+// Column c's sum_k part(c, e + k * stride), k < n in index order.  NR = 2: both columns' sums are formed in one walk
+// (lds_sum_pair, before the loop over the columns) and lds_sum_col picks column c's; other NR: column c's own walk.
+template <int NR>
+__device__ __forceinline__ double2 lds_sum_pair(const double* part, int e, int n, int stride)
+{
+    if constexpr (NR == 2) return lds_sum_strided2(part + 2 * e, n, stride);
+    else return make_double2(0.0, 0.0);
+}
+template <int NR>
+__device__ __forceinline__ double lds_sum_col(const double2& pair, const double* part, int cst, int c, int e, int n, int stride)
+{
+    if constexpr (NR == 2) return c == 0 ? pair.x : pair.y;
+    else return lds_sum_strided(part + c * cst + e, n, stride);
+}
+// One matrix item against every column of the image: part(c, ks * ldp + r) = sum_q R.m[q] * v(c, 8 ks + q).
+// (A backward item is the same walk with the roles swapped: lanes over the front's columns -- Rn = nc, ldp = ncpad --,
+// eight rows of z per item -- Kn = f --, items numbered column block fastest -- nrb = ncb.)
+template <int NR>
+__device__ __forceinline__ void item_apply_cols(const ItemRegs& R, const double* v, int cst, int Rn, int Kn, double* part,
+                                                int ldp, int it, int nrb, int lane)
+{
+    if constexpr (NR == 2) {
+        item_apply2(R.m, v, Rn, Kn, part, ldp, it, nrb, lane);
+    } else {
+#pragma unroll
+        for (int c = 0; c < NR; ++c) item_apply(R, v + c * cst, Rn, Kn, part + c * cst, ldp, it, nrb, lane);
+    }
+}
+
 typedef __attribute__((address_space(1))) double gdouble;
 typedef __attribute__((address_space(1))) int gint;
 #define LD_AGENT_F64(p) __hip_atomic_load((p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)

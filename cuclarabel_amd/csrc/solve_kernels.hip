@@ -279,7 +279,8 @@ __global__ __launch_bounds__(256) void k_bwd_small(SolveArgs A, RecSeg R, int be
 // Work is cut into items of 8 columns x 64 rows, 8 independent loads per lane in flight; partial
 // sums are combined in a fixed order (bit-reproducible).
 // LDS (doubles): forward NR * (1 + nks) * fpad  (y, then the partial sums per column slice),
-//                backward NR * (fpad + nrs * ncpad); column c's share sits behind column c - 1's.
+//                backward NR * (fpad + nrs * ncpad); column c's share sits behind column c - 1's -- except with two
+//                columns, which are interleaved (same size) and share one walk over each item (solve_common.hpp: lds_ix).
 
 template <int BS, int NR>
 __device__ __forceinline__ void fwd_block_body(const SolveArgs& A, const RecSeg& R, int begin, int bx)
@@ -314,8 +315,8 @@ __device__ __forceinline__ void fwd_block_body(const SolveArgs& A, const RecSeg&
     const int fpad = (f + 3) & ~3;
     const int nks = (nc + 7) >> 3, nrb = (f + 63) >> 6;
     const int cst = (1 + nks) * fpad;        // LDS doubles per column
-    double* y = smem;                        // column c: y at c * cst, its partial sums behind it
-    double* part = smem + fpad;
+    double* y = smem;                        // column c: y at c * cst, its partial sums behind it (NR = 2: interleaved)
+    double* part = lds_part<NR>(smem, fpad);
 
     // The wave's FIRST batch of matrix items is fetched with the values of the gather: both depend on the header only.
     constexpr int U = kItemsInFlight;
@@ -343,7 +344,7 @@ __device__ __forceinline__ void fwd_block_body(const SolveArgs& A, const RecSeg&
         for (int c = 0; c < NR; ++c) v[c] = (i < nc) ? A.b[c * A.ld_b + pi] : 0.0;
         gather_add<NR, false>(A, G, v);
 #pragma unroll
-        for (int c = 0; c < NR; ++c) y[c * cst + i] = v[c];
+        for (int c = 0; c < NR; ++c) y[lds_ix<NR>(c, cst, i)] = v[c];
     }
     __syncthreads();
     // kItemsInFlight items at a time: their loads are independent, so a wave keeps 8 x kItemsInFlight of them in flight
@@ -352,7 +353,9 @@ __device__ __forceinline__ void fwd_block_body(const SolveArgs& A, const RecSeg&
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int it = it0 + u * NW;
-            if (it < nrb * nks) {
+            if constexpr (NR == 2) {
+                if (it < nrb * nks) item_apply2(m[u], y, f, nc, part, fpad, it, nrb, lane);
+            } else if (it < nrb * nks) {
                 const int ks = it / nrb, rb = it - ks * nrb;
                 const int r = rb * 64 + lane, k0 = 8 * ks;
 #pragma unroll
@@ -368,10 +371,11 @@ __device__ __forceinline__ void fwd_block_body(const SolveArgs& A, const RecSeg&
     __syncthreads();
     for (int i = tid; i < f; i += BS) {
         double w[NR];
+        const double2 vp = lds_sum_pair<NR>(part, i, nks, fpad);
 #pragma unroll
         for (int c = 0; c < NR; ++c) {
-            const double v = lds_sum_strided(part + c * cst + i, nks, fpad);
-            w[c] = (i < nc) ? v : y[c * cst + i] - v;
+            const double v = lds_sum_col<NR>(vp, part, cst, c, i, nks, fpad);
+            w[c] = (i < nc) ? v : y[lds_ix<NR>(c, cst, i)] - v;
         }
         if (i < nc) stv<NR>(A.xp, c0 + i, w);
         else stv<NR>(A.uvec, rp + i - nc, w);
@@ -379,7 +383,7 @@ __device__ __forceinline__ void fwd_block_body(const SolveArgs& A, const RecSeg&
 }
 
 // backward items: 64 columns (lanes) x 8 rows of W' (= Wt, nc x f col-major), partial sums per row slice;
-// column c's z / part at c * cst
+// column c's z / part at c * cst (NR = 2: interleaved, one walk for both columns)
 struct BwdBatch { double m[kItemsInFlight][8]; };
 // the batch of matrix items starting at it0 (the first one is fetched before z is built: bwd_block_body)
 __device__ inline void bwd_load_items(BwdBatch& B, const double* __restrict__ Wt, int nc, int f, int it0, int NW, int lane)
@@ -407,7 +411,9 @@ __device__ inline void bwd_items(BwdBatch& B, const double* __restrict__ Wt, int
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int it = it0 + u * NW;
-            if (it < ncb * nrs) {
+            if constexpr (NR == 2) {
+                if (it < ncb * nrs) item_apply2(m[u], z, nc, f, part, ncpad, it, ncb, lane);
+            } else if (it < ncb * nrs) {
                 const int rs = it / ncb, cb = it - rs * ncb;
                 const int j = cb * 64 + lane, r0 = 8 * rs;
 #pragma unroll
@@ -456,7 +462,7 @@ __device__ __forceinline__ void bwd_block_body(const SolveArgs& A, const RecSeg&
     const int nrs = (f + 7) >> 3;
     const int cst = fpad + nrs * ncpad;
     double* z = smem;
-    double* part = smem + fpad;
+    double* part = lds_part<NR>(smem, fpad);
 
     BwdBatch first;                           // (in flight while z is built)
     bwd_load_items(first, Wt, nc, f, wv, NW, lane);
@@ -468,7 +474,7 @@ __device__ __forceinline__ void bwd_block_body(const SolveArgs& A, const RecSeg&
         double w[NR];
         ldv<NR>(A.xp, i < nc ? c0 + i : ri, w);
 #pragma unroll
-        for (int c = 0; c < NR; ++c) z[c * cst + i] = (i < nc) ? w[c] * di : -w[c];
+        for (int c = 0; c < NR; ++c) z[lds_ix<NR>(c, cst, i)] = (i < nc) ? w[c] * di : -w[c];
     }
     __syncthreads();
     bwd_items<NR>(first, Wt, nc, f, z, part, ncpad, cst, wv, NW, lane);
@@ -476,9 +482,10 @@ __device__ __forceinline__ void bwd_block_body(const SolveArgs& A, const RecSeg&
     for (int j = tid; j < nc; j += BS) {
         const int pi = j == tid ? idx : (rec ? rec_idx(rec, j) : T.perm[c0 + j]);
         double w[NR];
+        const double2 vp = lds_sum_pair<NR>(part, j, nrs, ncpad);
 #pragma unroll
         for (int c = 0; c < NR; ++c) {
-            const double v = lds_sum_strided(part + c * cst + j, nrs, ncpad);
+            const double v = lds_sum_col<NR>(vp, part, cst, c, j, nrs, ncpad);
             w[c] = v;
             A.out[c * A.ld_out + pi] = v;
         }
@@ -529,7 +536,9 @@ __global__ __launch_bounds__(BS) void k_bwd_level(SolveArgs A, RecSeg R, int beg
 // waves keep twice the loads in flight and park 64 items per workgroup (cfg2 0.303 -> 0.291 ms per solve, cfg3 0.263
 // -> 0.246, cfg5 with its 1.2 MB fronts 1.56 -> 1.31); and 512 threads with 7 parked (2 waves per SIMD, ~177 VGPRs),
 // kept selectable (HIPKKT_TOP_TALL=0).  NR right-hand sides: the parked matrix items and indices serve all of them;
-// column c's LDS vectors sit at c * cst.
+// column c's LDS vectors sit at c * cst -- two columns are interleaved instead (lds_ix) and every parked item is walked
+// once for both (item_apply2: 8 broadcast 16-byte reads and one 16-byte write per item instead of 16 + 2 accesses of
+// 8 bytes; lds_sum_strided2 likewise for the row sums).
 template <int BS, int kTopPF, int kTopPB, int NR>
 __global__ __launch_bounds__(BS, BS == 1024 ? 4 : 2) void k_top_solve(SolveArgs A, int begin, int* flags, int epoch, int ntop, int nflag)
 {
@@ -566,7 +575,7 @@ __global__ __launch_bounds__(BS, BS == 1024 ? 4 : 2) void k_top_solve(SolveArgs 
         const int nks = (nc + 7) >> 3, nrb = (f + 63) >> 6, nitF = nrb * nks;
         const int cst = (1 + nks) * fpad;
         double* y = smem;
-        double* part = smem + fpad;
+        double* part = lds_part<NR>(smem, fpad);
         ItemRegs rf[kTopPF];
 #pragma unroll
         for (int p = 0; p < kTopPF; ++p) {
@@ -647,7 +656,7 @@ __global__ __launch_bounds__(BS, BS == 1024 ? 4 : 2) void k_top_solve(SolveArgs 
                 }
             }
 #pragma unroll
-            for (int c = 0; c < NR; ++c) y[c * cst + tid] = bmine[c];
+            for (int c = 0; c < NR; ++c) y[lds_ix<NR>(c, cst, tid)] = bmine[c];
         }
         for (int i = tid + BS; i < f; i += BS) {          // fronts taller than the workgroup (rare)
             const int64_t lc = (int64_t)c0 + rp + i;
@@ -655,7 +664,7 @@ __global__ __launch_bounds__(BS, BS == 1024 ? 4 : 2) void k_top_solve(SolveArgs 
             for (int c = 0; c < NR; ++c) {
                 double v = (i < nc) ? A.b[c * A.ld_b + T.perm[c0 + i]] : 0.0;
                 for (int64_t g = T.gl_ptr[lc]; g < T.gl_ptr[lc + 1]; ++g) v += LD_AGENT_F64(A.uvec + (int64_t)(T.gl_src[g]) * NR + c);
-                y[c * cst + i] = v;
+                y[lds_ix<NR>(c, cst, i)] = v;
             }
         }
         __syncthreads();
@@ -663,10 +672,7 @@ __global__ __launch_bounds__(BS, BS == 1024 ? 4 : 2) void k_top_solve(SolveArgs 
 #pragma unroll
         for (int p = 0; p < kTopPF; ++p) {
             const int it = wv + p * NW;
-            if (it < nitF) {
-#pragma unroll
-                for (int c = 0; c < NR; ++c) item_apply(rf[p], y + c * cst, f, nc, part + c * cst, fpad, it, nrb, lane);
-            }
+            if (it < nitF) item_apply_cols<NR>(rf[p], y, cst, f, nc, part, fpad, it, nrb, lane);
         }
         // (tall fronts: the items beyond the parked ones, three at a time -- 24 loads per lane in flight)
         for (int it0 = wv + kTopPF * NW; it0 < nitF; it0 += 3 * NW) {
@@ -682,19 +688,17 @@ __global__ __launch_bounds__(BS, BS == 1024 ? 4 : 2) void k_top_solve(SolveArgs 
             }
 #pragma unroll
             for (int u = 0; u < 3; ++u)
-                if (it0 + u * NW < nitF) {
-#pragma unroll
-                    for (int c = 0; c < NR; ++c) item_apply(rr[u], y + c * cst, f, nc, part + c * cst, fpad, it0 + u * NW, nrb, lane);
-                }
+                if (it0 + u * NW < nitF) item_apply_cols<NR>(rr[u], y, cst, f, nc, part, fpad, it0 + u * NW, nrb, lane);
         }
         __syncthreads();
         TOP_STAMP(0, 4);
         for (int i = tid; i < f; i += BS) {
+            const double2 vp = lds_sum_pair<NR>(part, i, nks, fpad);
 #pragma unroll
             for (int c = 0; c < NR; ++c) {
-                const double v = lds_sum_strided(part + c * cst + i, nks, fpad);
+                const double v = lds_sum_col<NR>(vp, part, cst, c, i, nks, fpad);
                 if (i < nc) ST_AGENT_F64(A.xp + (int64_t)(c0 + i) * NR + c, v);
-                else ST_AGENT_F64(A.uvec + (int64_t)(rp + i - nc) * NR + c, y[c * cst + i] - v);
+                else ST_AGENT_F64(A.uvec + (int64_t)(rp + i - nc) * NR + c, y[lds_ix<NR>(c, cst, i)] - v);
             }
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every storing wave drains
@@ -719,7 +723,7 @@ __global__ __launch_bounds__(BS, BS == 1024 ? 4 : 2) void k_top_solve(SolveArgs 
         const int ncb = (nc + 63) >> 6, nrs = (f + 7) >> 3, nitB = ncb * nrs;
         const int cst = fpad + nrs * ncpad;
         double* z = smem;
-        double* part = smem + fpad;
+        double* part = lds_part<NR>(smem, fpad);
         ItemRegs rbk[kTopPB];
 #pragma unroll
         for (int p = 0; p < kTopPB; ++p) {
@@ -758,13 +762,13 @@ __global__ __launch_bounds__(BS, BS == 1024 ? 4 : 2) void k_top_solve(SolveArgs 
             }
 #pragma unroll
             for (int c = 0; c < NR; ++c)
-                if (tid < f) z[c * cst + tid] = (tid < nc) ? zv[c] * dinv : -zv[c];
+                if (tid < f) z[lds_ix<NR>(c, cst, tid)] = (tid < nc) ? zv[c] * dinv : -zv[c];
         }
 #pragma unroll
         for (int c = 0; c < NR; ++c) {
             const double* xc = A.xp + c;
             for (int i = tid + BS; i < f; i += BS)
-                z[c * cst + i] = (i < nc) ? LD_AGENT_F64(xc + (int64_t)(c0 + i) * NR) * A.Dinv[c0 + i]
+                z[lds_ix<NR>(c, cst, i)] = (i < nc) ? LD_AGENT_F64(xc + (int64_t)(c0 + i) * NR) * A.Dinv[c0 + i]
                                           : -LD_AGENT_F64(xc + (int64_t)T.rows[rp + i - nc] * NR);
         }
         __syncthreads();
@@ -772,7 +776,9 @@ __global__ __launch_bounds__(BS, BS == 1024 ? 4 : 2) void k_top_solve(SolveArgs 
 #pragma unroll
         for (int p = 0; p < kTopPB; ++p) {
             const int it = wv + p * NW;
-            if (it < nitB) {
+            if constexpr (NR == 2) {
+                if (it < nitB) item_apply_cols<NR>(rbk[p], z, cst, nc, f, part, ncpad, it, ncb, lane);
+            } else if (it < nitB) {
                 const int rs = it / ncb, cb = it - rs * ncb;
                 const int j = cb * 64 + lane, r0 = 8 * rs;
 #pragma unroll
@@ -798,7 +804,9 @@ __global__ __launch_bounds__(BS, BS == 1024 ? 4 : 2) void k_top_solve(SolveArgs 
 #pragma unroll
             for (int u = 0; u < 3; ++u) {
                 const int it = it0 + u * NW;
-                if (it < nitB) {
+                if constexpr (NR == 2) {
+                    if (it < nitB) item_apply2(m[u], z, nc, f, part, ncpad, it, ncb, lane);
+                } else if (it < nitB) {
                     const int rs = it / ncb, cb = it - rs * ncb;
                     const int j = cb * 64 + lane, r0 = 8 * rs;
 #pragma unroll
@@ -815,9 +823,10 @@ __global__ __launch_bounds__(BS, BS == 1024 ? 4 : 2) void k_top_solve(SolveArgs 
         TOP_STAMP(1, 4);
         for (int j = tid; j < nc; j += BS) {
             const int pi = j == tid ? ridx : T.perm[c0 + j];       // (fetched before the wait: it sat on every hop's path)
+            const double2 vp = lds_sum_pair<NR>(part, j, nrs, ncpad);
 #pragma unroll
             for (int c = 0; c < NR; ++c) {
-                const double v = lds_sum_strided(part + c * cst + j, nrs, ncpad);
+                const double v = lds_sum_col<NR>(vp, part, cst, c, j, nrs, ncpad);
                 ST_AGENT_F64(A.xp + (int64_t)(c0 + j) * NR + c, v);
                 A.out[c * A.ld_out + pi] = v;
             }
@@ -942,7 +951,7 @@ __global__ __launch_bounds__(BS, 4) void k_top_solve_sliced(SolveArgs A, int beg
             const int nks = (nc + 7) >> 3, nrb = (f + 63) >> 6, nitF = nrb * nks;
             const int cst = (1 + nks) * fpad;
             double* y = smem;
-            double* part = smem + fpad;
+            double* part = lds_part<NR>(smem, fpad);
             ItemRegs rf[4];
     #pragma unroll
             for (int p = 0; p < 4; ++p) {
@@ -999,7 +1008,7 @@ __global__ __launch_bounds__(BS, 4) void k_top_solve_sliced(SolveArgs A, int beg
                 if (NR == 1) bmine[0] = gather_rest<8>(T, A.uvec, g0 + GP, g1, bmine[0]);
                 else gather_rest_nr<8, NR>(T, A.uvec, g0 + GP, g1, bmine);
     #pragma unroll
-                for (int c = 0; c < NR; ++c) y[c * cst + tid] = bmine[c];
+                for (int c = 0; c < NR; ++c) y[lds_ix<NR>(c, cst, tid)] = bmine[c];
             }
             for (int i = tid + BS; i < f; i += BS) {          // fronts taller than the workgroup (rare)
                 const int64_t lc = (int64_t)c0 + rp + i;
@@ -1007,17 +1016,14 @@ __global__ __launch_bounds__(BS, 4) void k_top_solve_sliced(SolveArgs A, int beg
                 for (int c = 0; c < NR; ++c) {
                     double v = (i < nc) ? A.b[c * A.ld_b + T.perm[c0 + i]] : 0.0;
                     for (int64_t g = T.gl_ptr[lc]; g < T.gl_ptr[lc + 1]; ++g) v += LD_AGENT_F64(A.uvec + (int64_t)T.gl_src[g] * NR + c);
-                    y[c * cst + i] = v;
+                    y[lds_ix<NR>(c, cst, i)] = v;
                 }
             }
             __syncthreads();
     #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 const int it = wv + p * NW;
-                if (it < nitF) {
-    #pragma unroll
-                    for (int c = 0; c < NR; ++c) item_apply(rf[p], y + c * cst, f, nc, part + c * cst, fpad, it, nrb, lane);
-                }
+                if (it < nitF) item_apply_cols<NR>(rf[p], y, cst, f, nc, part, fpad, it, nrb, lane);
             }
             // (tall fronts: the items beyond the parked ones, three at a time -- 24 loads per lane in flight)
             for (int it0 = wv + 4 * NW; it0 < nitF; it0 += 3 * NW) {
@@ -1033,18 +1039,16 @@ __global__ __launch_bounds__(BS, 4) void k_top_solve_sliced(SolveArgs A, int beg
                 }
     #pragma unroll
                 for (int u = 0; u < 3; ++u)
-                    if (it0 + u * NW < nitF) {
-    #pragma unroll
-                        for (int c = 0; c < NR; ++c) item_apply(rr[u], y + c * cst, f, nc, part + c * cst, fpad, it0 + u * NW, nrb, lane);
-                    }
+                    if (it0 + u * NW < nitF) item_apply_cols<NR>(rr[u], y, cst, f, nc, part, fpad, it0 + u * NW, nrb, lane);
             }
             __syncthreads();
             for (int i = tid; i < f; i += BS) {
+                const double2 vp = lds_sum_pair<NR>(part, i, nks, fpad);
     #pragma unroll
                 for (int c = 0; c < NR; ++c) {
-                    const double v = lds_sum_strided(part + c * cst + i, nks, fpad);
+                    const double v = lds_sum_col<NR>(vp, part, cst, c, i, nks, fpad);
                     if (i < nc) ST_AGENT_F64(A.xp + (int64_t)(c0 + i) * NR + c, v);
-                    else ST_AGENT_F64(A.uvec + (int64_t)(rp + i - nc) * NR + c, y[c * cst + i] - v);
+                    else ST_AGENT_F64(A.uvec + (int64_t)(rp + i - nc) * NR + c, y[lds_ix<NR>(c, cst, i)] - v);
                 }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // every storing wave drains
@@ -1273,7 +1277,7 @@ __global__ __launch_bounds__(BS, 4) void k_top_solve_sliced(SolveArgs A, int beg
             const int ncb = (nc + 63) >> 6, nrs = (f + 7) >> 3, nitB = ncb * nrs;
             const int cst = fpad + nrs * ncpad;
             double* z = smem;
-            double* part = smem + fpad;
+            double* part = lds_part<NR>(smem, fpad);
             ItemRegs rbk[4];
     #pragma unroll
             for (int p = 0; p < 4; ++p) {
@@ -1304,18 +1308,20 @@ __global__ __launch_bounds__(BS, 4) void k_top_solve_sliced(SolveArgs A, int beg
                                        : (tid < f ? LD_AGENT_F64(A.xp + (int64_t)ridx * NR + c) : 0.0);
     #pragma unroll
                 for (int c = 0; c < NR; ++c)
-                    if (tid < f) z[c * cst + tid] = (tid < nc) ? zv[c] * dinv : -zv[c];
+                    if (tid < f) z[lds_ix<NR>(c, cst, tid)] = (tid < nc) ? zv[c] * dinv : -zv[c];
             }
     #pragma unroll
             for (int c = 0; c < NR; ++c)
                 for (int i = tid + BS; i < f; i += BS)
-                    z[c * cst + i] = (i < nc) ? LD_AGENT_F64(A.xp + (int64_t)(c0 + i) * NR + c) * A.Dinv[c0 + i]
+                    z[lds_ix<NR>(c, cst, i)] = (i < nc) ? LD_AGENT_F64(A.xp + (int64_t)(c0 + i) * NR + c) * A.Dinv[c0 + i]
                                               : -LD_AGENT_F64(A.xp + (int64_t)T.rows[rp + i - nc] * NR + c);
             __syncthreads();
     #pragma unroll
             for (int p = 0; p < 4; ++p) {
                 const int it = wv + p * NW;
-                if (it < nitB) {
+                if constexpr (NR == 2) {
+                    if (it < nitB) item_apply_cols<NR>(rbk[p], z, cst, nc, f, part, ncpad, it, ncb, lane);
+                } else if (it < nitB) {
                     const int rs = it / ncb, cb = it - rs * ncb;
                     const int j = cb * 64 + lane, r0 = 8 * rs;
     #pragma unroll
@@ -1341,7 +1347,9 @@ __global__ __launch_bounds__(BS, 4) void k_top_solve_sliced(SolveArgs A, int beg
     #pragma unroll
                 for (int u = 0; u < 3; ++u) {
                     const int it = it0 + u * NW;
-                    if (it < nitB) {
+                    if constexpr (NR == 2) {
+                        if (it < nitB) item_apply2(m[u], z, nc, f, part, ncpad, it, ncb, lane);
+                    } else if (it < nitB) {
                         const int rs = it / ncb, cb = it - rs * ncb;
                         const int j = cb * 64 + lane, r0 = 8 * rs;
     #pragma unroll
@@ -1357,9 +1365,10 @@ __global__ __launch_bounds__(BS, 4) void k_top_solve_sliced(SolveArgs A, int beg
             __syncthreads();
             for (int j = tid; j < nc; j += BS) {
                 const int pi = T.perm[c0 + j];
+                const double2 vp = lds_sum_pair<NR>(part, j, nrs, ncpad);
     #pragma unroll
                 for (int c = 0; c < NR; ++c) {
-                    const double v = lds_sum_strided(part + c * cst + j, nrs, ncpad);
+                    const double v = lds_sum_col<NR>(vp, part, cst, c, j, nrs, ncpad);
                     ST_AGENT_F64(A.xp + (int64_t)(c0 + j) * NR + c, v);
                     A.out[c * A.ld_out + pi] = v;
                 }
