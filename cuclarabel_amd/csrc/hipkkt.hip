@@ -2480,6 +2480,12 @@ struct hipkkt_kkt_s {
     DBuf<double> w, eta, soc_u, soc_v, soc_eta2, Hs;
     DBuf<int> fail;
     int nsoc = 0, npsd = 0, psd_kmax = 1;
+    // exponential and power cones: lists, per-cone index among them and alpha, grad f*(z) (3 each) and H*(z) (9 each);
+    // the strategy and mu of hipkkt_kkt_set_nonsymmetric_scaling travel to the scaling kernel as arguments
+    DBuf<int> c_explist, c_powlist, c_nsidx;
+    DBuf<double> c_param, ns_grad, ns_H;
+    int nexp = 0, npow = 0, ns_strategy = HIPKKT_SCALING_PRIMAL_DUAL;
+    double ns_mu = 0.0;
     DBuf<int> c_psdlist, c_psddim;
     DBuf<int64_t> c_psdaoff;
     DBuf<double> psdA, psdR, psdRinv;
@@ -2533,6 +2539,8 @@ struct hipkkt_kkt_s {
         C.kind = c_kind.p; C.off = c_off.p; C.numel = c_numel.p; C.boff = c_boff.p; C.sidx = c_sidx.p;
         C.soff = c_soff.p; C.elem_cone = c_elem.p; C.soc_list = c_soclist.p; C.nsoc = nsoc;
         C.psd_list = c_psdlist.p; C.psd_dim = c_psddim.p; C.psd_aoff = c_psdaoff.p; C.npsd = npsd; C.psd_kmax = psd_kmax;
+        C.exp_list = c_explist.p; C.nexp = nexp; C.pow_list = c_powlist.p; C.npow = npow; C.ns_index = c_nsidx.p;
+        C.param = c_param.p; C.ns_strategy = ns_strategy; C.ns_mu = ns_mu;
         return C;
     }
     ConeState cone_state()
@@ -2541,6 +2549,7 @@ struct hipkkt_kkt_s {
         S.w = w.p; S.eta = eta.p; S.u = soc_u.p; S.v = soc_v.p; S.eta2 = soc_eta2.p; S.Hs = Hs.p; S.fail = fail.p;
         S.psdA = psdA.p; S.psdR = psdR.p; S.psdRinv = psdRinv.p;
         S.lam = lam.p;
+        S.ns_grad = ns_grad.p; S.ns_H = ns_H.p;
         return S;
     }
 };
@@ -2874,6 +2883,15 @@ int hipkkt_kkt_create(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t* Pc
                       int64_t ncones, const int32_t* kinds, const int64_t* dims, const hipkkt_settings* settings,
                       int base)
 {
+    return hipkkt_kkt_create_ex(out, n, m, Pcolptr, Prowval, Pnzval, Acolptr, Arowval, Anzval, ncones, kinds, dims, nullptr,
+                                settings, base);
+}
+
+int hipkkt_kkt_create_ex(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t* Pcolptr, const int64_t* Prowval,
+                         const double* Pnzval, const int64_t* Acolptr, const int64_t* Arowval, const double* Anzval,
+                         int64_t ncones, const int32_t* kinds, const int64_t* dims, const double* cone_params,
+                         const hipkkt_settings* settings, int base)
+{
     return guarded([&]() {
         if (!out || !Pcolptr || !Acolptr || n < 0 || m < 0 || ncones < 0 || (ncones > 0 && (!kinds || !dims)))
             throw ArgError("hipkkt_kkt_create: bad argument");
@@ -2883,7 +2901,7 @@ int hipkkt_kkt_create(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t* Pc
         if (settings) h->st = *settings; else hipkkt_default_settings(&h->st);
         // host-side assembly first: a malformed (P, A, cones) is an argument error whether or not a device is there
         try {
-            assemble_kkt(n, m, Pcolptr, Prowval, Pnzval, Acolptr, Arowval, Anzval, ncones, kinds, dims, base, h->K);
+            assemble_kkt(n, m, Pcolptr, Prowval, Pnzval, Acolptr, Arowval, Anzval, ncones, kinds, dims, base, h->K, cone_params);
         } catch (const std::runtime_error& e) {
             throw ArgError(e.what());
         }
@@ -3023,6 +3041,8 @@ int hipkkt_kkt_create(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t* Pc
             size_t nc = K.cones.size();
             std::vector<int> kind(nc), off(nc), numel(nc), sidx(nc), soff(nc), elem((size_t)K.m), soclist, soc_of;
             std::vector<int64_t> boff(nc);
+            std::vector<int> explist, powlist, nsidx(nc, -1);
+            std::vector<double> param(nc, 0.0);
             soc_of.assign((size_t)K.sparse_len, 0);
             for (size_t c = 0; c < nc; ++c) {
                 const ConeInfo& ci = K.cones[c];
@@ -3031,6 +3051,9 @@ int hipkkt_kkt_create(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t* Pc
                 soff[c] = ci.sparse ? ci.soff : -1;
                 for (int t = 0; t < ci.numel; ++t) elem[ci.off + t] = (int)c;
                 if (ci.kind == HIPKKT_CONE_SOC) soclist.push_back((int)c);
+                if (ci.kind == HIPKKT_CONE_EXP) explist.push_back((int)c);
+                if (ci.kind == HIPKKT_CONE_POW) powlist.push_back((int)c);
+                nsidx[c] = ci.nsidx; param[c] = ci.param;
                 if (ci.kind == HIPKKT_CONE_PSD) {
                     h->has_psd = true;
                     if (ci.dim > kPsdMaxDim) h->psd_too_big = true;
@@ -3038,6 +3061,13 @@ int hipkkt_kkt_create(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t* Pc
                 if (ci.sparse) for (int t = 0; t < ci.numel; ++t) soc_of[ci.soff + t] = ci.sidx;
             }
             h->nsoc = (int)soclist.size();
+            h->nexp = (int)explist.size(); h->npow = (int)powlist.size();
+            if (K.nnonsym > 0) {
+                h->c_explist.upload(explist); h->c_powlist.upload(powlist); h->c_nsidx.upload(nsidx); h->c_param.upload(param);
+                h->ns_grad.alloc((size_t)3 * K.nnonsym); h->ns_H.alloc((size_t)9 * K.nnonsym);
+                HIP_CHECK(hipMemset(h->ns_grad.p, 0, (size_t)3 * K.nnonsym * sizeof(double)));
+                HIP_CHECK(hipMemset(h->ns_H.p, 0, (size_t)9 * K.nnonsym * sizeof(double)));
+            }
             {
                 std::vector<int> plist, pdim(nc, 0);
                 std::vector<int64_t> paoff(nc, 0);
@@ -4187,6 +4217,9 @@ int hipkkt_kkt_system_update_scaling(hipkkt_kkt_t h, const double* w, const doub
         if ((m && (!w || !lambda)) || (h->nsoc > 0 && !eta) || (h->npsd > 0 && (!psd_R || !psd_Rinv)))
             throw ArgError("hipkkt_kkt_system_update_scaling: missing scaling data");
         if (h->psd_too_big) throw ArgError("hipkkt_kkt_system_*: PSD cones with side > 48 are not covered by level C");
+        if (h->K.nnonsym > 0)
+            throw ArgError("hipkkt_kkt_system_update_scaling: (w, eta, lambda, R) cannot carry the 3 x 3 block of an exponential "
+                           "or power cone; use hipkkt_kkt_system_update_cones");
         HIP_CHECK(hipSetDevice(h->device));
         hipStream_t st = h->stream;
         if (m) {
@@ -4382,6 +4415,12 @@ int hipkkt_equilibrate(int64_t n, int64_t m, const int64_t* Pcolptr, const int64
         int64_t off = 0;
         for (int64_t k = 0; k < ncones; ++k) {
             const int64_t dim = cone_dims[k];
+            // (exponential and power cones take the default rectification, one scalar per cone: coneops_defaults.jl:32-44,
+            // which k_equil_rectify applies to every kind >= 2)
+            if (cone_kinds[k] < HIPKKT_CONE_ZERO || cone_kinds[k] > HIPKKT_CONE_POW || dim < 0)
+                throw ArgError("hipkkt_equilibrate: unknown cone kind or negative dimension");
+            if ((cone_kinds[k] == HIPKKT_CONE_EXP || cone_kinds[k] == HIPKKT_CONE_POW) && dim != 3)
+                throw ArgError("hipkkt_equilibrate: exponential and power cones have dimension 3");
             const int64_t ne = cone_kinds[k] == HIPKKT_CONE_PSD ? dim * (dim + 1) / 2 : dim;
             ckind[(size_t)k] = cone_kinds[k];
             coff[(size_t)k] = (int)off;
@@ -4545,6 +4584,34 @@ int hipkkt_kkt_get_scaling_w(hipkkt_kkt_t h, double* w, double* eta)
         HIP_CHECK(hipSetDevice(h->device));
         if (w && h->K.m) HIP_CHECK(hipMemcpyAsync(w, h->w.p, (size_t)h->K.m * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         if (eta && h->eta.n) HIP_CHECK(hipMemcpyAsync(eta, h->eta.p, h->eta.n * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_set_nonsymmetric_scaling(hipkkt_kkt_t h, int strategy, double mu)
+{
+    return guarded([&]() {
+        if (!h) throw ArgError("null handle");
+        if (strategy != HIPKKT_SCALING_PRIMAL_DUAL && strategy != HIPKKT_SCALING_DUAL)
+            throw ArgError("hipkkt_kkt_set_nonsymmetric_scaling: strategy must be PRIMAL_DUAL (0) or DUAL (1)");
+        if (h->K.nnonsym == 0) return HIPKKT_OK;
+        h->ns_strategy = strategy;
+        h->ns_mu = mu;
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_get_nonsymmetric(hipkkt_kkt_t h, double* grad, double* H_dual)
+{
+    return guarded([&]() {
+        if (!h) throw ArgError("null handle");
+        const size_t nn = (size_t)h->K.nnonsym;
+        if (nn == 0) return HIPKKT_OK;
+        if (!h->scaling_valid) throw ArgError("hipkkt_kkt_get_nonsymmetric needs a device-side scaling (hipkkt_kkt_update_from_sz)");
+        HIP_CHECK(hipSetDevice(h->device));
+        if (grad) HIP_CHECK(hipMemcpyAsync(grad, h->ns_grad.p, 3 * nn * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (H_dual) HIP_CHECK(hipMemcpyAsync(H_dual, h->ns_H.p, 9 * nn * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));
         return HIPKKT_OK;
     });

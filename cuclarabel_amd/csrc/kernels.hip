@@ -802,6 +802,234 @@ __global__ __launch_bounds__(256) void k_cone_scaling(ConeDev C, ConeState S, co
     if (ci < C.nsoc) cone_soc_body(C, S, s, z, ci, threadIdx.x & 63);
 }
 
+
+// -------------------------------------------------------------------------------------
+//  Exponential and power cones (coneops_expcone.jl, coneops_powcone.jl, coneops_nonsymmetric_common.jl): one THREAD per
+//  cone -- the work per cone is a few dozen scalar fp64 operations on three rows, and a problem that uses these cones has
+//  one per data sample.  The reference restated term for term (this file is compiled without FMA contraction):
+//    update_dual_grad_H      grad f*(z), H*(z)                          expcone :370-399, powcone :408-440
+//    gradient_primal         exp: Wright omega, two refinement rounds   expcone :284-297, :412-468
+//                            pow: one-sided Newton-Raphson              powcone :288-316, :449-478, common :170-193
+//    use_primal_dual_scaling with its four guards, else mu H*(z)        common :82-164
+//    use_dual_scaling        mu H*(z), mu from the caller               common :71-78
+//    pack_triu               into the Hs store                          mathutils.jl:402-412
+//  A z outside the dual cone, or a scaling that is not finite, raises the fail word (the update returns 1) and leaves
+//  the cone's Hs entries as they were.
+// -------------------------------------------------------------------------------------
+__device__ inline double ns_logsafe(double v) { return v > 0.0 ? log(v) : -HUGE_VAL; }
+
+__device__ inline double ns_wright_omega(double z)
+{
+    if (!(z >= 0.0)) return NAN;                   // the reference throws; reached only from outside the primal cone
+    double w;
+    if (z < 1.0 + 3.14159265358979323846) {
+        const double zm1 = z - 1.0;
+        double p = zm1;
+        w = 1.0 + 0.5 * p;
+        p *= zm1;
+        w += (1.0 / 16.0) * p;
+        p *= zm1;
+        w -= (1.0 / 192.0) * p;
+        p *= zm1;
+        w -= (1.0 / 3072.0) * p;
+        p *= zm1;
+        w += (13.0 / 61440.0) * p;
+    } else {
+        const double logz = ns_logsafe(z);
+        const double zinv = 1.0 / z;
+        w = z - logz;
+        double q = logz * zinv;
+        w += q;
+        q *= zinv;
+        w += q * (logz / 2.0 - 1.0);
+        // (:451 of the reference forms q*zinv and drops it: the cubic term is weighted by log(z)/z^2 there, and here)
+        w += q * (logz * logz / 3.0 - (3.0 / 2.0) * logz + 1.0);
+    }
+    double r = z - w - ns_logsafe(w);
+    for (int i = 0; i < 2; ++i) {
+        const double wp1 = w + 1.0;
+        const double t = wp1 * (wp1 + (2.0 * r) / 3.0);
+        w *= 1.0 + (r / wp1) * (t - 0.5 * r) / (t - r);
+        r = (2.0 * w * w - 8.0 * w - 1.0) / (72.0 * (wp1 * wp1 * wp1 * wp1 * wp1 * wp1)) * r * r * r * r;
+    }
+    return w;
+}
+
+__device__ inline double ns_newton_raphson_powcone(double s3, double phi, double a)
+{
+    const double eps = 2.220446049250313e-16, sqrt_eps = 1.4901161193847656e-08;
+    double x = -1.0 / s3 + (2.0 * s3 + sqrt(phi * phi / s3 / s3 + 3.0 * phi)) / (phi - s3 * s3);
+    const double t0 = -2.0 * a * ns_logsafe(a) - 2.0 * (1.0 - a) * ns_logsafe(1.0 - a);
+    auto f0 = [&](double y) {
+        const double t1 = y * y, t2 = 2.0 * y / s3;
+        return 2.0 * a * ns_logsafe(2.0 * a * t1 + (1.0 + a) * t2) + 2.0 * (1.0 - a) * ns_logsafe(2.0 * (1.0 - a) * t1 + (2.0 - a) * t2)
+               - ns_logsafe(phi) - ns_logsafe(t1 + t2) - 2.0 * ns_logsafe(t2) + t0;
+    };
+    // the one-sided iteration needs f0(x0) > 0; the reference's x0 lies right of the root for alpha away from 1/2 and its
+    // iteration then halts at once (ipm.py: _newton_raphson_powcone has the figures).  f0 -> +Inf as x -> 0+: halve.
+    for (int k = 0; k < 64 && !(f0(x) > 0.0); ++k) x *= 0.5;
+    for (int iter = 0; iter < 100; ++iter) {
+        const double t1 = x * x, t2 = x * 2.0 / s3;
+        const double dfdx = 2.0 * a * a / (a * x + (1.0 + a) / s3) + 2.0 * (1.0 - a) * (1.0 - a) / ((1.0 - a) * x + (2.0 - a) / s3)
+                            - 2.0 * (x + 1.0 / s3) / (t1 + t2);
+        const double dx = -f0(x) / dfdx;
+        if ((dx < eps) || (fabs(dx / x) < sqrt_eps) || (fabs(dfdx) < eps)) break;
+        x += dx;
+    }
+    return x;
+}
+
+// grad f*(z) -> g, H*(z) -> H (row-major 3 x 3); returns whether z is strictly inside the dual cone
+__device__ inline bool ns_exp_dual_grad_H(const double* z, double* g, double* H)
+{
+    const double l = ns_logsafe(-z[2] / z[0]);
+    const double r = -z[0] * l - z[0] + z[1];
+    const double c2 = 1.0 / r;
+    g[0] = c2 * l - 1.0 / z[0];
+    g[1] = -c2;
+    g[2] = (c2 * z[0] - 1.0) / z[2];
+    H[0] = (r * r - z[0] * r + l * l * z[0] * z[0]) / (r * z[0] * z[0] * r);
+    H[1] = H[3] = -l / (r * r);
+    H[4] = 1.0 / (r * r);
+    H[2] = H[6] = (z[1] - z[0]) / (r * r * z[2]);
+    H[5] = H[7] = -z[0] / (r * r * z[2]);
+    H[8] = (r * r - z[0] * r + z[0] * z[0]) / (r * r * z[2] * z[2]);
+    // is_dual_feasible (:269-281): res = z2 - z1 - z1 log(-z3/z1) is r in the order the reference sums it there
+    return z[2] > 0.0 && z[0] < 0.0 && (z[1] - z[0] - z[0] * l) > 0.0;
+}
+__device__ inline void ns_exp_gradient_primal(const double* s, double* g)
+{
+    const double w = ns_wright_omega(1.0 - s[0] / s[1] - ns_logsafe(s[1] / s[2]));
+    g[0] = 1.0 / ((w - 1.0) * s[1]);
+    g[1] = g[0] + g[0] * ns_logsafe(w * s[1] / s[2]) - 1.0 / s[1];
+    g[2] = w / ((1.0 - w) * s[2]);
+}
+__device__ inline bool ns_pow_dual_grad_H(const double* z, double a, double* g, double* H)
+{
+    const double phi = pow(z[0] / a, 2.0 * a) * pow(z[1] / (1.0 - a), 2.0 - 2.0 * a);
+    const double psi = phi - z[2] * z[2];
+    const double g0 = 2.0 * a * phi / (z[0] * psi), g1 = 2.0 * (1.0 - a) * phi / (z[1] * psi), g2 = -2.0 * z[2] / psi;
+    H[0] = g0 * g0 - 2.0 * a * (2.0 * a - 1.0) * phi / (z[0] * z[0] * psi) + (1.0 - a) / (z[0] * z[0]);
+    H[1] = H[3] = g0 * g1 - 4.0 * a * (1.0 - a) * phi / (z[0] * z[1] * psi);
+    H[4] = g1 * g1 - 2.0 * (1.0 - a) * (1.0 - 2.0 * a) * phi / (z[1] * z[1] * psi) + a / (z[1] * z[1]);
+    H[2] = H[6] = g0 * g2;
+    H[5] = H[7] = g1 * g2;
+    H[8] = g2 * g2 + 2.0 / psi;
+    g[0] = -2.0 * a * phi / (z[0] * psi) - (1.0 - a) / z[0];
+    g[1] = -2.0 * (1.0 - a) * phi / (z[1] * psi) - a / z[1];
+    g[2] = 2.0 * z[2] / psi;
+    // is_dual_feasible (:272-284)
+    if (!(z[0] > 0.0 && z[1] > 0.0)) return false;
+    return exp(2.0 * a * ns_logsafe(z[0] / a) + 2.0 * (1.0 - a) * ns_logsafe(z[1] / (1.0 - a))) - z[2] * z[2] > 0.0;
+}
+__device__ inline void ns_pow_gradient_primal(const double* s, double a, double* g)
+{
+    const double phi = pow(s[0], 2.0 * a) * pow(s[1], 2.0 - 2.0 * a);
+    const double abs_s = fabs(s[2]);
+    if (abs_s > 2.220446049250313e-16) {
+        g[2] = ns_newton_raphson_powcone(abs_s, phi, a);
+        if (s[2] < 0.0) g[2] = -g[2];
+        g[0] = -(a * g[2] * s[2] + 1.0 + a) / s[0];
+        g[1] = -((1.0 - a) * g[2] * s[2] + 2.0 - a) / s[1];
+    } else {
+        g[2] = 0.0;
+        g[0] = -(1.0 + a) / s[0];
+        g[1] = -(2.0 - a) / s[1];
+    }
+}
+
+// update_Hs for one cone; st = grad f*(z), H = H*(z), zt = gradient_primal(s) (read by the primal-dual strategy only)
+__device__ inline void ns_update_Hs(const double* s, const double* z, const double* st, const double* H, const double* zt,
+                                    int strategy, double mu_in, double* Hs /* 3 x 3 */)
+{
+    double mu = mu_in;
+    if (strategy == 0) {
+        const double dot_sz = z[0] * s[0] + z[1] * s[1] + z[2] * s[2];
+        mu = dot_sz / 3.0;
+        const double mut = (zt[0] * st[0] + zt[1] * st[1] + zt[2] * st[2]) / 3.0;
+        double dls[3], dlz[3], Hzt[3];
+        for (int i = 0; i < 3; ++i) { dls[i] = s[i] + mu * st[i]; dlz[i] = z[i] + mu * zt[i]; }
+        const double dot_dsz = dls[0] * dlz[0] + dls[1] * dlz[1] + dls[2] * dlz[2];
+        const double de1 = mu * mut - 1.0;
+        for (int i = 0; i < 3; ++i) Hzt[i] = H[3 * i] * zt[0] + H[3 * i + 1] * zt[1] + H[3 * i + 2] * zt[2];
+        const double de2 = (zt[0] * Hzt[0] + zt[1] * Hzt[1] + zt[2] * Hzt[2]) - 3.0 * mut * mut;
+        if (fabs(de1) > 1.4901161193847656e-08 && fabs(de2) > 2.220446049250313e-16 && dot_sz > 0.0 && dot_dsz > 0.0) {
+            double tmp[3];
+            for (int i = 0; i < 3; ++i) tmp[i] = mut * st[i] - H[3 * i] * zt[0] - H[3 * i + 1] * zt[1] - H[3 * i + 2] * zt[2];
+            double fro = 0.0;
+            for (int i = 0; i < 3; ++i)
+                for (int j = 0; j < 3; ++j) {
+                    const double wij = H[3 * i + j] - (st[i] * st[j] / 3.0 + tmp[i] * tmp[j] / de2);
+                    fro += wij * wij;
+                }
+            const double t = mu * sqrt(fro);
+            double ax[3] = {z[1] * zt[2] - z[2] * zt[1], z[2] * zt[0] - z[0] * zt[2], z[0] * zt[1] - z[1] * zt[0]};
+            const double an = sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
+            for (int i = 0; i < 3; ++i) ax[i] /= an;
+            for (int i = 0; i < 3; ++i)
+                for (int j = i; j < 3; ++j) {
+                    const double v = s[i] * s[j] / dot_sz + dls[i] * dls[j] / dot_dsz + t * ax[i] * ax[j];
+                    Hs[3 * i + j] = v;
+                    Hs[3 * j + i] = v;
+                }
+            return;
+        }
+    }
+    for (int i = 0; i < 9; ++i) Hs[i] = mu * H[i];
+}
+
+__device__ inline void cone_nonsym_body(const ConeDev& C, const ConeState& S, const double* __restrict__ s,
+                                        const double* __restrict__ z, int c, bool is_pow)
+{
+    const int off = C.off[c];
+    const double sv[3] = {s[off], s[off + 1], s[off + 2]};
+    const double zv[3] = {z[off], z[off + 1], z[off + 2]};
+    double g[3], H[9], zt[3] = {0.0, 0.0, 0.0}, Hs[9];
+    bool ok;
+    if (is_pow) {
+        const double a = C.param[c];
+        ok = ns_pow_dual_grad_H(zv, a, g, H);
+        if (ok && C.ns_strategy == 0) ns_pow_gradient_primal(sv, a, zt);
+    } else {
+        ok = ns_exp_dual_grad_H(zv, g, H);
+        if (ok && C.ns_strategy == 0) ns_exp_gradient_primal(sv, zt);
+    }
+    const int k = C.ns_index[c];
+    for (int i = 0; i < 3; ++i) S.ns_grad[3 * k + i] = g[i];
+    for (int i = 0; i < 9; ++i) S.ns_H[9 * k + i] = H[i];
+    if (ok) {
+        ns_update_Hs(sv, zv, g, H, zt, C.ns_strategy, C.ns_mu, Hs);
+        for (int i = 0; i < 9; ++i) ok = ok && isfinite(Hs[i]);
+    }
+    if (!ok) { *S.fail = 1; return; }
+    double* out = S.Hs + C.boff[c];
+    out[0] = Hs[0];                                   // pack_triu: columns of the upper triangle
+    out[1] = Hs[1]; out[2] = Hs[4];
+    out[3] = Hs[2]; out[4] = Hs[5]; out[5] = Hs[8];
+}
+
+// k_cone_scaling for a handle that holds exponential / power cones: the same elementwise and second-order workgroups,
+// then workgroups over exp_list, then over pow_list, a thread per cone.  A kernel of its own so that the one every
+// symmetric problem launches keeps its register count.
+__global__ __launch_bounds__(256) void k_cone_scaling_ns(ConeDev C, ConeState S, const double* __restrict__ s,
+                                                         const double* __restrict__ z, int m, int ge, int gs, int gx)
+{
+    const int bx = (int)blockIdx.x;
+    if (bx < ge) { cone_elementwise_body(C, S, s, z, m, bx, ge); return; }
+    if (bx < ge + gs) {
+        const int ci = (bx - ge) * 4 + (int)(threadIdx.x >> 6);
+        if (ci < C.nsoc) cone_soc_body(C, S, s, z, ci, threadIdx.x & 63);
+        return;
+    }
+    if (bx < ge + gs + gx) {
+        const int i = (bx - ge - gs) * 256 + (int)threadIdx.x;
+        if (i < C.nexp) cone_nonsym_body(C, S, s, z, C.exp_list[i], false);
+        return;
+    }
+    const int i = (bx - ge - gs - gx) * 256 + (int)threadIdx.x;
+    if (i < C.npow) cone_nonsym_body(C, S, s, z, C.pow_list[i], true);
+}
+
 // -------------------------------------------------------------------------------------
 //  PSD cones (coneops_psdtrianglecone.jl:78-161): one workgroup per cone, everything in LDS.
 //    S, Z from svec;  L1 = chol(S), L2 = chol(Z)  (failure => not interior);
@@ -1044,7 +1272,10 @@ void launch_cone_scaling(const ConeDev& C, const ConeState& S, const double* s, 
                          hipStream_t st)
 {
     const int ge = m > 0 ? grid_for(m, 256) : 0, gs = (C.nsoc + 3) / 4;
-    if (ge + gs > 0) hipLaunchKernelGGL(k_cone_scaling, dim3(ge + gs), dim3(256), 0, st, C, S, s, z, m, ge);
+    const int gx = (C.nexp + 255) / 256, gp = (C.npow + 255) / 256;
+    if (gx + gp > 0)
+        hipLaunchKernelGGL(k_cone_scaling_ns, dim3(ge + gs + gx + gp), dim3(256), 0, st, C, S, s, z, m, ge, gs, gx);
+    else if (ge + gs > 0) hipLaunchKernelGGL(k_cone_scaling, dim3(ge + gs), dim3(256), 0, st, C, S, s, z, m, ge);
     if (C.npsd > 0) {
         static PerDeviceOnce once;
         once.run([]() { return set_max_lds(k_cone_psd, 150 * 1024); });
@@ -1063,6 +1294,13 @@ __device__ inline void mul_Hs_elementwise_body(const ConeDev& C, const ConeState
         double v;
         if (kind == 0) v = 0.0;
         else if (kind == 1) v = S.w[i] * (S.w[i] * x[i]);
+        else if (kind >= 4) {
+            // exponential / power cone: row r of the stored 3 x 3 block (packed triu) times x (mul_Hs!, coneops_expcone.jl:103-115)
+            const int c = C.elem_cone[i], off = C.off[c], r = i - off;
+            const double* Hs = S.Hs + C.boff[c];
+            auto at = [&](int a, int b) { return a <= b ? Hs[b * (b + 1) / 2 + a] : Hs[a * (a + 1) / 2 + b]; };
+            v = at(r, 0) * x[off] + at(r, 1) * x[off + 1] + at(r, 2) * x[off + 2];
+        }
         else continue;
         y[i] = addend ? -(v + addend[i]) : v;
     }
@@ -1249,6 +1487,7 @@ __device__ inline void sys_offset_elementwise_body(const ConeDev& C, const ConeS
             const int kind = C.kind[C.elem_cone[i]];
             if (kind == 0) o = 0.0;                     // coneops_zerocone.jl:137-150
             else if (kind == 1) o = ds[i] / z[i];       // coneops_nncone.jl:140-148
+            else if (kind >= 4) o = ds[i];              // exponential / power: out = ds (coneops_expcone.jl:150-163)
             else continue;                              // second-order / PSD cones: k_sys_offset_soc / k_sys_offset_psd
         }
         konst[i] = o;

@@ -453,6 +453,15 @@ struct ConeDev {
     const int64_t* psd_aoff;     // per cone
     int npsd;
     int psd_kmax;
+    // lists of exponential and of power cones (kinds 4, 5; three rows each), so that neighbouring lanes of the scaling
+    // kernel run the same branch; ns_index = position among both (in cone order) or -1; param = alpha of a power cone
+    const int* exp_list = nullptr;
+    const int* pow_list = nullptr;
+    const int* ns_index = nullptr;   // per cone
+    const double* param = nullptr;   // per cone
+    int nexp = 0, npow = 0;
+    int ns_strategy = 0;             // 0 primal-dual, 1 dual (hipkkt_kkt_set_nonsymmetric_scaling)
+    double ns_mu = 0.0;              // read by the dual strategy only
 };
 struct ConeState {
     double* w;                   // m: NN: sqrt(s/z); SOC: normalised w
@@ -466,6 +475,8 @@ struct ConeState {
     double* psdR;                // per PSD cone: R = L1 V Lam^{-1/2} and Rinv = Lam^{-1/2} U' L2' (k x k col-major, same
     double* psdRinv;             //   offsets as psdA); the singular values Lam go to lam[off .. off + k), descending
     int* fail;                   // set to 1 when a point is not interior
+    double* ns_grad = nullptr;   // per exponential / power cone: grad f*(z), 3 doubles
+    double* ns_H = nullptr;      // ... and H*(z), 3 x 3
 };
 constexpr int kPsdMaxDim = 48;   // largest PSD side handled by the in-LDS scaling kernel
 void launch_cone_scaling(const ConeDev& C, const ConeState& S, const double* s, const double* z, int m,

@@ -15,7 +15,7 @@ static inline int64_t tri(int64_t k) { return k * (k + 1) / 2; }
 
 void assemble_kkt(int64_t n64, int64_t m64, const int64_t* Pp, const int64_t* Pi, const double* Px,
                   const int64_t* Ap, const int64_t* Ai, const double* Ax, int64_t ncones,
-                  const int32_t* kinds, const int64_t* dims, int base, KKTAssembly& K)
+                  const int32_t* kinds, const int64_t* dims, int base, KKTAssembly& K, const double* cone_params)
 {
     K = KKTAssembly();
     if (n64 < 0 || m64 < 0 || n64 + m64 > 1900000000) throw std::runtime_error("kkt: bad dimensions");
@@ -27,7 +27,18 @@ void assemble_kkt(int64_t n64, int64_t m64, const int64_t* Pp, const int64_t* Pi
     for (int64_t c = 0; c < ncones; ++c) {
         ConeInfo ci{};
         ci.kind = kinds[c];
-        if (ci.kind < HIPKKT_CONE_ZERO || ci.kind > HIPKKT_CONE_PSD) throw std::runtime_error("kkt: unknown cone kind");
+        if (ci.kind < HIPKKT_CONE_ZERO || ci.kind > HIPKKT_CONE_POW) throw std::runtime_error("kkt: unknown cone kind");
+        ci.nsidx = -1;
+        if (ci.kind == HIPKKT_CONE_EXP || ci.kind == HIPKKT_CONE_POW) {
+            if (dims[c] != 3) throw std::runtime_error("kkt: exponential and power cones have dimension 3");
+            if (ci.kind == HIPKKT_CONE_POW) {
+                if (!cone_params)
+                    throw std::runtime_error("kkt: a power cone needs its alpha: use hipkkt_kkt_create_ex with cone_params");
+                ci.param = cone_params[c];
+                if (!(ci.param > 0.0 && ci.param < 1.0)) throw std::runtime_error("kkt: power cone alpha must lie in (0, 1)");
+            }
+            ci.nsidx = K.nnonsym++;
+        }
         if (dims[c] < 0) throw std::runtime_error("kkt: negative cone dimension");
         ci.dim = (int)dims[c];
         ci.numel = ci.kind == HIPKKT_CONE_PSD ? (int)tri(dims[c]) : (int)dims[c];
@@ -36,7 +47,7 @@ void assemble_kkt(int64_t n64, int64_t m64, const int64_t* Pp, const int64_t* Pi
         off += ci.numel;
         ci.sparse = (ci.kind == HIPKKT_CONE_SOC && ci.dim > 4) ? 1 : 0;     // cone_types.jl:101-112
         ci.boff = boff;
-        bool dense = ci.kind == HIPKKT_CONE_PSD || (ci.kind == HIPKKT_CONE_SOC && !ci.sparse);
+        bool dense = cone_is_dense(ci);
         ci.blen = dense ? tri(ci.numel) : ci.numel;
         boff += ci.blen;
         if (ci.sparse) {
@@ -91,7 +102,7 @@ void assemble_kkt(int64_t n64, int64_t m64, const int64_t* Pp, const int64_t* Pi
     {
         int pcol = n + m;
         for (const ConeInfo& ci : K.cones) {
-            bool dense = ci.kind == HIPKKT_CONE_PSD || (ci.kind == HIPKKT_CONE_SOC && !ci.sparse);
+            bool dense = cone_is_dense(ci);
             for (int t = 0; t < ci.numel; ++t) len[n + ci.off + t] += dense ? t + 1 : 1;
             if (ci.sparse) {
                 len[pcol] += ci.numel + 1;
@@ -134,7 +145,7 @@ void assemble_kkt(int64_t n64, int64_t m64, const int64_t* Pp, const int64_t* Pi
     for (const ConeInfo& ci : K.cones) {
         int row0 = n + ci.off;
         int* block = K.mapHs.data() + ci.boff;
-        bool dense = ci.kind == HIPKKT_CONE_PSD || (ci.kind == HIPKKT_CONE_SOC && !ci.sparse);
+        bool dense = cone_is_dense(ci);
         if (dense) {
             int64_t kidx = 0;
             for (int t = 0; t < ci.numel; ++t)

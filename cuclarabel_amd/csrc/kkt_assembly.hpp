@@ -18,12 +18,17 @@ struct ConeInfo {
     int sparse;        // SOC with dim > 4: sparse expansion
     int sidx;          // index among sparse SOCs
     int soff;          // offset into the concatenated u / v
+    int nsidx;         // index among the exponential / power cones, -1 otherwise
+    double param;      // alpha of a power cone
 };
+// cones whose Hs block is a packed dense upper triangle
+inline bool cone_is_dense(const ConeInfo& ci) { return ci.kind == 3 || (ci.kind == 2 && !ci.sparse) || ci.kind == 4 || ci.kind == 5; }
 
 struct KKTAssembly {
     int n = 0, m = 0, p = 0, N = 0;
     int64_t nnzK = 0, nHs = 0;
     int nsparse = 0, sparse_len = 0;
+    int nnonsym = 0;               // exponential + power cones
     std::vector<ConeInfo> cones;
     // triu CSC
     std::vector<int64_t> colptr;
@@ -37,6 +42,7 @@ struct KKTAssembly {
 // P: triu CSC n x n; A: CSC m x n (any index base).  Throws std::runtime_error on bad input.
 void assemble_kkt(int64_t n, int64_t m, const int64_t* Pp, const int64_t* Pi, const double* Px,
                   const int64_t* Ap, const int64_t* Ai, const double* Ax, int64_t ncones,
-                  const int32_t* kinds, const int64_t* dims, int base, KKTAssembly& K);
+                  const int32_t* kinds, const int64_t* dims, int base, KKTAssembly& K,
+                  const double* cone_params = nullptr);
 
 }  // namespace hipkkt

@@ -1,7 +1,7 @@
 """Interior-point test driver over the KKT-solver boundary.
 
 A host-side (numpy) restatement of the reference's IPM loop for Zero / Nonnegative /
-SecondOrder / PSDTriangle cones, without presolve, equilibration or chordal decomposition:
+SecondOrder / PSDTriangle / Exponential / Power cones, without presolve, equilibration or chordal decomposition:
 
     solve!                          /root/reference/src/solver.jl:189-380
     default start                   solver.jl:383-404, kktsystem.jl:95-132, variables.jl:196-237
@@ -13,6 +13,11 @@ SecondOrder / PSDTriangle cones, without presolve, equilibration or chordal deco
     NT scaling, W, lambda           coneops_nncone.jl:77-114, coneops_socone.jl:75-154,302-412
     PSD cone                        coneops_psdtrianglecone.jl:8-44 (margins, shift), :78-143 (scaling), :164-254,
                                     :299-466 (mul_Hs!, ds offsets, W / W^-1, Jordan product, step length)
+
+    exponential / power cones       coneops_expcone.jl, coneops_powcone.jl, coneops_nonsymmetric_common.jl; the loop's
+                                    branches for them: solver.jl:221 (strategy), :383-404 (unit start), :407-442 (barrier
+                                    backtrack), :453-504 (checkpoints), variables.jl:46-72.  They fire only when such a cone
+                                    is present; a symmetric problem takes the code path it always took.
 
 It exists to drive a KKT backend through exactly the call sequence Clarabel uses
 (`kktsolver_update!` -> constant-RHS solve -> affine solve -> combined solve, every iteration)
@@ -27,12 +32,14 @@ from dataclasses import dataclass, field
 import numpy as np
 import scipy.sparse as sp
 
-from .cones import ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT
+from .cones import (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT,
+                    ExponentialConeT, PowerConeT)
 
 SOLVED, PRIMAL_INFEASIBLE, DUAL_INFEASIBLE = "SOLVED", "PRIMAL_INFEASIBLE", "DUAL_INFEASIBLE"
 MAX_ITERATIONS, NUMERICAL_ERROR, INSUFFICIENT_PROGRESS, UNSOLVED = \
     "MAX_ITERATIONS", "NUMERICAL_ERROR", "INSUFFICIENT_PROGRESS", "UNSOLVED"
 ALMOST_SOLVED = "ALMOST_SOLVED"
+PRIMAL_DUAL, DUAL = 0, 1      # ScalingStrategy (types.jl:74); the codes hipkkt_kkt_set_nonsymmetric_scaling takes
 
 
 @dataclass
@@ -46,6 +53,8 @@ class IPMSettings:            # settings.jl:70-106 (code defaults)
     tol_infeas_rel: float = 1e-8
     tol_ktratio: float = 1e-6
     min_terminate_step_length: float = 1e-4
+    min_switch_step_length: float = 1e-1       # non-symmetric cones only (settings.jl)
+    linesearch_backtrack_step: float = 0.8
     # reduced-accuracy tolerances (settings.jl:88-93), used by info_post_process! after an error exit
     reduced_tol_gap_abs: float = 5e-5
     reduced_tol_gap_rel: float = 5e-5
@@ -107,6 +116,12 @@ class _Zero(_Cone):
     def step_length(self, dz, ds, z, s, amax):
         return amax
 
+    def unit_initialization(self):                       # coneops_zerocone.jl unit_initialization!
+        return np.zeros(self.n), np.zeros(self.n)
+
+    def compute_barrier(self, z, s, dz, ds, a):
+        return 0.0
+
 
 class _NN(_Cone):
     @property
@@ -149,6 +164,13 @@ class _NN(_Cone):
         if m.any():
             a = min(a, float(np.min(-s[m] / ds[m])))
         return a
+
+    def unit_initialization(self):
+        return np.ones(self.n), np.ones(self.n)
+
+    def compute_barrier(self, z, s, dz, ds, a):          # coneops_nncone.jl:172-189
+        with np.errstate(all="ignore"):
+            return -float(sum(_logsafe(v) for v in (s + a * ds) * (z + a * dz)))
 
 
 def _soc_res(v):
@@ -290,6 +312,15 @@ class _SOC(_Cone):
     def step_length(self, dz, ds, z, s, amax):
         return min(self._step(z, dz, amax), self._step(s, ds, amax))
 
+    def unit_initialization(self):
+        e = np.zeros(self.n)
+        e[0] = 1.0
+        return e.copy(), e
+
+    def compute_barrier(self, z, s, dz, ds, a):          # coneops_socone.jl:287-305
+        rs, rz = _soc_res(s + a * ds), _soc_res(z + a * dz)
+        return -_logsafe(rs * rz) / 2 if rs > 0 and rz > 0 else np.inf
+
 
 def _svec_to_mat(x, k):                                  # coneops_psdtrianglecone.jl:469-483
     M = np.zeros((k, k))
@@ -394,6 +425,402 @@ class _PSD(_Cone):
     def step_length(self, dz, ds, z, s, amax):           # :230-254
         return min(self._step_component(self._W(dz), amax), self._step_component(self._WinvT(ds), amax))
 
+    def unit_initialization(self):
+        e = np.zeros(self.n)
+        e[self.diag] = 1.0
+        return e.copy(), e
+
+    def compute_barrier(self, z, s, dz, ds, a):          # coneops_psdtrianglecone.jl:256-295
+        out = 0.0
+        for v in (z + a * dz, s + a * ds):
+            try:
+                L = np.linalg.cholesky(_svec_to_mat(v, self.k))
+            except np.linalg.LinAlgError:
+                return np.inf
+            out -= 2.0 * float(np.sum(np.log(np.diag(L))))
+        return out
+
+
+# ------------------------------------------------------------------------------------------
+#  non-symmetric cones: exponential and power (coneops_expcone.jl, coneops_powcone.jl,
+#  coneops_nonsymmetric_common.jl), restated term for term; the device kernel restates the same
+# ------------------------------------------------------------------------------------------
+_EPS = np.finfo(float).eps
+
+
+def _logsafe(v):                                         # mathutils.jl:12-18; log(0) is -Inf as well
+    return np.log(v) if v > 0 else -np.inf
+
+
+def _wright_omega(z):                                    # coneops_expcone.jl:412-468
+    if not z >= 0:
+        return np.nan                                    # the reference throws; outside the cone only
+    if z < 1 + np.pi:
+        zm1 = z - 1
+        p = zm1
+        w = 1 + 0.5 * p
+        p *= zm1
+        w += (1 / 16.0) * p
+        p *= zm1
+        w -= (1 / 192.0) * p
+        p *= zm1
+        w -= (1 / 3072.0) * p
+        p *= zm1
+        w += (13 / 61440.0) * p
+    else:
+        logz = _logsafe(z)
+        zinv = 1.0 / z
+        w = z - logz
+        q = logz * zinv
+        w += q
+        q *= zinv
+        w += q * (logz / 2 - 1)
+        # the reference's next line computes q*zinv and drops it (:451), so the cubic term is
+        # weighted by log(z)/z^2; the two refinement rounds absorb the difference
+        w += q * (logz * logz / 3. - (3 / 2.) * logz + 1)
+    r = z - w - _logsafe(w)
+    for _ in range(2):
+        wp1 = w + 1
+        t = wp1 * (wp1 + (2. * r) / 3.0)
+        w *= 1 + (r / wp1) * (t - 0.5 * r) / (t - r)
+        r = (2 * w * w - 8 * w - 1) / (72.0 * (wp1 * wp1 * wp1 * wp1 * wp1 * wp1)) * r * r * r * r
+    return w
+
+
+def _newton_raphson_onesided(x0, f0, f1):                # coneops_nonsymmetric_common.jl:170-193
+    x, it = x0, 0
+    while it < 100:
+        it += 1
+        dfdx = f1(x)
+        dx = -f0(x) / dfdx
+        if (dx < _EPS) or (abs(dx / x) < np.sqrt(_EPS)) or (abs(dfdx) < _EPS):
+            break
+        x += dx
+    return x
+
+
+def _newton_raphson_powcone(s3, phi, a):                 # coneops_powcone.jl:449-478
+    x0 = -1.0 / s3 + (2 * s3 + np.sqrt(phi * phi / s3 / s3 + 3 * phi)) / (phi - s3 * s3)
+    t0 = -2 * a * _logsafe(a) - 2 * (1 - a) * _logsafe(1 - a)
+
+    def f0(x):
+        t1 = x * x; t2 = 2 * x / s3
+        return (2 * a * _logsafe(2 * a * t1 + (1 + a) * t2) + 2 * (1 - a) * _logsafe(2 * (1 - a) * t1 + (2 - a) * t2)
+                - _logsafe(phi) - _logsafe(t1 + t2) - 2 * _logsafe(t2) + t0)
+
+    def f1(x):
+        t1 = x * x; t2 = x * 2 / s3
+        return (2 * a * a / (a * x + (1 + a) / s3) + 2 * (1 - a) * (1 - a) / ((1 - a) * x + (2 - a) / s3)
+                - 2 * (x + 1 / s3) / (t1 + t2))
+
+    # The one-sided iteration needs f0(x0) > 0 (x0 left of the root), as the reference's own comment says (:455).  Its
+    # x0 was derived for a differently scaled barrier and lies to the RIGHT of the root for alpha well away from 1/2
+    # (alpha = 0.1, s = (1.03, 3.90, -2.28): x0 = 1.485, root 1.197), where the first Newton step is negative, the
+    # iteration halts at once and g(s) comes out up to 26 % off.  f0 -> +Inf as x -> 0+, so halving reaches the left
+    # side; this is the one deliberate departure from the reference, and the device kernel makes the same one.
+    for _ in range(64):
+        if f0(x0) > 0:
+            break
+        x0 *= 0.5
+    return _newton_raphson_onesided(x0, f0, f1)
+
+
+def _chol3_factor(A):                                    # mathutils.jl:427-451
+    L = np.zeros((3, 3))
+    t = A[0, 0]
+    if not t > 0:
+        return None
+    L[0, 0] = np.sqrt(t)
+    L[1, 0] = A[1, 0] / L[0, 0]
+    t = A[1, 1] - L[1, 0] * L[1, 0]
+    if not t > 0:
+        return None
+    L[1, 1] = np.sqrt(t)
+    L[2, 0] = A[2, 0] / L[0, 0]
+    L[2, 1] = (A[2, 1] - L[1, 0] * L[2, 0]) / L[1, 1]
+    t = A[2, 2] - L[2, 0] * L[2, 0] - L[2, 1] * L[2, 1]
+    if not t > 0:
+        return None
+    L[2, 2] = np.sqrt(t)
+    return L
+
+
+def _chol3_solve(L, b):                                  # mathutils.jl:455-466
+    c1 = b[0] / L[0, 0]
+    c2 = (b[1] * L[0, 0] - b[0] * L[1, 0]) / (L[0, 0] * L[1, 1])
+    c3 = (b[2] * L[0, 0] * L[1, 1] - b[1] * L[0, 0] * L[2, 1] + b[0] * L[1, 0] * L[2, 1] - b[0] * L[1, 1] * L[2, 0]) \
+        / (L[0, 0] * L[1, 1] * L[2, 2])
+    x1 = (c1 * L[1, 1] * L[2, 2] - c2 * L[1, 0] * L[2, 2] + c3 * L[1, 0] * L[2, 1] - c3 * L[1, 1] * L[2, 0]) \
+        / (L[0, 0] * L[1, 1] * L[2, 2])
+    x2 = (c2 * L[2, 2] - c3 * L[2, 1]) / (L[1, 1] * L[2, 2])
+    x3 = c3 / L[2, 2]
+    return np.array([x1, x2, x3])
+
+
+class _NonSym(_Cone):
+    """What the exponential and the power cone share (coneops_nonsymmetric_common.jl)."""
+    degree = 3
+    symmetric = False
+
+    def update_scaling(self, s, z, mu, strategy):        # update_scaling!: dual gradient and Hessian, then Hs
+        with np.errstate(all="ignore"):
+            s, z = np.asarray(s, dtype=np.float64), np.asarray(z, dtype=np.float64)
+            self.grad, self.H_dual = self.dual_grad_H(z)
+            if strategy == DUAL:
+                self.Hs = mu * self.H_dual
+                self.used_primal_dual = False
+            else:
+                self._primal_dual_scaling(s, z)
+            self.z = z.copy()
+        return bool(np.all(np.isfinite(self.Hs)))
+
+    def scaling_guards(self, s, z):
+        """(de1, de2, <s,z>, <ds,dz>) of use_primal_dual_scaling, for tests that must know how far a point is
+        from the branch."""
+        with np.errstate(all="ignore"):
+            st, H = self.dual_grad_H(z)
+            zt = self.gradient_primal(s)
+            dot_sz = z @ s
+            mu = dot_sz / 3
+            mut = (zt @ st) / 3
+            return mu * mut - 1, zt @ H @ zt - 3 * mut * mut, dot_sz, (s + mu * st) @ (z + mu * zt)
+
+    def _primal_dual_scaling(self, s, z):                # use_primal_dual_scaling, :82-164
+        st, H = self.grad, self.H_dual
+        zt = self.gradient_primal(s)
+        dot_sz = z[0] * s[0] + z[1] * s[1] + z[2] * s[2]
+        mu = dot_sz / 3
+        mut = (zt[0] * st[0] + zt[1] * st[1] + zt[2] * st[2]) / 3
+        dls = s + mu * st
+        dlz = z + mu * zt
+        dot_dsz = dls[0] * dlz[0] + dls[1] * dlz[1] + dls[2] * dlz[2]
+        de1 = mu * mut - 1
+        Hzt = np.array([H[i, 0] * zt[0] + H[i, 1] * zt[1] + H[i, 2] * zt[2] for i in range(3)])
+        de2 = (zt[0] * Hzt[0] + zt[1] * Hzt[1] + zt[2] * Hzt[2]) - 3 * mut * mut
+        if abs(de1) > np.sqrt(_EPS) and abs(de2) > _EPS and dot_sz > 0 and dot_dsz > 0:
+            tmp = np.array([mut * st[i] - H[i, 0] * zt[0] - H[i, 1] * zt[1] - H[i, 2] * zt[2] for i in range(3)])
+            W = H.copy()
+            for i in range(3):
+                for j in range(3):
+                    W[i, j] -= st[i] * st[j] / 3 + tmp[i] * tmp[j] / de2
+            t = mu * np.sqrt(np.sum(W * W))
+            ax = np.array([z[1] * zt[2] - z[2] * zt[1], z[2] * zt[0] - z[0] * zt[2], z[0] * zt[1] - z[1] * zt[0]])
+            ax = ax / np.sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2])
+            Hs = np.empty((3, 3))
+            for i in range(3):
+                for j in range(i, 3):
+                    Hs[i, j] = s[i] * s[j] / dot_sz + dls[i] * dls[j] / dot_dsz + t * ax[i] * ax[j]
+                    Hs[j, i] = Hs[i, j]
+            self.Hs = Hs
+            self.used_primal_dual = True
+        else:
+            self.Hs = mu * H                              # on the central path: mu H*(z) with the local mu
+            self.used_primal_dual = False
+
+    def get_Hs(self):                                    # pack_triu, mathutils.jl:402-412
+        return np.array([self.Hs[r, c] for c in range(3) for r in range(c + 1)])
+
+    def mul_Hs(self, x):
+        H = self.Hs
+        return np.array([H[i, 0] * x[0] + H[i, 1] * x[1] + H[i, 2] * x[2] for i in range(3)])
+
+    def affine_ds(self, s):
+        return s.copy()
+
+    def combined_ds_shift(self, dz, ds, sigma_mu):
+        with np.errstate(all="ignore"):
+            return self.grad * sigma_mu - self.higher_correction(ds, dz)
+
+    def ds_from_dz_offset(self, ds, z):
+        return ds.copy()
+
+    def _backtrack(self, dq, q, a, amin, step, in_cone):  # backtrack_search, :5-34
+        while True:
+            if in_cone(q + a * dq):
+                break
+            a *= step
+            if a < amin:
+                a = 0.0
+                break
+        return a
+
+    def step_length(self, dz, ds, z, s, amax, st=None):
+        st = st or IPMSettings()
+        step, amin = st.linesearch_backtrack_step, st.min_terminate_step_length
+        with np.errstate(all="ignore"):
+            az = self._backtrack(dz, z, amax, amin, step, self.is_dual_feasible)
+            as_ = self._backtrack(ds, s, amax, amin, step, self.is_primal_feasible)
+        return min(az, as_)
+
+    def compute_barrier(self, z, s, dz, ds, a):
+        with np.errstate(all="ignore"):
+            return self.barrier_dual(z + a * dz) + self.barrier_primal(s + a * ds)
+
+
+class _Exp(_NonSym):
+    """Primal: s3 >= s2 exp(s1/s2), s2, s3 > 0.  Dual: z3 >= -z1 exp(z2/z1 - 1), z3 > 0, z1 < 0.
+    Dual barrier f*(z) = -log(z2 - z1 - z1 log(z3/-z1)) - log(-z1) - log(z3)."""
+
+    def unit_initialization(self):                       # coneops_expcone.jl:36-52
+        s = np.array([-1.051383945322714, 0.556409619469370, 1.258967884768947])
+        return s.copy(), s
+
+    def barrier_dual(self, z):
+        l = _logsafe(-z[2] / z[0])
+        return -_logsafe(-z[2] * z[0]) - _logsafe(z[1] - z[0] - z[0] * l)
+
+    def barrier_primal(self, s):
+        w = _wright_omega(1 - s[0] / s[1] - _logsafe(s[1] / s[2]))
+        w = (w - 1) * (w - 1) / w
+        return -_logsafe(w) - 2 * _logsafe(s[1]) - _logsafe(s[2]) - 3
+
+    def is_primal_feasible(self, s):
+        return bool(s[2] > 0 and s[1] > 0 and s[1] * _logsafe(s[2] / s[1]) - s[0] > 0)
+
+    def is_dual_feasible(self, z):
+        return bool(z[2] > 0 and z[0] < 0 and z[1] - z[0] - z[0] * _logsafe(-z[2] / z[0]) > 0)
+
+    def gradient_primal(self, s):                        # :284-297
+        w = _wright_omega(1 - s[0] / s[1] - _logsafe(s[1] / s[2]))
+        g1 = 1.0 / ((w - 1.0) * s[1])
+        g2 = g1 + g1 * _logsafe(w * s[1] / s[2]) - 1.0 / s[1]
+        g3 = w / ((1.0 - w) * s[2])
+        return np.array([g1, g2, g3])
+
+    def dual_grad_H(self, z):                            # update_dual_grad_H, :370-399
+        l = _logsafe(-z[2] / z[0])
+        r = -z[0] * l - z[0] + z[1]
+        c2 = 1.0 / r
+        grad = np.array([c2 * l - 1 / z[0], -c2, (c2 * z[0] - 1) / z[2]])
+        H = np.empty((3, 3))
+        H[0, 0] = (r * r - z[0] * r + l * l * z[0] * z[0]) / (r * z[0] * z[0] * r)
+        H[0, 1] = H[1, 0] = -l / (r * r)
+        H[1, 1] = 1 / (r * r)
+        H[0, 2] = H[2, 0] = (z[1] - z[0]) / (r * r * z[2])
+        H[1, 2] = H[2, 1] = -z[0] / (r * r * z[2])
+        H[2, 2] = (r * r - z[0] * r + z[0] * z[0]) / (r * r * z[2] * z[2])
+        return grad, H
+
+    def higher_correction(self, ds, v):                  # :319-366
+        z = self.z
+        L = _chol3_factor(self.H_dual)
+        if L is None:
+            return np.zeros(3)
+        u = _chol3_solve(L, ds)
+        eta = np.zeros(3)
+        eta[1] = 1.0
+        eta[2] = -z[0] / z[2]
+        eta[0] = _logsafe(eta[2])
+        psi = z[0] * eta[0] - z[0] + z[1]
+        dpu = eta @ u
+        dpv = eta @ v
+        coef = ((u[0] * (v[0] / z[0] - v[2] / z[2]) + u[2] * (z[0] * v[2] / z[2] - v[0]) / z[2]) * psi
+                - 2 * dpu * dpv) / (psi * psi * psi)
+        eta *= coef
+        ip2 = 1.0 / psi / psi
+        eta[0] += (1 / psi - 2 / z[0]) * u[0] * v[0] / (z[0] * z[0]) - u[2] * v[2] / (z[2] * z[2]) / psi \
+            + dpu * ip2 * (v[0] / z[0] - v[2] / z[2]) + dpv * ip2 * (u[0] / z[0] - u[2] / z[2])
+        eta[2] += 2 * (z[0] / psi - 1) * u[2] * v[2] / (z[2] * z[2] * z[2]) \
+            - (u[2] * v[0] + u[0] * v[2]) / (z[2] * z[2]) / psi \
+            + dpu * ip2 * (z[0] * v[2] / (z[2] * z[2]) - v[0] / z[2]) \
+            + dpv * ip2 * (z[0] * u[2] / (z[2] * z[2]) - u[0] / z[2])
+        return eta / 2
+
+
+class _Pow(_NonSym):
+    """Primal: s1^a s2^(1-a) >= |s3|, s1, s2 >= 0.  Dual: (z1/a)^a (z2/(1-a))^(1-a) >= |z3|.
+    Dual barrier f*(z) = -log((z1/a)^2a (z2/(1-a))^(2-2a) - z3^2) - (1-a) log z1 - a log z2."""
+
+    def __init__(self, spec, off):
+        super().__init__(spec, off)
+        self.alpha = float(spec.alpha)
+
+    def unit_initialization(self):                       # coneops_powcone.jl:36-54
+        a = self.alpha
+        s = np.array([np.sqrt(1 + a), np.sqrt(1 + (1 - a)), 0.0])
+        return s.copy(), s
+
+    def barrier_dual(self, z):
+        a = self.alpha
+        return -_logsafe((z[0] / a) ** (2 * a) * (z[1] / (1 - a)) ** (2 - 2 * a) - z[2] * z[2]) \
+            - (1 - a) * _logsafe(z[0]) - a * _logsafe(z[1])
+
+    def barrier_primal(self, s):
+        a = self.alpha
+        g = self.gradient_primal(s)
+        return _logsafe((-g[0] / a) ** (2 * a) * (-g[1] / (1 - a)) ** (2 - 2 * a) - g[2] * g[2]) \
+            + (1 - a) * _logsafe(-g[0]) + a * _logsafe(-g[1]) - 3
+
+    def is_primal_feasible(self, s):
+        a = self.alpha
+        return bool(s[0] > 0 and s[1] > 0 and
+                    np.exp(2 * a * _logsafe(s[0]) + 2 * (1 - a) * _logsafe(s[1])) - s[2] * s[2] > 0)
+
+    def is_dual_feasible(self, z):
+        a = self.alpha
+        return bool(z[0] > 0 and z[1] > 0 and
+                    np.exp(2 * a * _logsafe(z[0] / a) + 2 * (1 - a) * _logsafe(z[1] / (1 - a))) - z[2] * z[2] > 0)
+
+    def gradient_primal(self, s):                        # :288-316
+        a = self.alpha
+        s = np.asarray(s, dtype=np.float64)
+        phi = s[0] ** (2 * a) * s[1] ** (2 - 2 * a)
+        g = np.zeros(3)
+        abs_s = abs(s[2])
+        if abs_s > _EPS:
+            g[2] = _newton_raphson_powcone(abs_s, phi, a)
+            if s[2] < 0:
+                g[2] = -g[2]
+            g[0] = -(a * g[2] * s[2] + 1 + a) / s[0]
+            g[1] = -((1 - a) * g[2] * s[2] + 2 - a) / s[1]
+        else:
+            g[2] = 0.0
+            g[0] = -(1 + a) / s[0]
+            g[1] = -(2 - a) / s[1]
+        return g
+
+    def dual_grad_H(self, z):                            # update_dual_grad_H, :408-440
+        a = self.alpha
+        z = np.asarray(z, dtype=np.float64)
+        phi = (z[0] / a) ** (2 * a) * (z[1] / (1 - a)) ** (2 - 2 * a)
+        psi = phi - z[2] * z[2]
+        g = np.array([2 * a * phi / (z[0] * psi), 2 * (1 - a) * phi / (z[1] * psi), -2 * z[2] / psi])
+        H = np.empty((3, 3))
+        H[0, 0] = g[0] * g[0] - 2 * a * (2 * a - 1) * phi / (z[0] * z[0] * psi) + (1 - a) / (z[0] * z[0])
+        H[0, 1] = H[1, 0] = g[0] * g[1] - 4 * a * (1 - a) * phi / (z[0] * z[1] * psi)
+        H[1, 1] = g[1] * g[1] - 2 * (1 - a) * (1 - 2 * a) * phi / (z[1] * z[1] * psi) + a / (z[1] * z[1])
+        H[0, 2] = H[2, 0] = g[0] * g[2]
+        H[1, 2] = H[2, 1] = g[1] * g[2]
+        H[2, 2] = g[2] * g[2] + 2 / psi
+        grad = np.array([-2 * a * phi / (z[0] * psi) - (1 - a) / z[0],
+                         -2 * (1 - a) * phi / (z[1] * psi) - a / z[1],
+                         2 * z[2] / psi])
+        return grad, H
+
+    def higher_correction(self, ds, v):                  # :329-404
+        z, a = self.z, self.alpha
+        L = _chol3_factor(self.H_dual)
+        if L is None:
+            return np.zeros(3)
+        u = _chol3_solve(L, ds)
+        phi = (z[0] / a) ** (2 * a) * (z[1] / (1 - a)) ** (2 - 2 * a)
+        psi = phi - z[2] * z[2]
+        eta = np.array([2 * a * phi / z[0], 2 * (1 - a) * phi / z[1], -2 * z[2]])
+        H11 = 2 * a * (2 * a - 1) * phi / (z[0] * z[0])
+        H12 = 4 * a * (1 - a) * phi / (z[0] * z[1])
+        H22 = 2 * (1 - a) * (1 - 2 * a) * phi / (z[1] * z[1])
+        dpu = eta @ u
+        dpv = eta @ v
+        Hv = np.array([H11 * v[0] + H12 * v[1], H12 * v[0] + H22 * v[1], -2 * v[2]])
+        coef = ((u @ Hv) * psi - 2 * dpu * dpv) / (psi * psi * psi)
+        coef2 = 4 * a * (2 * a - 1) * (1 - a) * phi * (u[0] / z[0] - u[1] / z[1]) * (v[0] / z[0] - v[1] / z[1]) / psi
+        ip2 = 1 / psi / psi
+        e0 = coef * eta[0] - 2 * (1 - a) * u[0] * v[0] / (z[0] * z[0] * z[0]) + coef2 / z[0] + Hv[0] * dpu * ip2
+        e1 = coef * eta[1] - 2 * a * u[1] * v[1] / (z[1] * z[1] * z[1]) - coef2 / z[1] + Hv[1] * dpu * ip2
+        e2 = coef * eta[2] + Hv[2] * dpu * ip2
+        Hu = np.array([H11 * u[0] + H12 * u[1], H12 * u[0] + H22 * u[1], -2 * u[2]])
+        return (np.array([e0, e1, e2]) + Hu * dpv * ip2) / 2
+
 
 def adopt_device_scaling(cones, dev_scaling):
     """Give the host PSD cone objects the (R, Rinv, lambda) triples `HipKKTSolver.scaling()` returns."""
@@ -438,8 +865,13 @@ def _make_cones(specs):
             out.append(_SOC(c, off))
         elif isinstance(c, PSDTriangleConeT):
             out.append(_PSD(c, off))
+        elif isinstance(c, ExponentialConeT):
+            out.append(_Exp(c, off))
+        elif isinstance(c, PowerConeT):
+            out.append(_Pow(c, off))
         else:
-            raise NotImplementedError("the IPM test driver covers Zero, Nonnegative, SecondOrder and PSDTriangle cones")
+            raise NotImplementedError("the IPM test driver covers Zero, Nonnegative, SecondOrder, PSDTriangle, "
+                                      "Exponential and Power cones")
         off += c.numel
     return out
 
@@ -522,20 +954,32 @@ def solve(P, q, A, b, cone_specs, backend, settings=None):
         ir_total += backend.last_ir_iterations
         return ok, xo, zo
 
-    # ---- default start (symmetric cones): solver.jl:383-404
+    # ---- default start: solver.jl:383-404
     x = np.zeros(n); s = np.zeros(m); z = np.zeros(m)
     system = getattr(backend, "system", None)          # device-resident DefaultKKTSystem (level C), if the backend has one
     if system is not None:
         system.init(q, b)
-    ok = backend.update_identity()
-    if system is not None:
+    # With a non-symmetric cone the start is the unit point on the central ray (variables_unit_initialization!):
+    # no identity update and no initial-point solve is issued.  `strategy` is the reference's `scaling` variable
+    # (solver.jl:221); it and its three checkpoints (:453-504) exist only on that path.
+    nonsym = any(isinstance(c, _NonSym) for c in cones)
+    strategy = PRIMAL_DUAL
+    x2 = z2 = None
+    if nonsym:
+        for c in cones:
+            z[c.rng], s[c.rng] = c.unit_initialization()
+    else:
+        ok = backend.update_identity()
+    if nonsym:
+        pass
+    elif system is not None:
         ok_c = system.solve_constant_rhs()
         ok1, x, s, z = system.solve_initial_point()
         ok2 = True
         x2 = z2 = None
     else:
         ok_c, x2, z2 = ksolve(-q, b)                   # kkt_update! also solves the constant RHS
-    if system is not None:
+    if system is not None or nonsym:
         pass
     elif Pt.nnz == 0:                                  # kktsystem.jl:101-120 (LP initialisation)
         ok1, x, s = ksolve(np.zeros(n), b)
@@ -563,8 +1007,9 @@ def solve(P, q, A, b, cone_specs, backend, settings=None):
             for c in cones:
                 c.unit_shift(v[c.rng], a, primal)
 
-    shift_to_interior(s, True)
-    shift_to_interior(z, False)
+    if not nonsym:
+        shift_to_interior(s, True)
+        shift_to_interior(z, False)
     tau, kappa = 1.0, 1.0
 
     it, alpha, sigma = 0, 0.0, 1.0
@@ -618,13 +1063,20 @@ def solve(P, q, A, b, cone_specs, backend, settings=None):
         if status != UNSOLVED:
             if status == INSUFFICIENT_PROGRESS and prev_vars is not None:
                 x, s, z, tau, kappa = prev_vars
+            if status == INSUFFICIENT_PROGRESS and nonsym and strategy == PRIMAL_DUAL:
+                # _strategy_checkpoint_insufficient_progress: go on from the previous iterate with dual scaling
+                strategy, status = DUAL, UNSOLVED
+                continue
             break
         # ---- scale cones, KKT update + constant-RHS solve (solver.jl:258-280, kktsystem.jl:62-92)
-        if not all(c.update_scaling(s[c.rng].copy(), z[c.rng].copy()) for c in cones):
+        if not all(c.update_scaling(s[c.rng].copy(), z[c.rng].copy(), mu, strategy) if isinstance(c, _NonSym)
+                   else c.update_scaling(s[c.rng].copy(), z[c.rng].copy()) for c in cones):
             status = NUMERICAL_ERROR
             break
         it += 1
         aff_step = None
+        if nonsym and system is not None:
+            backend.ks.set_nonsymmetric_scaling(strategy, mu)      # host-only; every update route below picks it up
         if system is not None and getattr(backend, "batch_affine", False):
             # kkt_update! and the affine kkt_solve! as ONE call: the constant and the affine right-hand side do not
             # depend on each other (kktsystem.jl:87-88 vs :170-171; the affine step does not read rhs.s, :157-158),
@@ -644,7 +1096,7 @@ def solve(P, q, A, b, cone_specs, backend, settings=None):
             if ok and any(isinstance(c, _PSD) and c.n for c in cones):
                 adopt_device_scaling(cones, backend.ks.scaling()[1])
         else:
-            ok = backend.update(s, z)
+            ok = backend.update(s, z, mu=mu, strategy=strategy) if nonsym else backend.update(s, z)
             if ok:
                 ok, x2, z2 = ksolve(-q, b)
 
@@ -676,9 +1128,36 @@ def solve(P, q, A, b, cone_specs, backend, settings=None):
             at = -tau / dtau if dtau < 0 else np.finfo(float).max
             ak = -kappa / dkappa if dkappa < 0 else np.finfo(float).max
             a = min(at, ak, 1.0)
+            if not nonsym:
+                for c in cones:
+                    a = min(a, c.step_length(dz[c.rng], ds[c.rng], z[c.rng], s[c.rng], a))
+                return a * st.max_step_fraction if combined else a
+            # coneops_compositecone.jl:205-243: symmetric cones first, then back off from the full step so that the
+            # logarithms of the non-symmetric cones do not fail right at the boundary, then those cones
             for c in cones:
-                a = min(a, c.step_length(dz[c.rng], ds[c.rng], z[c.rng], s[c.rng], a))
-            return a * st.max_step_fraction if combined else a
+                if not isinstance(c, _NonSym):
+                    a = min(a, c.step_length(dz[c.rng], ds[c.rng], z[c.rng], s[c.rng], a))
+            a = min(a, 1.0 - np.sqrt(_EPS))
+            for c in cones:
+                if isinstance(c, _NonSym):
+                    a = min(a, c.step_length(dz[c.rng], ds[c.rng], z[c.rng], s[c.rng], a, st))
+            if not combined:
+                return a
+            a *= st.max_step_fraction
+            if strategy == DUAL:                       # solver_backtrack_step_to_barrier, solver.jl:407-442
+                for _ in range(50):
+                    if barrier(dz, ds, dtau, dkappa, a) < 1.0:
+                        break
+                    a *= st.linesearch_backtrack_step
+            return a
+
+        def barrier(dz, ds, dtau, dkappa, a):                                              # variables.jl:46-72
+            ct, ck = tau + a * dtau, kappa + a * dkappa
+            mu_a = ((z + a * dz) @ (s + a * ds) + ct * ck) / (degree + 1)
+            out = (degree + 1) * _logsafe(mu_a) - _logsafe(ct) - _logsafe(ck)
+            for c in cones:
+                out += c.compute_barrier(z[c.rng], s[c.rng], dz[c.rng], ds[c.rng], a)
+            return out
 
         step = None
         if ok:
@@ -697,11 +1176,17 @@ def solve(P, q, A, b, cone_specs, backend, settings=None):
             ok, step = kkt_solve((1 - sigma) * rx, (1 - sigma) * rz, rhs_s, (1 - sigma) * rtau,
                                  -sigma * mu + mcorr * dtau * dkappa + tau * kappa, False)
         if not ok:
-            status = NUMERICAL_ERROR
             alpha = 0.0
+            if nonsym and strategy == PRIMAL_DUAL:     # _strategy_checkpoint_numerical_error
+                strategy = DUAL
+                continue
+            status = NUMERICAL_ERROR
             break
         dx, dz, ds, dtau, dkappa = step
         alpha = step_length(dz, ds, dtau, dkappa, True)
+        if nonsym and strategy == PRIMAL_DUAL and alpha < st.min_switch_step_length:
+            strategy, alpha = DUAL, 0.0                # _strategy_checkpoint_small_step
+            continue
         if alpha <= max(0.0, st.min_terminate_step_length):
             status = INSUFFICIENT_PROGRESS
             alpha = 0.0
@@ -755,7 +1240,9 @@ class HipBackend:
     def update_identity(self):
         return self.ks.kktsolver_update(*identity_scaling_data(self.specs))
 
-    def update(self, s, z):
+    def update(self, s, z, mu=None, strategy=None):
+        if strategy is not None:                       # only a problem with a non-symmetric cone passes these
+            self.ks.set_nonsymmetric_scaling(strategy, mu)
         return self.ks.kktsolver_update_from_sz(s, z)
 
     def kktsolver_setrhs(self, rx, rz):

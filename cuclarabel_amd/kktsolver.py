@@ -14,7 +14,7 @@ import scipy.sparse as sp
 
 from . import _lib
 from ._lib import check, f64, i64, ptr
-from .cones import cone_kinds_dims
+from .cones import cone_kinds_dims, cone_params, KIND_EXP, KIND_POW
 
 
 class LinearSolverInfo:
@@ -48,9 +48,15 @@ class HipKKTSolver:
         self._h = C.c_void_p()
         Pp, Pi, Px = i64(P.indptr), i64(P.indices), f64(P.data)
         Ap, Ai, Ax = i64(A.indptr), i64(A.indices), f64(A.data)
-        rc = L.hipkkt_kkt_create(C.byref(self._h), self.n, self.m, ptr(Pp), ptr(Pi), ptr(Px),
-                                 ptr(Ap), ptr(Ai), ptr(Ax), len(self.cones), ptr(kinds), ptr(dims),
-                                 C.byref(self.settings), 0)
+        if any(c.kind == KIND_POW for c in self.cones):          # a power cone's alpha travels through _ex only
+            params = cone_params(self.cones)
+            rc = L.hipkkt_kkt_create_ex(C.byref(self._h), self.n, self.m, ptr(Pp), ptr(Pi), ptr(Px),
+                                        ptr(Ap), ptr(Ai), ptr(Ax), len(self.cones), ptr(kinds), ptr(dims), ptr(params),
+                                        C.byref(self.settings), 0)
+        else:
+            rc = L.hipkkt_kkt_create(C.byref(self._h), self.n, self.m, ptr(Pp), ptr(Pi), ptr(Px),
+                                     ptr(Ap), ptr(Ai), ptr(Ax), len(self.cones), ptr(kinds), ptr(dims),
+                                     C.byref(self.settings), 0)
         if not check(rc, "hipkkt_kkt_create"):
             raise _lib.HipKKTError("hipkkt_kkt_create reported a numeric failure")
         self._nnzP, self._nnzA = P.nnz, A.nnz
@@ -217,6 +223,19 @@ class HipKKTSolver:
                 o += k * k
             off += c.numel
         return lam[:self.m], out
+
+    def set_nonsymmetric_scaling(self, strategy, mu=0.0):
+        """How the next device-side scaling treats exponential / power cones: strategy 0 primal-dual (mu unused),
+        1 dual (Hs = mu H*(z)).  Host-only; a no-op on a handle without such cones."""
+        return check(_lib.lib().hipkkt_kkt_set_nonsymmetric_scaling(self._h, int(strategy), float(mu)),
+                     "hipkkt_kkt_set_nonsymmetric_scaling")
+
+    def nonsymmetric(self):
+        """(grad (k, 3), H_dual (k, 3, 3)) of the k exponential / power cones, in cone order, after a device-side scaling."""
+        k = sum(1 for c in self.cones if c.kind in (KIND_EXP, KIND_POW))
+        grad, H = np.zeros(max(3 * k, 1)), np.zeros(max(9 * k, 1))
+        check(_lib.lib().hipkkt_kkt_get_nonsymmetric(self._h, ptr(grad), ptr(H)), "hipkkt_kkt_get_nonsymmetric")
+        return grad[:3 * k].reshape(k, 3), H[:9 * k].reshape(k, 3, 3)
 
     def scaling_w(self):
         """(w (m), eta (per cone)) of the device's NT scaling."""

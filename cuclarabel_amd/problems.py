@@ -10,7 +10,7 @@ from dataclasses import dataclass, field
 import numpy as np
 import scipy.sparse as sp
 
-from .cones import (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT,
+from .cones import (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT, ExponentialConeT,
                     total_numel)
 
 
@@ -383,3 +383,35 @@ ZOO_SMALL = [
     ("lp_transport_small", lambda: zoo_lp_transport(20, 30)),
     ("equality_2k", lambda: zoo_equality_heavy(n=2000)),
 ]
+
+
+def entropy_maximization(ncones=20_000, nrows=4, seed=3001):
+    """Entropy maximisation over the simplex with a few random equality rows: one exponential cone per variable,
+    so the cone count grows with the data.
+
+        maximise  -sum_i x_i log x_i   s.t.  sum x = 1,  F x = F x_feas,  x >= 0
+        as        minimise -sum_i t_i  s.t.  (t_i, x_i, 1) in K_exp   (x_i exp(t_i / x_i) <= 1)
+
+    Variables (x, t), n = 2 ncones; rows: 1 + nrows of the zero cone, then three per exponential cone.
+    (s0, z0) is the unit-initialisation point of the reference (coneops_expcone.jl:36-52), x0 = 0."""
+    rng = np.random.default_rng(seed)
+    N = int(ncones)
+    x_feas = rng.dirichlet(np.ones(N))
+    F = rng.standard_normal((nrows, N))
+    Aeq = sp.hstack([sp.csr_matrix(np.vstack([np.ones((1, N)), F])), sp.csr_matrix((1 + nrows, N))])
+    beq = np.concatenate([[1.0], F @ x_feas])
+    i = np.arange(N)
+    rows = np.concatenate([3 * i, 3 * i + 1])            # s = (t_i, x_i, 1)
+    cols = np.concatenate([N + i, i])
+    Aexp = sp.csr_matrix((-np.ones(2 * N), (rows, cols)), shape=(3 * N, 2 * N))
+    bexp = np.zeros(3 * N)
+    bexp[2::3] = 1.0
+    A = _csc(sp.vstack([Aeq, Aexp]))
+    b = np.concatenate([beq, bexp])
+    q = np.concatenate([np.zeros(N), -np.ones(N)])
+    P = _triu_csc(sp.csc_matrix((2 * N, 2 * N)))
+    cones = [ZeroConeT(1 + nrows)] + [ExponentialConeT() for _ in range(N)]
+    unit = np.array([-1.051383945322714, 0.556409619469370, 1.258967884768947])
+    s0 = np.concatenate([np.zeros(1 + nrows), np.tile(unit, N)])
+    return Problem(f"entropy_{N}", P, q, A, b, cones, s0, s0.copy(), np.zeros(2 * N),
+                   meta=dict(seed=seed, ncones=N, nrows=nrows))

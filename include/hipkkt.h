@@ -49,6 +49,14 @@ extern "C" {
 #define HIPKKT_CONE_NN 1
 #define HIPKKT_CONE_SOC 2
 #define HIPKKT_CONE_PSD 3
+/* the non-symmetric cones (coneops_expcone.jl, coneops_powcone.jl): dims[] must be 3.  A power cone's alpha comes
+ * through hipkkt_kkt_create_ex. */
+#define HIPKKT_CONE_EXP 4
+#define HIPKKT_CONE_POW 5
+
+/* scaling strategy of the non-symmetric cones (types.jl:74) */
+#define HIPKKT_SCALING_PRIMAL_DUAL 0
+#define HIPKKT_SCALING_DUAL 1
 
 /* fill-reducing ordering */
 #define HIPKKT_ORDER_AMD 0      /* approximate minimum degree (what the reference asks QDLDL for) */
@@ -161,6 +169,16 @@ int hipkkt_kkt_create(hipkkt_kkt_t *out, int64_t n, int64_t m,
                       const int64_t *Acolptr, const int64_t *Arowval, const double *Anzval,
                       int64_t ncones, const int32_t *cone_kinds, const int64_t *cone_dims,
                       const hipkkt_settings *settings, int index_base);
+/* hipkkt_kkt_create plus one double per cone: alpha of a power cone, in (0, 1); ignored for every other kind.
+ * cone_params may be NULL when the list holds no power cone.  hipkkt_kkt_create forwards here with NULL: it takes
+ * exponential cones and refuses power cones.
+ * An exponential or power cone is a dense 3 x 3 block of K with 6 packed-triu Hs entries -- the layout of a
+ * second-order cone of dimension 3 -- with no expansion columns and Dsigns -1 on its rows. */
+int hipkkt_kkt_create_ex(hipkkt_kkt_t *out, int64_t n, int64_t m,
+                         const int64_t *Pcolptr, const int64_t *Prowval, const double *Pnzval,
+                         const int64_t *Acolptr, const int64_t *Arowval, const double *Anzval,
+                         int64_t ncones, const int32_t *cone_kinds, const int64_t *cone_dims,
+                         const double *cone_params, const hipkkt_settings *settings, int index_base);
 void hipkkt_kkt_destroy(hipkkt_kkt_t h);
 int hipkkt_kkt_info(hipkkt_kkt_t h, hipkkt_info *info);
 
@@ -273,6 +291,9 @@ int hipkkt_kkt_system_update_cones(hipkkt_kkt_t h, const double *Hsblocks, const
  * lazy mode the call only enqueues, like hipkkt_kkt_system_update; the arrays may be reused when it returns. */
 int hipkkt_kkt_system_update_scaling(hipkkt_kkt_t h, const double *w, const double *eta, const double *lambda,
                                      const double *psd_R, const double *psd_Rinv);
+/* (w, eta, lambda, R, Rinv cannot carry the 3 x 3 block of an exponential or power cone: on a handle that holds one
+ * the call above returns HIPKKT_ERR_ARG; hipkkt_kkt_system_update_cones, whose Hs blocks are the whole scaling of
+ * such a cone, is the route from the caller's cone objects.) */
 /* The same entry points for a caller whose iterate lives in HOST memory (DefaultVariables are Vector{T},
  * variables.jl:1-30): vectors are staged through buffers the handle owns (n + 2m doubles each way per call).
  * hipkkt_kkt_system_solve_host: var_x = var_s = var_z = NULL means "the variables of the previous call" -- they do not
@@ -341,6 +362,16 @@ int hipkkt_kkt_get_Hs(hipkkt_kkt_t h, double *Hsblocks /* |Hs|, positive */);
 int hipkkt_kkt_get_scaling(hipkkt_kkt_t h, double *lambda, double *psd_R, double *psd_Rinv);
 /* the rest of the device's NT scaling: w (m) and eta (one per cone), as hipkkt_kkt_system_update_cones takes them */
 int hipkkt_kkt_get_scaling_w(hipkkt_kkt_t h, double *w, double *eta);
+/* How the next device-side scaling treats the exponential and power cones (update_Hs, coneops_nonsymmetric_common.jl:
+ * 50-67): strategy HIPKKT_SCALING_PRIMAL_DUAL (the default; mu is not read, the cone's own <s,z>/3 is used, :97-98) or
+ * HIPKKT_SCALING_DUAL (Hs = mu H*(z)).  Host-only, no device work: call it once per iteration before
+ * hipkkt_kkt_update_from_sz[_dev], hipkkt_kkt_system_update[_host] or hipkkt_kkt_system_update_and_solve_affine, in
+ * lazy mode too.  On a handle without such cones it does nothing and returns 0. */
+int hipkkt_kkt_set_nonsymmetric_scaling(hipkkt_kkt_t h, int strategy, double mu);
+/* After a device-side scaling: grad f*(z) (3 doubles) and the Hessian H*(z) (9 doubles, symmetric) of every exponential
+ * and power cone, in cone order -- K.grad and K.H_dual, which combined_ds_shift! reads.  Either may be NULL.  The caller sizes
+ * the arrays from its own cone list. */
+int hipkkt_kkt_get_nonsymmetric(hipkkt_kkt_t h, double *grad, double *H_dual);
 double hipkkt_kkt_last_regularizer(hipkkt_kkt_t h);
 int64_t hipkkt_kkt_last_ir_iterations(hipkkt_kkt_t h);
 /* (tests) the refinement rounds a solve enqueues ahead of its first status read-back -- what the previous solves took

@@ -28,7 +28,7 @@ import Clarabel: linear_solver_info, update_values!, scale_values!, refactor!, s
 import Clarabel: kktsolver_update!, kktsolver_setrhs!, kktsolver_solve!, kktsolver_update_P!,
                  kktsolver_update_A!, kktsolver_linear_solver_info
 import Clarabel: CompositeCone, ZeroCone, NonnegativeCone, SecondOrderCone, PSDTriangleCone,
-                 get_Hs!, is_sparse_expandable, numel
+                 ExponentialCone, PowerCone, get_Hs!, is_sparse_expandable, numel
 
 const libhipkkt = get(ENV, "HIPKKT_LIB", "libhipkkt.so")
 
@@ -143,23 +143,26 @@ mutable struct HipKKTSolver{T} <: AbstractKKTSolver{T}
                              m::DefaultInt, n::DefaultInt, settings::Settings{T}) where {T}
         T === Float64 || error("hipkkt supports Float64 only")
         kinds = Int32[]; dims = Int64[]
-        for c in cones
+        params = zeros(Float64, length(cones))      # alpha of a power cone (hipkkt_kkt_create_ex), 0 otherwise
+        for (i, c) in enumerate(cones)
             if     c isa ZeroCone         push!(kinds, 0); push!(dims, numel(c))
             elseif c isa NonnegativeCone  push!(kinds, 1); push!(dims, numel(c))
             elseif c isa SecondOrderCone  push!(kinds, 2); push!(dims, numel(c))
             elseif c isa PSDTriangleCone  push!(kinds, 3); push!(dims, c.n)
+            elseif c isa ExponentialCone  push!(kinds, 4); push!(dims, 3)
+            elseif c isa PowerCone        push!(kinds, 5); push!(dims, 3); params[i] = c.α
             else error("hipkkt: cone type $(typeof(c)) is not supported")
             end
         end
         h = Ref{Ptr{Cvoid}}(C_NULL)
         cs = Ref(csettings(settings))
         Pt = triu(P)                                # data.P is already triu; harmless otherwise
-        rc = GC.@preserve Pt A kinds dims ccall((:hipkkt_kkt_create, libhipkkt), Cint,
+        rc = GC.@preserve Pt A kinds dims params ccall((:hipkkt_kkt_create_ex, libhipkkt), Cint,
             (Ref{Ptr{Cvoid}}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble},
-             Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Int64, Ptr{Int32}, Ptr{Int64}, Ref{CSettings}, Cint),
+             Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Cdouble}, Ref{CSettings}, Cint),
             h, n, m, Pt.colptr, Pt.rowval, Pt.nzval, A.colptr, A.rowval, A.nzval,
-            length(kinds), kinds, dims, cs, 1)
-        check(rc, "hipkkt_kkt_create") || error("hipkkt_kkt_create: numeric failure")
+            length(kinds), kinds, dims, params, cs, 1)
+        check(rc, "hipkkt_kkt_create_ex") || error("hipkkt_kkt_create_ex: numeric failure")
         info = Ref{CInfo}()
         check(ccall((:hipkkt_kkt_info, libhipkkt), Cint, (Ptr{Cvoid}, Ref{CInfo}), h[], info), "hipkkt_kkt_info")
         obj = new(h[], m, n, zeros(T, info[].nHs), zeros(T, info[].sparse_soc_len),
@@ -293,6 +296,13 @@ kkt_update_A!(s::HipKKTSystem{T}, A::SparseMatrixCSC{T}) where {T} = kktsolver_u
 # caller that wants the reference's own rounding of those blocks.)
 function kkt_update!(s::HipKKTSystem{T}, data::DefaultProblemData{T}, cones::CompositeCone{T}) where {T}
     ks = s.kktsolver
+    if any(c -> c isa ExponentialCone || c isa PowerCone, cones)
+        # (w, eta, lambda, R) cannot carry an exponential / power cone's 3 x 3 block, and the cone objects were scaled on
+        # the host by update_scaling!(cones, s, z, mu, strategy) already: their get_Hs! block IS the scaling, and the
+        # device's mul_Hs reads it from the Hs store.  K.grad / K.H_dual stay in the cone objects for combined_ds_shift!.
+        # (This branch has not been executed: no Julia in the build container, as for the rest of this file.)
+        return kkt_update_cones_route!(s, cones)
+    end
     zoff = 0; poff = 0
     for (i, c) in enumerate(cones)
         d = numel(c)
@@ -313,6 +323,41 @@ function kkt_update!(s::HipKKTSystem{T}, data::DefaultProblemData{T}, cones::Com
     GC.@preserve s ks check(ccall((:hipkkt_kkt_system_update_scaling, libhipkkt), Cint,
         (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
         ks.handle, s.w, s.eta, s.lambda, s.psd_R, s.psd_Rinv), "hipkkt_kkt_system_update_scaling")
+end
+
+# kkt_update! through hipkkt_kkt_system_update_cones: get_Hs! blocks and the sparse second-order cones' u / v / eta^2 as
+# level B sends them, plus the NT scaling of the symmetric cones.  The route for problems with exponential / power cones.
+function kkt_update_cones_route!(s::HipKKTSystem{T}, cones::CompositeCone{T}) where {T}
+    ks = s.kktsolver
+    get_Hs!(cones, ks.Hsblocks)
+    zoff = 0; poff = 0; uoff = 0; k = 0
+    for (i, c) in enumerate(cones)
+        d = numel(c)
+        if c isa NonnegativeCone
+            s.w[zoff+1:zoff+d] .= c.w;  s.lambda[zoff+1:zoff+d] .= c.λ
+        elseif c isa SecondOrderCone
+            s.w[zoff+1:zoff+d] .= c.w;  s.lambda[zoff+1:zoff+d] .= c.λ;  s.eta[i] = c.η
+            if is_sparse_expandable(c)
+                k += 1
+                ks.soc_u[uoff+1:uoff+d] .= c.sparse_data.u;  ks.soc_v[uoff+1:uoff+d] .= c.sparse_data.v
+                ks.soc_eta2[k] = c.η^2
+                uoff += d
+            end
+        elseif c isa PSDTriangleCone
+            n = c.n
+            s.lambda[zoff+1:zoff+n] .= c.data.λ
+            s.psd_R[poff+1:poff+n*n]    .= vec(c.data.R)
+            s.psd_Rinv[poff+1:poff+n*n] .= vec(c.data.Rinv)
+            poff += n * n
+        end
+        zoff += d
+    end
+    s.variables_sent = false
+    GC.@preserve s ks check(ccall((:hipkkt_kkt_system_update_cones, libhipkkt), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+         Ptr{Cdouble}, Ptr{Cdouble}),
+        ks.handle, ks.Hsblocks, ks.soc_u, ks.soc_v, ks.soc_eta2, s.w, s.eta, s.lambda, s.psd_R, s.psd_Rinv),
+        "hipkkt_kkt_system_update_cones")
 end
 
 function kkt_solve_initial_point!(s::HipKKTSystem{T}, variables::DefaultVariables{T}, data::DefaultProblemData{T}) where {T}
