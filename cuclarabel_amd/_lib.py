@@ -82,6 +82,7 @@ SYMBOLS = {
     "hipkkt_ldl_fallbacks": (C.c_int, [_P, _P]),
     "hipkkt_kkt_create": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int]),
     "hipkkt_kkt_create_ex": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, C.c_int]),
+    "hipkkt_kkt_create_ex2": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.c_int]),
     "hipkkt_kkt_destroy": (None, [_P]),
     "hipkkt_kkt_info": (C.c_int, [_P, _P]),
     "hipkkt_kkt_update_cones": (C.c_int, [_P, _P, _P, _P, _P]),
@@ -129,6 +130,8 @@ SYMBOLS = {
     "hipkkt_kkt_get_scaling_w": (C.c_int, [_P, _P, _P]),
     "hipkkt_kkt_set_nonsymmetric_scaling": (C.c_int, [_P, C.c_int, C.c_double]),
     "hipkkt_kkt_get_nonsymmetric": (C.c_int, [_P, _P, _P]),
+    "hipkkt_kkt_get_genpow": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "hipkkt_kkt_get_genpow_maps": (C.c_int, [_P, _P, _P, _P, _P]),
     "hipkkt_kkt_last_regularizer": (C.c_double, [_P]),
     "hipkkt_kkt_last_ir_iterations": (C.c_int64, [_P]),
     "hipkkt_kkt_set_stream": (C.c_int, [_P, _P]),

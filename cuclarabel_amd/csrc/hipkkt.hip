@@ -2486,6 +2486,11 @@ struct hipkkt_kkt_s {
     DBuf<double> c_param, ns_grad, ns_H;
     int nexp = 0, npow = 0, ns_strategy = HIPKKT_SCALING_PRIMAL_DUAL;
     double ns_mu = 0.0;
+    // generalized power cones (kernels.hpp, ConeDev / ConeState); gp_mu: the mu of the scaling now on the device
+    DBuf<int> gp_cone, gp_dim1, gp_off, gp_small, gp_big, gp_mapP, gp_mapQR, gp_mapD;
+    DBuf<double> gp_alpha, gp_grad, gp_d, gp_p, gp_qr;
+    int ngp_small = 0, ngp_big = 0;
+    double gp_mu = 0.0;
     DBuf<int> c_psdlist, c_psddim;
     DBuf<int64_t> c_psdaoff;
     DBuf<double> psdA, psdR, psdRinv;
@@ -2541,6 +2546,9 @@ struct hipkkt_kkt_s {
         C.psd_list = c_psdlist.p; C.psd_dim = c_psddim.p; C.psd_aoff = c_psdaoff.p; C.npsd = npsd; C.psd_kmax = psd_kmax;
         C.exp_list = c_explist.p; C.nexp = nexp; C.pow_list = c_powlist.p; C.npow = npow; C.ns_index = c_nsidx.p;
         C.param = c_param.p; C.ns_strategy = ns_strategy; C.ns_mu = ns_mu;
+        C.gp_cone = gp_cone.p; C.gp_dim1 = gp_dim1.p; C.gp_off = gp_off.p; C.gp_alpha = gp_alpha.p;
+        C.gp_small = gp_small.p; C.gp_big = gp_big.p; C.ngp_small = ngp_small; C.ngp_big = ngp_big;
+        C.gp_mapP = gp_mapP.p; C.gp_mapQR = gp_mapQR.p; C.gp_mapD = gp_mapD.p; C.gp_mu = gp_mu;
         return C;
     }
     ConeState cone_state()
@@ -2550,6 +2558,8 @@ struct hipkkt_kkt_s {
         S.psdA = psdA.p; S.psdR = psdR.p; S.psdRinv = psdRinv.p;
         S.lam = lam.p;
         S.ns_grad = ns_grad.p; S.ns_H = ns_H.p;
+        S.gp_grad = gp_grad.p; S.gp_d = gp_d.p; S.gp_p = gp_p.p; S.gp_qr = gp_qr.p;
+        S.Kval = Kval.p; S.fval = fval_dirty ? nullptr : fval.p; S.kpos = kpos.p;
         return S;
     }
 };
@@ -2892,6 +2902,32 @@ int hipkkt_kkt_create_ex(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t*
                          int64_t ncones, const int32_t* kinds, const int64_t* dims, const double* cone_params,
                          const hipkkt_settings* settings, int base)
 {
+    // one double per cone -> the ragged form: a power cone's alpha is the only value that travels
+    std::vector<int64_t> pptr;
+    std::vector<double> pvals;
+    if (ncones > 0 && kinds) {
+        for (int64_t c = 0; c < ncones; ++c)
+            if (kinds[c] == HIPKKT_CONE_GENPOW) {
+                g_last_error = "a generalized power cone has one alpha per row of its first block: use hipkkt_kkt_create_ex2";
+                return HIPKKT_ERR_ARG;
+            }
+        if (cone_params) {
+            pptr.assign((size_t)ncones + 1, base);
+            for (int64_t c = 0; c < ncones; ++c) {
+                pptr[(size_t)c + 1] = pptr[(size_t)c];
+                if (kinds[c] == HIPKKT_CONE_POW) { pvals.push_back(cone_params[c]); pptr[(size_t)c + 1] += 1; }
+            }
+        }
+    }
+    return hipkkt_kkt_create_ex2(out, n, m, Pcolptr, Prowval, Pnzval, Acolptr, Arowval, Anzval, ncones, kinds, dims,
+                                 pptr.empty() ? nullptr : pptr.data(), pvals.data(), settings, base);
+}
+
+int hipkkt_kkt_create_ex2(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t* Pcolptr, const int64_t* Prowval,
+                          const double* Pnzval, const int64_t* Acolptr, const int64_t* Arowval, const double* Anzval,
+                          int64_t ncones, const int32_t* kinds, const int64_t* dims, const int64_t* cone_param_ptr,
+                          const double* cone_param_vals, const hipkkt_settings* settings, int base)
+{
     return guarded([&]() {
         if (!out || !Pcolptr || !Acolptr || n < 0 || m < 0 || ncones < 0 || (ncones > 0 && (!kinds || !dims)))
             throw ArgError("hipkkt_kkt_create: bad argument");
@@ -2901,7 +2937,8 @@ int hipkkt_kkt_create_ex(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t*
         if (settings) h->st = *settings; else hipkkt_default_settings(&h->st);
         // host-side assembly first: a malformed (P, A, cones) is an argument error whether or not a device is there
         try {
-            assemble_kkt(n, m, Pcolptr, Prowval, Pnzval, Acolptr, Arowval, Anzval, ncones, kinds, dims, base, h->K, cone_params);
+            assemble_kkt(n, m, Pcolptr, Prowval, Pnzval, Acolptr, Arowval, Anzval, ncones, kinds, dims, base, h->K, cone_param_ptr,
+                         cone_param_vals);
         } catch (const std::runtime_error& e) {
             throw ArgError(e.what());
         }
@@ -3068,6 +3105,28 @@ int hipkkt_kkt_create_ex(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t*
                 HIP_CHECK(hipMemset(h->ns_grad.p, 0, (size_t)3 * K.nnonsym * sizeof(double)));
                 HIP_CHECK(hipMemset(h->ns_H.p, 0, (size_t)9 * K.nnonsym * sizeof(double)));
             }
+            if (K.ngenpow > 0) {
+                std::vector<int> gcone, gdim1, goff, gsmall, gbig, mapQR((size_t)K.genpow_len);
+                std::vector<double> alpha((size_t)K.genpow_len, 0.0);
+                for (size_t c = 0; c < nc; ++c) {
+                    const ConeInfo& ci = K.cones[c];
+                    if (ci.kind != HIPKKT_CONE_GENPOW) continue;
+                    gcone.push_back((int)c); gdim1.push_back(ci.dim1); goff.push_back(ci.gpoff);
+                    (ci.numel <= kGenPowWaveMax ? gsmall : gbig).push_back(ci.gpidx);
+                    for (int t = 0; t < ci.dim1; ++t) {
+                        alpha[ci.gpoff + t] = K.gp_alpha[ci.gqoff + t];
+                        mapQR[ci.gpoff + t] = K.mapGP_q[ci.gqoff + t];
+                    }
+                    for (int t = ci.dim1; t < ci.numel; ++t) mapQR[ci.gpoff + t] = K.mapGP_r[ci.groff + t - ci.dim1];
+                }
+                h->ngp_small = (int)gsmall.size(); h->ngp_big = (int)gbig.size();
+                h->gp_cone.upload(gcone); h->gp_dim1.upload(gdim1); h->gp_off.upload(goff); h->gp_alpha.upload(alpha);
+                h->gp_small.upload(gsmall); h->gp_big.upload(gbig);
+                h->gp_mapP.upload(K.mapGP_p); h->gp_mapQR.upload(mapQR); h->gp_mapD.upload(K.mapGP_D);
+                const size_t gl = (size_t)K.genpow_len;
+                h->gp_grad.alloc(gl); h->gp_d.alloc(gl); h->gp_p.alloc(gl); h->gp_qr.alloc(gl);
+                for (double* q : {h->gp_grad.p, h->gp_d.p, h->gp_p.p, h->gp_qr.p}) HIP_CHECK(hipMemset(q, 0, gl * sizeof(double)));
+            }
             {
                 std::vector<int> plist, pdim(nc, 0);
                 std::vector<int64_t> paoff(nc, 0);
@@ -3169,6 +3228,9 @@ int hipkkt_kkt_update_cones(hipkkt_kkt_t h, const double* Hs, const double* soc_
         KKTAssembly& K = h->K;
         if ((K.nHs > 0 && !Hs) || (K.nsparse > 0 && (!soc_u || !soc_v || !soc_eta2)))
             throw ArgError("hipkkt_kkt_update_cones: missing cone data");
+        if (K.ngenpow > 0)
+            throw ArgError("hipkkt_kkt_update_cones: (Hs, u, v, eta^2) cannot carry p, q, r of a generalized power cone; such a "
+                           "handle is scaled on the device (hipkkt_kkt_update_from_sz, hipkkt_kkt_system_update)");
         HIP_CHECK(hipSetDevice(h->device));
         if (K.nHs) HIP_CHECK(hipMemcpyAsync(h->Hs.p, Hs, (size_t)K.nHs * sizeof(double), hipMemcpyHostToDevice, h->stream));
         if (K.nsparse) {
@@ -3191,6 +3253,7 @@ static int kkt_update_from_sz_dev_impl(hipkkt_kkt_t h, const double* d_s, const 
         HIP_CHECK(hipSetDevice(h->device));
         launch_zero_ints(h->fail.p, 1, h->stream);
         int pu = h->prof.begin(0, h->stream);
+        h->gp_mu = h->ns_mu;
         launch_cone_scaling(h->cone_dev(), h->cone_state(), d_s, d_z, h->K.m, h->stream);
         h->prof.end(pu, h->stream);
         h->scaling_valid = true;
@@ -4220,6 +4283,9 @@ int hipkkt_kkt_system_update_scaling(hipkkt_kkt_t h, const double* w, const doub
         if (h->K.nnonsym > 0)
             throw ArgError("hipkkt_kkt_system_update_scaling: (w, eta, lambda, R) cannot carry the 3 x 3 block of an exponential "
                            "or power cone; use hipkkt_kkt_system_update_cones");
+        if (h->K.ngenpow > 0)
+            throw ArgError("hipkkt_kkt_system_update_scaling: (w, eta, lambda, R) cannot carry p, q, r of a generalized power "
+                           "cone; such a handle is scaled on the device (hipkkt_kkt_system_update)");
         HIP_CHECK(hipSetDevice(h->device));
         hipStream_t st = h->stream;
         if (m) {
@@ -4417,7 +4483,7 @@ int hipkkt_equilibrate(int64_t n, int64_t m, const int64_t* Pcolptr, const int64
             const int64_t dim = cone_dims[k];
             // (exponential and power cones take the default rectification, one scalar per cone: coneops_defaults.jl:32-44,
             // which k_equil_rectify applies to every kind >= 2)
-            if (cone_kinds[k] < HIPKKT_CONE_ZERO || cone_kinds[k] > HIPKKT_CONE_POW || dim < 0)
+            if (cone_kinds[k] < HIPKKT_CONE_ZERO || cone_kinds[k] > HIPKKT_CONE_GENPOW || dim < 0)
                 throw ArgError("hipkkt_equilibrate: unknown cone kind or negative dimension");
             if ((cone_kinds[k] == HIPKKT_CONE_EXP || cone_kinds[k] == HIPKKT_CONE_POW) && dim != 3)
                 throw ArgError("hipkkt_equilibrate: exponential and power cones have dimension 3");
@@ -4595,7 +4661,7 @@ int hipkkt_kkt_set_nonsymmetric_scaling(hipkkt_kkt_t h, int strategy, double mu)
         if (!h) throw ArgError("null handle");
         if (strategy != HIPKKT_SCALING_PRIMAL_DUAL && strategy != HIPKKT_SCALING_DUAL)
             throw ArgError("hipkkt_kkt_set_nonsymmetric_scaling: strategy must be PRIMAL_DUAL (0) or DUAL (1)");
-        if (h->K.nnonsym == 0) return HIPKKT_OK;
+        if (h->K.nnonsym == 0 && h->K.ngenpow == 0) return HIPKKT_OK;
         h->ns_strategy = strategy;
         h->ns_mu = mu;
         return HIPKKT_OK;
@@ -4613,6 +4679,44 @@ int hipkkt_kkt_get_nonsymmetric(hipkkt_kkt_t h, double* grad, double* H_dual)
         if (grad) HIP_CHECK(hipMemcpyAsync(grad, h->ns_grad.p, 3 * nn * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         if (H_dual) HIP_CHECK(hipMemcpyAsync(H_dual, h->ns_H.p, 9 * nn * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_get_genpow(hipkkt_kkt_t h, double* grad, double* d, double* p, double* q, double* r)
+{
+    return guarded([&]() {
+        if (!h) throw ArgError("null handle");
+        const KKTAssembly& K = h->K;
+        if (K.ngenpow == 0) return HIPKKT_OK;
+        if (!h->scaling_valid) throw ArgError("hipkkt_kkt_get_genpow needs a device-side scaling (hipkkt_kkt_update_from_sz)");
+        HIP_CHECK(hipSetDevice(h->device));
+        const size_t gl = (size_t)K.genpow_len;
+        if (grad) HIP_CHECK(hipMemcpyAsync(grad, h->gp_grad.p, gl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (d) HIP_CHECK(hipMemcpyAsync(d, h->gp_d.p, gl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        if (p) HIP_CHECK(hipMemcpyAsync(p, h->gp_p.p, gl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        std::vector<double> qr;
+        if (q || r) {
+            qr.resize(gl);
+            HIP_CHECK(hipMemcpyAsync(qr.data(), h->gp_qr.p, gl * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        }
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        if (q || r)
+            for (const ConeInfo& ci : K.cones) {
+                if (ci.kind != HIPKKT_CONE_GENPOW) continue;
+                if (q) std::copy(qr.begin() + ci.gpoff, qr.begin() + ci.gpoff + ci.dim1, q + ci.gqoff);
+                if (r) std::copy(qr.begin() + ci.gpoff + ci.dim1, qr.begin() + ci.gpoff + ci.numel, r + ci.groff);
+            }
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_get_genpow_maps(hipkkt_kkt_t h, int64_t* map_p, int64_t* map_q, int64_t* map_r, int64_t* map_D)
+{
+    return guarded([&]() {
+        if (!h) throw ArgError("null handle");
+        auto cp = [](const std::vector<int>& v, int64_t* dst) { if (dst) for (size_t i = 0; i < v.size(); ++i) dst[i] = v[i]; };
+        cp(h->K.mapGP_p, map_p); cp(h->K.mapGP_q, map_q); cp(h->K.mapGP_r, map_r); cp(h->K.mapGP_D, map_D);
         return HIPKKT_OK;
     });
 }

@@ -1008,12 +1008,125 @@ __device__ inline void cone_nonsym_body(const ConeDev& C, const ConeState& S, co
     out[3] = Hs[2]; out[4] = Hs[5]; out[5] = Hs[8];
 }
 
-// k_cone_scaling for a handle that holds exponential / power cones: the same elementwise and second-order workgroups,
-// then workgroups over exp_list, then over pow_list, a thread per cone.  A kernel of its own so that the one every
+
+// -------------------------------------------------------------------------------------
+//  Generalized power cones (coneops_genpowcone.jl): update_dual_grad_H (:336-389), get_Hs! (:91-108) and
+//  _csc_update_sparsecone (directldl_datamaps.jl:146-167) in one pass per cone.  NT = 64: one wave per cone; NT = 256: one
+//  workgroup per cone, the waves' partial results meet in LDS.  phi = prod (z_i / alpha_i)^(2 alpha_i) and ||w||^2 are
+//  reduced in a FIXED order -- each lane its strided rows in ascending order, a butterfly over the lanes, the waves
+//  left to right -- so two runs give the same bits.  The reference's running product visits the rows in another
+//  order; the difference is round-off of the size DESIGN.md section 4.3 states.
+//  mu H*(z) = mu (D + p p' - q q' - r r'): mu d goes to the Hs store (k_update_values scatters -Hs as for every cone),
+//  -sqrt(mu) (q, r, p) and (-1, -1, +1) go straight into K here.  z outside the dual cone raises the fail word and leaves
+//  the cone's entries as they were.
+// -------------------------------------------------------------------------------------
+template <int NT, bool PROD>
+__device__ inline void gp_reduce3(double& a, double& b, double& c, double* sh)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ao = __shfl_xor(a, o, 64);
+        a = PROD ? a * ao : a + ao;
+        b += __shfl_xor(b, o, 64);
+        c += __shfl_xor(c, o, 64);
+    }
+    if (NT > 64) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if (lane == 0) { sh[3 * wave] = a; sh[3 * wave + 1] = b; sh[3 * wave + 2] = c; }
+        __syncthreads();
+        a = PROD ? (sh[0] * sh[3]) * (sh[6] * sh[9]) : (sh[0] + sh[3]) + (sh[6] + sh[9]);
+        b = (sh[1] + sh[4]) + (sh[7] + sh[10]);
+        c = (sh[2] + sh[5]) + (sh[8] + sh[11]);
+    }
+}
+
+template <int NT>
+__device__ inline void cone_genpow_body(const ConeDev& C, const ConeState& S, const double* __restrict__ z, int k, int tid,
+                                        double* sh)
+{
+    const int c = C.gp_cone[k], off = C.off[c], n = C.numel[c], d1 = C.gp_dim1[k], g = C.gp_off[k];
+    const double* zc = z + off;
+    const double* al = C.gp_alpha + g;
+    double phi = 1.0, nw = 0.0, bad = 0.0;
+    for (int i = tid; i < n; i += NT) {
+        const double zi = zc[i];
+        if (i < d1) {
+            const double a = al[i];
+            if (!(zi > 0.0)) bad = 1.0;
+            phi *= pow(zi / a, 2.0 * a);
+        } else nw += zi * zi;
+    }
+    gp_reduce3<NT, true>(phi, nw, bad, sh);
+    const double zeta = phi - nw;
+    if (bad != 0.0 || !(zeta > 0.0) || !isfinite(zeta)) { if (tid == 0) *S.fail = 1; return; }
+    const double p0 = sqrt(phi * (phi + nw) / 2.0);
+    const double p1 = -2.0 * phi / p0;
+    const double q0 = sqrt(zeta * phi / 2.0);
+    const double r1 = 2.0 * sqrt(zeta / (phi + nw));
+    const double d2 = 2.0 / zeta;
+    const double mu = C.ns_mu, nsm = -sqrt(mu);
+    double* Hs = S.Hs + C.boff[c];
+    for (int i = tid; i < n; i += NT) {
+        const double zi = zc[i];
+        double gr, d, p, qr;
+        if (i < d1) {
+            const double a = al[i];
+            const double tau = 2.0 * a / zi;
+            gr = -tau * phi / zeta - (1.0 - a) / zi;
+            d = tau * phi / (zeta * zi) + (1.0 - a) / (zi * zi);
+            p = p0 * tau / zeta;
+            qr = tau * (q0 / zeta);
+        } else {
+            gr = 2.0 * zi / zeta;
+            d = d2;
+            p = p1 * zi / zeta;
+            qr = r1 * zi / zeta;
+        }
+        S.gp_grad[g + i] = gr;
+        S.gp_d[g + i] = d;
+        S.gp_p[g + i] = p;
+        S.gp_qr[g + i] = qr;
+        Hs[i] = mu * d;
+        put_k(S.Kval, S.fval, S.kpos, C.gp_mapQR[g + i], qr * nsm);
+        put_k(S.Kval, S.fval, S.kpos, C.gp_mapP[g + i], p * nsm);
+    }
+    if (tid < 3) put_k(S.Kval, S.fval, S.kpos, C.gp_mapD[3 * k + tid], tid == 2 ? 1.0 : -1.0);
+}
+
+// y = mu (D x + p (p'x) - q (q'x1) - r (r'x2))   (mul_Hs!, coneops_genpowcone.jl:110-135)
+template <int NT>
+__device__ inline void mul_Hs_genpow_body(const ConeDev& C, const ConeState& S, double* __restrict__ y,
+                                          const double* __restrict__ x, const double* __restrict__ addend, int k, int tid,
+                                          double* sh)
+{
+    const int c = C.gp_cone[k], off = C.off[c], n = C.numel[c], d1 = C.gp_dim1[k], g = C.gp_off[k];
+    const double* p = S.gp_p + g;
+    const double* qr = S.gp_qr + g;
+    const double* d = S.gp_d + g;
+    double cp = 0.0, cq = 0.0, cr = 0.0;
+    for (int i = tid; i < n; i += NT) {
+        const double xi = x[off + i];
+        cp += p[i] * xi;
+        if (i < d1) cq += qr[i] * xi; else cr += qr[i] * xi;
+    }
+    gp_reduce3<NT, false>(cp, cq, cr, sh);
+    const double mu = C.gp_mu;
+    for (int i = tid; i < n; i += NT) {
+        double v = d[i] * x[off + i] - (i < d1 ? cq : cr) * qr[i];
+        v += cp * p[i];
+        v *= mu;
+        y[off + i] = addend ? -(v + addend[off + i]) : v;
+    }
+}
+
+// k_cone_scaling for a handle that holds non-symmetric cones: the same elementwise and second-order workgroups, then
+// workgroups over exp_list, then over pow_list, a thread per cone; behind them the generalized power cones, four small
+// ones to a workgroup (a wave each), then a workgroup for each big one.  A kernel of its own so that the one every
 // symmetric problem launches keeps its register count.
 __global__ __launch_bounds__(256) void k_cone_scaling_ns(ConeDev C, ConeState S, const double* __restrict__ s,
-                                                         const double* __restrict__ z, int m, int ge, int gs, int gx)
+                                                         const double* __restrict__ z, int m, int ge, int gs, int gx, int gp)
 {
+    __shared__ double sh[12];
     const int bx = (int)blockIdx.x;
     if (bx < ge) { cone_elementwise_body(C, S, s, z, m, bx, ge); return; }
     if (bx < ge + gs) {
@@ -1026,8 +1139,18 @@ __global__ __launch_bounds__(256) void k_cone_scaling_ns(ConeDev C, ConeState S,
         if (i < C.nexp) cone_nonsym_body(C, S, s, z, C.exp_list[i], false);
         return;
     }
-    const int i = (bx - ge - gs - gx) * 256 + (int)threadIdx.x;
-    if (i < C.npow) cone_nonsym_body(C, S, s, z, C.pow_list[i], true);
+    if (bx < ge + gs + gx + gp) {
+        const int i = (bx - ge - gs - gx) * 256 + (int)threadIdx.x;
+        if (i < C.npow) cone_nonsym_body(C, S, s, z, C.pow_list[i], true);
+        return;
+    }
+    const int gq = (C.ngp_small + 3) / 4, b0 = bx - ge - gs - gx - gp;
+    if (b0 < gq) {
+        const int i = b0 * 4 + (int)(threadIdx.x >> 6);
+        if (i < C.ngp_small) cone_genpow_body<64>(C, S, z, C.gp_small[i], threadIdx.x & 63, nullptr);
+        return;
+    }
+    cone_genpow_body<256>(C, S, z, C.gp_big[b0 - gq], threadIdx.x, sh);
 }
 
 // -------------------------------------------------------------------------------------
@@ -1273,8 +1396,9 @@ void launch_cone_scaling(const ConeDev& C, const ConeState& S, const double* s, 
 {
     const int ge = m > 0 ? grid_for(m, 256) : 0, gs = (C.nsoc + 3) / 4;
     const int gx = (C.nexp + 255) / 256, gp = (C.npow + 255) / 256;
-    if (gx + gp > 0)
-        hipLaunchKernelGGL(k_cone_scaling_ns, dim3(ge + gs + gx + gp), dim3(256), 0, st, C, S, s, z, m, ge, gs, gx);
+    const int gg = (C.ngp_small + 3) / 4 + C.ngp_big;
+    if (gx + gp + gg > 0)
+        hipLaunchKernelGGL(k_cone_scaling_ns, dim3(ge + gs + gx + gp + gg), dim3(256), 0, st, C, S, s, z, m, ge, gs, gx, gp);
     else if (ge + gs > 0) hipLaunchKernelGGL(k_cone_scaling, dim3(ge + gs), dim3(256), 0, st, C, S, s, z, m, ge);
     if (C.npsd > 0) {
         static PerDeviceOnce once;
@@ -1294,7 +1418,7 @@ __device__ inline void mul_Hs_elementwise_body(const ConeDev& C, const ConeState
         double v;
         if (kind == 0) v = 0.0;
         else if (kind == 1) v = S.w[i] * (S.w[i] * x[i]);
-        else if (kind >= 4) {
+        else if (kind == 4 || kind == 5) {
             // exponential / power cone: row r of the stored 3 x 3 block (packed triu) times x (mul_Hs!, coneops_expcone.jl:103-115)
             const int c = C.elem_cone[i], off = C.off[c], r = i - off;
             const double* Hs = S.Hs + C.boff[c];
@@ -1340,6 +1464,28 @@ __global__ __launch_bounds__(256) void k_mul_Hs(ConeDev C, ConeState S, double* 
     if ((int)blockIdx.x < ge) { mul_Hs_elementwise_body(C, S, y, x, m, addend, blockIdx.x, ge); return; }
     const int ci = ((int)blockIdx.x - ge) * 4 + (int)(threadIdx.x >> 6);
     if (ci < C.nsoc) mul_Hs_soc_body(C, S, y, x, addend, ci, threadIdx.x & 63);
+}
+// k_mul_Hs for a handle that holds generalized power cones: their waves and workgroups ride behind the second-order
+// cones' (a kernel of its own for the reason k_cone_scaling_ns is one)
+__global__ __launch_bounds__(256) void k_mul_Hs_gp(ConeDev C, ConeState S, double* __restrict__ y, const double* __restrict__ x,
+                                                   int m, const double* __restrict__ addend, int ge, int gs, Publish P)
+{
+    __shared__ double sh[12];
+    if (P.dst && blockIdx.x == gridDim.x - 1 && threadIdx.x == 255) publish_record(P);
+    const int bx = (int)blockIdx.x;
+    if (bx < ge) { mul_Hs_elementwise_body(C, S, y, x, m, addend, bx, ge); return; }
+    if (bx < ge + gs) {
+        const int ci = (bx - ge) * 4 + (int)(threadIdx.x >> 6);
+        if (ci < C.nsoc) mul_Hs_soc_body(C, S, y, x, addend, ci, threadIdx.x & 63);
+        return;
+    }
+    const int gq = (C.ngp_small + 3) / 4, b0 = bx - ge - gs;
+    if (b0 < gq) {
+        const int i = b0 * 4 + (int)(threadIdx.x >> 6);
+        if (i < C.ngp_small) mul_Hs_genpow_body<64>(C, S, y, x, addend, C.gp_small[i], threadIdx.x & 63, nullptr);
+        return;
+    }
+    mul_Hs_genpow_body<256>(C, S, y, x, addend, C.gp_big[b0 - gq], threadIdx.x, sh);
 }
 // A = R R' per PSD cone, from a caller-supplied R (hipkkt_kkt_system_update_cones); one workgroup per cone
 __global__ __launch_bounds__(256) void k_psd_A_from_R(ConeDev C, ConeState S)
@@ -1458,7 +1604,10 @@ void launch_mul_Hs(const ConeDev& C, const ConeState& S, double* y, const double
 {
     const int ge = m > 0 ? grid_for(m, 256) : 0, gs = (C.nsoc + 3) / 4;
     const bool ride = ge + gs > 0 && C.npsd == 0;          // (the publication rides with the LAST kernel of the call)
-    if (ge + gs > 0) hipLaunchKernelGGL(k_mul_Hs, dim3(ge + gs), dim3(256), 0, st, C, S, y, x, m, addend, ge, ride ? pub : Publish{});
+    const int gg = (C.ngp_small + 3) / 4 + C.ngp_big;
+    if (gg > 0)
+        hipLaunchKernelGGL(k_mul_Hs_gp, dim3(ge + gs + gg), dim3(256), 0, st, C, S, y, x, m, addend, ge, gs, ride ? pub : Publish{});
+    else if (ge + gs > 0) hipLaunchKernelGGL(k_mul_Hs, dim3(ge + gs), dim3(256), 0, st, C, S, y, x, m, addend, ge, ride ? pub : Publish{});
     if (C.npsd > 0) {
         const size_t lds = (size_t)3 * C.psd_kmax * C.psd_kmax * sizeof(double);
         hipLaunchKernelGGL(k_mul_Hs_psd, dim3(C.npsd), dim3(256), lds, st, C, S, y, x, addend);
@@ -1487,7 +1636,8 @@ __device__ inline void sys_offset_elementwise_body(const ConeDev& C, const ConeS
             const int kind = C.kind[C.elem_cone[i]];
             if (kind == 0) o = 0.0;                     // coneops_zerocone.jl:137-150
             else if (kind == 1) o = ds[i] / z[i];       // coneops_nncone.jl:140-148
-            else if (kind >= 4) o = ds[i];              // exponential / power: out = ds (coneops_expcone.jl:150-163)
+            else if (kind >= 4) o = ds[i];              // exponential / power / generalized power: out = ds
+                                                        // (coneops_expcone.jl:150-163, coneops_genpowcone.jl:170-183)
             else continue;                              // second-order / PSD cones: k_sys_offset_soc / k_sys_offset_psd
         }
         konst[i] = o;

@@ -461,8 +461,27 @@ struct ConeDev {
     const double* param = nullptr;   // per cone
     int nexp = 0, npow = 0;
     int ns_strategy = 0;             // 0 primal-dual, 1 dual (hipkkt_kkt_set_nonsymmetric_scaling)
-    double ns_mu = 0.0;              // read by the dual strategy only
+    double ns_mu = 0.0;              // read by the dual strategy only, and by the generalized power cones always
+    // generalized power cones (kind 6), k = index among them in cone order: gp_cone[k] = cone, gp_dim1[k] = number of
+    // alphas, gp_off[k] = start of the cone's rows in the concatenated per-row arrays (gp_alpha holds the alphas in the
+    // first dim1 slots of a cone; gp_mapP the K entries of column p; gp_mapQR those of q, then of r).  gp_small lists the
+    // k that one wave takes (numel <= kGenPowWaveMax), gp_big those that take a workgroup.  gp_mu: the mu of the scaling
+    // that the stored p, q, r, d belong to (mul_Hs).
+    const int* gp_cone = nullptr;
+    const int* gp_dim1 = nullptr;
+    const int* gp_off = nullptr;
+    const double* gp_alpha = nullptr;
+    const int* gp_small = nullptr;
+    const int* gp_big = nullptr;
+    const int* gp_mapP = nullptr;
+    const int* gp_mapQR = nullptr;
+    const int* gp_mapD = nullptr;    // three per cone
+    int ngp_small = 0, ngp_big = 0;
+    double gp_mu = 0.0;
 };
+// A generalized power cone of up to this many rows is scaled (and multiplied) by one wave, four cones to a workgroup: 8
+// rows per lane, all loads of a pass in flight at once.  A larger one takes a workgroup of 256 with an LDS stage.
+constexpr int kGenPowWaveMax = 512;
 struct ConeState {
     double* w;                   // m: NN: sqrt(s/z); SOC: normalised w
     double* lam;                 // m: scaled point lambda = W z (NN: sqrt(s z); SOC: coneops_socone.jl:113-123); may be null
@@ -477,6 +496,15 @@ struct ConeState {
     int* fail;                   // set to 1 when a point is not interior
     double* ns_grad = nullptr;   // per exponential / power cone: grad f*(z), 3 doubles
     double* ns_H = nullptr;      // ... and H*(z), 3 x 3
+    // generalized power cones, per row at gp_off: grad f*(z), d = (d1, d2 ...), p, and q followed by r -- all unscaled
+    double* gp_grad = nullptr;
+    double* gp_d = nullptr;
+    double* gp_p = nullptr;
+    double* gp_qr = nullptr;
+    // where their expansion columns go in the same launch: K.nzval and the residual's CSR-ordered copy (put_k)
+    double* Kval = nullptr;
+    double* fval = nullptr;
+    const int* kpos = nullptr;
 };
 constexpr int kPsdMaxDim = 48;   // largest PSD side handled by the in-LDS scaling kernel
 void launch_cone_scaling(const ConeDev& C, const ConeState& S, const double* s, const double* z, int m,

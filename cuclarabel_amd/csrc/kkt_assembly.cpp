@@ -4,6 +4,8 @@
 // (directldl_kkt_assembly.jl:161-165).
 #include "kkt_assembly.hpp"
 
+#include <cmath>
+#include <limits>
 #include <stdexcept>
 #include <string>
 
@@ -15,7 +17,8 @@ static inline int64_t tri(int64_t k) { return k * (k + 1) / 2; }
 
 void assemble_kkt(int64_t n64, int64_t m64, const int64_t* Pp, const int64_t* Pi, const double* Px,
                   const int64_t* Ap, const int64_t* Ai, const double* Ax, int64_t ncones,
-                  const int32_t* kinds, const int64_t* dims, int base, KKTAssembly& K, const double* cone_params)
+                  const int32_t* kinds, const int64_t* dims, int base, KKTAssembly& K, const int64_t* param_ptr,
+                  const double* param_vals)
 {
     K = KKTAssembly();
     if (n64 < 0 || m64 < 0 || n64 + m64 > 1900000000) throw std::runtime_error("kkt: bad dimensions");
@@ -27,19 +30,44 @@ void assemble_kkt(int64_t n64, int64_t m64, const int64_t* Pp, const int64_t* Pi
     for (int64_t c = 0; c < ncones; ++c) {
         ConeInfo ci{};
         ci.kind = kinds[c];
-        if (ci.kind < HIPKKT_CONE_ZERO || ci.kind > HIPKKT_CONE_POW) throw std::runtime_error("kkt: unknown cone kind");
+        if (ci.kind < HIPKKT_CONE_ZERO || ci.kind > HIPKKT_CONE_GENPOW) throw std::runtime_error("kkt: unknown cone kind");
         ci.nsidx = -1;
+        ci.gpidx = -1;
+        const int64_t npar = param_ptr ? param_ptr[c + 1] - param_ptr[c] : 0;
+        const double* par = param_ptr ? param_vals + (param_ptr[c] - base) : nullptr;
+        if (npar < 0 || (npar > 0 && !param_vals)) throw std::runtime_error("kkt: malformed cone_param_ptr / cone_param_vals");
         if (ci.kind == HIPKKT_CONE_EXP || ci.kind == HIPKKT_CONE_POW) {
             if (dims[c] != 3) throw std::runtime_error("kkt: exponential and power cones have dimension 3");
             if (ci.kind == HIPKKT_CONE_POW) {
-                if (!cone_params)
+                if (npar != 1)
                     throw std::runtime_error("kkt: a power cone needs its alpha: use hipkkt_kkt_create_ex with cone_params");
-                ci.param = cone_params[c];
+                ci.param = par[0];
                 if (!(ci.param > 0.0 && ci.param < 1.0)) throw std::runtime_error("kkt: power cone alpha must lie in (0, 1)");
             }
             ci.nsidx = K.nnonsym++;
         }
         if (dims[c] < 0) throw std::runtime_error("kkt: negative cone dimension");
+        if (ci.kind == HIPKKT_CONE_GENPOW) {
+            // GenPowerConeT's constructor (cone_api.jl:37-47); dims[c] = dim1 + dim2
+            if (npar < 1) throw std::runtime_error("kkt: a generalized power cone needs dim1 >= 1 alphas: use hipkkt_kkt_create_ex2");
+            if (dims[c] - npar < 1) throw std::runtime_error("kkt: a generalized power cone needs dim2 = dim - dim1 >= 1");
+            double sum = 0.0;
+            for (int64_t i = 0; i < npar; ++i) {
+                if (!(par[i] > 0.0) || !std::isfinite(par[i]))
+                    throw std::runtime_error("kkt: generalized power cone alphas must be positive and finite");
+                sum += par[i];
+            }
+            if (!(std::fabs(sum - 1.0) <= std::numeric_limits<double>::epsilon() * (double)npar / 2.0))
+                throw std::runtime_error("kkt: generalized power cone alphas must sum to 1");
+            ci.gpidx = K.ngenpow++;
+            ci.dim1 = (int)npar;
+            ci.gpoff = K.genpow_len;
+            ci.gqoff = K.genpow_len1;
+            ci.groff = K.genpow_len - K.genpow_len1;
+            K.genpow_len += (int)dims[c];
+            K.genpow_len1 += (int)npar;
+            K.gp_alpha.insert(K.gp_alpha.end(), par, par + npar);
+        }
         ci.dim = (int)dims[c];
         ci.numel = ci.kind == HIPKKT_CONE_PSD ? (int)tri(dims[c]) : (int)dims[c];
         if (ci.kind == HIPKKT_CONE_SOC && ci.dim < 2) throw std::runtime_error("kkt: second-order cone needs dim >= 2");
@@ -55,11 +83,14 @@ void assemble_kkt(int64_t n64, int64_t m64, const int64_t* Pp, const int64_t* Pi
             ci.soff = K.sparse_len;
             K.sparse_len += ci.numel;
         }
+        // sparse maps are taken in cone order and pcol += pdim(map) (directldl_kkt_assembly.jl:77-98)
+        ci.pcol = K.p;
+        ci.pwidth = ci.sparse ? 2 : ci.kind == HIPKKT_CONE_GENPOW ? 3 : 0;
+        K.p += ci.pwidth;
         K.cones.push_back(ci);
     }
     if (off != m) throw std::runtime_error("kkt: cone dimensions do not sum to m");
     K.nHs = boff;
-    K.p = 2 * K.nsparse;
     const int N = K.N = n + m + K.p;
 
     // ---- the caller's CSC arrays: a wrong index_base or a malformed colptr must end as an argument error, not as
@@ -99,16 +130,17 @@ void assemble_kkt(int64_t n64, int64_t m64, const int64_t* Pp, const int64_t* Pi
         if (r < 0 || r >= m) throw std::runtime_error("kkt: A row index out of range");
         len[n + r] += 1;
     }
-    {
-        int pcol = n + m;
-        for (const ConeInfo& ci : K.cones) {
-            bool dense = cone_is_dense(ci);
-            for (int t = 0; t < ci.numel; ++t) len[n + ci.off + t] += dense ? t + 1 : 1;
-            if (ci.sparse) {
-                len[pcol] += ci.numel + 1;
-                len[pcol + 1] += ci.numel + 1;
-                pcol += 2;
-            }
+    for (const ConeInfo& ci : K.cones) {
+        const int pcol = n + m + ci.pcol;
+        bool dense = cone_is_dense(ci);
+        for (int t = 0; t < ci.numel; ++t) len[n + ci.off + t] += dense ? t + 1 : 1;
+        if (ci.sparse) {
+            len[pcol] += ci.numel + 1;
+            len[pcol + 1] += ci.numel + 1;
+        } else if (ci.kind == HIPKKT_CONE_GENPOW) {          // q, r, p (directldl_datamaps.jl:101-122)
+            len[pcol] += ci.dim1 + 1;
+            len[pcol + 1] += ci.numel - ci.dim1 + 1;
+            len[pcol + 2] += ci.numel + 1;
         }
     }
     K.colptr.assign((size_t)N + 1, 0);
@@ -124,6 +156,10 @@ void assemble_kkt(int64_t n64, int64_t m64, const int64_t* Pp, const int64_t* Pi
     K.mapU.assign((size_t)K.sparse_len, 0);
     K.mapV.assign((size_t)K.sparse_len, 0);
     K.mapD.assign((size_t)2 * K.nsparse, 0);
+    K.mapGP_p.assign((size_t)K.genpow_len, 0);
+    K.mapGP_q.assign((size_t)K.genpow_len1, 0);
+    K.mapGP_r.assign((size_t)(K.genpow_len - K.genpow_len1), 0);
+    K.mapGP_D.assign((size_t)3 * K.ngenpow, 0);
 
     std::vector<int64_t> nxt(K.colptr.begin(), K.colptr.end() - 1);
     auto put = [&](int col, int row, double v) -> int {
@@ -141,8 +177,8 @@ void assemble_kkt(int64_t n64, int64_t m64, const int64_t* Pp, const int64_t* Pi
     for (int j = 0; j < n; ++j)
         for (int64_t q = Ap[j] - base; q < Ap[j + 1] - base; ++q) K.mapA[q] = put(n + (int)(Ai[q] - base), j, Ax[q]);
     // lower-right blocks per cone, then the sparse-expansion columns (v first, then u)
-    int pcol = n + m;
     for (const ConeInfo& ci : K.cones) {
+        const int pcol = n + m + ci.pcol;
         int row0 = n + ci.off;
         int* block = K.mapHs.data() + ci.boff;
         bool dense = cone_is_dense(ci);
@@ -158,7 +194,12 @@ void assemble_kkt(int64_t n64, int64_t m64, const int64_t* Pp, const int64_t* Pi
             for (int t = 0; t < ci.numel; ++t) K.mapU[ci.soff + t] = put(pcol + 1, row0 + t, 0.0);
             K.mapD[2 * ci.sidx] = put(pcol, pcol, 0.0);
             K.mapD[2 * ci.sidx + 1] = put(pcol + 1, pcol + 1, 0.0);
-            pcol += 2;
+        } else if (ci.kind == HIPKKT_CONE_GENPOW) {          // directldl_datamaps.jl:124-144, triu
+            const int d1 = ci.dim1, d2 = ci.numel - ci.dim1;
+            for (int t = 0; t < d1; ++t) K.mapGP_q[ci.gqoff + t] = put(pcol, row0 + t, 0.0);
+            for (int t = 0; t < d2; ++t) K.mapGP_r[ci.groff + t] = put(pcol + 1, row0 + d1 + t, 0.0);
+            for (int t = 0; t < ci.numel; ++t) K.mapGP_p[ci.gpoff + t] = put(pcol + 2, row0 + t, 0.0);
+            for (int t = 0; t < 3; ++t) K.mapGP_D[3 * ci.gpidx + t] = put(pcol + t, pcol + t, 0.0);
         }
     }
     for (int j = 0; j < N; ++j) {
@@ -169,9 +210,16 @@ void assemble_kkt(int64_t n64, int64_t m64, const int64_t* Pp, const int64_t* Pi
     // expected pivot signs
     K.dsigns.assign((size_t)N, 1);
     for (int i = n; i < n + m; ++i) K.dsigns[i] = -1;
-    for (int t = 0; t < K.nsparse; ++t) {
-        K.dsigns[n + m + 2 * t] = -1;          // Dsigns(::SOCExpansionMap) = (-1, 1)
-        K.dsigns[n + m + 2 * t + 1] = 1;
+    for (const ConeInfo& ci : K.cones) {
+        const int pcol = n + m + ci.pcol;
+        if (ci.sparse) {
+            K.dsigns[pcol] = -1;               // Dsigns(::SOCExpansionMap) = (-1, 1)
+            K.dsigns[pcol + 1] = 1;
+        } else if (ci.kind == HIPKKT_CONE_GENPOW) {
+            K.dsigns[pcol] = -1;               // Dsigns(::GenPowExpansionMap) = (-1, -1, 1)
+            K.dsigns[pcol + 1] = -1;
+            K.dsigns[pcol + 2] = 1;
+        }
     }
 }
 

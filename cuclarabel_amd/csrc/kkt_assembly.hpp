@@ -20,6 +20,12 @@ struct ConeInfo {
     int soff;          // offset into the concatenated u / v
     int nsidx;         // index among the exponential / power cones, -1 otherwise
     double param;      // alpha of a power cone
+    // sparse expansion (directldl_datamaps.jl): columns [pcol, pcol + pwidth) behind n + m; a sparse second-order cone
+    // has two, a generalized power cone three, every other cone none
+    int pcol, pwidth;
+    // generalized power cone (kind 6): index among them (-1 otherwise), dim1 = number of alphas, offsets into the
+    // concatenated p (numel per cone), q (dim1 per cone) and r (dim2 per cone)
+    int gpidx, dim1, gpoff, gqoff, groff;
 };
 // cones whose Hs block is a packed dense upper triangle
 inline bool cone_is_dense(const ConeInfo& ci) { return ci.kind == 3 || (ci.kind == 2 && !ci.sparse) || ci.kind == 4 || ci.kind == 5; }
@@ -29,6 +35,8 @@ struct KKTAssembly {
     int64_t nnzK = 0, nHs = 0;
     int nsparse = 0, sparse_len = 0;
     int nnonsym = 0;               // exponential + power cones
+    int ngenpow = 0, genpow_len = 0, genpow_len1 = 0;   // generalized power cones, their rows, their alphas
+    std::vector<double> gp_alpha;  // genpow_len1: the alphas, cone after cone
     std::vector<ConeInfo> cones;
     // triu CSC
     std::vector<int64_t> colptr;
@@ -36,13 +44,17 @@ struct KKTAssembly {
     std::vector<double> nzval;
     // LDLDataMap (directldl_datamaps.jl:170-214)
     std::vector<int> mapP, mapA, mapHs, map_diag, mapU, mapV, mapD;
+    // GenPowExpansionMap (directldl_datamaps.jl:81-99), concatenated in cone order; mapGP_D has three entries per cone
+    std::vector<int> mapGP_p, mapGP_q, mapGP_r, mapGP_D;
     std::vector<int> dsigns;       // kktsolver_directldl.jl:112-126
 };
 
 // P: triu CSC n x n; A: CSC m x n (any index base).  Throws std::runtime_error on bad input.
+// param_ptr (ncones + 1 offsets in the same base) / param_vals: the ragged cone parameters -- one alpha for a power cone,
+// dim1 alphas for a generalized power cone, none for every other kind.
 void assemble_kkt(int64_t n, int64_t m, const int64_t* Pp, const int64_t* Pi, const double* Px,
                   const int64_t* Ap, const int64_t* Ai, const double* Ax, int64_t ncones,
                   const int32_t* kinds, const int64_t* dims, int base, KKTAssembly& K,
-                  const double* cone_params = nullptr);
+                  const int64_t* param_ptr = nullptr, const double* param_vals = nullptr);
 
 }  // namespace hipkkt

@@ -14,6 +14,7 @@ SecondOrder / PSDTriangle / Exponential / Power cones, without presolve, equilib
     PSD cone                        coneops_psdtrianglecone.jl:8-44 (margins, shift), :78-143 (scaling), :164-254,
                                     :299-466 (mul_Hs!, ds offsets, W / W^-1, Jordan product, step length)
 
+    generalized power cones         coneops_genpowcone.jl (dual scaling only, no higher-order correction)
     exponential / power cones       coneops_expcone.jl, coneops_powcone.jl, coneops_nonsymmetric_common.jl; the loop's
                                     branches for them: solver.jl:221 (strategy), :383-404 (unit start), :407-442 (barrier
                                     backtrack), :453-504 (checkpoints), variables.jl:46-72.  They fire only when such a cone
@@ -33,7 +34,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from .cones import (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT,
-                    ExponentialConeT, PowerConeT)
+                    ExponentialConeT, PowerConeT, GenPowerConeT)
 
 SOLVED, PRIMAL_INFEASIBLE, DUAL_INFEASIBLE = "SOLVED", "PRIMAL_INFEASIBLE", "DUAL_INFEASIBLE"
 MAX_ITERATIONS, NUMERICAL_ERROR, INSUFFICIENT_PROGRESS, UNSOLVED = \
@@ -822,12 +823,170 @@ class _Pow(_NonSym):
         return (np.array([e0, e1, e2]) + Hu * dpv * ip2) / 2
 
 
+def _newton_raphson_genpowcone(norm_r, p, phi, alpha, psi):   # coneops_genpowcone.jl:437-472
+    x0 = -1.0 / norm_r + (psi * norm_r + np.sqrt((phi / norm_r / norm_r + psi * psi - 1.0) * phi)) / (phi - norm_r * norm_r)
+
+    def f0(x):
+        out = -_logsafe(2 * x / norm_r + x * x)
+        for i in range(len(alpha)):
+            out += 2 * alpha[i] * (_logsafe(x * norm_r + (1 + alpha[i]) / alpha[i]) - _logsafe(p[i]))
+        return out
+
+    def f1(x):
+        out = -(2 * x + 2 / norm_r) / (x * x + 2 * x / norm_r)
+        for i in range(len(alpha)):
+            out += 2 * alpha[i] * norm_r / (norm_r * x + (1 + alpha[i]) / alpha[i])
+        return out
+
+    # the one-sided iteration needs f0(x0) > 0 (it stops at the first non-positive step); f0 -> +Inf as x -> 0+, so a
+    # start right of the root is halved until it is left of it -- the guard _newton_raphson_powcone has
+    k = 0
+    while k < 64 and not f0(x0) > 0:
+        x0, k = 0.5 * x0, k + 1
+    return _newton_raphson_onesided(x0, f0, f1)
+
+
+class _GenPow(_NonSym):
+    """Primal: prod_i s_i^a_i >= ||s[d1:]||, s[:d1] >= 0.  Dual: prod_i (z_i/a_i)^a_i >= ||z[d1:]||, z[:d1] >= 0.
+    Dual barrier f*(z) = -log(prod_i (z_i/a_i)^(2 a_i) - ||z[d1:]||^2) - sum_i (1 - a_i) log z_i
+    (coneops_genpowcone.jl).  Dual scaling only (allows_primal_dual_scaling is false): Hs = mu H*(z) =
+    mu (diag(d) + p p' - q q' - r r'), which enters K as a diagonal block and three expansion columns."""
+
+    def __init__(self, spec, off):
+        super().__init__(spec, off)
+        self.alpha = np.array(spec.alpha, dtype=np.float64)
+        self.d1, self.d2 = len(spec.alpha), int(spec.dim2)
+        self.degree = self.d1 + 1
+        self.psi = 1.0 / float(self.alpha @ self.alpha)          # cone_types.jl:301
+        self.mu = 1.0
+
+    def unit_initialization(self):                       # :34-53
+        s = np.concatenate([np.sqrt(1.0 + self.alpha), np.zeros(self.d2)])
+        return s.copy(), s
+
+    def dual_grad_H(self, z):                            # update_dual_grad_H, :336-389: (grad, (d, p, q, r))
+        a, d1 = self.alpha, self.d1
+        z = np.asarray(z, dtype=np.float64)
+        phi = 1.0
+        for i in range(d1):
+            phi *= (z[i] / a[i]) ** (2 * a[i])
+        norm2w = 0.0
+        for i in range(d1, self.n):
+            norm2w += z[i] * z[i]
+        zeta = phi - norm2w
+        u, w = z[:d1], z[d1:]
+        tau = 2 * a / u
+        grad = np.concatenate([-tau * phi / zeta - (1 - a) / u, 2 * w / zeta])
+        p0 = np.sqrt(phi * (phi + norm2w) / 2)
+        p1 = -2 * phi / p0
+        q0 = np.sqrt(zeta * phi / 2)
+        r1 = 2 * np.sqrt(zeta / (phi + norm2w))
+        dd = np.concatenate([tau * phi / (zeta * u) + (1 - a) / (u * u), np.full(self.d2, 2 / zeta)])
+        p = np.concatenate([p0 * tau / zeta, p1 * w / zeta])
+        q = tau * (q0 / zeta)
+        r = r1 * w / zeta
+        self.zeta = zeta
+        return grad, (dd, p, q, r)
+
+    def update_scaling(self, s, z, mu, strategy):        # :64-82; the strategy is not read
+        with np.errstate(all="ignore"):
+            z = np.asarray(z, dtype=np.float64)
+            self.grad, (self.d, self.p, self.q, self.r) = self.dual_grad_H(z)
+            self.mu = mu
+            self.z = z.copy()
+            self.used_primal_dual = False
+        # (the reference asserts zeta > 0 here)
+        return bool(self.zeta > 0 and np.all(z[:self.d1] > 0) and np.all(np.isfinite(self.p)))
+
+    @property
+    def H_dual(self):                                    # dense H*(z), for tests
+        P = np.diag(self.d) + np.outer(self.p, self.p)
+        P[:self.d1, :self.d1] -= np.outer(self.q, self.q)
+        P[self.d1:, self.d1:] -= np.outer(self.r, self.r)
+        return P
+
+    @property
+    def Hs(self):
+        return self.mu * self.H_dual
+
+    def get_Hs(self):                                    # :91-108: the diagonal block only
+        return self.mu * self.d
+
+    def sparse_data(self):                               # _csc_update_sparsecone: (q, r, p) scaled by -sqrt(mu), D
+        sm = -np.sqrt(self.mu)
+        return self.q * sm, self.r * sm, self.p * sm, np.array([-1.0, -1.0, 1.0])
+
+    def mul_Hs(self, x):                                 # :110-135
+        d1 = self.d1
+        cp, cq, cr = self.p @ x, self.q @ x[:d1], self.r @ x[d1:]
+        y = self.d * x
+        y[:d1] -= cq * self.q
+        y[d1:] -= cr * self.r
+        y += cp * self.p
+        return y * self.mu
+
+    def combined_ds_shift(self, dz, ds, sigma_mu):       # :149-168: no higher-order correction
+        return self.grad * sigma_mu
+
+    def _phi2(self, v, scaled):                          # exp(sum 2 a_i log(v_i [/ a_i])) - ||v[d1:]||^2
+        a, d1 = self.alpha, self.d1
+        res = 0.0
+        for i in range(d1):
+            res += 2 * a[i] * _logsafe(v[i] / a[i] if scaled else v[i])
+        return np.exp(res) - float(v[d1:] @ v[d1:])
+
+    def is_primal_feasible(self, s):                     # :249-269
+        return bool(np.all(s[:self.d1] > 0) and self._phi2(s, False) > 0)
+
+    def is_dual_feasible(self, z):                       # :272-292
+        return bool(np.all(z[:self.d1] > 0) and self._phi2(z, True) > 0)
+
+    def barrier_dual(self, z):                           # :313-333
+        out = -_logsafe(self._phi2(z, True))
+        for i in range(self.d1):
+            out -= (1 - self.alpha[i]) * _logsafe(z[i])
+        return out
+
+    def barrier_primal(self, s):                         # :294-310
+        return -self.barrier_dual(-self.gradient_primal(s)) - self.degree
+
+    def gradient_primal(self, s):                        # :393-426
+        a, d1 = self.alpha, self.d1
+        s = np.asarray(s, dtype=np.float64)
+        phi = 1.0
+        for i in range(d1):
+            phi *= s[i] ** (2 * a[i])
+        pp, rr = s[:d1], s[d1:]
+        norm_r = float(np.sqrt(rr @ rr))
+        g = np.zeros(self.n)
+        if norm_r > _EPS:
+            g1 = _newton_raphson_genpowcone(norm_r, pp, phi, a, self.psi)
+            g[d1:] = g1 * rr / norm_r
+            g[:d1] = -(1 + a + a * g1 * norm_r) / pp
+        else:
+            g[:d1] = -(1 + a) / pp
+        return g
+
+    def higher_correction(self, ds, v):
+        return np.zeros(self.n)
+
+
 def adopt_device_scaling(cones, dev_scaling):
     """Give the host PSD cone objects the (R, Rinv, lambda) triples `HipKKTSolver.scaling()` returns."""
     it = iter(dev_scaling)
     for c in cones:
         if isinstance(c, _PSD):
             c.R, c.Rinv, c.lam = next(it)
+
+
+def adopt_device_genpow(cones, dev_genpow):
+    """Give the host generalized power cones the (grad, d, p, q, r) `HipKKTSolver.genpow()` returns.  In the reference
+    one cone object serves K, mul_Hs! and combined_ds_shift!.  zeta = phi - ||w||^2 cancels towards the boundary, so a
+    host scaling that reduces phi in another order than the device differs from the device's by eps phi / zeta, and
+    ds = -(Hs dz + ...) formed with it does not belong to the dz that the device's K gave: the primal residual then
+    stops falling short of the tolerance."""
+    for c, (grad, d, p, q, r) in zip([c for c in cones if isinstance(c, _GenPow)], dev_genpow):
+        c.grad, c.d, c.p, c.q, c.r = grad, d, p, q, r
 
 
 def host_cone_data(cones):
@@ -869,9 +1028,11 @@ def _make_cones(specs):
             out.append(_Exp(c, off))
         elif isinstance(c, PowerConeT):
             out.append(_Pow(c, off))
+        elif isinstance(c, GenPowerConeT):
+            out.append(_GenPow(c, off))
         else:
             raise NotImplementedError("the IPM test driver covers Zero, Nonnegative, SecondOrder, PSDTriangle, "
-                                      "Exponential and Power cones")
+                                      "Exponential, Power and GenPower cones")
         off += c.numel
     return out
 
@@ -1099,6 +1260,9 @@ def solve(P, q, A, b, cone_specs, backend, settings=None):
             ok = backend.update(s, z, mu=mu, strategy=strategy) if nonsym else backend.update(s, z)
             if ok:
                 ok, x2, z2 = ksolve(-q, b)
+
+        if ok and hasattr(backend, "ks") and any(isinstance(c, _GenPow) for c in cones):
+            adopt_device_genpow(cones, backend.ks.genpow())
 
         def kkt_solve(rhs_x, rhs_z, rhs_s, rhs_tau, rhs_kappa, affine, lhs_z_work=None):   # kktsystem.jl:135-215
             nonlocal ir_total

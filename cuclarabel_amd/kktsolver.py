@@ -14,7 +14,7 @@ import scipy.sparse as sp
 
 from . import _lib
 from ._lib import check, f64, i64, ptr
-from .cones import cone_kinds_dims, cone_params, KIND_EXP, KIND_POW
+from .cones import cone_kinds_dims, cone_param_ptr_vals, KIND_EXP, KIND_POW, KIND_GENPOW
 
 
 class LinearSolverInfo:
@@ -48,11 +48,11 @@ class HipKKTSolver:
         self._h = C.c_void_p()
         Pp, Pi, Px = i64(P.indptr), i64(P.indices), f64(P.data)
         Ap, Ai, Ax = i64(A.indptr), i64(A.indices), f64(A.data)
-        if any(c.kind == KIND_POW for c in self.cones):          # a power cone's alpha travels through _ex only
-            params = cone_params(self.cones)
-            rc = L.hipkkt_kkt_create_ex(C.byref(self._h), self.n, self.m, ptr(Pp), ptr(Pi), ptr(Px),
-                                        ptr(Ap), ptr(Ai), ptr(Ax), len(self.cones), ptr(kinds), ptr(dims), ptr(params),
-                                        C.byref(self.settings), 0)
+        pptr, pvals = cone_param_ptr_vals(self.cones)
+        if len(pvals):                                           # cone parameters travel through _ex2 only
+            rc = L.hipkkt_kkt_create_ex2(C.byref(self._h), self.n, self.m, ptr(Pp), ptr(Pi), ptr(Px),
+                                         ptr(Ap), ptr(Ai), ptr(Ax), len(self.cones), ptr(kinds), ptr(dims), ptr(pptr),
+                                         ptr(pvals), C.byref(self.settings), 0)
         else:
             rc = L.hipkkt_kkt_create(C.byref(self._h), self.n, self.m, ptr(Pp), ptr(Pi), ptr(Px),
                                      ptr(Ap), ptr(Ai), ptr(Ax), len(self.cones), ptr(kinds), ptr(dims),
@@ -201,6 +201,12 @@ class HipKKTSolver:
                    soc_D=np.zeros(2 * i["nsparse_soc"], np.int64), dsigns=np.zeros(self.N, np.int64))
         check(_lib.lib().hipkkt_kkt_get_maps(self._h, *[ptr(out[k]) for k in
               ("P", "A", "Hsblocks", "diag_full", "soc_u", "soc_v", "soc_D", "dsigns")]), "hipkkt_kkt_get_maps")
+        gp = [c for c in self.cones if c.kind == KIND_GENPOW]
+        if gp:
+            out.update(genpow_p=np.zeros(sum(c.dim for c in gp), np.int64), genpow_q=np.zeros(sum(c.dim1 for c in gp), np.int64),
+                       genpow_r=np.zeros(sum(c.dim2 for c in gp), np.int64), genpow_D=np.zeros(3 * len(gp), np.int64))
+            check(_lib.lib().hipkkt_kkt_get_genpow_maps(self._h, *[ptr(out[k]) for k in
+                  ("genpow_p", "genpow_q", "genpow_r", "genpow_D")]), "hipkkt_kkt_get_genpow_maps")
         return out
 
     def perm(self):
@@ -236,6 +242,21 @@ class HipKKTSolver:
         grad, H = np.zeros(max(3 * k, 1)), np.zeros(max(9 * k, 1))
         check(_lib.lib().hipkkt_kkt_get_nonsymmetric(self._h, ptr(grad), ptr(H)), "hipkkt_kkt_get_nonsymmetric")
         return grad[:3 * k].reshape(k, 3), H[:9 * k].reshape(k, 3, 3)
+
+    def genpow(self):
+        """[(grad, d, p, q, r) per generalized power cone], in cone order, after a device-side scaling: all unscaled,
+        Hs = mu (diag(d) + p p' - q q' - r r'); d is (d1, then d2 repeated)."""
+        gp = [c for c in self.cones if c.kind == KIND_GENPOW]
+        n, n1 = sum(c.dim for c in gp), sum(c.dim1 for c in gp)
+        grad, d, p = np.zeros(max(n, 1)), np.zeros(max(n, 1)), np.zeros(max(n, 1))
+        q, r = np.zeros(max(n1, 1)), np.zeros(max(n - n1, 1))
+        check(_lib.lib().hipkkt_kkt_get_genpow(self._h, ptr(grad), ptr(d), ptr(p), ptr(q), ptr(r)), "hipkkt_kkt_get_genpow")
+        out, o, o1, o2 = [], 0, 0, 0
+        for c in gp:
+            out.append((grad[o:o + c.dim].copy(), d[o:o + c.dim].copy(), p[o:o + c.dim].copy(),
+                        q[o1:o1 + c.dim1].copy(), r[o2:o2 + c.dim2].copy()))
+            o, o1, o2 = o + c.dim, o1 + c.dim1, o2 + c.dim2
+        return out
 
     def scaling_w(self):
         """(w (m), eta (per cone)) of the device's NT scaling."""

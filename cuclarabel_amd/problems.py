@@ -11,7 +11,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from .cones import (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT, ExponentialConeT,
-                    total_numel)
+                    GenPowerConeT, total_numel)
 
 
 @dataclass
@@ -415,3 +415,57 @@ def entropy_maximization(ncones=20_000, nrows=4, seed=3001):
     s0 = np.concatenate([np.zeros(1 + nrows), np.tile(unit, N)])
     return Problem(f"entropy_{N}", P, q, A, b, cones, s0, s0.copy(), np.zeros(2 * N),
                    meta=dict(seed=seed, ncones=N, nrows=nrows))
+
+
+def normalised_alphas(a):
+    """Positive weights scaled to sum to one within GenPowerConeT's tolerance (eps len / 2, summed left to right): the
+    last weight takes up the rounding of the others."""
+    a = np.array(a, dtype=np.float64)
+    a /= a.sum()
+    t = 0.0
+    for v in a[:-1]:
+        t += float(v)
+    a[-1] = 1.0 - t
+    return a
+
+
+# (dim1, dim2) of generalized_power_mix: every dimension at 1, 63, 64 and 65 -- the lanes of a wave -- and cones on both
+# sides of the 512 rows up to which the device gives a cone one wave
+GENPOW_MIX_SHAPES = ((1, 1), (2, 1), (1, 63), (63, 1), (64, 1), (1, 64), (65, 2), (3, 65), (32, 32), (31, 32), (33, 32),
+                     (200, 312), (256, 257), (300, 400), (10, 600), (5, 3))
+
+
+def generalized_power_mix(copies=4, seed=3101, shapes=GENPOW_MIX_SHAPES):
+    """Many generalized power cones of mixed sizes: for every cone k with weights alpha_k, a point u_k on the simplex
+    and w_k under its weighted geometric mean,
+
+        minimise  -sum_k c_k' w_k   s.t.  sum(u_k) = dim1_k,  (u_k, w_k) in K_genpow(alpha_k, dim2_k)
+
+    with unit vectors c_k, so the optimum is finite (||w_k|| <= prod u_k,i^alpha_k,i <= dim1_k) and u_k stays of order one
+    whatever dim1_k is.  Variables (u_k, w_k) cone
+    after cone; rows: one zero-cone row per cone, then the cones' own rows (s = x).  (s0, z0) is the reference's unit
+    initialisation (coneops_genpowcone.jl:34-53), x0 = 0."""
+    rng = np.random.default_rng(seed)
+    specs = []
+    for _ in range(copies):
+        for d1, d2 in shapes:
+            specs.append(GenPowerConeT(normalised_alphas(rng.uniform(0.5, 1.5, size=d1)), d2))
+    n = sum(c.dim for c in specs)
+    q = np.zeros(n)
+    rows, cols = [], []
+    off = 0
+    for k, c in enumerate(specs):
+        v = rng.standard_normal(c.dim2)
+        q[off + c.dim1:off + c.dim] = -v / np.linalg.norm(v)
+        rows += [k] * c.dim1
+        cols += list(range(off, off + c.dim1))
+        off += c.dim
+    Aeq = sp.csr_matrix((np.ones(len(rows)), (rows, cols)), shape=(len(specs), n))
+    A = _csc(sp.vstack([Aeq, -sp.identity(n, format="csr")]))
+    b = np.concatenate([np.array([float(c.dim1) for c in specs]), np.zeros(n)])
+    P = _triu_csc(sp.csc_matrix((n, n)))
+    cones = [ZeroConeT(len(specs))] + specs
+    s0 = np.concatenate([np.zeros(len(specs))] +
+                        [np.concatenate([np.sqrt(1.0 + np.array(c.alpha)), np.zeros(c.dim2)]) for c in specs])
+    return Problem(f"genpow_mix_{len(specs)}", P, q, A, b, cones, s0, s0.copy(), np.zeros(n),
+                   meta=dict(seed=seed, copies=copies, ncones=len(specs)))

@@ -53,6 +53,12 @@ extern "C" {
  * through hipkkt_kkt_create_ex. */
 #define HIPKKT_CONE_EXP 4
 #define HIPKKT_CONE_POW 5
+/* the generalized power cone (coneops_genpowcone.jl): prod_i s_i^alpha_i >= ||s[dim1:]||, s[:dim1] >= 0.  dims[] is
+ * dim1 + dim2; dim1 is the number of alphas the cone gets through hipkkt_kkt_create_ex2.  It has no unexpanded form:
+ * its rows carry a DIAGONAL Hs block and K gets three expansion columns behind n + m -- q (rows 0 .. dim1 of the cone),
+ * r (rows dim1 .. dim), p (all rows) -- with Dsigns (-1, -1, +1), in cone order among the sparse second-order cones'
+ * pairs of columns (directldl_datamaps.jl:81-167). */
+#define HIPKKT_CONE_GENPOW 6
 
 /* scaling strategy of the non-symmetric cones (types.jl:74) */
 #define HIPKKT_SCALING_PRIMAL_DUAL 0
@@ -179,6 +185,21 @@ int hipkkt_kkt_create_ex(hipkkt_kkt_t *out, int64_t n, int64_t m,
                          const int64_t *Acolptr, const int64_t *Arowval, const double *Anzval,
                          int64_t ncones, const int32_t *cone_kinds, const int64_t *cone_dims,
                          const double *cone_params, const hipkkt_settings *settings, int index_base);
+/* hipkkt_kkt_create_ex with RAGGED cone parameters: cone c has the values cone_param_vals[cone_param_ptr[c] ..
+ * cone_param_ptr[c + 1]) (ncones + 1 offsets in index_base).  A power cone has one value (alpha), a generalized power
+ * cone its dim1 >= 1 values of alpha, every other kind none.  Both may be NULL when no cone has a parameter.  A
+ * generalized power cone is validated as GenPowerConeT is (cone_api.jl:37-47): every alpha positive and finite,
+ * |sum(alpha) - 1| <= eps dim1 / 2, and dim2 = cone_dims[c] - dim1 >= 1.
+ * hipkkt_kkt_create and hipkkt_kkt_create_ex forward here; given HIPKKT_CONE_GENPOW they return HIPKKT_ERR_ARG.
+ * A handle that holds a generalized power cone is scaled on the device only (hipkkt_kkt_update_from_sz[_dev],
+ * hipkkt_kkt_system_update*): hipkkt_kkt_update_cones, hipkkt_kkt_system_update_cones and
+ * hipkkt_kkt_system_update_scaling have no way to receive its p, q, r and return HIPKKT_ERR_ARG on it. */
+int hipkkt_kkt_create_ex2(hipkkt_kkt_t *out, int64_t n, int64_t m,
+                          const int64_t *Pcolptr, const int64_t *Prowval, const double *Pnzval,
+                          const int64_t *Acolptr, const int64_t *Arowval, const double *Anzval,
+                          int64_t ncones, const int32_t *cone_kinds, const int64_t *cone_dims,
+                          const int64_t *cone_param_ptr, const double *cone_param_vals,
+                          const hipkkt_settings *settings, int index_base);
 void hipkkt_kkt_destroy(hipkkt_kkt_t h);
 int hipkkt_kkt_info(hipkkt_kkt_t h, hipkkt_info *info);
 
@@ -354,6 +375,8 @@ int hipkkt_kkt_get_values(hipkkt_kkt_t h, double *nzval /* nnzK, un-regularised 
 int hipkkt_kkt_get_maps(hipkkt_kkt_t h, int64_t *mapP, int64_t *mapA, int64_t *mapHs,
                         int64_t *map_diag_full, int64_t *map_soc_u, int64_t *map_soc_v,
                         int64_t *map_soc_D, int64_t *dsigns);   /* any may be NULL */
+/* the GenPowExpansionMaps, concatenated in cone order: p (dim per cone), q (dim1), r (dim2), D (3); any may be NULL */
+int hipkkt_kkt_get_genpow_maps(hipkkt_kkt_t h, int64_t *map_p, int64_t *map_q, int64_t *map_r, int64_t *map_D);
 int hipkkt_kkt_get_perm(hipkkt_kkt_t h, int64_t *perm /* N, 0-based */);
 int hipkkt_kkt_get_Hs(hipkkt_kkt_t h, double *Hsblocks /* |Hs|, positive */);
 /* the NT scaling held on the device after hipkkt_kkt_update_from_sz*: the scaled point lambda (length m; a PSD cone
@@ -366,12 +389,19 @@ int hipkkt_kkt_get_scaling_w(hipkkt_kkt_t h, double *w, double *eta);
  * 50-67): strategy HIPKKT_SCALING_PRIMAL_DUAL (the default; mu is not read, the cone's own <s,z>/3 is used, :97-98) or
  * HIPKKT_SCALING_DUAL (Hs = mu H*(z)).  Host-only, no device work: call it once per iteration before
  * hipkkt_kkt_update_from_sz[_dev], hipkkt_kkt_system_update[_host] or hipkkt_kkt_system_update_and_solve_affine, in
- * lazy mode too.  On a handle without such cones it does nothing and returns 0. */
+ * lazy mode too.  On a handle without such cones it does nothing and returns 0.
+ * A generalized power cone always takes Hs = mu H*(z) (allows_primal_dual_scaling is false, coneops_genpowcone.jl:21):
+ * mu is read for it under BOTH strategies. */
 int hipkkt_kkt_set_nonsymmetric_scaling(hipkkt_kkt_t h, int strategy, double mu);
 /* After a device-side scaling: grad f*(z) (3 doubles) and the Hessian H*(z) (9 doubles, symmetric) of every exponential
  * and power cone, in cone order -- K.grad and K.H_dual, which combined_ds_shift! reads.  Either may be NULL.  The caller sizes
  * the arrays from its own cone list. */
 int hipkkt_kkt_get_nonsymmetric(hipkkt_kkt_t h, double *grad, double *H_dual);
+/* After a device-side scaling, for the generalized power cones, concatenated in cone order: grad f*(z) (dim per cone --
+ * K.data.grad, which combined_ds_shift! reads), d (dim per cone: d1, then d2 repeated dim2 times), p (dim), q (dim1),
+ * r (dim2), all unscaled: Hs = mu (diag(d) + p p' - q q' - r r') (update_dual_grad_H, coneops_genpowcone.jl:336-389).
+ * Any may be NULL.  hipkkt_kkt_get_nonsymmetric covers the exponential and power cones only. */
+int hipkkt_kkt_get_genpow(hipkkt_kkt_t h, double *grad, double *d, double *p, double *q, double *r);
 double hipkkt_kkt_last_regularizer(hipkkt_kkt_t h);
 int64_t hipkkt_kkt_last_ir_iterations(hipkkt_kkt_t h);
 /* (tests) the refinement rounds a solve enqueues ahead of its first status read-back -- what the previous solves took

@@ -28,7 +28,7 @@ import Clarabel: linear_solver_info, update_values!, scale_values!, refactor!, s
 import Clarabel: kktsolver_update!, kktsolver_setrhs!, kktsolver_solve!, kktsolver_update_P!,
                  kktsolver_update_A!, kktsolver_linear_solver_info
 import Clarabel: CompositeCone, ZeroCone, NonnegativeCone, SecondOrderCone, PSDTriangleCone,
-                 ExponentialCone, PowerCone, get_Hs!, is_sparse_expandable, numel
+                 ExponentialCone, PowerCone, GenPowerCone, get_Hs!, is_sparse_expandable, numel
 
 const libhipkkt = get(ENV, "HIPKKT_LIB", "libhipkkt.so")
 
@@ -143,26 +143,30 @@ mutable struct HipKKTSolver{T} <: AbstractKKTSolver{T}
                              m::DefaultInt, n::DefaultInt, settings::Settings{T}) where {T}
         T === Float64 || error("hipkkt supports Float64 only")
         kinds = Int32[]; dims = Int64[]
-        params = zeros(Float64, length(cones))      # alpha of a power cone (hipkkt_kkt_create_ex), 0 otherwise
+        # ragged cone parameters of hipkkt_kkt_create_ex2: one alpha for a power cone, dim1 alphas for a generalized
+        # power cone, none otherwise; offsets 1-based like every index handed over here
+        pptr = Int64[1]; pvals = Float64[]
         for (i, c) in enumerate(cones)
             if     c isa ZeroCone         push!(kinds, 0); push!(dims, numel(c))
             elseif c isa NonnegativeCone  push!(kinds, 1); push!(dims, numel(c))
             elseif c isa SecondOrderCone  push!(kinds, 2); push!(dims, numel(c))
             elseif c isa PSDTriangleCone  push!(kinds, 3); push!(dims, c.n)
             elseif c isa ExponentialCone  push!(kinds, 4); push!(dims, 3)
-            elseif c isa PowerCone        push!(kinds, 5); push!(dims, 3); params[i] = c.α
+            elseif c isa PowerCone        push!(kinds, 5); push!(dims, 3); push!(pvals, c.α)
+            elseif c isa GenPowerCone     push!(kinds, 6); push!(dims, numel(c)); append!(pvals, c.α)
             else error("hipkkt: cone type $(typeof(c)) is not supported")
             end
+            push!(pptr, length(pvals) + 1)
         end
         h = Ref{Ptr{Cvoid}}(C_NULL)
         cs = Ref(csettings(settings))
         Pt = triu(P)                                # data.P is already triu; harmless otherwise
-        rc = GC.@preserve Pt A kinds dims params ccall((:hipkkt_kkt_create_ex, libhipkkt), Cint,
+        rc = GC.@preserve Pt A kinds dims pptr pvals ccall((:hipkkt_kkt_create_ex2, libhipkkt), Cint,
             (Ref{Ptr{Cvoid}}, Int64, Int64, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble},
-             Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Cdouble}, Ref{CSettings}, Cint),
+             Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Int64, Ptr{Int32}, Ptr{Int64}, Ptr{Int64}, Ptr{Cdouble}, Ref{CSettings}, Cint),
             h, n, m, Pt.colptr, Pt.rowval, Pt.nzval, A.colptr, A.rowval, A.nzval,
-            length(kinds), kinds, dims, params, cs, 1)
-        check(rc, "hipkkt_kkt_create_ex") || error("hipkkt_kkt_create_ex: numeric failure")
+            length(kinds), kinds, dims, pptr, pvals, cs, 1)
+        check(rc, "hipkkt_kkt_create_ex2") || error("hipkkt_kkt_create_ex2: numeric failure")
         info = Ref{CInfo}()
         check(ccall((:hipkkt_kkt_info, libhipkkt), Cint, (Ptr{Cvoid}, Ref{CInfo}), h[], info), "hipkkt_kkt_info")
         obj = new(h[], m, n, zeros(T, info[].nHs), zeros(T, info[].sparse_soc_len),
@@ -296,6 +300,12 @@ kkt_update_A!(s::HipKKTSystem{T}, A::SparseMatrixCSC{T}) where {T} = kktsolver_u
 # caller that wants the reference's own rounding of those blocks.)
 function kkt_update!(s::HipKKTSystem{T}, data::DefaultProblemData{T}, cones::CompositeCone{T}) where {T}
     ks = s.kktsolver
+    if any(c -> c isa GenPowerCone, cones)
+        # p, q, r of a generalized power cone have no slot in the caller-scaled entry points (they return HIPKKT_ERR_ARG on
+        # such a handle): the supported route is the device-scaled one, hipkkt_kkt_set_nonsymmetric_scaling(h, strategy, mu)
+        # then hipkkt_kkt_system_update_host(h, s, z), which needs the iterate -- kkt_update! does not get it (solver.jl:279).
+        error("hipkkt: a problem with a GenPowerCone must be updated from (s, z): hipkkt_kkt_system_update_host")
+    end
     if any(c -> c isa ExponentialCone || c isa PowerCone, cones)
         # (w, eta, lambda, R) cannot carry an exponential / power cone's 3 x 3 block, and the cone objects were scaled on
         # the host by update_scaling!(cones, s, z, mu, strategy) already: their get_Hs! block IS the scaling, and the
