@@ -820,6 +820,39 @@ private:
             r.off[0] = Lb.rec.off[0]; r.stride[0] = Lb.rec.stride[0]; r.fmax[0] = Lb.rec.fmax[0];
             return r;
         };
+        // diagnostic (HIPKKT_VERBOSE): which path this sweep takes, once per distinct plan of this engine -- the three
+        // launch ranges, the persistent kernel and its grid, whether W was still pending and the record layout; at level 2
+        // the kernel family and workgroup size of every per-level launch as well (the tests' way to assert a path)
+        if (knobs().verbose >= 1) {
+            const bool sliced = ntl > 0 && top_ntask > 0;
+            const int pgrid = ntl == 0 ? 0 : (sliced ? (nr == 2 ? top_sgrid2 : top_sgrid) : std::min(tgrid, ncount));
+            char buf[256];
+            std::snprintf(buf, sizeof buf, "nr %d per-level [0,%zu) chained [%zu,%zu) persistent [%zu,%zu) grid %d kernel %s threads %d w_pending %d packed %d",
+                          nr, nper, nper, nl - ntl, nl - ntl, nl, pgrid, ntl == 0 ? "none" : (sliced ? "sliced" : "top"),
+                          ntl == 0 ? 0 : (sliced || top_tall ? 1024 : 512), w_pending ? 1 : 0, a.recs ? 1 : 0);
+            bool seen = false;
+            for (const std::string& s : sweep_plans_seen) seen = seen || s == buf;
+            if (!seen) {
+                sweep_plans_seen.push_back(buf);
+                std::fprintf(stderr, "[hipkkt] sweep plan: %s\n", buf);
+                if (knobs().verbose >= 2)
+                    for (size_t q = 0; q < nper; ++q) {
+                        const Launch& L = launches[q];
+                        if (pair_at(q)) {
+                            const Launch& Ls = launches[q + 1];
+                            std::fprintf(stderr, "[hipkkt] sweep launch %zu+%zu level %d: family level solve_bs %d fmax %d block %d wave %d tiny %d\n", q, q + 1,
+                                         L.level, L.solve_bs, std::max(L.fmax, Ls.fmax), L.count, Ls.count - Ls.ntiny, Ls.ntiny);
+                            ++q;
+                        } else if (L.small) {
+                            std::fprintf(stderr, "[hipkkt] sweep launch %zu level %d: family small solve_bs 256 fmax %d block 0 wave %d tiny %d\n", q, L.level,
+                                         L.fmax, L.count - L.ntiny, L.ntiny);
+                        } else {
+                            std::fprintf(stderr, "[hipkkt] sweep launch %zu level %d: family %s solve_bs %d fmax %d block %d wave 0 tiny 0\n", q, L.level,
+                                         L.ntall == 0 ? "block" : (L.ntall == L.count ? "tall" : "block+tall"), L.solve_bs, L.fmax, L.count);
+                        }
+                    }
+            }
+        }
         bool chain_stamp = false;
         ChainArgs ca;
         int ca_wgs = 0;
@@ -1027,8 +1060,9 @@ private:
         HIP_CHECK(hipGetLastError());
     }
 
+    std::vector<std::string> sweep_plans_seen;      // (HIPKKT_VERBOSE: the plans enqueue_solve has printed)
     // the side stream may still be forming the top fronts' solve matrices (enqueue_factor)
-    bool w_pending = false, w2_pending = false;     // (w2: the last formation rode on the tile stream: ev_join2)
+    bool w_pending = false, w2_pending = false;    // (w2: the last formation rode on the tile stream: ev_join2)
     void wait_w(hipStream_t st)
     {
         if (!w_pending) return;

@@ -328,6 +328,106 @@ def solve_bs_table():
     return {f"solve_bs_{n}": (designed(40, 0, n), (n, 40, 40, 0, n), "block") for n in (1023, 1024)}
 
 
+# --------------------------------------------------------------------------- forests for the sweep-path tests
+# (tests/test_gpu_sweep_paths.py): the constructors above side by side, so that a LEVEL holds a chosen number of fronts
+# of chosen classes, and towers tall enough for a chained range below a persistent set.
+def forest(*parts):
+    """Independent trees side by side: the specs concatenated, parent indices shifted."""
+    spec = []
+    for part in parts:
+        b = len(spec)
+        spec += [(nc, nb, p if p < 0 else p + b) for nc, nb, p in part]
+    return spec
+
+
+def tower(links):
+    """One tree that is a chain of fronts, lowest first: links = [(nc, nb), ..., (nc, 0)].  A link's nb rows are the
+    first nb columns of the link above it; every link must stay out of the one above (stays_separate)."""
+    for (nc, nb), (rp, sp) in zip(links, links[1:]):
+        if nb > rp or not stays_separate(nc, nb, rp, sp):
+            raise ValueError(f"link ({nc}, {nb}) would merge into ({rp}, {sp})")
+    if links[-1][1] != 0:
+        raise ValueError("the last link is the root")
+    return [(nc, nb, i + 1 if i + 1 < len(links) else -1) for i, (nc, nb) in enumerate(links)]
+
+
+# A tree with the fronts that SURVIVE amalgamation, per level (leaves = level 0), as (f, nc) pairs -- from the
+# constructions' own reasoning, not from the symbolic phase: test_front_shapes_host compares.
+def _t_root(nc):
+    return [(nc, 0, -1)], [[(nc, nc)]]
+
+
+def _t_designed(nc, nb):
+    st = stick(nc, nb)
+    return designed(nc, nb, st=st), [[(nc + nb, nc)], [(sum(st) + 1, sum(st) + 1)]]        # T; the stick merged into its root
+
+
+def _t_sibling(nc, nb, R=40):
+    return beside_sibling(nc, nb, R), [[(nc + nb, nc)], [(21 + R, 21)], [(R + 1, R + 1)]]    # T; P with S absorbed; G
+
+
+def _t_tower(links):
+    return tower(links), [[(nc + nb, nc)] for nc, nb in links]
+
+
+def _grow(klass_, *trees):
+    """(spec, per level (count, fmax, ncmax, n_f<=8, n_f<=64), class) of the trees side by side."""
+    depth = max(len(t[1]) for t in trees)
+    lev = [[fr for t in trees if l < len(t[1]) for fr in t[1][l]] for l in range(depth)]
+    tup = tuple((len(v), max(f for f, _ in v), max(nc for _, nc in v), sum(f <= 8 for f, _ in v), sum(f <= 64 for f, _ in v))
+                for v in lev)
+    return forest(*[t[0] for t in trees]), tup, klass_
+
+
+def _tiny_group(n):
+    """n tiny fronts in level 0, f in {1, 2, 8} mixed: the first two with update rows (f = 8: (2, 6), f = 2: (1, 1)),
+    the others roots of 1, 2 and 8 columns in turn."""
+    with_rows = [_t_sibling(2, 6), _t_sibling(1, 1)][:min(n, 2)]
+    return with_rows + [_t_root((1, 2, 8)[i % 3]) for i in range(n - len(with_rows))]
+
+
+# the two lowest levels hold one-wave fronts only (launches of their own), the three above block-class fronts (the
+# persistent set): five launches, the chained range [0, 2) below the set
+_TOWER = [(20, 4), (20, 4), (40, 4), (40, 4), (40, 0)]
+
+
+def sweep_table():
+    """name -> (spec, level tuples of EVERY level, classes in level 0)."""
+    T = {}
+    # tiny fronts: eight to a wave, so counts around 8 and 32 (a 256-thread workgroup's worth)
+    for n in (1, 7, 8, 9, 31, 32, 33):
+        T[f"tiny_n{n}"] = _grow("tiny", *_tiny_group(n))
+    # one-wave fronts: four to a 256-thread workgroup
+    for n in (3, 4, 5):
+        T[f"wave9_n{n}"] = _grow("wave", *[_t_root(9)] * n)
+        T[f"wave39_n{n}"] = _grow("wave", *[_t_root(39)] * n)
+        T[f"wave_16_28_n{n}"] = _grow("wave", *[_t_designed(16, 28)] * n)
+        T[f"wave_1_38_n{n}"] = _grow("wave", *[_t_sibling(1, 38)] * n)
+    # all three classes in one level: few enough one-wave fronts to ride in the block-class launch (merge_small), and
+    # one more than that (129 = 96 one-wave + 33 tiny: a launch of their own beside the block-class one)
+    T["mixed_few"] = _grow("tiny+wave+block", *_tiny_group(9), *[_t_root(39)] * 5, _t_root(96))
+    T["mixed_129"] = _grow("tiny+wave+block", *_tiny_group(33), *[_t_root(9)] * 96, _t_root(40), _t_root(40))
+    # taller trees
+    T["tall_wave"] = _grow("wave", _t_tower(_TOWER), _t_tower(_TOWER))
+    # ... with a level 0 of all three classes (one block-class launch: the small ones ride along), one-wave fronts alone
+    # in level 1: the chained range holds a block-class launch
+    T["tall_mixed"] = _grow("tiny+wave+block", _t_tower(_TOWER), _t_tower(_TOWER), _t_root(40), _t_root(40),
+                            _t_root(1), _t_root(2), _t_root(8))
+    return T
+
+
+# cases of the shape table that ride along in the sweep-path tests: the merge_small threshold, a workgroup-size edge,
+# a chain of panels and the widest trapezoid
+SWEEP_EXTRA = ("merge_128", "merge_129", "bs_f129", "chain_nc97", "trap_96_151")
+
+
+def sweep_cases():
+    T = {n: c for n, c in sweep_table().items()}
+    A = all_cases()
+    T.update({n: A[n] for n in SWEEP_EXTRA})
+    return T
+
+
 def klass(f, nc):
     """Kernel class of a front of f rows and nc columns, as the schedule decides it (kernels.hpp: one-wave when
     f <= 64 and f * nc + nb^2 <= 1536; tiny fronts are one-wave fronts with a solve kernel of their own)."""

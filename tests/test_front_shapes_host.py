@@ -15,6 +15,7 @@ from tests import test_gpu_front_shapes as g
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CASES = fs.all_cases()
+SWEEP = fs.sweep_table()         # the forests of tests/test_gpu_sweep_paths.py
 
 _DUMP_SCRIPT = r"""
 import json, sys
@@ -22,7 +23,7 @@ import numpy as np
 sys.path.insert(0, {root!r})
 from cuclarabel_amd import _lib
 from tests import front_shapes as fs
-T = fs.all_cases()
+T = dict(fs.all_cases(), **fs.sweep_table())
 for name in {names!r}:
     spec = T[name][0]
     c = fs.make_case(spec, 1)
@@ -35,11 +36,9 @@ for name in {names!r}:
 _LEVEL = re.compile(r"\[levels\]\s+(\d+):\s+(\d+) fronts \(\s*(\d+) f<=8,\s+(\d+) f<=64\) fmax\s+(\d+) ncmax\s+(\d+)")
 
 
-@pytest.fixture(scope="module")
-def dumps():
-    """[levels] lines and info of every case, from ONE child process (HIPKKT_DUMP_LEVELS is read once per process)."""
+def _dump(names):
     env = dict(os.environ, HIPKKT_DUMP_LEVELS="1")
-    r = subprocess.run([sys.executable, "-c", _DUMP_SCRIPT.format(root=ROOT, names=list(CASES))], env=env, cwd=ROOT,
+    r = subprocess.run([sys.executable, "-c", _DUMP_SCRIPT.format(root=ROOT, names=list(names))], env=env, cwd=ROOT,
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     infos = {d["name"]: d for d in map(json.loads, r.stdout.split("\n")[:-1])}
@@ -48,6 +47,17 @@ def dumps():
         name, rest = chunk.split("\n", 1)
         levels[name.strip()] = [(int(m[2]), int(m[5]), int(m[6]), int(m[3]), int(m[4])) for m in _LEVEL.finditer(rest)]
     return infos, levels   # per level: (fronts, fmax, ncmax, f<=8 count, f<=64 count)
+
+
+@pytest.fixture(scope="module")
+def dumps():
+    """[levels] lines and info of every case, from ONE child process (HIPKKT_DUMP_LEVELS is read once per process)."""
+    return _dump(CASES)
+
+
+@pytest.fixture(scope="module")
+def sweep_dumps():
+    return _dump(SWEEP)
 
 
 @pytest.mark.parametrize("name", list(CASES))
@@ -79,11 +89,49 @@ def test_symbolic_gives_the_designed_fronts(dumps, name):
         assert fs.klass(level0[1], level0[2]) == ("block" if want == "chain" else want), (name, level0)
 
 
+@pytest.mark.parametrize("name", list(SWEEP))
+def test_symbolic_gives_the_forests_their_levels(sweep_dumps, name):
+    """Every level of a forest holds the fronts its constructors reason out: count, tallest, widest, tiny and f <= 64."""
+    infos, levels = sweep_dumps
+    spec, want, _ = SWEEP[name]
+    assert infos[name]["identity"], "ORDER_NATURAL must eliminate these matrices in index order"
+    assert tuple(levels[name]) == want, (levels[name], want)
+    assert infos[name]["nlevels"] == len(want)
+    assert infos[name]["nsuper"] == sum(l[0] for l in want)
+    assert infos[name]["max_front"] == max(l[1] for l in want)
+
+
+def test_the_forests_hold_the_counts_and_classes_they_are_for():
+    """Packing edges of the sweep kernels: tiny fronts go eight to a wave, one-wave fronts four to a 256-thread
+    workgroup; a level with block-class fronts keeps up to merge_small (128) small ones in its launch."""
+    lv0 = {n: SWEEP[n][1][0] for n in SWEEP}
+    assert sorted(lv0[f"tiny_n{n}"][3] for n in (1, 7, 8, 9, 31, 32, 33)) == [1, 7, 8, 9, 31, 32, 33]
+    for n in (1, 7, 8, 9, 31, 32, 33):
+        fronts = {(nc + nb) for nc, nb, _ in SWEEP[f"tiny_n{n}"][0][:1]} | {nc for nc, nb, p in SWEEP[f"tiny_n{n}"][0] if p < 0 and nc <= 8}
+        assert lv0[f"tiny_n{n}"][0] == n and (n < 9 or fronts == {1, 2, 8}), (n, fronts)
+    for stem, f, nc in (("wave9", 9, 9), ("wave39", 39, 39), ("wave_16_28", 44, 16), ("wave_1_38", 39, 1)):
+        for n in (3, 4, 5):
+            assert lv0[f"{stem}_n{n}"] == (n, f, nc, 0, n) and fs.klass(f, nc) == "wave"
+    # all three classes in one level, on either side of merge_small
+    cnt, fmax, ncmax, n8, n64 = lv0["mixed_few"]
+    assert n8 == 9 and n64 - n8 == 5 and cnt - n64 == 1 and n64 <= 128 and fs.klass(fmax, ncmax) == "block"
+    cnt, fmax, ncmax, n8, n64 = lv0["mixed_129"]
+    assert n8 == 33 and cnt == 33 + 96 + 2 and (fmax, ncmax) == (40, 40) and fs.klass(40, 40) == "block" and cnt - 2 == 129
+    # taller trees: two levels of one-wave fronts alone (launches of their own), three block-class levels above them
+    for n in ("tall_wave", "tall_mixed"):
+        lv = SWEEP[n][1]
+        assert len(lv) == 5 and lv[1][:3] == (2, 24, 20) and all(l[:3] == (2, 44 if l is not lv[4] else 40, 40) for l in lv[2:]), lv
+    assert fs.klass(24, 20) == "wave" and fs.klass(44, 40) == "block"
+    assert SWEEP["tall_wave"][1][0] == (2, 24, 20, 0, 2)
+    assert SWEEP["tall_mixed"][1][0] == (7, 40, 40, 3, 7)         # 3 tiny, 2 one-wave (24, 20), 2 block-class (40, 40)
+    assert not fs.UNREACHABLE.keys() & set(SWEEP)
+
+
 def _case(name, seed=1):
-    return fs.make_case(CASES[name][0], seed)
+    return fs.make_case((CASES.get(name) or SWEEP[name])[0], seed)
 
 
-@pytest.mark.parametrize("name", [n for n in CASES if not n.startswith("solve_bs")] + ["solve_bs_1024"])
+@pytest.mark.parametrize("name", [n for n in CASES if not n.startswith("solve_bs")] + ["solve_bs_1024"] + list(SWEEP))
 def test_references_are_exact_calibrated_and_discriminating(name):
     c = _case(name)
     # b = K~ x_true was rounded once from long double
