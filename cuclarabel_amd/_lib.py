@@ -123,6 +123,7 @@ SYMBOLS = {
     "hipkkt_kkt_speculative_rounds": (C.c_int, [_P, C.c_int]),
     "hipkkt_kkt_get_pattern": (C.c_int, [_P, _P, _P]),
     "hipkkt_kkt_get_values": (C.c_int, [_P, _P]),
+    "hipkkt_kkt_get_residual": (C.c_int, [_P, C.c_int, C.c_int64, _P, _P, _P, _P, _P]),
     "hipkkt_kkt_get_maps": (C.c_int, [_P] * 9),
     "hipkkt_kkt_get_perm": (C.c_int, [_P, _P]),
     "hipkkt_kkt_get_Hs": (C.c_int, [_P, _P]),

@@ -4630,6 +4630,73 @@ int hipkkt_kkt_get_values(hipkkt_kkt_t h, double* nzval)
     });
 }
 
+// e = b - K_sym x through the launch functions and the SpmvDev of the solves (test infrastructure; hipkkt.h).  The CSR
+// image is K's own (unpermuted) order, as the solves' work vectors are: the fill-reducing permutation lives inside the
+// sweeps.  Only the many-column work buffers are written, and for route 1 the refinement state's scratch words, which
+// every solve initialises before it reads them.
+int hipkkt_kkt_get_residual(hipkkt_kkt_t h, int route, int64_t nrhs, const double* x, const double* b, double* e,
+                            double* norm_e, double* norm_b)
+{
+    return guarded([&]() {
+        if (!h || !x || !b || !norm_e || nrhs < 1 || nrhs > 65535 || route < 0 || route > 2)
+            throw ArgError("hipkkt_kkt_get_residual: bad argument");
+        HIP_CHECK(hipSetDevice(h->device));
+        const int k = (int)nrhs, N = (int)h->K.N;
+        if (route == 1 && !(kkt_partials_mode(h, k) && (k == 1 || k == 2 || k == 4)))
+            throw ArgError("hipkkt_kkt_get_residual: route 1 (partials) needs no long rows and 1, 2 or 4 columns");
+        if (route == 2 && h->nlong != 0) throw ArgError("hipkkt_kkt_get_residual: route 2 (row-major) needs no long rows");
+        kkt_multi_reserve(h, (size_t)k);
+        const SpmvDev A = kkt_spmv(h);                   // (after the reserve: it may move the long rows' partial sums)
+        const size_t bytes = (size_t)N * k * sizeof(double);
+        std::vector<double> hn(2 * (size_t)h->mcap, 0.0);
+        const double* e_dev = h->mE.p;
+        if (route == 2) {
+            const int KP = (k + 15) & ~15;
+            // column-major staging in the candidate buffer, as hipkkt_kkt_solve_multi does; all N rows are "x rows" here
+            HIP_CHECK(hipMemcpyAsync(h->mC.p, x, bytes, hipMemcpyHostToDevice, h->stream));
+            launch_pack_rhs_rm(h->mX.p, h->mC.p, nullptr, N, 0, 0, k, KP, h->stream);
+            HIP_CHECK(hipMemcpyAsync(h->mC.p, b, bytes, hipMemcpyHostToDevice, h->stream));
+            launch_pack_rhs_rm(h->mB.p, h->mC.p, nullptr, N, 0, 0, k, KP, h->stream);
+            launch_residual_rm(A, h->mB.p, h->mX.p, h->mE.p, h->mpartial.p, h->mnorms.p, h->mnorms.p + KP, KP, h->stream);
+            launch_unpack_lhs_rm(h->mC.p, nullptr, h->mE.p, N, 0, k, KP, h->stream);
+            e_dev = h->mC.p;
+            HIP_CHECK(hipMemcpyAsync(hn.data(), h->mnorms.p, 2 * (size_t)KP * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIP_CHECK(hipStreamSynchronize(h->stream));
+            for (int c = 0; c < k; ++c) { norm_e[c] = hn[c]; if (norm_b) norm_b[c] = hn[KP + c]; }
+        } else {
+            const int64_t ld = N;
+            HIP_CHECK(hipMemcpyAsync(h->mX.p, x, bytes, hipMemcpyHostToDevice, h->stream));
+            HIP_CHECK(hipMemcpyAsync(h->mB.p, b, bytes, hipMemcpyHostToDevice, h->stream));
+            if (route == 0) {
+                launch_residual(A, h->Kval.p, h->mB.p, h->mX.p, h->mE.p, h->mpartial.p, h->mnorms.p, h->stream, k, ld);
+                launch_norm_inf(h->mB.p, N, h->mpartial.p, h->mnorms.p + k, h->stream, k, ld);
+                HIP_CHECK(hipMemcpyAsync(hn.data(), h->mnorms.p, 2 * (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            } else {
+                // what kkt_solve_core enqueues ahead of a solve's first decision (kkt_enqueue_refine_error + kkt_launch_ir
+                // with r = 0): the partial maxima stay un-finished, ||b|| rides along, k_ir_round reduces both
+                const hipkkt_settings& st = h->st;
+                const IrNorms nm = kkt_ir_norms(h, k);
+                launch_residual(A, h->Kval.p, h->mB.p, h->mX.p, h->mE.p, h->mpartial.p, nullptr, h->stream, k,
+                                k > 1 ? ld : 0, nullptr, nullptr, nm.normb);
+                IrPartials Q;
+                Q.np = residual_grid(A) + 1;
+                Q.e0 = h->mpartial.p;
+                Q.b0 = Q.e0 + (size_t)k * Q.np;
+                launch_ir_round(h->ir_state, h->ir_stride, 0, true, nm.norme0, nm.normb, nm.cand, nullptr, h->mX.p, h->mC.p, N, k,
+                                st.iterative_refinement_abstol, st.iterative_refinement_reltol, st.iterative_refinement_stop_ratio,
+                                std::max(st.iterative_refinement_max_iter, 0), h->ir_readback, nullptr, h->stream, Q);
+                HIP_CHECK(hipMemcpyAsync(hn.data(), nm.norme0, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+                HIP_CHECK(hipMemcpyAsync(hn.data() + k, nm.normb, (size_t)k * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            }
+            HIP_CHECK(hipStreamSynchronize(h->stream));
+            for (int c = 0; c < k; ++c) { norm_e[c] = hn[c]; if (norm_b) norm_b[c] = hn[k + c]; }
+        }
+        if (e) HIP_CHECK(hipMemcpyAsync(e, e_dev, bytes, hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        return HIPKKT_OK;
+    });
+}
+
 int hipkkt_kkt_get_maps(hipkkt_kkt_t h, int64_t* mapP, int64_t* mapA, int64_t* mapHs, int64_t* map_diag,
                         int64_t* mapU, int64_t* mapV, int64_t* mapD, int64_t* dsigns)
 {

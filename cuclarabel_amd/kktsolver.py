@@ -193,6 +193,23 @@ class HipKKTSolver:
         check(L.hipkkt_kkt_get_values(self._h, ptr(nzval)), "hipkkt_kkt_get_values")
         return sp.csc_matrix((nzval, rowval, colptr), shape=(self.N, self.N))
 
+    def residual(self, x, b, route=0):
+        """(tests) e = b - K x on the current un-regularised K through the solves' own residual and norm kernels
+        (hipkkt_kkt_get_residual).  x, b: (N,) or (N, k) in K's order.  route 0 = column-major with a finishing kernel,
+        1 = partial maxima reduced by the refinement-round kernel (k in 1, 2, 4; no long rows), 2 = row-major (no long
+        rows).  Returns (e, norm_e (k), norm_b (k)); a route the handle cannot take raises HipKKTError."""
+        one = np.ndim(x) == 1
+        X = np.asfortranarray(np.reshape(x, (self.N, -1), order="F"), dtype=np.float64)
+        B = np.asfortranarray(np.reshape(b, (self.N, -1), order="F"), dtype=np.float64)
+        if X.shape != B.shape or X.shape[1] < 1:
+            raise ValueError("x and b must both be (N,) or (N, k)")
+        k = X.shape[1]
+        E = np.zeros((self.N, k), order="F")
+        ne, nb = np.zeros(k), np.zeros(k)
+        check(_lib.lib().hipkkt_kkt_get_residual(self._h, int(route), k, ptr(X), ptr(B), ptr(E), ptr(ne), ptr(nb)),
+              "hipkkt_kkt_get_residual")
+        return (E[:, 0] if one else E), ne, nb
+
     def maps(self):
         i = self.info
         out = dict(P=np.zeros(self._nnzP, np.int64), A=np.zeros(self._nnzA, np.int64),

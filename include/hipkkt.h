@@ -372,6 +372,24 @@ int hipkkt_kkt_mul_Hs(hipkkt_kkt_t h, double *y, const double *x);
 /* introspection used by the parity tests: the assembled K (triu CSC, 0-based) and data maps */
 int hipkkt_kkt_get_pattern(hipkkt_kkt_t h, int64_t *colptr /* N+1 */, int64_t *rowval /* nnzK */);
 int hipkkt_kkt_get_values(hipkkt_kkt_t h, double *nzval /* nnzK, un-regularised */);
+/* e = b - K_sym x on the current un-regularised values (the residual of _iterative_refinement,
+ * kktsolver_directldl.jl:455-466), by the residual, norm and refinement-round kernels of the solves themselves, launched
+ * as a solve of nrhs columns would launch them.  Test infrastructure (tests/test_gpu_residual.py): it lets the kernels be
+ * compared with a high-precision residual directly, not through a refined solution.  x, b: host, N x nrhs column-major
+ * (all N = n + m + p rows, in K's order -- the order of hipkkt_kkt_get_pattern); e: host, the same shape, may be NULL;
+ * norm_e, norm_b: host, nrhs infinity norms each, norm_b may be NULL.  A column holding a non-finite entry has a
+ * non-finite norm; that is a result, and the call still returns HIPKKT_OK.
+ *   route 0 "columns"    column-major kernels with a finishing kernel behind them, any nrhs >= 1 (two columns per matrix
+ *                        walk when nrhs is even); ||b|| by a separate reduction: hipkkt_kkt_solve_multi on K with long rows
+ *   route 1 "partials"   the partial maxima left to the refinement-round kernel, ||b|| riding along with the residual:
+ *                        hipkkt_kkt_solve and the 2..8-column solves.  Needs nrhs in {1, 2, 4} and no row of K longer
+ *                        than 4096 entries, HIPKKT_ERR_ARG otherwise
+ *   route 2 "row-major"  N x KP work vectors, KP = nrhs rounded up to 16: hipkkt_kkt_solve_multi with 9 or more columns.
+ *                        Needs no row of K longer than 4096 entries, HIPKKT_ERR_ARG otherwise
+ * Synchronises.  Writes only the many-column work buffers: the right-hand side of hipkkt_kkt_setrhs and the last solution
+ * are kept. */
+int hipkkt_kkt_get_residual(hipkkt_kkt_t h, int route, int64_t nrhs, const double *x, const double *b, double *e,
+                            double *norm_e, double *norm_b);
 int hipkkt_kkt_get_maps(hipkkt_kkt_t h, int64_t *mapP, int64_t *mapA, int64_t *mapHs,
                         int64_t *map_diag_full, int64_t *map_soc_u, int64_t *map_soc_v,
                         int64_t *map_soc_D, int64_t *dsigns);   /* any may be NULL */
