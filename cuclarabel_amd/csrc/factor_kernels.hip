@@ -329,12 +329,11 @@ __device__ inline double fast_recip(double d)
     r = fma(fma(-d, r, 1.0), r, r);
     return r;          // d = 0 or not finite: NaN (the caller only asks whether the result is finite)
 }
-constexpr int NB = 16;
+constexpr int NB = kPanelNB;       // (launch_shapes.hpp, with kBdCols: the host sizes the kernel's LDS from them)
 // The panel lives in LDS as a TRAPEZOID: column j holds rows j .. f-1, columns back to back.  Entry (i, j), i >= j,
 // sits at i + pcol(j, f); nothing above the diagonal is ever stored or read.  That is f*nc - nc(nc-1)/2 doubles
 // instead of f*nc: a 231 x 87 panel fits where the rectangle would have to be split (one more tree level).
 __device__ __forceinline__ int pcol(int j, int f) { return (j * (2 * f - 1 - j)) >> 1; }
-constexpr int kBdCols = 128;       // trailing columns per block whose d*L copy is kept (nc - 16 <= 128 enforced by host)
 
 // apply the extend-add items [i0, i1) (whole columns, owned by this wave) into the LDS panel P (ld f):
 // eight items in flight -- one round of descriptor loads, one round of (rel, value) loads, then
@@ -1080,12 +1079,6 @@ void launch_concurrency_probe(int* word2, hipStream_t first, hipStream_t second)
 {
     hipLaunchKernelGGL(k_probe_wait, dim3(1), dim3(64), 0, first, word2);
     hipLaunchKernelGGL(k_probe_set, dim3(1), dim3(64), 0, second, word2);
-}
-
-size_t panel_lds_bytes(int fmax, int panel_max)
-{
-    (void)fmax;
-    return ((size_t)8 * NB + 2 * NB * NB + (kBdCols + NB) + 2 + (size_t)panel_max + 256) * sizeof(double);
 }
 
 static void init_factor_lds()

@@ -23,20 +23,13 @@
 #include "kkt_assembly.hpp"
 #include "symbolic.hpp"
 #include "knobs.hpp"
+#include "schedule.hpp"
 
 namespace hipkkt {
 
 static thread_local std::string g_last_error;
 
 struct ArgError : std::runtime_error { using std::runtime_error::runtime_error; };
-
-// the panel-shape settings of knobs.hpp over SymbolicOptions' defaults
-static void apply_knobs(SymbolicOptions& opt)
-{
-    if (knobs().panel_cap >= 0) opt.panel_cap = knobs().panel_cap;
-    if (knobs().panel_max_cols >= 0) opt.panel_max_cols = knobs().panel_max_cols;
-    if (knobs().panel_slice_below >= 0) opt.panel_slice_below = knobs().panel_slice_below;
-}
 
 #define HIP_CHECK(expr)                                                                          \
     do {                                                                                         \
@@ -69,31 +62,8 @@ struct DBuf {
     }
 };
 
-struct Launch {
-    int begin, count;
-    bool small;                 // one wave per front
-    int bs_panel, nbk, slice;   // panel kernel block size / block-column width; small-front LDS slice
-    size_t lds_panel, lds_solve;
-    int fmax, ncmax;            // largest front / column count in the launch
-    int solve_bs;               // workgroup size of the block solve kernels for this launch (128 or 256 = the default 512-thread one)
-    int ntiny;                  // one-wave launches: the last ntiny fronts have f <= 8 (eight to a wave in the solves)
-    int tile_begin, ntiles;     // Schur tiles of this launch's fronts
-    int tile_nc = 0;            // panel columns per tile, averaged over the launch's tiles (the depth of a tile's product)
-    int tinv_begin, tinv_count, tinv_ncmax;   // this launch's supernodes that need T = L11^{-1}
-    int nsliced;                // the last nsliced fronts of a block-class launch are factorised in row slices ...
-    int slice_begin, slice_count;   // ... their slice records in d_sdesc
-    size_t lds_sliced;
-    int ntall;                  // the last ntall fronts of a block-class launch are too tall for the block sweep kernels' LDS
-                                //   (beyond ~10 000 rows): k_fwd_tall / k_bwd_tall; such a launch stays out of the persistent kernels
-    int level;                  // tree level: a level has at most one block-class launch, followed by its one-wave launch
-    RecSeg rec;                 // packed sweep records of the launch's fronts (kernels.hpp): class 0 for a block-class launch, 1 and 2 for a one-wave one
-};
-
-static constexpr size_t kLdsCap = 160 * 1024 - 512;
 static constexpr int kMaxNR = 4;          // right-hand sides the single-column solve path takes in one sweep (1, 2 or 4)
 // (environment settings: knobs.hpp -- one table, read once per process)
-// grid of the side-stream W formation while the tree is still being factorised: 3/8 of the CUs (96 of 256) unless set
-
 
 // WHAT MAY RUN BESIDE WHAT ON ONE DEVICE, ACROSS HANDLES.  Three mechanisms of this library put kernels on the device
 // whose workgroups WAIT for other workgroups: the factorisation's overlap mode (panel workgroups that hold a CU each
@@ -162,34 +132,43 @@ public:
         apply_knobs(opt);
         // user_perm arrives in the caller's index base; analyse() applies `base` to it
         analyse(N, colptr, rowval, base, opt, S);
-        panel_cap = opt.panel_cap;
-        panel_max_slices = std::max(1, opt.panel_max_slices);
         dyn_eps = st.dynamic_regularization_eps;
         dyn_delta = st.dynamic_regularization_delta;
-        build_schedule();
+        // what the device contributes to the schedule: its CU count (256 where the query fails) and the persistent
+        // kernels' occupancy answers, asked where schedule.cpp needs them
+        {
+            int d = 0;
+            hipDeviceProp_t prop;
+            if (hipGetDevice(&d) == hipSuccess && hipGetDeviceProperties(&prop, d) == hipSuccess) dev.n_cus = prop.multiProcessorCount;
+            else (void)hipGetLastError();
+        }
+        dev.top_solve_capacity = [](size_t lds, bool tall) { return top_solve_capacity(lds, tall); };
+        dev.top_solve_capacity_nr = [](size_t lds_total, int nr) { return top_solve_capacity_nr(lds_total, nr); };
+        dev.top_solve_sliced_capacity = [](size_t lds, int nr) { return top_solve_sliced_capacity(lds, nr); };
+        sch = build_schedule(S, dev, opt.panel_cap, std::max(1, opt.panel_max_slices));
         upload(dsigns);
         if (knobs().verbose) {
             int nblock = 0, nsl_fronts = 0, ov_slices = 0;
-            for (const Launch& L : launches) if (!L.small) { nblock += L.count; nsl_fronts += L.nsliced; }
-            if (overlap_wanted()) for (size_t q = ov_first; q < launches.size(); ++q) ov_slices += launches[q].slice_count;
+            for (const Launch& L : sch.launches) if (!L.small) { nblock += L.count; nsl_fronts += L.nsliced; }
+            if (overlap_wanted()) for (size_t q = sch.ov_first; q < sch.launches.size(); ++q) ov_slices += sch.launches[q].slice_count;
             std::fprintf(stderr, "[hipkkt] N %d, %d supernodes in %zu levels (%zu launches), %d block-class fronts, %d of them in "
                          "%zu row slices; persistent solve set: last %zu launches, %d fronts on %d workgroups, %d (front, slice) tasks; "
                          "factorisation overlap: last %zu launches (%d row slices in them)\n",
-                         S.N, S.nsuper, S.levels.size(), launches.size(), nblock, nsl_fronts, slice_list.size(), top_launches,
-                         top_count, top_ntask > 0 ? top_sgrid : top_grid, top_ntask, overlap_wanted() ? launches.size() - ov_first : (size_t)0,
+                         S.N, S.nsuper, S.levels.size(), sch.launches.size(), nblock, nsl_fronts, sch.slice_list.size(), sch.top_launches,
+                         sch.top_count, sch.top_ntask > 0 ? sch.top_sgrid : sch.top_grid, sch.top_ntask, overlap_wanted() ? sch.launches.size() - sch.ov_first : (size_t)0,
                          ov_slices);
             {
                 int ntall_all = 0;
-                for (const Launch& L : launches) ntall_all += L.ntall;
+                for (const Launch& L : sch.launches) ntall_all += L.ntall;
                 if (ntall_all) std::fprintf(stderr, "[hipkkt] %d fronts too tall for the block sweep kernels (k_fwd_tall / k_bwd_tall)\n", ntall_all);
             }
             if (knobs().verbose >= 2)
-                for (size_t q = 0; q < launches.size(); ++q) {
-                    const Launch& L = launches[q];
+                for (size_t q = 0; q < sch.launches.size(); ++q) {
+                    const Launch& L = sch.launches[q];
                     int fmin = 1 << 30, ncmin = 1 << 30;
                     double flops = 0;
                     for (int t = L.begin; t < L.begin + L.count; ++t) {
-                        const int sn = sched[(size_t)t], nc = S.sn_start[sn + 1] - S.sn_start[sn], f = front_size(sn);
+                        const int sn = sch.sched[(size_t)t], nc = S.sn_start[sn + 1] - S.sn_start[sn], f = front_size(sn);
                         fmin = std::min(fmin, f); ncmin = std::min(ncmin, nc);
                         flops += (double)nc * (f - nc) * (f - nc) + (double)nc * nc * (f - nc) + (double)nc * nc * nc / 3;
                     }
@@ -198,10 +177,10 @@ public:
                                  L.ntiles, L.tile_nc, flops * 1e-9);
                 }
             if (overlap_wanted())
-                for (size_t q = ov_first; q < launches.size(); ++q)
+                for (size_t q = sch.ov_first; q < sch.launches.size(); ++q)
                     std::fprintf(stderr, "[hipkkt] overlap admission: launch %zu: %d panel workgroups, %d tiles behind a gate, %d CUs\n", q,
-                                 ov_group_of[q] >= 0 ? ov_groups[(size_t)ov_group_of[q]].count : launches[q].count - launches[q].nsliced + launches[q].slice_count,
-                                 launches[q].ntiles, n_cus);
+                                 sch.ov_group_of[q] >= 0 ? sch.ov_groups[(size_t)sch.ov_group_of[q]].count : sch.launches[q].count - sch.launches[q].nsliced + sch.launches[q].slice_count,
+                                 sch.launches[q].ntiles, dev.n_cus);
         }
     }
 
@@ -246,7 +225,7 @@ public:
         if (no_graph || nr > 1 || n_solve_calls++ == 0) {
             // the persistent kernel AND the chained launches hold workgroups that wait for other workgroups: class S
             // (DevOp); not admitted, this sweep goes level by level
-            const bool waits = allow_top && ((!top_disabled && top_launches > 0) || (!chain_disabled && chain_from < launches.size()));
+            const bool waits = allow_top && ((!top_disabled && sch.top_launches > 0) || (!chain_disabled && sch.chain_from < sch.launches.size()));
             const bool tok = waits && claim_dev(kOpS);
             TokenRelease rel{this, tok};
             enqueue_solve(d_b, d_x, stream, tok, nr, ldb, ldx, tok);
@@ -268,24 +247,7 @@ public:
         }
         HIP_CHECK(hipGraphLaunch(it->second, stream));
     }
-    // The single-column kernels' NR-column instances keep NR times the vectors in LDS: possible when every level's
-    // share still fits a CU (the (front, slice) kernel of sets with very tall fronts: two columns at most).
-    bool supports_nr(int nr) const
-    {
-        if (nr == 1) return true;
-        if (nr != 2 && nr != 4) return false;
-        // A set with very tall fronts ((front, slice) kernel): two columns at most, and only the launches BELOW the set
-        // have to fit -- the set's own fronts (1531 x 96: one column's vectors fill a CU's LDS in the per-level kernels)
-        // go through the persistent kernel, or, where that is not available (no claim, given up), column by column
-        // (enqueue_solve).
-        if (top_ntask > 0 && (nr != 2 || top_sgrid2 <= 0)) return false;
-        const size_t below = top_ntask > 0 ? launches.size() - top_launches : launches.size();
-        for (size_t q = 0; q < below; ++q)
-            if (!launches[q].small && (launches[q].ntall > 0 || launches[q].lds_solve * (size_t)nr > kLdsCap)) return false;
-        // (fronts too tall for the block kernels take one column in the per-level path; inside the (front, slice) set they
-        //  are slices like any other)
-        return true;
-    }
+    bool supports_nr(int nr) const { return hipkkt::supports_nr(sch, nr); }
 
     // nrhs right-hand sides at once: column j of d_B at stride ldb, of d_X at stride ldx (may alias d_B).
     // Every level is one launch (grid.y = block of 16 columns, 8 for the one-wave fronts): the per-level latency
@@ -321,7 +283,7 @@ private:
         if (KP / 8 > 65535) throw ArgError("solve_multi: too many right-hand sides per call");
         {   // the block kernels' grid.y is (fronts of a launch / 8) x (column blocks of 16)
             int64_t widest = 0;
-            for (const Launch& L : launches) if (!L.small) widest = std::max<int64_t>(widest, (L.count + 7) / 8);
+            for (const Launch& L : sch.launches) if (!L.small) widest = std::max<int64_t>(widest, (L.count + 7) / 8);
             if (widest * (KP / 16) > 65535) throw ArgError("solve_multi: too many right-hand sides per call for this structure (split the call)");
         }
         wait_w(stream);
@@ -349,9 +311,9 @@ private:
         a.top_limit = 5000000;       // (the multi-column path has no persistent kernel)
         a.tk_pos = nullptr; a.tk_sl = nullptr; a.tbase = nullptr; a.xf = nullptr; a.chain_cnt = nullptr; a.recs = nullptr; a.tall_ws = nullptr;
         launch_pull_leaves_multi(a, n_pull_rows, KP, stream);        // (the pulled leaves' terms, summed per receiving row)
-        for (const Launch& L : launches) launch_fwd_multi(a, L.begin, L.count, L.small, L.ncmax, KP, stream);
-        for (size_t q = launches.size(); q-- > 0;) {
-            const Launch& L = launches[q];
+        for (const Launch& L : sch.launches) launch_fwd_multi(a, L.begin, L.count, L.small, L.ncmax, KP, stream);
+        for (size_t q = sch.launches.size(); q-- > 0;) {
+            const Launch& L = sch.launches[q];
             launch_bwd_multi(a, L.begin, L.count, L.small, L.ncmax, KP, stream, L.level == 0);
         }
     }
@@ -499,13 +461,13 @@ private:
         // (3.43 -> 3.365 ms per step; with the round's earlier, slower W formation the first sweep waited for W by as
         // much as the factorisation ended earlier).
         const bool want_ov = overlap_wanted();
-        const bool use_ov = want_ov && !side && !want_stamps && !ov_disabled && ov_first < launches.size();
+        const bool use_ov = want_ov && !side && !want_stamps && !ov_disabled && sch.ov_first < sch.launches.size();
         // Whatever this factorisation does on more than ONE stream needs admission (DevOp): the overlap mode (class X:
         // its kernels wait across streams) or, failing that, the side stream's W formation with its fork / join events
         // (class M).  Not admitted, it keeps to its main stream, where every packet depends on earlier packets of the same
         // stream only.
         const bool no_overlap = knobs().no_overlap;
-        const bool side_w = !side && !no_overlap && !want_stamps && late_launches > 0 && late_launches < launches.size();
+        const bool side_w = !side && !no_overlap && !want_stamps && sch.late_launches > 0 && sch.late_launches < sch.launches.size();
         const bool tok_x = use_ov && claim_dev(kOpX);
         const bool tok = tok_x || (side_w && claim_dev(kOpM));
         TokenRelease ov_release{this, tok};      // (the "enqueuing" mark ends with this call, however it ends)
@@ -522,14 +484,14 @@ private:
         // correct on one queue as well).
         // (the merged kernels only where the two streams run side by side)
         auto group_of = [&](size_t q) -> const MergeGroup* {
-            return (ov_concurrent && q < ov_group_of.size() && ov_group_of[q] >= 0) ? &ov_groups[(size_t)ov_group_of[q]] : nullptr;
+            return (ov_concurrent && q < sch.ov_group_of.size() && sch.ov_group_of[q] >= 0) ? &sch.ov_groups[(size_t)sch.ov_group_of[q]] : nullptr;
         };
-        const size_t merge_from = (ov_concurrent && !ov_groups.empty()) ? ov_groups.back().first : ~(size_t)0;
+        const size_t merge_from = (ov_concurrent && !sch.ov_groups.empty()) ? sch.ov_groups.back().first : ~(size_t)0;
         if (ov_on) {
             zl.add(d_ov_prog.p, S.nsuper);
             zl.add(d_ov_done.p, S.nsuper);
-            if (!slice_list.empty()) zl.add(d_ov_sprog.p, (int)slice_list.size());
-            zl.add(d_ov_started.p, (int)launches.size());
+            if (!sch.slice_list.empty()) zl.add(d_ov_sprog.p, (int)sch.slice_list.size());
+            zl.add(d_ov_started.p, (int)sch.launches.size());
         }
         launch_zero_ints_multi(zl, st);
         FactorArgs a;
@@ -550,7 +512,7 @@ private:
         a.stamps = nullptr;
         a.stamp_row = 0;
         if (want_stamps) {
-            if (!stamps.p) { stamps.alloc(launches.size() * 16); }
+            if (!stamps.p) { stamps.alloc(sch.launches.size() * 16); }
             stamps.zero(st);
             a.stamps = (long long*)stamps.p;
         }
@@ -573,17 +535,17 @@ private:
         // (every W formation of this factorisation goes through form_w)
         auto form_w = [&](const int* list, int count, int ncmax, hipStream_t on, int max_blocks) {
             const size_t i0 = (size_t)(list - d_tinv_list.p);
-            const int nsmall = i0 + (size_t)count < tinv_small_prefix.size() ? tinv_small_prefix[i0 + (size_t)count] - tinv_small_prefix[i0] : 0;
+            const int nsmall = i0 + (size_t)count < sch.tinv_small_prefix.size() ? sch.tinv_small_prefix[i0 + (size_t)count] - sch.tinv_small_prefix[i0] : 0;
             if (!skip_w) launch_tinv(a.T, fronts.p, tinv.p, list, count, ncmax, on, max_blocks, nsmall);
         };
         // eager mode: once the tree narrows to its top levels most CUs idle, so the solve matrices
         // W = [T; M] of everything below are formed on a side stream meanwhile (HIPKKT_NO_OVERLAP=1 disables)
-        const size_t nl = launches.size();
-        const size_t first_top = (tok && side_w) ? nl - late_launches : nl;
+        const size_t nl = sch.launches.size();
+        const size_t first_top = (tok && side_w) ? nl - sch.late_launches : nl;
         bool eager_fork = false;
         int w_done = 0;
         for (size_t q = 0; q < nl; ++q) {
-            const Launch& L = launches[q];
+            const Launch& L = sch.launches[q];
             a.stamp_row = li++;
             // fork points of the side stream: a few levels before the narrow top (the bulk of the fronts), at the narrow
             // top, and a few levels before the root -- behind the tree only the last levels' handful of fronts is left,
@@ -607,19 +569,19 @@ private:
             };
             const bool fork_here = first_top < nl && (q == fork_at(first_top >= (size_t)std::max(0, knobs().winv_early) ? first_top - (size_t)std::max(0, knobs().winv_early) : nl) ||
                                                       q == fork_at(first_top) || (q > first_top && (run_first || q == tail_fork)));
-            if (fork_here && launches[q].tinv_begin > w_done) {
+            if (fork_here && sch.launches[q].tinv_begin > w_done) {
                 ensure_capture_streams();
                 HIP_CHECK(hipEventRecord(ev_fork, st));
                 HIP_CHECK(hipStreamWaitEvent(cap_side, ev_fork, 0));
                 // a bounded grid: the top panels need whole CUs (their LDS), which a full-width launch would hold
-                form_w(d_tinv_list.p + w_done, launches[q].tinv_begin - w_done, tinv_ncmax, cap_side, side_winv_blocks);
+                form_w(d_tinv_list.p + w_done, sch.launches[q].tinv_begin - w_done, sch.tinv_ncmax, cap_side, sch.side_winv_blocks);
                 eager_fork = true;
-                w_done = launches[q].tinv_begin;
+                w_done = sch.launches[q].tinv_begin;
                 // the fronts below the narrow top are used by the next sweep's first launches: the factorisation ends
                 // with a wait for this event (normally long past by then)
                 if (q <= first_top) HIP_CHECK(hipEventRecord(ev_side, cap_side));
             }
-            if (ov_on && q >= ov_first) {
+            if (ov_on && q >= sch.ov_first) {
                 // Panels on the main stream, the level's Schur tiles on the overlap stream,
                 // submitted in this order -- panel L, tiles L, panel L+1, ... -- which is correct even if the two streams
                 // share a hardware queue.  Tiles of level L become ready only when the tiles of level L-1 have finished,
@@ -643,7 +605,7 @@ private:
                     if (g->sliced) launch_panel_sliced(a, L.slice_begin, g->count, g->lds, st);
                     else launch_panel(a, L.begin, g->count, 1024, g->lds, st);
                 }
-                if (q == ov_first) {
+                if (q == sch.ov_first) {
                     HIP_CHECK(hipEventRecord(ev_ov_fork, st));
                     HIP_CHECK(hipStreamWaitEvent(ov_stream, ev_ov_fork, 0));
                 } else if (L.ntiles > 0 && !no_gate) {
@@ -687,13 +649,13 @@ private:
             HIP_CHECK(hipStreamWaitEvent(st, ev_side, 0));
             HIP_CHECK(hipEventRecord(ev_fork, st));
             HIP_CHECK(hipStreamWaitEvent(last_on, ev_fork, 0));
-            form_w(d_tinv_list.p + done, (int)tinv_list.size() - done, tinv_ncmax, last_on, 0);
+            form_w(d_tinv_list.p + done, (int)sch.tinv_list.size() - done, sch.tinv_ncmax, last_on, 0);
             HIP_CHECK(hipEventRecord(ev_join, cap_side));
             if (ov_on) { HIP_CHECK(hipEventRecord(ev_join2, ov_stream)); w2_pending = true; }
             w_pending = true;
         } else {
             // one launch over every supernode, after the tree (all of them independent)
-            form_w(d_tinv_list.p, (int)tinv_list.size(), tinv_ncmax, st, 0);
+            form_w(d_tinv_list.p, (int)sch.tinv_list.size(), sch.tinv_ncmax, st, 0);
         }
         if (ov_on) {
             // The tile stream is joined by the NEXT factorisation, not by this one's tail: every tile has been counted
@@ -710,17 +672,17 @@ private:
         }
         HIP_CHECK(hipGetLastError());
         if (want_stamps) {
-            std::vector<long long> h(launches.size() * 16);
+            std::vector<long long> h(sch.launches.size() * 16);
             HIP_CHECK(hipMemcpyAsync(h.data(), stamps.p, h.size() * 8, hipMemcpyDeviceToHost, st));
             HIP_CHECK(hipStreamSynchronize(st));
             static int printed = 0;
             if (printed++ == 2) {
-                for (size_t r = 0; r < launches.size(); ++r) {
+                for (size_t r = 0; r < sch.launches.size(); ++r) {
                     const long long* q = &h[r * 16];
-                    if (launches[r].small) continue;
+                    if (sch.launches[r].small) continue;
                     std::fprintf(stderr, "[stamps2] launch %zu: wave 0's items %.1f us (first batch's loads %.1f us), then all waves %.1f us\n", r, (q[7] - q[6]) * 0.01, (q[15] - q[6]) * 0.01, (q[3] - q[7]) * 0.01);
                     std::fprintf(stderr, "[stamps] launch %zu fronts %d f=%lld nc=%lld kids=%lld | zero %.1f K %.1f kids %.1f factor %.1f "
-                                 "(diag %.1f trsm %.1f trail %.1f) store %.1f us  clk %.0f MHz\n", r, launches[r].count, q[11], q[12], q[13],
+                                 "(diag %.1f trsm %.1f trail %.1f) store %.1f us  clk %.0f MHz\n", r, sch.launches[r].count, q[11], q[12], q[13],
                                  (q[1] - q[0]) * 0.01, (q[2] - q[1]) * 0.01, (q[3] - q[2]) * 0.01, (q[4] - q[3]) * 0.01,
                                  q[8] * 0.01, q[9] * 0.01, q[10] * 0.01, (q[5] - q[4]) * 0.01,
                                  (double)q[14] / ((q[5] - q[0]) * 0.01));
@@ -741,19 +703,16 @@ private:
         uvec.alloc(std::max<size_t>(S.rows.size(), 1) * nr);
         nr_cap = (size_t)nr;
     }
-    int top_grid_for(int nr)
-    {
-        if (nr == 1) return top_grid;
-        if (top_ntask > 0) return nr == 2 ? top_sgrid2 : 0;
-        int& g = top_grid_nr[nr == 2 ? 0 : 1];
-        if (g < 0) g = std::min(top_grid, top_solve_capacity_nr(top_lds * (size_t)nr, nr));
-        return g;
-    }
-
     // use_top: the persistent kernel may be used (claimed); allow_chain: the caller reads the abort word afterwards and
-    // repeats the solve if a bounded wait expired (the same promise use_top implies), so the chained launches may be used
+    // repeats the solve if a bounded wait expired (the same promise use_top implies), so the chained launches may be used.
+    // How the sweep is split is decided by plan_sweep (schedule.cpp); this function launches the plan.
     void enqueue_solve(const double* d_b, double* d_x, hipStream_t st, bool use_top, int nr, int64_t ldb, int64_t ldx, bool allow_chain = false)
     {
+        const SweepPlan plan = plan_sweep(sch, SweepState{use_top, allow_chain, top_disabled, chain_disabled, w_pending}, nr, dev, top_grid_nr);
+        if (plan.split_columns) {
+            for (int c = 0; c < nr; ++c) enqueue_solve(d_b + (int64_t)c * ldb, d_x + (int64_t)c * ldx, st, use_top, 1, 0, 0, allow_chain);
+            return;
+        }
         SolveArgs a;
         a.T = tree();
         a.fronts = fronts.p;
@@ -763,94 +722,27 @@ private:
         a.out = d_x;
         a.xp = xp.p;
         a.uvec = uvec.p;
-        const long long top_limit = knobs().top_test_limit;
-        a.top_limit = top_limit;
+        a.top_limit = knobs().top_test_limit;
         // diagnostic (HIPKKT_TOP_STAMPS=n): the n-th single-column sweep over the full persistent set records eight time
         // stamps per front and direction, printed per level afterwards (this call then synchronises)
         const int stamp_call = knobs().top_stamps;
         a.top_stamps = nullptr;
-        bool stamp_now = false;
         a.ld_b = ldb; a.ld_out = ldx; a.ld_xp = S.N; a.ld_uvec = (int64_t)std::max<size_t>(S.rows.size(), 1);
         a.tk_pos = d_tk_pos.p; a.tk_sl = d_tk_sl.p; a.tbase = d_tbase.p; a.xf = xf.p; a.add = nullptr;
         a.chain_cnt = nullptr;       // (set below when this sweep chains its lower levels)
         a.recs = d_recs.p ? reinterpret_cast<const char*>(d_recs.p) : nullptr;
         a.tall_ws = tall_ws.p;
-        const bool no_top = knobs().no_top;
-        if (nr > 1 && top_ntask > 0 && (no_top || !use_top || top_disabled || top_sgrid2 <= 0)) {
-            // two columns through a set with very tall fronts need its persistent kernel (supports_nr): without it, one
-            // column after the other
-            for (int c = 0; c < nr; ++c) enqueue_solve(d_b + (int64_t)c * ldb, d_x + (int64_t)c * ldx, st, use_top, 1, 0, 0, allow_chain);
-            return;
-        }
-        const size_t nl = launches.size();
-        // the persistent kernel covers the last ntl launches.  Right after a factorisation the W of the narrow top is
-        // still being formed on the side stream: that sweep keeps the per-level launches for the levels below the
-        // narrow top, so that the formation hides behind them
-        // Chained launches (chain_kernels.hip): the launches from chain_from on -- the levels with few enough fronts that
-        // a launch per level is one front's latency chain, not throughput -- as segments of ONE grid per direction, ordered
-        // by counters in memory instead of kernel boundaries; the wide levels below keep their launches.  The persistent
-        // kernel keeps its set -- its 1024-thread workgroups park a whole front's matrix items before the wait, a hop
-        // costs ~4 us against ~4.2 forward / ~6.3 backward in the 512-thread chained kernel -- and the launches between
-        // chain_from and the set are chained (cfg2: levels 3 and 4, 32 -> 26 us forward).  Both need the device's token
-        // (allow_chain / use_top: the caller holds it).  HIPKKT_CHAIN=0: off; HIPKKT_CHAIN_TOP=0: chain to the root
-        // instead of the persistent kernel (measured: cfg2's sweep pair 0.2675 against 0.260 ms).
-        const bool chain_env = knobs().chain;
-        const bool chain_top = knobs().chain_top;
-        // (a set with very tall fronts keeps its (front, slice) kernel: such fronts do not fit one workgroup's LDS)
-        const bool chain_want = chain_env && allow_chain && !chain_disabled && chain_from < nl && chain_lds * (size_t)nr <= 150 * 1024;
-        const bool keep_top = chain_want && (chain_top || top_ntask > 0);
-        const int tgrid = (no_top || !use_top || top_disabled || (chain_want && !keep_top)) ? 0 : top_grid_for(nr);
-        size_t ntl = tgrid > 0 ? top_launches : 0;
-        int ncount = top_count;
-        // (two columns through a set with very tall fronts: the whole set or nothing -- its lower levels do not fit the
-        //  per-level kernels with two columns; the sweep then waits for W at the set's first level)
-        if (ntl > 0 && w_pending && late_launches > 0 && late_launches < ntl && !(nr > 1 && top_ntask > 0)) { ntl = late_launches; ncount = late_count; }
-        const size_t first_w = nl - std::min(nl, late_launches);    // fronts from here on get their W late (w_pending)
-        const bool chain_on = chain_want && chain_from + 2 <= nl - ntl;
-        const size_t nper = chain_on ? chain_from : nl - ntl;        // launches [0, nper) go level by level, [nper, nl - ntl) chained
-        // a level's block-class launch and the one-wave launch behind it (sched order) go out as one launch
-        const bool no_merge = knobs().no_level_merge;
-        auto pair_at = [&](size_t q) {      // launches q (block-class) and q + 1 (one-wave) belong to one level
-            return !no_merge && q + 1 < nper && !launches[q].small && launches[q].ntall == 0 && launches[q + 1].small &&
-                   launches[q].level == launches[q + 1].level;
-        };
-        // (a level's block-class launch and the one-wave launch behind it as one kernel launch: the records of both)
-        auto pair_rec = [](const Launch& Lb, const Launch& Ls) {
-            RecSeg r = Ls.rec;
-            r.off[0] = Lb.rec.off[0]; r.stride[0] = Lb.rec.stride[0]; r.fmax[0] = Lb.rec.fmax[0];
-            return r;
-        };
-        // diagnostic (HIPKKT_VERBOSE): which path this sweep takes, once per distinct plan of this engine -- the three
-        // launch ranges, the persistent kernel and its grid, whether W was still pending and the record layout; at level 2
-        // the kernel family and workgroup size of every per-level launch as well (the tests' way to assert a path)
+        const std::vector<Launch>& launches = sch.launches;
+        const size_t nl = launches.size(), nper = plan.nper, ntl = plan.ntl, first_w = plan.first_w;
+        const bool chain_on = plan.chain_on;
+        const int ncount = plan.ncount;
+        // diagnostic (HIPKKT_VERBOSE): the plan, once per distinct plan of this engine (describe: schedule.cpp)
         if (knobs().verbose >= 1) {
-            const bool sliced = ntl > 0 && top_ntask > 0;
-            const int pgrid = ntl == 0 ? 0 : (sliced ? (nr == 2 ? top_sgrid2 : top_sgrid) : std::min(tgrid, ncount));
-            char buf[256];
-            std::snprintf(buf, sizeof buf, "nr %d per-level [0,%zu) chained [%zu,%zu) persistent [%zu,%zu) grid %d kernel %s threads %d w_pending %d packed %d",
-                          nr, nper, nper, nl - ntl, nl - ntl, nl, pgrid, ntl == 0 ? "none" : (sliced ? "sliced" : "top"),
-                          ntl == 0 ? 0 : (sliced || top_tall ? 1024 : 512), w_pending ? 1 : 0, a.recs ? 1 : 0);
-            bool seen = false;
-            for (const std::string& s : sweep_plans_seen) seen = seen || s == buf;
-            if (!seen) {
-                sweep_plans_seen.push_back(buf);
-                std::fprintf(stderr, "[hipkkt] sweep plan: %s\n", buf);
-                if (knobs().verbose >= 2)
-                    for (size_t q = 0; q < nper; ++q) {
-                        const Launch& L = launches[q];
-                        if (pair_at(q)) {
-                            const Launch& Ls = launches[q + 1];
-                            std::fprintf(stderr, "[hipkkt] sweep launch %zu+%zu level %d: family level solve_bs %d fmax %d block %d wave %d tiny %d\n", q, q + 1,
-                                         L.level, L.solve_bs, std::max(L.fmax, Ls.fmax), L.count, Ls.count - Ls.ntiny, Ls.ntiny);
-                            ++q;
-                        } else if (L.small) {
-                            std::fprintf(stderr, "[hipkkt] sweep launch %zu level %d: family small solve_bs 256 fmax %d block 0 wave %d tiny %d\n", q, L.level,
-                                         L.fmax, L.count - L.ntiny, L.ntiny);
-                        } else {
-                            std::fprintf(stderr, "[hipkkt] sweep launch %zu level %d: family %s solve_bs %d fmax %d block %d wave 0 tiny 0\n", q, L.level,
-                                         L.ntall == 0 ? "block" : (L.ntall == L.count ? "tall" : "block+tall"), L.solve_bs, L.fmax, L.count);
-                        }
-                    }
+            const std::string text = describe(plan, sch, nr, w_pending, a.recs != nullptr);
+            if (std::find(sweep_plans_seen.begin(), sweep_plans_seen.end(), text) == sweep_plans_seen.end()) {
+                sweep_plans_seen.push_back(text);
+                std::fprintf(stderr, "[hipkkt] sweep plan: %s\n", text.c_str());
+                if (knobs().verbose >= 2) std::fputs(describe_launches(plan, sch).c_str(), stderr);
             }
         }
         bool chain_stamp = false;
@@ -859,7 +751,7 @@ private:
         size_t ca_lds = 0;
         auto chain_reset = [&]() {
             ca.nseg = 0; ca.lo = 1 << 30; ca.hi = 0; ca.cnt = d_chain.p; ca.done = d_chain.p + S.nsuper; ca.nchild = d_chain_nchild.p;
-            ca.abort_word = top_flags.p + 2 * top_nflag; ca.epoch = chain_epoch;
+            ca.abort_word = top_flags.p + 2 * sch.top_nflag; ca.epoch = chain_epoch;
             ca.lo0 = chain_on ? launches[nper].begin : 0;
             ca.nstamp = chain_on ? launches[nl - ntl - 1].begin + launches[nl - ntl - 1].count - ca.lo0 : 0;
             ca_wgs = 0; ca_lds = 0;
@@ -895,16 +787,14 @@ private:
             // diagnostic (HIPKKT_TOP_STAMPS=n): the n-th single-column chained sweep records six time stamps per
             // block-class front and direction, printed per launch afterwards
             if (stamp_call > 0 && nr == 1 && !w_pending && ++n_stamp_sweeps == stamp_call) {
-                const size_t nst = (size_t)(launches[nl - ntl - 1].begin + launches[nl - ntl - 1].count - launches[nper].begin);
-                top_stamps.alloc(2 * nst * 8);
-                top_stamps.zero(st);
+                start_stamps((size_t)(launches[nl - ntl - 1].begin + launches[nl - ntl - 1].count - launches[nper].begin), st);
                 chain_stamp = true;
             }
         }
         for (size_t q = 0; q < nper; ++q) {
             const Launch& L = launches[q];
             if (q == first_w) wait_w(st);
-            if (pair_at(q)) {
+            if (pair_at(sch, q, plan)) {
                 const Launch& Ls = launches[q + 1];
                 if (q + 1 == first_w) wait_w(st);
                 launch_fwd_level(a, pair_rec(L, Ls), L.begin, L.count, Ls.count - Ls.ntiny, Ls.ntiny, L.solve_bs, L.lds_solve, st, nr);
@@ -925,128 +815,39 @@ private:
             chain_flush(true);
         }
         wait_w(st);
-        if (ntl > 0) {
-            const Launch& L0 = launches[nl - ntl];
-            if (top_ntask > 0) {
-                // the set holds very tall fronts: the (front, slice) kernel; positions count from the full set's first front
-                const Launch& Lfull = launches[nl - top_launches];
-                const int pos0 = top_count - ncount;
-                const int task0 = h_tbase[(size_t)pos0];
-                bool sl_stamp = false;
-                if (stamp_call > 0 && !chain_on && nr == 1 && ntl == top_launches && ++n_stamp_sweeps == stamp_call) {
-                    top_stamps.alloc((size_t)2 * (top_ntask - task0) * 8);
-                    top_stamps.zero(st);
-                    a.top_stamps = (long long*)top_stamps.p;
-                    sl_stamp = true;
-                }
-                launch_top_solve_sliced(a, Lfull.begin, pos0, task0, top_ntask, nr == 2 ? top_sgrid2 : top_sgrid, top_slds, top_flags.p,
-                                        top_nflag, ++top_epoch, st, nr);
-                a.top_stamps = nullptr;
-                if (sl_stamp) {
-                    // (front, slice) tasks: per direction the mean time from a task's start to its flags seen, from there
-                    // to its publication, and the sweep's span
-                    const size_t nt = (size_t)(top_ntask - task0);
-                    std::vector<long long> h(2 * nt * 8);
-                    HIP_CHECK(hipMemcpyAsync(h.data(), top_stamps.p, h.size() * 8, hipMemcpyDeviceToHost, st));
-                    HIP_CHECK(hipStreamSynchronize(st));
-                    for (int dir = 0; dir < 2; ++dir) {
-                        double wait = 0, work = 0;
-                        long long lo = h[(size_t)dir * nt * 8], hi = 0;
-                        std::vector<double> works;
-                        for (size_t t = 0; t < nt; ++t) {
-                            const long long* e = &h[((size_t)dir * nt + t) * 8];
-                            wait += (e[2] - e[0]) * 0.01;
-                            work += (e[5] - e[2]) * 0.01;
-                            works.push_back((e[5] - e[2]) * 0.01);
-                            lo = std::min(lo, e[0]); hi = std::max(hi, e[5]);
-                        }
-                        std::sort(works.begin(), works.end());
-                        std::fprintf(stderr, "[top stamps] sliced %s: %zu tasks, span %.1f us; per task: start->flags seen %.2f us (mean), flags seen->publish "
-                                     "%.2f us (mean), %.2f (median), %.2f (max)\n", dir == 0 ? "fwd" : "bwd", nt, (hi - lo) * 0.01, wait / nt, work / nt,
-                                     works[nt / 2], works.back());
-                    }
-                }
-            } else {
-                const int stamp_nr = knobs().top_stamps_nr;
-                if (stamp_call > 0 && !chain_on && nr == stamp_nr && ntl == top_launches && ++n_stamp_sweeps == stamp_call) {
-                    top_stamps.alloc((size_t)2 * ncount * 8);
-                    top_stamps.zero(st);
-                    a.top_stamps = (long long*)top_stamps.p;
-                    stamp_now = true;
-                }
-                launch_top_solve(a, L0.begin, ncount, std::min(tgrid, ncount), top_lds, top_flags.p, top_count, ++top_epoch, st, top_tall, nr);
-                a.top_stamps = nullptr;
+        if (plan.kernel == TopKernel::sliced) {
+            // the set holds very tall fronts: the (front, slice) kernel; positions count from the full set's first front
+            const Launch& Lfull = launches[nl - sch.top_launches];
+            const int pos0 = sch.top_count - ncount;
+            const int task0 = sch.h_tbase[(size_t)pos0];
+            const bool sl_stamp = stamp_call > 0 && !chain_on && nr == 1 && ntl == sch.top_launches && ++n_stamp_sweeps == stamp_call;
+            if (sl_stamp) {
+                start_stamps((size_t)(sch.top_ntask - task0), st);
+                a.top_stamps = (long long*)top_stamps.p;
             }
-        }
-        if (stamp_now) {
-            std::vector<long long> h((size_t)2 * ncount * 8);
-            HIP_CHECK(hipMemcpyAsync(h.data(), top_stamps.p, h.size() * 8, hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            long long t0 = h[0];
-            for (int p = 0; p < ncount; ++p) t0 = std::min(t0, h[(size_t)p * 8]);
-            const int pbase = launches[nl - ntl].begin;
-            for (int dir = 0; dir < 2; ++dir) {
-                double prev_done = 0.0;
-                for (size_t qq = 0; qq < ntl; ++qq) {
-                    const size_t q = dir == 0 ? nl - ntl + qq : nl - 1 - qq;
-                    const Launch& L = launches[q];
-                    double d[5] = {0, 0, 0, 0, 0}, first_start = 1e30, last_seen = 0, last_done = 0, crit[5] = {0, 0, 0, 0, 0};
-                    for (int t = L.begin; t < L.begin + L.count; ++t) {
-                        const long long* e = &h[((size_t)dir * ncount + (size_t)(t - pbase)) * 8];
-                        for (int k = 0; k < 5; ++k) d[k] += (e[k + 1] - e[k]) * 0.01;
-                        first_start = std::min(first_start, (e[0] - t0) * 0.01);
-                        last_seen = std::max(last_seen, (e[2] - t0) * 0.01);
-                        if ((e[5] - t0) * 0.01 > last_done) {
-                            last_done = (e[5] - t0) * 0.01;
-                            for (int k = 0; k < 5; ++k) crit[k] = (e[k + 1] - e[k]) * 0.01;
-                        }
-                    }
-                    std::fprintf(stderr, "[top stamps] %s level %2d: %4d fronts, first starts %7.2f, last sees its flags %7.2f, last publishes %7.2f "
-                                 "(hop %5.2f) us | mean: preload %5.2f wait %6.2f gather %5.2f products %5.2f reduce+store %5.2f | "
-                                 "last front: %5.2f %6.2f %5.2f %5.2f %5.2f\n", dir == 0 ? "fwd" : "bwd", L.level, L.count, first_start, last_seen,
-                                 last_done, last_done - prev_done, d[0] / L.count, d[1] / L.count, d[2] / L.count, d[3] / L.count,
-                                 d[4] / L.count, crit[0], crit[1], crit[2], crit[3], crit[4]);
-                    prev_done = last_done;
-                }
+            launch_top_solve_sliced(a, Lfull.begin, pos0, task0, sch.top_ntask, plan.pgrid, sch.top_slds, top_flags.p,
+                                    sch.top_nflag, ++top_epoch, st, nr);
+            a.top_stamps = nullptr;
+            if (sl_stamp) print_sliced_stamps((size_t)(sch.top_ntask - task0), st);
+        } else if (plan.kernel == TopKernel::top) {
+            const bool stamp_now = stamp_call > 0 && !chain_on && nr == knobs().top_stamps_nr && ntl == sch.top_launches && ++n_stamp_sweeps == stamp_call;
+            if (stamp_now) {
+                start_stamps((size_t)ncount, st);
+                a.top_stamps = (long long*)top_stamps.p;
             }
+            launch_top_solve(a, launches[nl - ntl].begin, ncount, plan.pgrid, sch.top_lds, top_flags.p, sch.top_count, ++top_epoch, st, sch.top_tall, nr);
+            a.top_stamps = nullptr;
+            if (stamp_now) print_top_stamps(plan, st);
         }
         if (chain_on) {
             chain_reset();
             for (size_t q = nl - ntl; q-- > nper;) chain_add(launches[q], false);
             chain_flush(false);
-            if (chain_stamp) {
-                const int lo0 = launches[nper].begin;
-                const size_t nst = (size_t)(launches[nl - ntl - 1].begin + launches[nl - ntl - 1].count - lo0);
-                std::vector<long long> h(2 * nst * 8);
-                HIP_CHECK(hipMemcpyAsync(h.data(), top_stamps.p, h.size() * 8, hipMemcpyDeviceToHost, st));
-                HIP_CHECK(hipStreamSynchronize(st));
-                for (int dir = 0; dir < 2; ++dir) {
-                    long long t00 = 0;
-                    for (size_t k = 0; k < nst; ++k) { const long long v = h[((size_t)dir * nst + k) * 8]; if (v && (!t00 || v < t00)) t00 = v; }
-                    for (size_t qq = nper; qq + ntl < nl; ++qq) {
-                        const size_t q = dir == 0 ? qq : nl - ntl - 1 - (qq - nper);
-                        const Launch& L = launches[q];
-                        if (L.small) continue;
-                        double d[5] = {0, 0, 0, 0, 0}, first_start = 1e30, last_start = 0, last_seen = 0, first_done = 1e30, last_done = 0;
-                        for (int t = L.begin; t < L.begin + L.count; ++t) {
-                            const long long* e = &h[((size_t)dir * nst + (size_t)(t - lo0)) * 8];
-                            for (int k = 0; k < 5; ++k) d[k] += (e[k + 1] - e[k]) * 0.01;
-                            first_start = std::min(first_start, (e[0] - t00) * 0.01);
-                            last_start = std::max(last_start, (e[0] - t00) * 0.01);
-                            last_seen = std::max(last_seen, (e[2] - t00) * 0.01);
-                            first_done = std::min(first_done, (e[5] - t00) * 0.01);
-                            last_done = std::max(last_done, (e[5] - t00) * 0.01);
-                        }
-                        std::fprintf(stderr, "[chain stamps] %s launch %2zu level %2d: %4d fronts, starts %6.2f .. %6.2f, last sees its flag %6.2f, done %6.2f .. %6.2f us | "
-                                     "mean: preload %5.2f wait %6.2f gather %5.2f products %5.2f reduce+store %5.2f\n", dir == 0 ? "fwd" : "bwd", q, L.level, L.count,
-                                     first_start, last_start, last_seen, first_done, last_done, d[0] / L.count, d[1] / L.count, d[2] / L.count, d[3] / L.count, d[4] / L.count);
-                    }
-                }
-            }
+            if (chain_stamp) print_chain_stamps(plan, st);
         }
         for (size_t q = nper; q-- > 0;) {
             const Launch& L = launches[q];
-            if (q > 0 && pair_at(q - 1)) {
+            if (q > 0 && pair_at(sch, q - 1, plan)) {
                 const Launch& Lb = launches[q - 1];
                 launch_bwd_level(a, pair_rec(Lb, L), Lb.begin, Lb.count, L.count - L.ntiny, L.ntiny, Lb.solve_bs, Lb.lds_solve, st, nr);
                 --q;
@@ -1058,6 +859,114 @@ private:
             }
         }
         HIP_CHECK(hipGetLastError());
+    }
+
+    // ---- diagnostic time stamps (HIPKKT_TOP_STAMPS): eight stamps per record and direction in top_stamps, n records per
+    // direction; read back behind the sweep (synchronises) and printed by the kernel that wrote them
+    void start_stamps(size_t n, hipStream_t st)
+    {
+        top_stamps.alloc(2 * n * 8);
+        top_stamps.zero(st);
+    }
+    std::vector<long long> read_stamps(size_t n, hipStream_t st)
+    {
+        std::vector<long long> h(2 * n * 8);
+        HIP_CHECK(hipMemcpyAsync(h.data(), top_stamps.p, h.size() * 8, hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return h;
+    }
+    // one front's five phases (preload, wait, gather, products, reduce + store) in us, added to d
+    static void add_phases(const long long* e, double d[5])
+    {
+        for (int k = 0; k < 5; ++k) d[k] += (e[k + 1] - e[k]) * 0.01;
+    }
+    // (front, slice) tasks: per direction the mean time from a task's start to its flags seen, from there
+    // to its publication, and the sweep's span
+    void print_sliced_stamps(size_t nt, hipStream_t st)
+    {
+        const std::vector<long long> h = read_stamps(nt, st);
+        for (int dir = 0; dir < 2; ++dir) {
+            double wait = 0, work = 0;
+            long long lo = h[(size_t)dir * nt * 8], hi = 0;
+            std::vector<double> works;
+            for (size_t t = 0; t < nt; ++t) {
+                const long long* e = &h[((size_t)dir * nt + t) * 8];
+                wait += (e[2] - e[0]) * 0.01;
+                work += (e[5] - e[2]) * 0.01;
+                works.push_back((e[5] - e[2]) * 0.01);
+                lo = std::min(lo, e[0]); hi = std::max(hi, e[5]);
+            }
+            std::sort(works.begin(), works.end());
+            std::fprintf(stderr, "[top stamps] sliced %s: %zu tasks, span %.1f us; per task: start->flags seen %.2f us (mean), flags seen->publish "
+                         "%.2f us (mean), %.2f (median), %.2f (max)\n", dir == 0 ? "fwd" : "bwd", nt, (hi - lo) * 0.01, wait / nt, work / nt,
+                         works[nt / 2], works.back());
+        }
+    }
+    // the persistent kernel, per level of its part of the set
+    void print_top_stamps(const SweepPlan& plan, hipStream_t st)
+    {
+        const std::vector<Launch>& launches = sch.launches;
+        const size_t nl = launches.size(), ntl = plan.ntl;
+        const int ncount = plan.ncount;
+        const std::vector<long long> h = read_stamps((size_t)ncount, st);
+        long long t0 = h[0];
+        for (int p = 0; p < ncount; ++p) t0 = std::min(t0, h[(size_t)p * 8]);
+        const int pbase = launches[nl - ntl].begin;
+        for (int dir = 0; dir < 2; ++dir) {
+            double prev_done = 0.0;
+            for (size_t qq = 0; qq < ntl; ++qq) {
+                const size_t q = dir == 0 ? nl - ntl + qq : nl - 1 - qq;
+                const Launch& L = launches[q];
+                double d[5] = {0, 0, 0, 0, 0}, first_start = 1e30, last_seen = 0, last_done = 0, crit[5] = {0, 0, 0, 0, 0};
+                for (int t = L.begin; t < L.begin + L.count; ++t) {
+                    const long long* e = &h[((size_t)dir * ncount + (size_t)(t - pbase)) * 8];
+                    add_phases(e, d);
+                    first_start = std::min(first_start, (e[0] - t0) * 0.01);
+                    last_seen = std::max(last_seen, (e[2] - t0) * 0.01);
+                    if ((e[5] - t0) * 0.01 > last_done) {
+                        last_done = (e[5] - t0) * 0.01;
+                        for (int k = 0; k < 5; ++k) crit[k] = (e[k + 1] - e[k]) * 0.01;
+                    }
+                }
+                std::fprintf(stderr, "[top stamps] %s level %2d: %4d fronts, first starts %7.2f, last sees its flags %7.2f, last publishes %7.2f "
+                             "(hop %5.2f) us | mean: preload %5.2f wait %6.2f gather %5.2f products %5.2f reduce+store %5.2f | "
+                             "last front: %5.2f %6.2f %5.2f %5.2f %5.2f\n", dir == 0 ? "fwd" : "bwd", L.level, L.count, first_start, last_seen,
+                             last_done, last_done - prev_done, d[0] / L.count, d[1] / L.count, d[2] / L.count, d[3] / L.count,
+                             d[4] / L.count, crit[0], crit[1], crit[2], crit[3], crit[4]);
+                prev_done = last_done;
+            }
+        }
+    }
+    // the chained kernels, per block-class launch of the chained range
+    void print_chain_stamps(const SweepPlan& plan, hipStream_t st)
+    {
+        const std::vector<Launch>& launches = sch.launches;
+        const size_t nl = launches.size(), nper = plan.nper, ntl = plan.ntl;
+        const int lo0 = launches[nper].begin;
+        const size_t nst = (size_t)(launches[nl - ntl - 1].begin + launches[nl - ntl - 1].count - lo0);
+        const std::vector<long long> h = read_stamps(nst, st);
+        for (int dir = 0; dir < 2; ++dir) {
+            long long t00 = 0;
+            for (size_t k = 0; k < nst; ++k) { const long long v = h[((size_t)dir * nst + k) * 8]; if (v && (!t00 || v < t00)) t00 = v; }
+            for (size_t qq = nper; qq + ntl < nl; ++qq) {
+                const size_t q = dir == 0 ? qq : nl - ntl - 1 - (qq - nper);
+                const Launch& L = launches[q];
+                if (L.small) continue;
+                double d[5] = {0, 0, 0, 0, 0}, first_start = 1e30, last_start = 0, last_seen = 0, first_done = 1e30, last_done = 0;
+                for (int t = L.begin; t < L.begin + L.count; ++t) {
+                    const long long* e = &h[((size_t)dir * nst + (size_t)(t - lo0)) * 8];
+                    add_phases(e, d);
+                    first_start = std::min(first_start, (e[0] - t00) * 0.01);
+                    last_start = std::max(last_start, (e[0] - t00) * 0.01);
+                    last_seen = std::max(last_seen, (e[2] - t00) * 0.01);
+                    first_done = std::min(first_done, (e[5] - t00) * 0.01);
+                    last_done = std::max(last_done, (e[5] - t00) * 0.01);
+                }
+                std::fprintf(stderr, "[chain stamps] %s launch %2zu level %2d: %4d fronts, starts %6.2f .. %6.2f, last sees its flag %6.2f, done %6.2f .. %6.2f us | "
+                             "mean: preload %5.2f wait %6.2f gather %5.2f products %5.2f reduce+store %5.2f\n", dir == 0 ? "fwd" : "bwd", q, L.level, L.count,
+                             first_start, last_start, last_seen, first_done, last_done, d[0] / L.count, d[1] / L.count, d[2] / L.count, d[3] / L.count, d[4] / L.count);
+            }
+        }
     }
 
     std::vector<std::string> sweep_plans_seen;      // (HIPKKT_VERBOSE: the plans enqueue_solve has printed)
@@ -1076,11 +985,8 @@ private:
     DBuf<int> d_chain;           // [0, nsuper): forward counters (zero between sweeps); [nsuper, 2 nsuper): backward epoch words
     int chain_epoch = 0;
     bool chain_disabled = false;
-    size_t chain_from = ~(size_t)0;  // first chained launch (>= launches.size(): none)
-    size_t chain_lds = 0;            // LDS of the largest block-class front in the chained launches, per right-hand side
     DBuf<int> d_chain_nchild;    // per supernode: its children in chained launches (the ones that count themselves in)
-    std::vector<int64_t> h_toff; // (upload: solve-matrix offsets and chained-children counts, kept for build_records)
-    std::vector<int> h_nch;
+    std::vector<int64_t> h_toff; // (upload: solve-matrix offsets, kept for build_records)
     DBuf<int64_t> d_recs;        // packed sweep records (kernels.hpp: SolveHdr); empty: the legacy layout
     DBuf<double> tall_ws;        // work space of the tall-front sweep kernels (allocated when the schedule holds such fronts)
 
@@ -1179,7 +1085,7 @@ private:
 
 public:
     // device word set by the persistent kernel when one of its bounded waits expired (nullptr: no such kernel)
-    const int* top_abort_word() const { return (top_flags.p && (top_launches > 0 || chain_from < launches.size())) ? top_flags.p + 2 * top_nflag : nullptr; }
+    const int* top_abort_word() const { return (top_flags.p && (sch.top_launches > 0 || sch.chain_from < sch.launches.size())) ? top_flags.p + 2 * sch.top_nflag : nullptr; }
     // The caller has synchronised and found the abort word set: clear it and never use the kernel again.
     int64_t n_ov_fallbacks = 0, n_top_fallbacks = 0;      // lifetime counts (hipkkt_profile, hipkkt_ldl_fallbacks)
     int64_t n_ov_busy = 0;       // factorisations that were not admitted as class X / M (DevOp) and ran on fewer streams
@@ -1189,7 +1095,7 @@ public:
         top_disabled = true;
         chain_disabled = true;       // (the chained launches share the abort word: whichever wait expired, both go)
         ++n_top_fallbacks;
-        launch_zero_ints(top_flags.p + 2 * top_nflag, 1, stream);
+        launch_zero_ints(top_flags.p + 2 * sch.top_nflag, 1, stream);
         if (d_chain.p) launch_zero_ints(d_chain.p, 2 * S.nsuper, stream);       // (an abandoned sweep leaves counters behind)
         std::fprintf(stderr, "[hipkkt] persistent top-of-tree kernel gave up waiting (GPU shared with another "
                              "resident kernel?); falling back to one launch per level\n");
@@ -1228,25 +1134,25 @@ public:
                          "(saw %d of %d)", w[3], sn, w[5], w[6]);
             if ((w[3] == 1 || w[3] == 2) && sn >= 0 && sn < S.nsuper) {
                 int q = -1;
-                for (size_t k = 0; k < sched.size(); ++k) if (sched[k] == sn) q = (int)k;
+                for (size_t k = 0; k < sch.sched.size(); ++k) if (sch.sched[k] == sn) q = (int)k;
                 size_t lq = 0;
-                while (lq < launches.size() && !(q >= launches[lq].begin && q < launches[lq].begin + launches[lq].count)) ++lq;
+                while (lq < sch.launches.size() && !(q >= sch.launches[lq].begin && q < sch.launches[lq].begin + sch.launches[lq].count)) ++lq;
                 std::fprintf(stderr, "; supernode %d is in launch %zu of %zu (overlap from %zu, %zu merged runs, the first from %zu), level %d, parent %d", sn, lq,
-                             launches.size(), ov_first, ov_groups.size(), ov_groups.empty() ? launches.size() : ov_groups.front().first, lq < launches.size() ? launches[lq].level : -1, S.sn_parent[sn]);
+                             sch.launches.size(), sch.ov_first, sch.ov_groups.size(), sch.ov_groups.empty() ? sch.launches.size() : sch.ov_groups.front().first, lq < sch.launches.size() ? sch.launches[lq].level : -1, S.sn_parent[sn]);
             }
             std::fprintf(stderr, "\n");
             // the lowest overlapped launch with unfinished fronts: progress of its panels and tiles as the abort left them
-            std::vector<int> prog((size_t)S.nsuper), done((size_t)S.nsuper), nt((size_t)S.nsuper), started(launches.size());
+            std::vector<int> prog((size_t)S.nsuper), done((size_t)S.nsuper), nt((size_t)S.nsuper), started(sch.launches.size());
             (void)hipMemcpy(prog.data(), d_ov_prog.p, prog.size() * sizeof(int), hipMemcpyDeviceToHost);
             (void)hipMemcpy(done.data(), d_ov_done.p, done.size() * sizeof(int), hipMemcpyDeviceToHost);
             (void)hipMemcpy(nt.data(), d_ov_ntiles.p, nt.size() * sizeof(int), hipMemcpyDeviceToHost);
             (void)hipMemcpy(started.data(), d_ov_started.p, started.size() * sizeof(int), hipMemcpyDeviceToHost);
             int shown = 0;
-            for (size_t q = ov_first; q < launches.size() && shown < 12; ++q) {
-                const Launch& L = launches[q];
+            for (size_t q = sch.ov_first; q < sch.launches.size() && shown < 12; ++q) {
+                const Launch& L = sch.launches[q];
                 int unfinished = 0;
                 for (int t = L.begin; t < L.begin + L.count; ++t) {
-                    const int s2 = sched[(size_t)t];
+                    const int s2 = sch.sched[(size_t)t];
                     const int ncs = S.sn_start[s2 + 1] - S.sn_start[s2];
                     if (prog[(size_t)s2] < ncs || done[(size_t)s2] < nt[(size_t)s2]) {
                         if (shown < 12) {
@@ -1257,8 +1163,8 @@ public:
                                 const int c = S.child_idx[e];
                                 if (nt[(size_t)c] > 0) std::fprintf(stderr, " %d(%d/%d)", c, done[(size_t)c], nt[(size_t)c]);
                             }
-                            if (ov_group_of[q] >= 0) {
-                                const MergeGroup& g = ov_groups[(size_t)ov_group_of[q]];
+                            if (sch.ov_group_of[q] >= 0) {
+                                const MergeGroup& g = sch.ov_groups[(size_t)sch.ov_group_of[q]];
                                 std::fprintf(stderr, " | merged kernel of launches %zu..%zu: %d of %d workgroups started", g.first, g.end - 1, started[g.first], g.count);
                             }
                             std::fprintf(stderr, "\n");
@@ -1276,7 +1182,7 @@ public:
     {
         return knobs().factor_overlap;
     }
-    bool ov_active() const { return overlap_wanted() && !ov_disabled && ov_first < launches.size(); }
+    bool ov_active() const { return overlap_wanted() && !ov_disabled && sch.ov_first < sch.launches.size(); }
 
     int* flags_ptr() { return flags.p; }
 
@@ -1295,8 +1201,6 @@ private:
     int n_skipw_calls = 0;
 #endif
     DBuf<int> d_tinv_list;
-    std::vector<int> tinv_list, tinv_small_prefix;
-    int tinv_ncmax = 1;
     DBuf<int> flags;
     DBuf<int64_t> stamps;
     DBuf<int64_t> d_tiles;       // int2 {supernode, ti<<16|tj}
@@ -1310,48 +1214,27 @@ private:
     DBuf<int64_t> d_tile_cut;
     DBuf<int64_t> d_desc;        // FrontDesc = 8 x int64
     DBuf<int64_t> d_sdesc;       // FrontDesc per row slice of the sliced panels
-    std::vector<std::array<int, 3>> slice_list;   // (supernode, slice, slices) in launch order
     std::vector<int64_t> slice_kptr;              // per slice: its K scatter list in ksrc / kdst
     std::vector<int> slice_nk;
-    int64_t panel_cap = 0;
-    int panel_max_slices = 1;
     DBuf<int> d_spos, d_sn_parent, top_flags;
     DBuf<int> d_tk_pos, d_tk_sl, d_tbase;      // tasks of k_top_solve_sliced (SolveArgs::tk_*); empty unless the set has tall fronts
     DBuf<double> xf;
-    std::vector<int> h_tbase;
-    int top_ntask = 0, top_nflag = 0, top_sgrid = 0, top_sgrid2 = 0;
-    size_t top_slds = 0;
-    size_t top_launches = 0, late_launches = 0, top_lds = 0;
-    // overlap mode of the factorisation (factor_kernels.hip): the launches from ov_first on (the narrow top of the tree)
-    size_t ov_first = 0;         // == launches.size(): none
     bool ov_disabled = false;
-    int n_cus = 256, side_winv_blocks = 96;
-    // overlap mode: runs of consecutive launches whose panels go out as ONE kernel each (upload: overlap admission)
-    struct MergeGroup {
-        size_t first, end;           // launches [first, end)
-        int count;                   // panel workgroups of the kernel (whole fronts, or row slices: sliced)
-        size_t lds;
-        bool sliced;
-    };
-    std::vector<MergeGroup> ov_groups;        // in launch order
-    std::vector<int> ov_group_of;             // per launch: index into ov_groups, -1 = a kernel of its own
     bool ov_concurrent = false;          // the main and the tile stream run side by side (choose_side_streams)
     DBuf<int> d_ov_prog, d_ov_done, d_ov_ntiles, d_ov_sprog, d_ov_sbase, d_ov_started;
     hipStream_t ov_stream = nullptr;
     hipEvent_t ev_ov_fork = nullptr, ev_ov_join = nullptr, ev_dev_done = nullptr;
     bool ov_join_pending = false;    // ev_ov_join recorded, not yet waited for (enqueue_factor)
     size_t nr_cap = 1;           // right-hand sides xp / uvec are sized for
-    int top_grid_nr[2] = {-1, -1};   // the persistent kernel's grid for 2 / 4 right-hand sides (asked on first use)
-    int top_count = 0, late_count = 0, top_grid = 0, top_epoch = 0;
-    bool top_tall = true;        // the persistent kernel's 1024-thread build (default) or its 512-thread one
-    std::vector<int64_t> tile_base;   // per supernode: index of its first tile in `tiles` (-1: none)
+    int top_epoch = 0;
     DBuf<int> d_gl_src, d_udst;
     DBuf<int64_t> d_glm_ptr, d_hp_lidx, d_pr_ptr;     // many-column sweeps: gather lists without the pulled leaves, and the pulled terms
     DBuf<int> d_udst_m, d_hp_col, d_hp_row, d_pr_slot;
     int n_pull_rows = 0;
-    std::vector<Launch> launches;
-    std::vector<int> sched;
-    std::vector<int64_t> tiles;
+    // ---- what was decided (schedule.cpp) and what the device contributed to it
+    Schedule sch;
+    DeviceLimits dev;
+    NrGrids top_grid_nr;         // the persistent kernel's grid for 2 / 4 right-hand sides (asked on first use)
 
     TreeDev tree() const
     {
@@ -1369,257 +1252,28 @@ private:
         return t;
     }
 
-    int front_size(int s) const
-    {
-        return (S.sn_start[s + 1] - S.sn_start[s]) + (int)(S.rowptr[s + 1] - S.rowptr[s]);
-    }
+    int front_size(int s) const { return hipkkt::front_size(S, s); }
 
-    // too tall for the LDS of the block sweep kernels / of k_top_solve (solve_kernels.hip, k_fwd_tall)
-    // (HIPKKT_SOLVE_TALL_ROWS=n: fronts of n rows or more count as tall as well -- the tests' way to those paths)
-    bool front_is_tall(int s) const
-    {
-        const int tall_rows = knobs().solve_tall_rows;
-        const int f = front_size(s), nc = S.sn_start[s + 1] - S.sn_start[s];
-        return solve_lds_bytes(f, nc) > kLdsCap || (tall_rows > 0 && f >= tall_rows);
-    }
-
-    void build_schedule()
-    {
-        sched.clear();
-        launches.clear();
-        tiles.clear();
-        tinv_list.clear();
-        slice_list.clear();
-        tile_base.assign(S.nsuper, -1);
-        auto ncols = [&](int s) { return S.sn_start[s + 1] - S.sn_start[s]; };
-        auto is_small = [&](int s) {
-            int f = front_size(s), nc = ncols(s), nb = f - nc;
-            return f <= kSmallFrontMax && f * nc + nb * nb <= kSmallSliceMax;
-        };
-        int sched_cus = 256;
-        {
-            int dev = 0;
-            hipDeviceProp_t prop;
-            if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) sched_cus = prop.multiProcessorCount;
-            else (void)hipGetLastError();
-        }
-        int level_no = -1;
-        for (const Level& lv : S.levels) {
-            ++level_no;
-            std::vector<int> small, big;
-            for (int t = lv.begin; t < lv.end; ++t) {
-                int s = S.level_sn[t];
-                (is_small(s) ? small : big).push_back(s);
-            }
-            // a handful of one-wave fronts beside a block-class launch is not worth launches of its own (one in the
-            // factorisation, two per solve, each ~5-45 us of pure latency): they ride with the block-class fronts
-            const int merge_small = knobs().merge_small;
-            if (!big.empty() && (int)small.size() <= merge_small) {
-                big.insert(big.end(), small.begin(), small.end());
-                small.clear();
-            }
-            const int slice_rows = knobs().slice_rows;
-            const bool slice_fit = knobs().slice_fit;
-            int level_slice_rows = slice_rows;
-            auto slices_of = [&](int s) {        // row slices the panel kernel needs for this front (1: fits one CU)
-                if (panel_cap <= 0) return 1;
-                const int nc = ncols(s), nb = front_size(s) - nc;
-                int r = panel_slices_needed(nc, nb, panel_cap, std::min(panel_max_slices, std::max(1, nb)));
-                if (r == 0) throw std::runtime_error("panel does not fit LDS even in row slices (panel_cap too large?)");
-                // More, shorter slices than LDS needs: a slice's block step is bound by its WORKER waves when it holds many
-                // rows (250 rows x 90 columns: 75 trailing tiles per block on 12 waves = 4-5 us against the diagonal
-                // chain's 3.7), and its assembly by what one CU can load; the price is one more redundant copy of the
-                // diagonal block's factorisation per slice.  128 rows (0 = as few slices as LDS allows): cfg5's
-                // factorisation 5.30 -> 5.06 ms, cfg3's 1.21 -> 1.23 (slices have K and item lists of their own, so the
-                // per-slice overhead no longer grows with their number).
-                // (the preference stops at 16 slices: beyond that only what LDS needs -- a 6289-row front in 49 slices of 128
-                //  rows measured 44.9 ms per factorisation against 40.3 in 16)
-                if (r > 1 && level_slice_rows > 0) r = std::max(r, std::min(std::min(panel_max_slices, 16), (nb + level_slice_rows - 1) / level_slice_rows));
-                return r;
-            };
-            // One round of panel workgroups where possible: every slice needs a CU to itself, so a level with more slices
-            // than CUs runs its panel kernel in two rounds (cfg3's second level: 99 fronts x 3 slices of 114 rows = 297
-            // workgroups, 112 us; x 2 slices of 171 rows = 198 workgroups, one round).  Such a level takes the shortest
-            // slices (>= the default 128 rows) that bring it down to the CU count, if LDS allows any.
-            level_slice_rows = slice_rows;
-            if (slice_fit && slice_rows > 0) {
-                auto total = [&]() {
-                    int t = 0;
-                    bool any = false;
-                    for (int s : big) { const int r = slices_of(s); t += r; any = any || r > 1; }
-                    return any ? t : 0;
-                };
-                if (total() > sched_cus) {
-                    static const int cand[] = {144, 160, 176, 192, 224, 256, 320, 384, 512, 1 << 20};
-                    for (int c : cand) {
-                        level_slice_rows = c;
-                        if (total() <= sched_cus) break;
-                    }
-                    if (total() > sched_cus) level_slice_rows = slice_rows;
-                }
-            }
-            auto work = [&](int s) { return (double)front_size(s) * front_size(s) * ncols(s); };
-            auto by_work = [&](int a, int b) { double wa = work(a), wb = work(b); return wa != wb ? wa > wb : a < b; };
-            std::sort(small.begin(), small.end(), by_work);
-            std::sort(big.begin(), big.end(), by_work);
-            // fronts factorised in row slices go to the end of the block-class launch (own panel kernel launch)
-            std::stable_partition(big.begin(), big.end(), [&](int s) { return slices_of(s) == 1; });
-            auto is_tall = [&](int s) { return front_is_tall(s); };
-            std::stable_partition(big.begin(), big.end(), [&](int s) { return !is_tall(s); });
-            // the tiny fronts (f <= 8) go to the end of the one-wave launch: the solves give them their own kernel
-            std::stable_partition(small.begin(), small.end(), [&](int s) { return front_size(s) > 8; });
-            const int ntiny_level = (int)std::count_if(small.begin(), small.end(), [&](int s) { return front_size(s) <= 8; });
-            for (int cls = 0; cls < 2; ++cls) {
-                const std::vector<int>& v = cls == 0 ? big : small;
-                if (v.empty()) continue;
-                Launch L{};
-                L.begin = (int)sched.size();
-                L.count = (int)v.size();
-                L.small = cls == 1;
-                L.level = level_no;
-                L.ntiny = cls == 1 ? ntiny_level : 0;
-                int fmax = 0, slice = 0;
-                for (int s : v) {
-                    int f = front_size(s), nc = ncols(s), nb = f - nc;
-                    fmax = std::max(fmax, f);
-                    if (!(cls == 1 && f <= 8)) slice = std::max(slice, f * nc + nb * nb);     // (tiny fronts: own kernel)
-                }
-                L.slice = (slice + 1) & ~1;
-                int pmax = 0;                       // LDS doubles of the largest panel: a trapezoid (panel kernel)
-                int64_t smax = 0;
-                L.nsliced = 0;
-                L.slice_begin = (int)slice_list.size();
-                // A launch that holds row-sliced fronts runs ALL its fronts through the sliced panel kernel, a whole front
-                // as a front of one slice: two panel kernels one after the other (whole, then sliced) cost a level of
-                // cfg5 30-57 us for the one to four whole fronts that sit beside its hundreds of slices.
-                bool all_sliced = false;
-                if (cls == 0) for (int s : v) all_sliced = all_sliced || slices_of(s) > 1;
-                for (int s : v) {
-                    const int r = cls == 0 ? slices_of(s) : 1;
-                    const int nc = ncols(s), nb = front_size(s) - nc;
-                    if (r == 1 && !all_sliced) {
-                        pmax = std::max(pmax, front_size(s) * nc - nc * (nc - 1) / 2);
-                    } else {
-                        ++L.nsliced;
-                        smax = std::max(smax, panel_slice_doubles(nc, nb, r));
-                        for (int q = 0; q < r; ++q) slice_list.push_back({s, q, r});
-                    }
-                }
-                L.slice_count = (int)slice_list.size() - L.slice_begin;
-                L.lds_sliced = L.nsliced ? panel_lds_bytes(0, (int)smax) : 0;
-                L.nbk = kMaxNbk;
-                // (swept on cfg2 after the tree got shorter and wider: 128 / 192 beat the earlier 96 / 128 by 2 %)
-                L.bs_panel = fmax > 192 ? 1024 : (fmax > 128 ? 512 : 256);
-                L.lds_panel = panel_lds_bytes(fmax, pmax);
-                if (!L.small && L.lds_panel > kLdsCap)
-                    throw std::runtime_error("panel does not fit LDS (panel_cap too large?)");
-                if (L.lds_sliced > kLdsCap) throw std::runtime_error("panel slice does not fit LDS (panel_cap too large?)");
-                int ncmax = 0;
-                for (int s : v) ncmax = std::max(ncmax, ncols(s));
-                // (per front, then the maximum: the tallest front of a launch is a narrow panel and its widest a short one --
-                //  sized from (fmax, ncmax) jointly, a level with a 7000-row panel beside a 96-column one asked for LDS
-                //  nobody needs and the structure was refused as "too large")
-                L.lds_solve = 0;
-                L.ntall = 0;
-                if (!L.small) for (int s : v) {
-                    if (is_tall(s)) { ++L.ntall; continue; }
-                    L.lds_solve = std::max(L.lds_solve, solve_lds_bytes(front_size(s), ncols(s)));
-                }
-                L.fmax = fmax;
-                L.ncmax = ncmax;
-                const int small_bs_count = knobs().bs128_count;
-                const int small_bs_f = knobs().bs128_f;
-                L.solve_bs = (L.count >= small_bs_count && fmax <= small_bs_f) ? 128 : 256;
-                L.tinv_begin = (int)tinv_list.size();
-                L.tinv_ncmax = 1;
-                if (!L.small) for (int s : v) {
-                    tinv_list.push_back(s);
-                    L.tinv_ncmax = std::max(L.tinv_ncmax, ncols(s));
-                    tinv_ncmax = std::max(tinv_ncmax, ncols(s));
-                }
-                L.tinv_count = (int)tinv_list.size() - L.tinv_begin;
-                if (L.lds_solve > kLdsCap) throw std::runtime_error("front too large for the solve kernels");
-                L.tile_begin = (int)tiles.size();
-                int64_t tile_cols = 0;
-                if (!L.small) {
-                    for (int s : v) {
-                        int nb = front_size(s) - ncols(s);
-                        int nt = (nb + 63) / 64;
-                        tile_base[s] = (int64_t)tiles.size();
-                        tile_cols += (int64_t)ncols(s) * (nt * (nt + 1) / 2);
-                        for (int ti = 0; ti < nt; ++ti)
-                            for (int tj = 0; tj <= ti; ++tj) {
-                                // int2 {x = s, y = ti<<16 | tj}, little endian in one int64
-                                uint64_t lo = (uint32_t)s, hi = (uint32_t)((ti << 16) | tj);
-                                tiles.push_back((int64_t)(lo | (hi << 32)));
-                            }
-                    }
-                }
-                L.ntiles = (int)tiles.size() - L.tile_begin;
-                L.tile_nc = L.ntiles > 0 ? (int)(tile_cols / L.ntiles) : 0;
-                launches.push_back(L);
-                sched.insert(sched.end(), v.begin(), v.end());
-            }
-        }
-    }
-
-    // Packed sweep records (kernels.hpp: SolveHdr / RecSeg): per launch and size class one record size, so that a
-    // kernel finds a front's record from its place in the launch and fetches header and row slots in one round of loads.
-    // HIPKKT_PACKED=0, or more than HIPKKT_PACKED_MAX_MB (4096) of records -- a wide level with one very tall front pays
-    // that front's height for every front --: the legacy layout.
+    // The byte image of the packed sweep records, in the layout schedule.cpp decided (layout_records: Launch::rec,
+    // sch.rec_bytes; 0 = the legacy layout, nothing to build).
     void build_records(const std::vector<int64_t>& glptr, const std::vector<int>& gsrc)
     {
-        const bool packed_on = knobs().packed;
-        const int64_t max_mb = knobs().packed_max_mb;
-        for (Launch& L : launches) L.rec = RecSeg{};
-        if (!packed_on) return;
-        static_assert(sizeof(SolveHdr) == 64, "SolveHdr layout");
-        int64_t total = 0;
-        struct Cls { int first, count, cls; };
-        auto classes = [&](const Launch& L) {
-            std::vector<Cls> v;
-            if (L.small) {
-                if (L.count - L.ntiny > 0) v.push_back({L.begin, L.count - L.ntiny, 1});
-                if (L.ntiny > 0) v.push_back({L.begin + L.count - L.ntiny, L.ntiny, 2});
-            } else if (L.count > 0) {
-                v.push_back({L.begin, L.count, 0});
-            }
-            return v;
-        };
-        // no gather slots for the one-wave launch of tree level 0 (its fronts have no children, and its kernels are told
-        // so: `leaf`) -- unless a block-class launch of that level sits in front of it: the two may then go out as one
-        // level kernel, whose one-wave bodies read the slots
-        auto no_slots = [&](size_t q) {
-            const Launch& L = launches[q];
-            return L.small && L.level == 0 && !(q > 0 && !launches[q - 1].small && launches[q - 1].level == 0);
-        };
-        for (size_t q = 0; q < launches.size(); ++q) {
-            Launch& L = launches[q];
-            const bool leaf = no_slots(q);
-            for (const Cls& c : classes(L)) {
-                const int fmax = c.cls == 0 ? ((L.fmax + 3) & ~3) : (c.cls == 1 ? 64 : 8);
-                const int64_t stride = ((int64_t)sizeof(SolveHdr) + 4 * (int64_t)fmax + (leaf ? 0 : 32 * (int64_t)fmax) + 63) & ~(int64_t)63;
-                if (stride > (1 << 30)) return;
-                L.rec.off[c.cls] = total;
-                L.rec.stride[c.cls] = (int)stride;
-                L.rec.fmax[c.cls] = fmax;
-                total += stride * c.count;
-            }
-        }
-        if (total > max_mb * (1 << 20)) {
-            for (Launch& L : launches) L.rec = RecSeg{};
-            if (knobs().verbose) std::fprintf(stderr, "[hipkkt] packed sweep records would take %.0f MB: legacy layout\n", total / 1048576.0);
-            return;
-        }
+        if (sch.rec_refused_bytes && knobs().verbose)
+            std::fprintf(stderr, "[hipkkt] packed sweep records would take %.0f MB: legacy layout\n", sch.rec_refused_bytes / 1048576.0);
+        const int64_t total = sch.rec_bytes;
+        if (total <= 0) return;
         std::vector<int64_t> store((size_t)(total / 8) + 8, 0);
         char* base = reinterpret_cast<char*>(store.data());
-        for (size_t q = 0; q < launches.size(); ++q) {
-            const Launch& L = launches[q];
-            const bool leaf = no_slots(q);
-            for (const Cls& c : classes(L)) {
+        for (size_t q = 0; q < sch.launches.size(); ++q) {
+            const Launch& L = sch.launches[q];
+            const bool leaf = rec_no_slots(sch.launches, q);
+            RecClass classes[2];
+            const int nclasses = rec_classes(L, classes);
+            for (int ci = 0; ci < nclasses; ++ci) {
+                const RecClass& c = classes[ci];
                 const int fmax = L.rec.fmax[c.cls];
                 for (int k = 0; k < c.count; ++k) {
-                    const int sn = sched[(size_t)(c.first + k)];
+                    const int sn = sch.sched[(size_t)(c.first + k)];
                     char* rec = base + L.rec.off[c.cls] + (int64_t)k * L.rec.stride[c.cls];
                     const int nc = S.sn_start[sn + 1] - S.sn_start[sn], nb = (int)(S.rowptr[sn + 1] - S.rowptr[sn]), f = nc + nb;
                     if (f > fmax) throw std::runtime_error("packed record: front larger than its class");
@@ -1628,7 +1282,7 @@ private:
                     h.rp = S.rowptr[sn];
                     h.s = sn; h.c0 = S.sn_start[sn]; h.nc = nc; h.nb = nb;
                     h.par = S.sn_parent[sn];
-                    h.nchild = h_nch.empty() ? 0 : h_nch[(size_t)sn];
+                    h.nchild = sch.nch.empty() ? 0 : sch.nch[(size_t)sn];
                     std::memcpy(rec, &h, sizeof(h));
                     int* idx = reinterpret_cast<int*>(rec + sizeof(SolveHdr));
                     for (int i = 0; i < nc; ++i) idx[i] = S.perm[(size_t)(h.c0 + i)];
@@ -1650,7 +1304,6 @@ private:
                 }
             }
         }
-        store.resize((size_t)(total / 8) + 8);
         d_recs.upload(store);
         if (knobs().verbose) std::fprintf(stderr, "[hipkkt] packed sweep records: %.1f MB\n", total / 1048576.0);
     }
@@ -1663,8 +1316,8 @@ private:
         std::vector<char> pulled((size_t)S.nsuper, 0);
         {
             std::vector<char> in_small((size_t)S.nsuper, 0);       // (one-wave launches only: the block kernels do not know the flag)
-            for (const Launch& L : launches)
-                if (L.small) for (int t = L.begin; t < L.begin + L.count; ++t) in_small[(size_t)sched[(size_t)t]] = 1;
+            for (const Launch& L : sch.launches)
+                if (L.small) for (int t = L.begin; t < L.begin + L.count; ++t) in_small[(size_t)sch.sched[(size_t)t]] = 1;
             for (int s = 0; pull_on && s < S.nsuper; ++s) {
                 const int nb = (int)(S.rowptr[s + 1] - S.rowptr[s]);
                 pulled[(size_t)s] = in_small[(size_t)s] && S.child_ptr[s + 1] == S.child_ptr[s] && S.sn_start[s + 1] - S.sn_start[s] == 1 &&
@@ -1690,16 +1343,16 @@ private:
         d_child_idx.upload(S.child_idx);
         d_kptr.upload(S.kptr);
         std::vector<int> ks_all(S.ksrc);
-        slice_kptr.assign(slice_list.size(), 0);
-        slice_nk.assign(slice_list.size(), 0);
+        slice_kptr.assign(sch.slice_list.size(), 0);
+        slice_nk.assign(sch.slice_list.size(), 0);
         {
             // the panel kernel keeps a block-class front as a trapezoid in LDS (factor_kernels.hip: pcol): its K
             // entries get their packed position; one-wave fronts keep lrow + lcol*f
             std::vector<int> kd(S.kdst);
-            for (const Launch& L : launches) {
+            for (const Launch& L : sch.launches) {
                 if (L.small) continue;
                 for (int q = L.begin; q < L.begin + L.count - L.nsliced; ++q) {      // (sliced fronts keep lrow + lcol*f)
-                    const int s = sched[q];
+                    const int s = sch.sched[q];
                     const int f = front_size(s);
                     for (int64_t e = S.kptr[s]; e < S.kptr[s + 1]; ++e) {
                         const int lcol = kd[e] / f, lrow = kd[e] - lcol * f;
@@ -1709,8 +1362,8 @@ private:
             }
             // A row slice of a sliced front gets a K list of its own, with the positions in ITS LDS image (top block +
             // its rows, as a trapezoid): the panel kernel neither scans the other slices' entries nor divides per entry.
-            for (size_t q = 0; q < slice_list.size(); ++q) {
-                const int s = slice_list[q][0], sl = slice_list[q][1], nsl = slice_list[q][2];
+            for (size_t q = 0; q < sch.slice_list.size(); ++q) {
+                const int s = sch.slice_list[q][0], sl = sch.slice_list[q][1], nsl = sch.slice_list[q][2];
                 const int ff = front_size(s), nc = S.sn_start[s + 1] - S.sn_start[s], nb = ff - nc;
                 const int rsmax = (nb + nsl - 1) / nsl, r_lo = nc + sl * rsmax;
                 const int rs = std::max(0, std::min(rsmax, ff - r_lo)), f = nc + rs;
@@ -1728,91 +1381,16 @@ private:
             d_kdst.upload(kd);
             d_ksrc.upload(ks_all);
         }
-        d_sched.upload(sched);
+        d_sched.upload(sch.sched);
         // (d_tiles is uploaded with the tile work lists below: the launch order of a level's tiles may be permuted there)
         {
-            // Overlap admission.  In overlap mode a level's PANEL workgroups (each needs a CU to itself: ~150 KB of LDS) run
-            // beside the level's TILE workgroups on the overlap stream (53 KB: they fit beside each other, but one of them
-            // on a CU is enough to keep a panel out) and the side stream's W formation.  Tiles wait for their panel's
-            // blocks and panels wait for their children's tiles, so forward progress needs every panel workgroup of a
-            // launch to be RESIDENT before a tile of that launch may wait for it.  That is enforced, not hoped for: the
-            // launch's tile kernel sits behind a gate (k_ov_gate) that opens when all its panel workgroups have started.
-            // Everything else on the device is work that ends by itself (the previous launch's tiles, whose panels are
-            // resident or done; the W formation, which waits for nothing), so the panel workgroups do get their CUs,
-            // provided there are enough CUs for all of them plus the gate's wave at once:
-            //     panel workgroups of the launch + 1 + margin <= CUs.
-            // Below that bound the width is a matter of speed only: wide launches were measured slower in the mode
-            // (panels that wait hold whole CUs the tiles could use), so the default admits launches of up to 120 panel
-            // workgroups; HIPKKT_OV_MAX_FRONTS moves that, never beyond the bound.  (The bounded waits remain for what
-            // this argument cannot see: another process, or another handle's kernels, on the same device.)
-            {
-                int dev = 0;
-                hipDeviceProp_t prop;
-                if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) n_cus = prop.multiProcessorCount;
-                side_winv_blocks = knobs().winv_blocks > 0 ? knobs().winv_blocks : std::max(8, n_cus * 3 / 8);
-            }
-            constexpr int kOvMargin = 8;
-            // (the environment override is per process, the default per handle: n_cus is this handle's device's)
-            const int ov_max_env = knobs().ov_max_fronts;
-            const int ov_max = std::min(ov_max_env > 0 ? ov_max_env : 120 * n_cus / 256, n_cus - 1 - kOvMargin);
-            auto panel_wgs = [&](const Launch& L) { return L.count - L.nsliced + L.slice_count; };   // whole panels + row slices
-            size_t first = launches.size();
-            while (first > 0) {
-                const Launch& L = launches[first - 1];
-                if (L.small || panel_wgs(L) > ov_max) break;
-                --first;
-            }
-            // Launches with thousands of tiles stay out of the mode, and with them the whole handle (the overlapped launches
-            // are the schedule's tail): there the tiles ARE the level -- nothing to hide them behind -- and a tile of the mode
-            // is the slower one (54 KB of LDS instead of 33: two workgroups per CU instead of four; operands and results
-            // past the L2's write-back path).  Measured with the mode on / off, by the largest launch of the region:
-            // 1080 tiles 6.25 / 6.45 ms, 1279 tiles 3.17 / 3.65, 1145 tiles 3.74 / 3.72 | 2310 tiles 18.6 / 17.6,
-            // 2428 tiles 9.5 / 8.2, 4253 tiles 10.0 / 7.8, 13 041 tiles 54 / 27, cfg2 with 1 % long-range couplings
-            // (24 000 tiles) 143 / 61 ms.  (cfg2's overlapped launches have at most 418 tiles, cfg5's 630.)
-            const int ov_max_tiles = knobs().ov_max_tiles;
-            bool heavy_tiles = false;
-            for (size_t q = first; q < launches.size(); ++q) heavy_tiles = heavy_tiles || launches[q].ntiles > ov_max_tiles;
-            ov_first = (!heavy_tiles && launches.size() - first >= 3) ? first : launches.size();
-            {
-                // Runs of narrow launches whose panels share one kernel, found from the root downwards: all launches of a run
-                // are of one kind (whole panels, or row slices -- a launch with sliced fronts runs all its fronts as slices),
-                // a run has at most ov_merge_max workgroups in all (HIPKKT_OV_MERGE, 0 = off) and at least two launches, a
-                // launch in a run has at most ov_merge_wide workgroups (HIPKKT_OV_MERGE_WIDE: the workgroups of a run hold
-                // their CUs from the start of the run, which the tiles of a WIDE level below them would miss), and the first
-                // overlapped launch is in none (its tiles are released by an event).
-                const int ov_merge_max = knobs().ov_merge;
-                const int ov_merge_wide = knobs().ov_merge_wide;
-                const int ov_merge_groups = knobs().ov_merge_groups;
-                ov_groups.clear();
-                ov_group_of.assign(launches.size(), -1);
-                size_t m = launches.size();
-                const int cap = std::min(ov_merge_max, ov_max);
-                while (m > ov_first + 1 && (int)ov_groups.size() < ov_merge_groups) {
-                    MergeGroup g{m, m, 0, 0, launches[m - 1].nsliced > 0};
-                    // (the root's run takes launches of any width, as it always did; the runs below it narrow ones only)
-                    const int wide = ov_groups.empty() ? cap : ov_merge_wide;
-                    while (g.first > ov_first + 1 && !launches[g.first - 1].small &&
-                           (g.sliced ? launches[g.first - 1].nsliced == launches[g.first - 1].count : launches[g.first - 1].nsliced == 0) &&
-                           panel_wgs(launches[g.first - 1]) <= wide && g.count + panel_wgs(launches[g.first - 1]) <= cap) {
-                        const Launch& L = launches[g.first - 1];
-                        g.count += panel_wgs(L);
-                        g.lds = std::max(g.lds, g.sliced ? L.lds_sliced : L.lds_panel);
-                        --g.first;
-                    }
-                    if (g.end - g.first < 2) break;
-                    ov_groups.insert(ov_groups.begin(), g);
-                    m = g.first;
-                }
-                for (size_t k = 0; k < ov_groups.size(); ++k)
-                    for (size_t q = ov_groups[k].first; q < ov_groups[k].end; ++q) ov_group_of[q] = (int)k;
-            }
-            d_ov_started.alloc(std::max<size_t>(launches.size(), 1));
-            HIP_CHECK(hipMemset(d_ov_started.p, 0, std::max<size_t>(launches.size(), 1) * sizeof(int)));
+            d_ov_started.alloc(std::max<size_t>(sch.launches.size(), 1));
+            HIP_CHECK(hipMemset(d_ov_started.p, 0, std::max<size_t>(sch.launches.size(), 1) * sizeof(int)));
             std::vector<int> nt((size_t)S.nsuper, 0);
-            for (size_t q = ov_first; q < launches.size(); ++q) {
-                const Launch& L = launches[q];
+            for (size_t q = sch.ov_first; q < sch.launches.size(); ++q) {
+                const Launch& L = sch.launches[q];
                 for (int t = L.begin; t < L.begin + L.count; ++t) {
-                    const int sn = sched[(size_t)t];
+                    const int sn = sch.sched[(size_t)t];
                     const int nb = front_size(sn) - (S.sn_start[sn + 1] - S.sn_start[sn]);
                     const int k = (nb + 63) / 64;
                     nt[(size_t)sn] = k * (k + 1) / 2;
@@ -1821,10 +1399,10 @@ private:
             d_ov_ntiles.upload(nt);
             // fronts factorised in row slices publish their progress per slice
             std::vector<int> sbase((size_t)std::max(S.nsuper, 1), -1);
-            for (size_t q = slice_list.size(); q-- > 0;) sbase[(size_t)slice_list[q][0]] = (int)q;      // (slices of a front are consecutive)
+            for (size_t q = sch.slice_list.size(); q-- > 0;) sbase[(size_t)sch.slice_list[q][0]] = (int)q;      // (slices of a front are consecutive)
             d_ov_sbase.upload(sbase);
-            d_ov_sprog.alloc(std::max<size_t>(slice_list.size(), 1));
-            HIP_CHECK(hipMemset(d_ov_sprog.p, 0, std::max<size_t>(slice_list.size(), 1) * sizeof(int)));
+            d_ov_sprog.alloc(std::max<size_t>(sch.slice_list.size(), 1));
+            HIP_CHECK(hipMemset(d_ov_sprog.p, 0, std::max<size_t>(sch.slice_list.size(), 1) * sizeof(int)));
             d_ov_prog.alloc((size_t)S.nsuper);
             d_ov_done.alloc((size_t)S.nsuper);
             HIP_CHECK(hipMemset(d_ov_prog.p, 0, (size_t)std::max(S.nsuper, 1) * sizeof(int)));
@@ -1833,7 +1411,7 @@ private:
         {
             std::vector<int64_t> toff(S.nsuper + 1, 0);
             std::vector<char> in_list(S.nsuper, 0);
-            for (int s : tinv_list) in_list[s] = 1;
+            for (int s : sch.tinv_list) in_list[s] = 1;
             // (level by level like the panel and update stores: symbolic.cpp, step 10)
             {
                 int64_t wo = 0;
@@ -1849,9 +1427,9 @@ private:
             d_tinv_off.upload(toff);
             h_toff = toff;
             static_assert(sizeof(FrontDesc) == 64, "FrontDesc layout");
-            std::vector<FrontDesc> desc(sched.size());
-            for (size_t q = 0; q < sched.size(); ++q) {
-                const int s = sched[q];
+            std::vector<FrontDesc> desc(sch.sched.size());
+            for (size_t q = 0; q < sch.sched.size(); ++q) {
+                const int s = sch.sched[q];
                 FrontDesc d;
                 d.front_off = S.front_off[s]; d.upd_off = S.upd_off[s]; d.w_off = toff[s]; d.rp = S.rowptr[s];
                 d.kptr = S.kptr[s]; d.s = s; d.c0 = S.sn_start[s]; d.nc = S.sn_start[s + 1] - S.sn_start[s];
@@ -1863,151 +1441,29 @@ private:
             std::memcpy(rawd.data(), desc.data(), desc.size() * sizeof(FrontDesc));
             d_desc.upload(rawd);
             std::vector<int> pos_of(S.nsuper, -1);
-            for (size_t q = 0; q < sched.size(); ++q) pos_of[sched[q]] = (int)q;
-            std::vector<int64_t> raws(std::max<size_t>(slice_list.size(), 1) * 8, 0);
-            for (size_t q = 0; q < slice_list.size(); ++q) {
-                FrontDesc d = desc[(size_t)pos_of[slice_list[q][0]]];
-                d.pad = (slice_list[q][1] << 16) | slice_list[q][2];
+            for (size_t q = 0; q < sch.sched.size(); ++q) pos_of[sch.sched[q]] = (int)q;
+            std::vector<int64_t> raws(std::max<size_t>(sch.slice_list.size(), 1) * 8, 0);
+            for (size_t q = 0; q < sch.slice_list.size(); ++q) {
+                FrontDesc d = desc[(size_t)pos_of[sch.slice_list[q][0]]];
+                d.pad = (sch.slice_list[q][1] << 16) | sch.slice_list[q][2];
                 d.kptr = slice_kptr[q]; d.nk = slice_nk[q];             // (its own K list, positions in the slice's image)
                 std::memcpy(raws.data() + q * 8, &d, sizeof(FrontDesc));
             }
             d_sdesc.upload(raws);
-            std::vector<int> spos(S.nsuper, -1);
-            for (size_t q = 0; q < sched.size(); ++q) spos[sched[q]] = (int)q;
-            d_spos.upload(spos);
+            d_spos.upload(sch.spos);
             d_sn_parent.upload(S.sn_parent);
-            // late_launches: the longest suffix of block-class launches with <= kTopMaxFronts fronts in total -- the
-            // narrow top of the tree, whose W is formed behind the factorisation (enqueue_factor / wait_w)
-            late_launches = 0;
-            {
-                int cnt = 0;
-                for (size_t q = launches.size(); q-- > 0;) {
-                    const Launch& L = launches[q];
-                    if (L.small || cnt + L.count > kTopMaxFronts) break;
-                    cnt += L.count;
-                    ++late_launches;
-                }
-                late_count = cnt;
-                if (late_launches < 3) { late_launches = 0; late_count = 0; }
+            if (!sch.tp.empty()) {       // the set has sliced fronts: the tasks of k_top_solve_sliced
+                d_tk_pos.upload(sch.tp); d_tk_sl.upload(sch.ts); d_tbase.upload(sch.h_tbase);
+                xf.alloc((size_t)S.N * 2);
             }
-            // persistent top: the longest suffix of block-class launches none of which holds more than 1.5 x as many
-            // fronts as the device keeps resident workgroups of the persistent kernel (a workgroup then has at most two
-            // fronts per level; k_top_solve walks its fronts in level order)
-            top_launches = 0; top_count = 0; top_lds = 0; top_grid = 0;
-            {
-                size_t lds = 0;
-                for (size_t q = launches.size(); q-- > 0 && !launches[q].small;) lds = std::max(lds, launches[q].lds_solve);
-                const int tall_env = knobs().top_tall;
-                top_tall = tall_env != 0;           // the 1024-thread build unless HIPKKT_TOP_TALL=0 (solve_kernels.hip)
-                const int cap_env = knobs().top_cap;
-                const int cap = std::min(std::min(kTopMaxFronts, cap_env), top_solve_capacity(lds, top_tall));
-                for (size_t q = launches.size(); q-- > 0;) {
-                    const Launch& L = launches[q];
-                    // (measured on cfg2 with 240 workgroups: x1 0.313, x1.25-1.7 0.307, x2.5 0.319, x6 0.346 ms per solve)
-                    const double mult = knobs().top_mult;
-                    if (L.small || L.count > mult * cap) break;
-                    top_count += L.count;
-                    top_lds = std::max(top_lds, L.lds_solve);
-                    ++top_launches;
-                }
-                top_grid = std::min(cap, top_count);
-            }
-            if (top_launches < 3) { top_launches = 0; top_count = 0; top_grid = 0; }     // not worth a special kernel
-            top_ntask = 0;
-            top_nflag = std::max(top_count, 1);
-            {
-                // Sets with very tall fronts (solve matrix > 3 x slice_kb: far more than a CU should stream per hop) run the
-                // (front, slice) kernel: such a front is cut into slices of ~slice_kb (at most slice_max), the others are one task
-                // (r03, cfg5: slices of ~80 KB, at most 16, instead of ~120 KB / 8: sweep pair 0.765 -> 0.729 ms; 60 KB / 16 and
-                //  40 KB / 32: 0.74 -- a hop is mostly its fixed latencies by then.  A front is sliced when its W exceeds
-                //  HIPKKT_SOLVE_SLICE_FROM KB, by default 4.5 slices' worth: cfg3's 395 KB fronts are faster whole)
-                // (r04: at most 64 slices instead of 16 -- cfg5's 1.2 MB fronts take 15 either way, the long-range cfg2
-                //  variant's 14 154-row panels (11 MB each, 148 of them in a chain) were streamed in 680 KB pieces: sweep pair
-                //  4.98 -> 3.85 ms, unit 89.5 -> 81.7 ms; 96 and 128 slices: the same)
-                const int slice_kb = knobs().solve_slice_kb;
-                const int slice_max = std::max(1, std::min(64, knobs().solve_slice_max));
-                const int64_t slice_from = knobs().solve_slice_from >= 0 ? knobs().solve_slice_from * 1024 : (int64_t)slice_kb * 1024 * 9 / 2;
-                std::vector<int> tp, ts;
-                h_tbase.assign((size_t)top_count + 1, 0);
-                const int b0 = top_launches ? launches[launches.size() - top_launches].begin : 0;
-                bool any_sliced = false, set_has_tall = false, tall_unsliceable = false;
-                size_t slds = 0;
-                for (int p = 0; p < top_count; ++p) {
-                    const int sn = sched[(size_t)b0 + p];
-                    const int f = front_size(sn), nc = S.sn_start[sn + 1] - S.sn_start[sn], nb = f - nc;
-                    const int64_t wbytes = (int64_t)f * nc * 8;
-                    int R = 1;
-                    if (slice_kb > 0 && wbytes > slice_from)
-                        R = (int)std::min<int64_t>(slice_max, (wbytes + (int64_t)slice_kb * 1024 - 1) / ((int64_t)slice_kb * 1024));
-                    const bool tallf = front_is_tall(sn);                        // (too tall for k_top_solve's LDS: slices only)
-                    if (tallf) R = std::max(R, 2);
-                    set_has_tall = set_has_tall || tallf;
-                    R = std::max(1, std::min(R, std::max(1, nb)));
-                    if (tallf && R < 2) tall_unsliceable = true;
-                    any_sliced = any_sliced || R > 1;
-                    h_tbase[(size_t)p] = (int)tp.size();
-                    for (int q = 0; q < R; ++q) { tp.push_back(p); ts.push_back(q | (R << 8)); }
-                    const size_t nloc = (size_t)nc + (size_t)((nb + R - 1) / R) + 8;
-                    const size_t fwd = (size_t)((nc + 3) & ~3) + nloc * (1 + (size_t)((nc + 7) >> 3));
-                    const size_t bwd = (size_t)((f + 3) & ~3) + 16 * 16;
-                    slds = std::max(slds, std::max(fwd, bwd) * sizeof(double));
-                }
-                h_tbase[(size_t)top_count] = (int)tp.size();
-                if (any_sliced && top_count > 0) {
-                    top_ntask = (int)tp.size();
-                    top_nflag = top_ntask;
-                    top_slds = slds;
-                    top_sgrid = std::min(top_solve_sliced_capacity(slds), top_ntask);
-                    // (two right-hand sides per sweep: twice the LDS, the same grid or none)
-                    top_sgrid2 = slds * 2 <= 150 * 1024 ? std::min(top_solve_sliced_capacity(slds * 2, 2), top_ntask) : 0;
-                    if (top_sgrid2 < top_sgrid) top_sgrid2 = 0;
-                    d_tk_pos.upload(tp); d_tk_sl.upload(ts); d_tbase.upload(h_tbase);
-                    xf.alloc((size_t)S.N * 2);
-                    if (top_sgrid <= 0) top_ntask = 0;
-                }
-                if (set_has_tall && (top_ntask == 0 || tall_unsliceable)) {
-                    // fronts too tall for the one-front-per-workgroup kernel, and the (front, slice) kernel cannot take the set
-                    // either (a slice's vectors beyond a CU's LDS: fronts of ~18 000 rows and more): no persistent set at all,
-                    // the sweeps go level by level (k_fwd_tall / k_bwd_tall for those fronts)
-                    top_launches = 0; top_count = 0; top_grid = 0; top_ntask = 0; top_nflag = 1;
-                }
-            }
-            top_flags.alloc((size_t)2 * std::max(top_nflag, 1) + 4);
+            top_flags.alloc((size_t)2 * std::max(sch.top_nflag, 1) + 4);
             HIP_CHECK(hipMemset(top_flags.p, 0, top_flags.n * sizeof(int)));
-            // chained launches: every launch must fit the chained kernels (no front beyond the block kernels' LDS)
-            // chain_from: the longest suffix of launches with at most chain_max workgroups each (HIPKKT_CHAIN_MAX; the wide
-            // levels below are throughput-bound: a launch each costs them little, while their thousands of waiting
-            // workgroups would crowd a chained grid), every front of which fits the chained kernels' LDS
-            {
-                const int chain_max = knobs().chain_max;
-                size_t q = launches.size();
-                while (q > 0) {
-                    const Launch& L = launches[q - 1];
-                    ChainSeg sg{L.begin, L.small ? 0 : L.count, L.small ? L.count - L.ntiny : 0, L.small ? L.ntiny : 0, 0, 0, RecSeg{}};
-                    if (L.ntall > 0 || (!L.small && L.lds_solve > 150 * 1024) || chain_seg_wgs(sg) > chain_max) break;
-                    if (!L.small) chain_lds = std::max(chain_lds, L.lds_solve);
-                    --q;
-                }
-                chain_from = launches.size() - q >= 2 ? q : launches.size();
-                std::vector<int> nch((size_t)std::max(S.nsuper, 1), 0);
-                if (chain_from < launches.size()) {
-                    const int p0 = launches[chain_from].begin;
-                    for (int c = 0; c < S.nsuper; ++c)
-                        if (S.sn_parent[c] >= 0 && spos[(size_t)c] >= p0) nch[(size_t)S.sn_parent[c]]++;
-                }
-                d_chain_nchild.upload(nch);
-                h_nch = nch;
-            }
+            d_chain_nchild.upload(sch.nch);
             d_chain.alloc((size_t)2 * std::max(S.nsuper, 1));
             HIP_CHECK(hipMemset(d_chain.p, 0, d_chain.n * sizeof(int)));
             tinv.alloc((size_t)toff[S.nsuper]);
             HIP_CHECK(hipMemset(tinv.p, 0, std::max<size_t>(tinv.n, 1) * sizeof(double)));
-            d_tinv_list.upload(tinv_list);
-            tinv_small_prefix.assign(tinv_list.size() + 1, 0);      // (how many narrow supernodes a stretch of the list holds: launch_tinv)
-            for (size_t k = 0; k < tinv_list.size(); ++k) {
-                const int s = tinv_list[k];
-                tinv_small_prefix[k + 1] = tinv_small_prefix[k] + (S.sn_start[s + 1] - S.sn_start[s] <= winv_small_nc() ? 1 : 0);
-            }
+            d_tinv_list.upload(sch.tinv_list);
         }
         {
             std::vector<int64_t> cut_ptr(S.nsuper + 1, 0);
@@ -2050,14 +1506,14 @@ private:
                     }
             }
             if (S.rows.size() >= ((size_t)1 << 31)) throw std::runtime_error("row structure exceeds int32 indexing");
-            if (knobs().verbose >= 2 && top_launches > 0) {
+            if (knobs().verbose >= 2 && sch.top_launches > 0) {
                 // gather-list lengths of the rows of the persistent solve set (what k_top_solve's parked indices must cover)
                 long hist[6] = {0, 0, 0, 0, 0, 0};
                 long fronts_over8 = 0, fronts_over12 = 0, nf = 0;
                 int64_t gmax = 0;
-                for (size_t q = launches.size() - top_launches; q < launches.size(); ++q)
-                    for (int t = launches[q].begin; t < launches[q].begin + launches[q].count; ++t) {
-                        const int sn = sched[(size_t)t];
+                for (size_t q = sch.launches.size() - sch.top_launches; q < sch.launches.size(); ++q)
+                    for (int t = sch.launches[q].begin; t < sch.launches[q].begin + sch.launches[q].count; ++t) {
+                        const int sn = sch.sched[(size_t)t];
                         const int f = front_size(sn);
                         int64_t fm = 0;
                         for (int i = 0; i < f; ++i) {
@@ -2087,7 +1543,7 @@ private:
             const bool dense_on = knobs().dense_child;
             int64_t n_dense = 0;
             for (int p = 0; dense_on && p < S.nsuper; ++p) {
-                if (tile_base[p] < 0) continue;                              // block-class parents only
+                if (sch.tile_base[p] < 0) continue;                              // block-class parents only
                 const int fp = front_size(p);
                 for (int e = S.child_ptr[p]; e < S.child_ptr[p + 1]; ++e) {
                     const int c = S.child_idx[e];
@@ -2146,7 +1602,7 @@ private:
                 }
             }
             // 16 slices of each supernode's panel items, cut on column boundaries
-            std::vector<int64_t> wcut(((size_t)S.nsuper + slice_list.size()) * 17, 0);
+            std::vector<int64_t> wcut(((size_t)S.nsuper + sch.slice_list.size()) * 17, 0);
             for (int s = 0; s < S.nsuper; ++s) {
                 const int nc = S.sn_start[s + 1] - S.sn_start[s];
                 const int64_t* cp = pptr.data() + S.sn_start[s];      // nc + 1 column pointers
@@ -2162,8 +1618,8 @@ private:
             // A row slice of a sliced front gets an item list of its own: the pieces that reach its rows or the top block,
             // in the same order, cut into 16 wave slices of whole columns again -- instead of every slice walking the whole
             // front's list in rounds that are mostly skipped pieces.
-            for (size_t q = 0; q < slice_list.size(); ++q) {
-                const int s = slice_list[q][0], sl = slice_list[q][1], nsl = slice_list[q][2];
+            for (size_t q = 0; q < sch.slice_list.size(); ++q) {
+                const int s = sch.slice_list[q][0], sl = sch.slice_list[q][1], nsl = sch.slice_list[q][2];
                 const int ff = front_size(s), nc = S.sn_start[s + 1] - S.sn_start[s], nb = ff - nc;
                 const int rsmax = (nb + nsl - 1) / nsl, r_lo = nc + sl * rsmax;
                 const int rs = std::max(0, std::min(rsmax, ff - r_lo));
@@ -2194,8 +1650,8 @@ private:
             d_wave_cut.upload(wcut);
             if (knobs().verbose) {
                 if (knobs().verbose >= 2) {            // the extend-add work of the last fronts of the schedule
-                    for (size_t q = sched.size() > 12 ? sched.size() - 12 : 0; q < sched.size(); ++q) {
-                        const int sn = sched[q];
+                    for (size_t q = sch.sched.size() > 12 ? sch.sched.size() - 12 : 0; q < sch.sched.size(); ++q) {
+                        const int sn = sch.sched[q];
                         const int64_t* w = wcut.data() + (size_t)sn * 17;
                         int64_t mx = 0, rows = 0;
                         for (int k = 0; k < 16; ++k) mx = std::max(mx, w[k + 1] - w[k]);
@@ -2209,11 +1665,11 @@ private:
             // Schur sub-items: every child update column that lands in a U column, cut at the parent's
             // 64-row tile boundaries, grouped by (tile, tile column), children in fixed order
             static_assert(sizeof(SubItem) == 16, "SubItem layout");
-            const int64_t ntile = (int64_t)tiles.size();
+            const int64_t ntile = (int64_t)sch.tiles.size();
             std::vector<int64_t> cnt((size_t)ntile * 64 + 1, 0);
             auto for_each_sub = [&](auto&& fn) {
                 for (int p = 0; p < S.nsuper; ++p) {
-                    if (tile_base[p] < 0) continue;
+                    if (sch.tile_base[p] < 0) continue;
                     const int pnc = S.sn_start[p + 1] - S.sn_start[p];
                     for (int e = S.child_ptr[p]; e < S.child_ptr[p + 1]; ++e) {
                         const int c = S.child_idx[e];
@@ -2228,7 +1684,7 @@ private:
                                 const int ti = (rl[a] - pnc) >> 6;
                                 int a2 = a;
                                 while (a2 < nbc && ((rl[a2] - pnc) >> 6) == ti) ++a2;
-                                const int64_t tile = tile_base[p] + (int64_t)ti * (ti + 1) / 2 + tj;
+                                const int64_t tile = sch.tile_base[p] + (int64_t)ti * (ti + 1) / 2 + tj;
                                 fn(tile, j & 63, c, b, a, a2 - a, nbc);
                                 a = a2;
                             }
@@ -2263,6 +1719,7 @@ private:
                 }
                 tcut[t * 5 + 4] = I1;
             }
+            std::vector<int64_t> tiles_up(sch.tiles);       // (the tiles in the order they are launched in)
             {
                 // XCD-aware launch order of a wide level's tiles (HIPKKT_TILE_XCD=n: launches with at least n fronts;
                 // 0 = off): workgroup i of a launch runs on XCD i mod 8, each XCD has its own L2, and every tile of a front
@@ -2274,19 +1731,17 @@ private:
                 // levels as well costs time (>= 32: 1.766 / 1.770 -- a handful of fronts' tiles then crowd one XCD).
                 const int tile_xcd = knobs().tile_xcd;
                 if (tile_xcd > 0) {
-                    std::vector<int64_t> nt2(tiles.size()), nc2(tcut.size(), 0);
-                    nt2 = tiles;
-                    nc2 = tcut;
-                    for (const Launch& L : launches) {
+                    std::vector<int64_t> nc2(tcut);
+                    for (const Launch& L : sch.launches) {
                         if (L.small || L.count < tile_xcd || L.ntiles <= 0) continue;
                         // the launch's fronts and their (contiguous) logical tile ranges
                         std::vector<std::pair<int64_t, int64_t>> rng;       // [first, last) per front, launch order
                         for (int t = L.begin; t < L.begin + L.count; ++t) {
-                            const int sn = sched[(size_t)t];
-                            if (tile_base[sn] < 0) continue;
+                            const int sn = sch.sched[(size_t)t];
+                            if (sch.tile_base[sn] < 0) continue;
                             const int nb = front_size(sn) - (S.sn_start[sn + 1] - S.sn_start[sn]);
                             const int k = (nb + 63) / 64;
-                            if (k > 0) rng.push_back({tile_base[sn], tile_base[sn] + (int64_t)k * (k + 1) / 2});
+                            if (k > 0) rng.push_back({sch.tile_base[sn], sch.tile_base[sn] + (int64_t)k * (k + 1) / 2});
                         }
                         int64_t pos = L.tile_begin;
                         for (size_t g0 = 0; g0 < rng.size(); g0 += 8) {
@@ -2297,18 +1752,17 @@ private:
                                 for (size_t x = g0; x < g1; ++x)
                                     if (rng[x].first + j < rng[x].second) {
                                         const int64_t from = rng[x].first + j;
-                                        nt2[(size_t)pos] = tiles[(size_t)from];
+                                        tiles_up[(size_t)pos] = sch.tiles[(size_t)from];
                                         for (int w = 0; w < 5; ++w) nc2[(size_t)pos * 5 + w] = tcut[(size_t)from * 5 + w];
                                         ++pos;
                                     }
                         }
                         if (pos != (int64_t)L.tile_begin + L.ntiles) throw std::runtime_error("tile permutation lost a tile");
                     }
-                    tiles.swap(nt2);
                     tcut.swap(nc2);
                 }
             }
-            d_tiles.upload(tiles);
+            d_tiles.upload(tiles_up);
             std::vector<int64_t> raw2(sit.size() * 2);
             std::memcpy(raw2.data(), sit.data(), sit.size() * sizeof(SubItem));
             d_sitems.upload(raw2);
@@ -2370,7 +1824,7 @@ private:
         d_psign.upload(ps);
         {
             size_t ws = 0;
-            for (const Launch& L : launches) if (L.ntall > 0) ws = std::max(ws, tall_ws_doubles(S.N, L.ntall, L.fmax));
+            for (const Launch& L : sch.launches) if (L.ntall > 0) ws = std::max(ws, tall_ws_doubles(S.N, L.ntall, L.fmax));
             if (ws) { tall_ws.alloc(ws); tall_ws.zero(nullptr); HIP_CHECK(hipStreamSynchronize(nullptr)); }     // (its first N doubles: ticket words, zero between sweeps)
         }
         fronts.alloc((size_t)S.front_store);

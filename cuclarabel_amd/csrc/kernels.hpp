@@ -11,6 +11,7 @@
 //   uvec          per supernode s: nb_s doubles, forward-solve contributions to the ancestors.
 #pragma once
 #include <hip/hip_runtime.h>
+#include "launch_shapes.hpp"
 #include <cstdint>
 #include <mutex>
 #include <stdexcept>
@@ -80,7 +81,7 @@ struct FrontDesc {               // everything a kernel needs to know about one 
     int pad;                     // row-sliced panels (TreeDev::sdesc): slice << 16 | number of slices
 };
 
-// Packed sweep records (hipkkt.hip, build_records): what a sweep kernel needs to know about a front, laid out so that it
+// Packed sweep records (layout: schedule.cpp, layout_records; byte image: hipkkt.hip, build_records): what a sweep kernel needs to know about a front, laid out so that it
 // arrives in ONE round of loads.  The fronts of a launch and size class (block-class / one-wave / tiny) have records of one
 // size, so a record's address follows from the front's place in the launch alone: [SolveHdr (64 B)] [idx: fmax ints]
 // [gather slots: fmax x 32 B, absent on tree level 0] -- a thread fetches the header and its row's slots side by side,
@@ -96,11 +97,8 @@ struct SolveHdr {
     int nchild;                  // children swept by chained launches (ChainArgs::nchild)
     int64_t pad[3];
 };
-struct RecSeg {                  // the records of one kernel launch's fronts, by size class: 0 block-class, 1 one-wave, 2 tiny
-    int64_t off[3];              // byte offset in SolveArgs::recs of the class's first record
-    int stride[3];               // bytes per record
-    int fmax[3];                 // row slots per record (a multiple of 4)
-};
+static_assert(sizeof(SolveHdr) == kSolveHdrBytes, "SolveHdr layout");
+// (RecSeg, the records of one kernel launch's fronts by size class: launch_shapes.hpp)
 
 struct TreeDev {                 // device copies of the symbolic structure
     int nsuper;
@@ -237,10 +235,8 @@ struct SolveArgs {
 };
 
 constexpr int kSolveChunk = 128;  // diagonal chunk of the triangular solves: one wave, two unknowns per lane
-constexpr int kMaxNbk = 16;
-size_t solve_lds_bytes(int fmax, int ncmax);
+// (kMaxNbk, solve_lds_bytes, kTopMaxFronts, winv_small_nc, kSmallFrontMax / kSmallSliceMax, panel_lds_bytes: launch_shapes.hpp)
 // persistent kernel over the top `count` fronts (schedule positions begin ..): forward then backward sweep
-constexpr int kTopMaxFronts = 480;
 int top_solve_capacity(size_t lds, bool tall);   // resident workgroups the device guarantees for the persistent kernel
                                                 // (tall: its 1024-thread build for sets with very tall fronts)
 int top_solve_capacity_nr(size_t lds_total, int nr);     // the same for the 1024-thread build's NR-column instance
@@ -255,12 +251,9 @@ void launch_top_solve_sliced(const SolveArgs& a, int begin, int pos0, int task0,
 // workgroups (solve_kernels.hip: k_winv)
 void launch_tinv(const TreeDev& T, const double* fronts, double* tinv, const int* list, int count, int ncmax,
                  hipStream_t st, int max_blocks = 0, int nsmall = 0);
-int winv_small_nc();
 
 // factorisation of one level: small fronts (one wave each), panels (one workgroup each), then the
 // update blocks tiled over many workgroups
-constexpr int kSmallFrontMax = 64;         // f <= 64 ...
-constexpr int kSmallSliceMax = 1536;       // ... and f*nc + nb*nb <= this many doubles of LDS per wave
 void launch_front_wave(const FactorArgs& a, int begin, int count, int slice_doubles, hipStream_t st);
 void launch_front_tiny(const FactorArgs& a, int begin, int count, hipStream_t st);     // fronts with f <= 8, eight to a wave
 void launch_panel(const FactorArgs& a, int begin, int count, int bs, size_t lds, hipStream_t st);
@@ -273,7 +266,6 @@ void launch_ov_gate(const int* started, int target, int* abort_word, long long l
 // word2[0] must be 0; afterwards word2[1] = 1 iff a kernel on `second`, submitted behind a waiting kernel on `first`, ran
 // while that one waited -- i.e. the two streams do not share a hardware queue
 void launch_concurrency_probe(int* word2, hipStream_t first, hipStream_t second);
-size_t panel_lds_bytes(int fmax, int panel_max);
 // litmus test of the hand-over contract (factor_kernels.hip): 2 * pairs workgroups, producer / consumer pairs
 void launch_handover_litmus(int variant, double* payload, int* sig, int* ack, int pairs, int words, int rounds,
                             unsigned long long* mismatches, unsigned long long* timeouts, hipStream_t st);
@@ -327,8 +319,7 @@ struct ChainArgs {
 // lds = bytes per right-hand side of the largest block-class front in the segments (0: none)
 void launch_fwd_chain(const SolveArgs& a, const ChainArgs& c, int nwg, size_t lds, hipStream_t st, int nr);
 void launch_bwd_chain(const SolveArgs& a, const ChainArgs& c, int nwg, size_t lds, hipStream_t st, int nr);
-constexpr int kChainBS = 512;    // workgroup size of the chained kernels: one block-class front, 8 one-wave or 64 tiny fronts
-inline int chain_seg_wgs(const ChainSeg& s) { return s.nblock + (s.nwave + kChainBS / 64 - 1) / (kChainBS / 64) + (s.ntiny + kChainBS / 8 - 1) / (kChainBS / 8); }
+inline int chain_seg_wgs(const ChainSeg& s) { return chain_seg_wgs(s.nblock, s.nwave, s.ntiny); }     // (kChainBS: launch_shapes.hpp)
 
 // ---- KKT value updates (kktsolver_directldl.jl:130-188, 211-245, 374-386)
 void launch_scatter(double* Kval, const int* idx, const double* vals, int64_t n, double scale, hipStream_t st);

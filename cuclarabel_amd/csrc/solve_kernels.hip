@@ -1507,7 +1507,7 @@ __global__ __launch_bounds__(BS, 4) void k_top_solve_sliced(SolveArgs A, int beg
 //      no exchange between the two.
 // Then M = L21 * T, a wave per strip of 16 rows against T in LDS (A operands of a strip fetched ahead of the products).
 constexpr int kWinvThreads = 512;
-constexpr int kWinvSmallThreads = 128, kWinvSmallNc = 32;     // narrow supernodes: k_winv's small build (below)
+constexpr int kWinvSmallThreads = 128;     // (kWinvSmallNc: launch_shapes.hpp) narrow supernodes: k_winv's small build (below)
 template <int NT>
 __device__ inline void winv_one(const TreeDev& T, const double* __restrict__ fronts, double* __restrict__ wst, int s,
                                 double* smem)
@@ -1848,14 +1848,6 @@ void launch_bwd_tall(const SolveArgs& a, int begin, int count, int fmax, int N, 
     const int BR = tall_block_rows();
     const int nblk = (fmax + BR - 1) / BR;
     hipLaunchKernelGGL(k_bwd_tall, dim3(nblk, count), dim3(1024), (size_t)BR * sizeof(double), st, a, begin, BR, N);
-}
-
-size_t solve_lds_bytes(int fmax, int ncmax)
-{
-    const size_t fpad = (size_t)((fmax + 3) & ~3), ncpad = (size_t)((ncmax + 3) & ~3);
-    const size_t nks = (size_t)((ncmax + 7) >> 3), nrs = (size_t)((fmax + 7) >> 3);
-    const size_t fwd = fpad + nks * fpad, bwd = fpad + nrs * ncpad;
-    return (fwd > bwd ? fwd : bwd) * sizeof(double);
 }
 
 void launch_fwd(const SolveArgs& a, const RecSeg& rs, int begin, int count, int bs, size_t lds, hipStream_t st, int nr)
@@ -2629,7 +2621,6 @@ void launch_top_solve_sliced(const SolveArgs& a, int begin, int pos0, int task0,
         hipLaunchKernelGGL((k_top_solve_sliced<1024, 1>), dim3(std::min(grid, ntask)), dim3(1024), lds, st, a, begin, pos0, task0, task1,
                            flags, epoch, nflag);
 }
-int winv_small_nc() { return kWinvSmallNc; }
 void launch_tinv(const TreeDev& T, const double* fronts, double* tinv, const int* list, int count, int ncmax,
                  hipStream_t st, int max_blocks, int nsmall)
 {

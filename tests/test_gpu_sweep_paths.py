@@ -3,7 +3,7 @@
 tests/test_gpu_front_shapes.py does this for the factorisation; its trees are two or three launches tall and its one
 solve per case is the one right after refactor().  Here the forests of tests/front_shapes.py (sweep_table: tiny and
 one-wave fronts at the packing edges of their kernels, all three classes in one level, trees tall enough for a chained
-range below a persistent set) go through every way enqueue_solve (csrc/hipkkt.hip) can split a sweep, forced by the
+range below a persistent set) go through every way plan_sweep (csrc/schedule.cpp) can split a sweep, forced by the
 HIPKKT_* knobs and ASSERTED from the "[hipkkt] sweep plan" line of HIPKKT_VERBOSE:
 
     a. level A (hipkkt_ldl_*): refactor(), then four solves with four known x_true -- the first with W still pending,
@@ -65,7 +65,7 @@ _LAUNCH = re.compile(r"\[hipkkt\] sweep launch (\d+)(?:\+(\d+))? level (\d+): fa
 
 
 def _sweep_plans(stderr):
-    """The HIPKKT_VERBOSE sweep-plan lines of enqueue_solve (hipkkt.hip), one dict per line, each with the per-level
+    """The HIPKKT_VERBOSE sweep-plan lines (describe, csrc/schedule.cpp; printed by enqueue_solve), one dict per line, each with the per-level
     launch lines (HIPKKT_VERBOSE=2) that follow it."""
     plans = []
     for line in stderr.split("\n"):
