@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <array>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -1999,6 +2000,7 @@ struct hipkkt_kkt_s {
     DBuf<double> lam;                                        // scaled point, m
     DBuf<double> sq, snegq, sb, sx2, sz2, sworkx, sworkz, sconic, spa, spb, spc;
     DBuf<double> sys_partial, sys_dots, sys_cached, sys_in;
+    DBuf<double> step_partial, step_rec;                     // step length / margins: partial slots and the 2-double result record
     bool sys_ready = false;
     bool sys_lazy = false;           // hipkkt_kkt_system_set_lazy: kkt_update! leaves (x2, z2) = K \ (-q, b) to the affine kkt_solve!
     bool sys_const_pending = false;  // ... and that solve is still due
@@ -3698,6 +3700,107 @@ int hipkkt_kkt_system_solve(hipkkt_kkt_t h, double* d_lhs_x, double* d_lhs_s, do
         if (!h) throw ArgError("null handle");
         return sys_solve_step(h, d_lhs_x, d_lhs_s, d_lhs_z, lhs_tau_kappa, d_rhs_x, d_rhs_s, d_rhs_z, rhs_tau, rhs_kappa,
                               d_var_x, d_var_s, d_var_z, var_tau, var_kappa, steptype);
+    });
+}
+
+// ---- the cone operations between the solves (step_kernels.hip): affine_ds!, the combined step's d.s, step_length,
+// _shift_to_cone_interior! on the caller's device vectors
+static void step_guard(hipkkt_kkt_t h, const char* who, bool need_scaling)
+{
+    if (!h) throw ArgError("null handle");
+    if (!h->sys_ready) throw ArgError("hipkkt_kkt_system_*: call hipkkt_kkt_system_init first");
+    if (h->deferred) throw ArgError("hipkkt_kkt_system_*: level C reads its scalars back (deferred status is for level B)");
+    if (h->K.nnonsym > 0 || h->K.ngenpow > 0)
+        throw ArgError(std::string(who) + ": symmetric cones only (the handle holds an exponential, power or generalized power cone)");
+    if (h->psd_too_big) throw ArgError(std::string(who) + ": PSD cones with side > 48 are not covered");
+    if (need_scaling && !h->scaling_valid)
+        throw ArgError(std::string(who) + ": needs the cone scaling of hipkkt_kkt_system_update");
+    HIP_CHECK(hipSetDevice(h->device));
+    if (!h->step_rec.p) {
+        h->step_partial.alloc((size_t)2 * step_partials(h->cone_dev()));
+        h->step_rec.alloc(2);
+    }
+}
+
+// the record of a finishing kernel (nrec doubles) on the host: published by that kernel into the pinned block and
+// sequence-checked, or -- where such stores do not arrive -- copied
+static const double* step_read_record(hipkkt_kkt_t h, int nrec, const std::function<void(const Publish&)>& enqueue)
+{
+    double* dst = h->pin->h + 52;                     // [52 .. 52 + nrec) the record, then the sequence number
+    if (h->publish_ok) {
+        enqueue(Publish{dst, h->step_rec.p, nrec, 0, (double)++h->publish_seq});
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        if (dst[nrec] == (double)h->publish_seq && !knobs().test_publish_fail) return dst;
+        h->publish_ok = false;                        // (the record itself is still on the device: nothing is repeated)
+        if (knobs().verbose) std::fprintf(stderr, "[hipkkt] status record not published to host memory: copying it from now on\n");
+    } else {
+        enqueue(Publish{});
+    }
+    HIP_CHECK(hipMemcpyAsync(dst, h->step_rec.p, (size_t)nrec * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    return dst;
+}
+
+int hipkkt_kkt_system_affine_ds(hipkkt_kkt_t h, double* d_out)
+{
+    return guarded([&]() {
+        step_guard(h, "hipkkt_kkt_system_affine_ds", true);
+        if (h->K.m && !d_out) throw ArgError("hipkkt_kkt_system_affine_ds: bad argument");
+        launch_step_ds(h->cone_dev(), h->cone_state(), d_out, nullptr, nullptr, 0.0, 0.0, h->K.m, false, h->stream);
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_combined_ds(hipkkt_kkt_t h, double* d_out, const double* d_step_z, const double* d_step_s,
+                                  double sigma_mu, double m_corr)
+{
+    return guarded([&]() {
+        step_guard(h, "hipkkt_kkt_system_combined_ds", true);
+        if (h->K.m && (!d_out || !d_step_z || !d_step_s || d_out == d_step_z || d_out == d_step_s))
+            throw ArgError("hipkkt_kkt_system_combined_ds: bad argument (d_out must not alias an input)");
+        launch_step_ds(h->cone_dev(), h->cone_state(), d_out, d_step_z, d_step_s, sigma_mu, m_corr, h->K.m, true, h->stream);
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_step_length(hipkkt_kkt_t h, const double* d_step_z, const double* d_step_s, const double* d_z,
+                                  const double* d_s, double step_tau, double step_kappa, double tau, double kappa,
+                                  double* alpha_out)
+{
+    return guarded([&]() {
+        step_guard(h, "hipkkt_kkt_system_step_length", true);
+        if ((h->K.m && (!d_step_z || !d_step_s || !d_z || !d_s)) || !alpha_out)
+            throw ArgError("hipkkt_kkt_system_step_length: bad argument");
+        const double* rec = step_read_record(h, 1, [&](const Publish& pub) {
+            launch_step_length(h->cone_dev(), h->cone_state(), d_step_z, d_step_s, d_z, d_s, step_tau, step_kappa, tau, kappa,
+                               h->step_partial.p, h->step_rec.p, pub, h->K.m, h->stream);
+        });
+        *alpha_out = rec[0];
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_shift_to_interior(hipkkt_kkt_t h, double* d_v, int primal, double* margins_out)
+{
+    return guarded([&]() {
+        step_guard(h, "hipkkt_kkt_system_shift_to_interior", false);
+        if ((h->K.m && !d_v) || (primal != 0 && primal != 1)) throw ArgError("hipkkt_kkt_system_shift_to_interior: bad argument");
+        const ConeDev C = h->cone_dev();
+        const double* rec = step_read_record(h, 2, [&](const Publish& pub) {
+            launch_margins(C, d_v, h->step_partial.p, h->step_rec.p, pub, h->K.m, h->stream);
+        });
+        const double min_margin = rec[0], pos_margin = rec[1];
+        if (margins_out) { margins_out[0] = min_margin; margins_out[1] = pos_margin; }
+        double degree = 0.0;                          // degree(cones): nonnegative n, second-order 1, PSD its side
+        for (const ConeInfo& ci : h->K.cones)
+            degree += ci.kind == HIPKKT_CONE_NN ? ci.numel : ci.kind == HIPKKT_CONE_SOC ? 1 : ci.kind == HIPKKT_CONE_PSD ? ci.dim : 0;
+        const double target = degree > 0.0 ? std::max(1.0, 0.1 * pos_margin / degree) : 1.0;
+        // variables.jl:186-204
+        if (min_margin <= 0.0) launch_unit_shift(C, d_v, -min_margin, target, true, primal == 1, h->K.m, h->stream);
+        else if (min_margin < target) launch_unit_shift(C, d_v, target - min_margin, 0.0, false, primal == 1, h->K.m, h->stream);
+        else launch_unit_shift(C, d_v, 0.0, 0.0, false, primal == 1, h->K.m, h->stream);
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        return HIPKKT_OK;
     });
 }
 

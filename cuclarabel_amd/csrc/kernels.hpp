@@ -550,6 +550,25 @@ void launch_dots_sys_step(const DotPairs& P, double* partial, double* cached, do
 // (keep_x2 / keep_z2: (x2, z2) copied there on the way -- it came out of this call's own solve and outlives the call)
 void launch_neg_copy(double* y, const double* a, int n, hipStream_t st);                    // y = -a
 
+// ---- the cone operations of the loop BETWEEN the solves, on device vectors (step_kernels.hip); symmetric cones only
+// (zero, nonnegative, second-order, PSD side <= kPsdMaxDim) -- the caller refuses other handles.
+constexpr int kStepGridCap = 2048;          // workgroups of the elementwise part (grid-stride beyond 2048 * 256 rows)
+// slots of the step-length partials (one per elementwise workgroup, second-order cone and PSD cone); margins needs twice as many
+inline int step_partials(const ConeDev& C) { return kStepGridCap + C.nsoc + C.npsd; }
+// out = lambda o lambda (affine_ds!, coneops_compositecone.jl:153-165), and with `combined`
+//       + (W^{-T} step_s) o (W (m_corr step_z)) - sigma_mu e (_combined_ds_shift_symmetric!, coneops_symmetric_common.jl:1-35)
+void launch_step_ds(const ConeDev& C, const ConeState& S, double* out, const double* step_z, const double* step_s,
+                    double sigma_mu, double m_corr, int m, bool combined, hipStream_t st);
+// rec[0] = min(1, tau limit, kappa limit, every cone's alpha_z, alpha_s) (variables.jl:14-43 without max_step_fraction),
+// handed to the host through `pub` by the finishing kernel
+void launch_step_length(const ConeDev& C, const ConeState& S, const double* dz, const double* ds, const double* z,
+                        const double* s, double step_tau, double step_kappa, double tau, double kappa, double* partial,
+                        double* rec, const Publish& pub, int m, hipStream_t st);
+// rec[0..1] = (min_margin, pos_margin) of v over all cones (coneops_compositecone.jl:49-63)
+void launch_margins(const ConeDev& C, const double* v, double* partial, double* rec, const Publish& pub, int m, hipStream_t st);
+// scaled_unit_shift! over all cones: v += a1 e, then (two) += a2 e; a primal zero cone's rows are set to 0
+void launch_unit_shift(const ConeDev& C, double* v, double a1, double a2, bool two, bool primal, int m, hipStream_t st);
+
 
 // ---- Ruiz equilibration of (P, A, q, b) (problemdata.jl:133-221, mathutils.jl:129-269), all vectors on the device
 struct EquilDev {

@@ -1,0 +1,583 @@
+// The cone operations an interior-point loop performs BETWEEN its KKT solves, on device vectors (see kernels.hpp):
+//   affine_ds!, combined_ds_shift!      coneops_compositecone.jl:153-182
+//   step_length                         coneops_compositecone.jl:205-243
+//   margins, scaled_unit_shift!         coneops_compositecone.jl:49-76
+// for the symmetric cones (zero, nonnegative, second-order, PSD side <= kPsdMaxDim).  Launch shapes as k_sys_offset /
+// k_sys_offset_psd: an elementwise grid-stride part with one wave per second-order cone riding behind it, one 256-thread
+// workgroup per PSD cone with its matrices in LDS.  Compiled without FMA contraction: the exact-zero branches of the
+// second-order step length are tested on products and differences formed as the reference forms them.
+//
+// Every reduction has a fixed layout (a slot per workgroup / wave / cone in a partials array, folded by one workgroup in
+// a fixed order) and there is no floating-point atomic: the same call on the same data gives the same bits.
+#include "kernels.hpp"
+#include <cfloat>
+#include <cmath>
+
+namespace hipkkt {
+
+namespace {
+
+constexpr double kIs2 = 0.70710678118654752440;
+constexpr double kS2 = 1.41421356237309504880;
+
+__device__ inline double st_wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+__device__ inline void st_svec_index(int idx, int& row, int& col)     // idx = col(col+1)/2 + row, row <= col
+{
+    int c = (int)((sqrt(8.0 * (double)idx + 1.0) - 1.0) * 0.5);
+    while (c * (c + 1) / 2 > idx) --c;
+    while ((c + 1) * (c + 2) / 2 <= idx) ++c;
+    col = c;
+    row = idx - c * (c + 1) / 2;
+}
+
+struct OpMin { __device__ double operator()(double a, double b) const { return fmin(a, b); } };
+struct OpMax { __device__ double operator()(double a, double b) const { return fmax(a, b); } };
+struct OpSum { __device__ double operator()(double a, double b) const { return a + b; } };
+
+// fixed tree over the 256 threads of a workgroup; every thread gets the result
+template <class Op>
+__device__ inline double block_reduce_256(double v, double* sh, Op op)
+{
+    const int tid = threadIdx.x;
+    sh[tid] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) sh[tid] = op(sh[tid], sh[tid + o]);
+        __syncthreads();
+    }
+    const double r = sh[0];
+    __syncthreads();
+    return r;
+}
+
+__device__ inline void st_publish(const Publish& P)
+{
+    for (int i = 0; i < P.n; ++i) P.dst[i] = P.rec[i];
+    P.dst[P.n] = P.seq;
+    for (int i = 0; i < P.nzero; ++i) P.rec[i] = 0.0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+//  Eigenvalues of a symmetric k x k matrix in LDS (both triangles stored, column-major): cyclic two-sided Jacobi with the
+//  round-robin pairing of k_cone_psd -- m/2 disjoint pairs (p, q) per step, eight lanes per pair.  A step is
+//      1. every pair reads (a_pp, a_qq, a_pq) and forms its rotation (c, s)         [barrier]
+//      2. A <- A J: the pair rotates its two columns                                [barrier]
+//      3. A <- J'A: the pair rotates its two rows; the 2 x 2 block gets its exact values (a_pq = 0)   [barrier]
+//  The pairs of a step touch disjoint columns in 2 and disjoint rows in 3.  Unlike the one-sided sweep (an SVD) this
+//  keeps the signs, and its error in every eigenvalue is ABSOLUTE, a modest multiple of k u ||A|| -- what the step
+//  length needs of the smallest one (the reference calls LAPACK's syevr).  Rotations stop when a whole sweep saw no
+//  off-diagonal entry above 2^-60 ||A||_F.  On return the eigenvalues are the diagonal.  All 256 threads call.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ inline void sym_jacobi_eig(double* A, int k, double* sh)
+{
+    const int tid = threadIdx.x;
+    double f = 0.0;
+    for (int idx = tid; idx < k * k; idx += 256) f += A[idx] * A[idx];
+    f = sqrt(block_reduce_256(f, sh, OpSum{}));
+    if (!(f > 0.0) || !(f <= DBL_MAX)) return;          // the zero matrix (or a non-finite one: unspecified input)
+    const double thr_conv = ldexp(f, -60), thr_skip = ldexp(f, -80);
+    const int mm = (k + 1) & ~1, npair = mm / 2;         // k <= 48: at most 24 pairs
+    const int grp = tid >> 3, sub = tid & 7;
+    for (int sweep = 0; sweep < 40; ++sweep) {
+        double myoff = 0.0;
+        for (int step = 0; step < mm - 1; ++step) {
+            bool act = false;
+            int p = 0, q = 0;
+            double c = 1.0, s = 0.0, app2 = 0.0, aqq2 = 0.0;
+            if (grp < npair) {
+                if (grp == 0) { p = mm - 1; q = step; }
+                else { p = (step + grp) % (mm - 1); q = (step - grp + (mm - 1)) % (mm - 1); }
+                if (p > q) { const int tmp = p; p = q; q = tmp; }
+                if (q < k) {                                           // (q == k: the dummy index of an odd k)
+                    const double apq = A[p + q * k], app = A[p + p * k], aqq = A[q + q * k];
+                    myoff = fmax(myoff, fabs(apq));
+                    if (fabs(apq) > thr_skip) {
+                        act = true;
+                        const double theta = (aqq - app) / (2.0 * apq);
+                        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(1.0 + theta * theta));
+                        c = 1.0 / sqrt(1.0 + t * t);
+                        s = c * t;
+                        app2 = app - t * apq;
+                        aqq2 = aqq + t * apq;
+                    }
+                }
+            }
+            __syncthreads();
+            if (act) {
+                for (int i = sub; i < k; i += 8) {
+                    const double ap = A[i + p * k], aq = A[i + q * k];
+                    A[i + p * k] = c * ap - s * aq;
+                    A[i + q * k] = s * ap + c * aq;
+                }
+            }
+            __syncthreads();
+            if (act) {
+                for (int j = sub; j < k; j += 8) {
+                    if (j == p) { A[p + p * k] = app2; A[q + p * k] = 0.0; }
+                    else if (j == q) { A[p + q * k] = 0.0; A[q + q * k] = aqq2; }
+                    else {
+                        const double ap = A[p + j * k], aq = A[q + j * k];
+                        A[p + j * k] = c * ap - s * aq;
+                        A[q + j * k] = s * ap + c * aq;
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        const double offn = block_reduce_256(myoff, sh, OpMax{});
+        if (offn <= thr_conv) break;
+    }
+}
+
+// X = mat(scale * x) of an svec vector (coneops_psdtrianglecone.jl:469-483), both triangles
+__device__ inline void psd_load_mat(double* X, const double* __restrict__ x, double scale, int k)
+{
+    const int t = k * (k + 1) / 2;
+    for (int idx = threadIdx.x; idx < t; idx += 256) {
+        int r, cl;
+        st_svec_index(idx, r, cl);
+        const double v = scale * x[idx] * (r == cl ? 1.0 : kIs2);
+        X[r + cl * k] = v;
+        X[cl + r * k] = v;
+    }
+}
+
+// M = G' X G for symmetric X, exactly symmetric (each pair (r, c) from both orders, averaged).  mul_W!(:N) is G = R
+// (R' X R, :409-437 with :N), mul_Winv!(:T) is G = Rinv' (Rinv X Rinv').  T: work matrix.  Ends with a barrier.
+__device__ inline void psd_congruence(double* M, double* T, const double* G, const double* X, int k)
+{
+    const int tid = threadIdx.x, kk = k * k, t = k * (k + 1) / 2;
+    for (int idx = tid; idx < kk; idx += 256) {          // T = X G
+        const int r = idx % k, cl = idx / k;
+        double acc = 0.0;
+        for (int q = 0; q < k; ++q) acc = fma(X[r + q * k], G[q + cl * k], acc);
+        T[idx] = acc;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < t; idx += 256) {           // M = G' T
+        int r, cl;
+        st_svec_index(idx, r, cl);
+        double a1 = 0.0, a2 = 0.0;
+        for (int q = 0; q < k; ++q) { a1 = fma(G[q + r * k], T[q + cl * k], a1); a2 = fma(G[q + cl * k], T[q + r * k], a2); }
+        const double v = r == cl ? a1 : 0.5 * (a1 + a2);
+        M[r + cl * k] = v;
+        M[cl + r * k] = v;
+    }
+    __syncthreads();
+}
+
+// G = R (transpose = 0) or Rinv' (transpose = 1) into LDS
+__device__ inline void psd_load_G(double* G, const double* __restrict__ src, int k, int transpose)
+{
+    for (int idx = threadIdx.x; idx < k * k; idx += 256) {
+        const int r = idx % k, cl = idx / k;
+        G[idx] = transpose ? src[cl + r * k] : src[idx];
+    }
+}
+
+// =====================================================================================================================
+//  affine_ds! / combined ds: out = lambda o lambda [+ (W^{-T} step_s) o (W (m step_z)) - sigma_mu e]
+// =====================================================================================================================
+__device__ inline void step_ds_elementwise_body(const ConeDev& C, const ConeState& S, double* __restrict__ out,
+                                                const double* __restrict__ dz, const double* __restrict__ ds,
+                                                double sigma_mu, double m_corr, int m, int combined, int bx, int nb)
+{
+    for (int i = bx * 256 + threadIdx.x; i < m; i += nb * 256) {
+        const int kind = C.kind[C.elem_cone[i]];
+        if (kind == 0) out[i] = 0.0;                                    // coneops_zerocone.jl
+        else if (kind == 1) {                                           // coneops_nncone.jl:117-126, :196-227
+            const double l = S.lam[i];
+            double o = l * l;
+            if (combined) {
+                const double w = S.w[i];
+                o += (ds[i] / w) * (w * (m_corr * dz[i])) - sigma_mu;
+            }
+            out[i] = o;
+        }
+    }
+}
+
+// one wave per second-order cone: circ_op! (coneops_socone.jl:376-392), mul_W! / mul_Winv! (:313-357)
+__device__ inline void step_ds_soc_body(const ConeDev& C, const ConeState& S, double* __restrict__ out,
+                                        const double* __restrict__ dz, const double* __restrict__ ds, double sigma_mu,
+                                        double m_corr, int combined, int ci, int lane)
+{
+    const int c = C.soc_list[ci];
+    const int off = C.off[c], n = C.numel[c];
+    const double* lam = S.lam + off;
+    const double* w = S.w + off;
+    double ll = 0.0, zz = 0.0, zs = 0.0;
+    for (int i = lane; i < n; i += 64) ll += lam[i] * lam[i];
+    if (combined)
+        for (int i = 1 + lane; i < n; i += 64) {
+            zz += w[i] * (m_corr * dz[off + i]);
+            zs += w[i] * ds[off + i];
+        }
+    ll = st_wave_sum(ll);
+    const double l0 = lam[0];
+    if (!combined) {
+        for (int i = lane; i < n; i += 64) out[off + i] = i == 0 ? ll : l0 * lam[i] + l0 * lam[i];
+        return;
+    }
+    zz = st_wave_sum(zz);
+    zs = st_wave_sum(zs);
+    const double eta = S.eta[c], etainv = 1.0 / eta, w0 = w[0];
+    const double dz0 = m_corr * dz[off], ds0 = ds[off];
+    const double cz = dz0 + zz / (1.0 + w0), cs = -ds0 + zs / (1.0 + w0);
+    const double Z0 = eta * (w0 * dz0 + zz), Y0 = etainv * (w0 * ds0 - zs);
+    double yz = 0.0;
+    for (int i = 1 + lane; i < n; i += 64) {
+        const double Zi = eta * (m_corr * dz[off + i] + cz * w[i]);
+        const double Yi = etainv * (ds[off + i] + cs * w[i]);
+        yz += Yi * Zi;
+        out[off + i] = (l0 * lam[i] + l0 * lam[i]) + (Y0 * Zi + Z0 * Yi);
+    }
+    yz = st_wave_sum(yz);
+    if (lane == 0) out[off] = ll + ((Y0 * Z0 + yz) - sigma_mu);
+}
+
+__global__ __launch_bounds__(256) void k_step_ds(ConeDev C, ConeState S, double* __restrict__ out, const double* __restrict__ dz,
+                                                 const double* __restrict__ ds, double sigma_mu, double m_corr, int m,
+                                                 int combined, int ge)
+{
+    if ((int)blockIdx.x < ge) { step_ds_elementwise_body(C, S, out, dz, ds, sigma_mu, m_corr, m, combined, blockIdx.x, ge); return; }
+    const int ci = ((int)blockIdx.x - ge) * 4 + (int)(threadIdx.x >> 6);
+    if (ci < C.nsoc) step_ds_soc_body(C, S, out, dz, ds, sigma_mu, m_corr, combined, ci, threadIdx.x & 63);
+}
+
+// PSD cones (coneops_psdtrianglecone.jl:189-205, circ_op! :361-382): Z = R'mat(m dz)R, Y = Rinv mat(ds) Rinv',
+// out = svec((YZ + ZY)/2) with lambda_i^2 - sigma_mu added on the diagonal.  LDS: four k x k matrices.
+__global__ __launch_bounds__(256) void k_step_ds_psd(ConeDev C, ConeState S, double* __restrict__ out,
+                                                    const double* __restrict__ dz, const double* __restrict__ ds,
+                                                    double sigma_mu, double m_corr, int combined)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int tid = threadIdx.x;
+    const int c = C.psd_list[blockIdx.x];
+    const int k = C.psd_dim[c], off = C.off[c], kk = k * k, t = k * (k + 1) / 2;
+    if (k == 0) return;
+    const double* lam = S.lam + off;
+    if (!combined) {
+        for (int idx = tid; idx < t; idx += 256) {
+            int r, cl;
+            st_svec_index(idx, r, cl);
+            out[off + idx] = r == cl ? lam[r] * lam[r] : 0.0;
+        }
+        return;
+    }
+    double* G = smem;
+    double* X = smem + kk;          // mat(ds), then Y
+    double* T = smem + 2 * kk;
+    double* Z = smem + 3 * kk;
+    psd_load_G(G, S.psdR + C.psd_aoff[c], k, 0);
+    psd_load_mat(X, dz + off, m_corr, k);
+    __syncthreads();
+    psd_congruence(Z, T, G, X, k);
+    psd_load_G(G, S.psdRinv + C.psd_aoff[c], k, 1);
+    psd_load_mat(X, ds + off, 1.0, k);
+    __syncthreads();
+    psd_congruence(X, T, G, X, k);                       // (the product X G is complete before X is overwritten)
+    const double* Y = X;
+    for (int idx = tid; idx < t; idx += 256) {
+        int r, cl;
+        st_svec_index(idx, r, cl);
+        double a1 = 0.0, a2 = 0.0;
+        for (int q = 0; q < k; ++q) { a1 = fma(Y[r + q * k], Z[q + cl * k], a1); a2 = fma(Z[r + q * k], Y[q + cl * k], a2); }
+        const double v = 0.5 * (a1 + a2);
+        out[off + idx] = r == cl ? lam[r] * lam[r] + (v - sigma_mu) : v * kS2;
+    }
+}
+
+// =====================================================================================================================
+//  step_length: every cone's limit is min(alpha_max, f(cone)), so the composite's sequential tightening of alpha_max
+//  (coneops_compositecone.jl:205-243) is an order-free minimum: each workgroup / wave / PSD cone leaves its f in a slot
+//  of `partial` (DBL_MAX where nothing binds), and the finishing kernel takes the minimum with the tau / kappa limits.
+// =====================================================================================================================
+__device__ inline void step_length_elementwise_body(const ConeDev& C, const double* __restrict__ dz, const double* __restrict__ ds,
+                                                    const double* __restrict__ z, const double* __restrict__ s, int m,
+                                                    double* __restrict__ partial, int bx, int nb, double* sh)
+{
+    double a = DBL_MAX;
+    for (int i = bx * 256 + threadIdx.x; i < m; i += nb * 256) {
+        if (C.kind[C.elem_cone[i]] != 1) continue;                     // coneops_nncone.jl:151-170
+        const double dzi = dz[i], dsi = ds[i];
+        if (dzi < 0.0) a = fmin(a, -z[i] / dzi);
+        if (dsi < 0.0) a = fmin(a, -s[i] / dsi);
+    }
+    a = block_reduce_256(a, sh, OpMin{});
+    if (threadIdx.x == 0) partial[bx] = a;
+}
+
+// _step_length_soc_component (coneops_socone.jl:443-512) with alpha_max = DBL_MAX; ny = ||y[2:end]||, nx = ||x[2:end]||,
+// xy = <x[2:end], y[2:end]>
+__device__ inline double soc_step_component(double x0, double y0, double nx, double ny, double xy)
+{
+    double amax = DBL_MAX;
+    if (x0 >= 0.0 && y0 < 0.0) amax = fmin(amax, -x0 / y0);
+    const double a = (y0 - ny) * (y0 + ny);                            // _soc_residual, :415-419
+    const double b = 2.0 * (x0 * y0 - xy);
+    const double c = fmax(0.0, (x0 - nx) * (x0 + nx));
+    const double d = b * b - 4.0 * a * c;
+    if ((a > 0.0 && b > 0.0) || d < 0.0) return amax;
+    if (a == 0.0) return amax;
+    if (c == 0.0) return a >= 0.0 ? amax : 0.0;
+    const double t = b >= 0.0 ? (-b - sqrt(d)) : (-b + sqrt(d));
+    double r1 = (2.0 * c) / t, r2 = t / (2.0 * a);
+    if (r1 < 0.0) r1 = DBL_MAX;
+    if (r2 < 0.0) r2 = DBL_MAX;
+    return fmin(amax, fmin(r1, r2));
+}
+
+__device__ inline void step_length_soc_body(const ConeDev& C, const double* __restrict__ dz, const double* __restrict__ ds,
+                                            const double* __restrict__ z, const double* __restrict__ s,
+                                            double* __restrict__ slot, int ci, int lane)
+{
+    const int c = C.soc_list[ci];
+    const int off = C.off[c], n = C.numel[c];
+    double zz = 0.0, dd = 0.0, zd = 0.0, ss = 0.0, ee = 0.0, se = 0.0;
+    for (int i = 1 + lane; i < n; i += 64) {
+        const double zi = z[off + i], di = dz[off + i], si = s[off + i], ei = ds[off + i];
+        zz += zi * zi; dd += di * di; zd += zi * di;
+        ss += si * si; ee += ei * ei; se += si * ei;
+    }
+    zz = sqrt(st_wave_sum(zz)); dd = sqrt(st_wave_sum(dd)); zd = st_wave_sum(zd);
+    ss = sqrt(st_wave_sum(ss)); ee = sqrt(st_wave_sum(ee)); se = st_wave_sum(se);
+    if (lane == 0) {
+        const double az = soc_step_component(z[off], dz[off], zz, dd, zd);
+        const double as = soc_step_component(s[off], ds[off], ss, ee, se);
+        *slot = fmin(az, as);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_step_length(ConeDev C, const double* __restrict__ dz, const double* __restrict__ ds,
+                                                     const double* __restrict__ z, const double* __restrict__ s, int m,
+                                                     double* __restrict__ partial, int ge)
+{
+    __shared__ double sh[256];
+    if ((int)blockIdx.x < ge) { step_length_elementwise_body(C, dz, ds, z, s, m, partial, blockIdx.x, ge, sh); return; }
+    const int ci = ((int)blockIdx.x - ge) * 4 + (int)(threadIdx.x >> 6);
+    if (ci < C.nsoc) step_length_soc_body(C, dz, ds, z, s, partial + ge + ci, ci, threadIdx.x & 63);
+}
+
+// PSD cones (coneops_psdtrianglecone.jl:230-254, :439-466): both components by the cone's workgroup.
+// gamma = lambda_min(Lam^{-1/2} mat(d) Lam^{-1/2}), d = W dz or W^{-T} ds; the limit is 1/(-gamma) where gamma < 0.
+__global__ __launch_bounds__(256) void k_step_length_psd(ConeDev C, ConeState S, const double* __restrict__ dz,
+                                                        const double* __restrict__ ds, double* __restrict__ slots)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    __shared__ double sh[256];
+    const int tid = threadIdx.x;
+    const int c = C.psd_list[blockIdx.x];
+    const int k = C.psd_dim[c], off = C.off[c], kk = k * k;
+    if (k == 0) { if (tid == 0) slots[blockIdx.x] = DBL_MAX; return; }
+    double* G = smem;
+    double* X = smem + kk;
+    double* T = smem + 2 * kk;
+    double* M = smem + 3 * kk;
+    const double* lam = S.lam + off;
+    double alpha = DBL_MAX;
+    for (int comp = 0; comp < 2; ++comp) {
+        psd_load_G(G, (comp == 0 ? S.psdR : S.psdRinv) + C.psd_aoff[c], k, comp);
+        psd_load_mat(X, (comp == 0 ? dz : ds) + off, 1.0, k);
+        __syncthreads();
+        psd_congruence(M, T, G, X, k);
+        for (int idx = tid; idx < kk; idx += 256) {      // lrscale! with Lam^{-1/2} (symmetric entries get the same factors)
+            const int r = idx % k, cl = idx / k;
+            M[idx] = M[idx] * ((1.0 / sqrt(lam[r])) * (1.0 / sqrt(lam[cl])));
+        }
+        __syncthreads();
+        sym_jacobi_eig(M, k, sh);
+        double g = DBL_MAX;
+        for (int i = 0; i < k; ++i) g = fmin(g, M[i + i * k]);          // uniform: every thread reads the same words
+        if (g < 0.0) alpha = fmin(alpha, 1.0 / (-g));
+        __syncthreads();
+    }
+    if (tid == 0) slots[blockIdx.x] = alpha;
+}
+
+// variables_calc_step_length (variables.jl:14-43) without max_step_fraction: min(1, tau limit, kappa limit, cones)
+__global__ __launch_bounds__(256) void k_step_length_finish(const double* __restrict__ partial, int np, double step_tau,
+                                                            double step_kappa, double tau, double kappa,
+                                                            double* __restrict__ rec, Publish P)
+{
+    __shared__ double sh[256];
+    double v = DBL_MAX;
+    for (int i = threadIdx.x; i < np; i += 256) v = fmin(v, partial[i]);
+    v = block_reduce_256(v, sh, OpMin{});
+    if (threadIdx.x == 0) {
+        const double at = step_tau < 0.0 ? -tau / step_tau : DBL_MAX;
+        const double ak = step_kappa < 0.0 ? -kappa / step_kappa : DBL_MAX;
+        rec[0] = fmin(fmin(fmin(at, ak), 1.0), v);
+        if (P.dst) st_publish(P);
+    }
+}
+
+// =====================================================================================================================
+//  margins (composite :49-63) and scaled_unit_shift!
+// =====================================================================================================================
+__global__ __launch_bounds__(256) void k_margins(ConeDev C, const double* __restrict__ v, int m, double* __restrict__ pmin,
+                                                 double* __restrict__ psum, int ge)
+{
+    __shared__ double sh[256];
+    const int bx = blockIdx.x;
+    if (bx < ge) {                                                     // coneops_nncone.jl:19-39; zero cone: (floatmax, 0)
+        double mn = DBL_MAX, sum = 0.0;
+        for (int i = bx * 256 + threadIdx.x; i < m; i += ge * 256) {
+            if (C.kind[C.elem_cone[i]] != 1) continue;
+            const double x = v[i];
+            mn = fmin(mn, x);
+            if (x > 0.0) sum += x;
+        }
+        mn = block_reduce_256(mn, sh, OpMin{});
+        sum = block_reduce_256(sum, sh, OpSum{});
+        if (threadIdx.x == 0) { pmin[bx] = mn; psum[bx] = sum; }
+        return;
+    }
+    const int ci = (bx - ge) * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (ci >= C.nsoc) return;
+    const int c = C.soc_list[ci];                                      // coneops_socone.jl:13-23
+    const int off = C.off[c], n = C.numel[c];
+    double sq = 0.0;
+    for (int i = 1 + lane; i < n; i += 64) sq += v[off + i] * v[off + i];
+    sq = st_wave_sum(sq);
+    if (lane == 0) {
+        const double a = v[off] - sqrt(sq);
+        pmin[ge + ci] = a;
+        psum[ge + ci] = fmax(0.0, a);
+    }
+}
+
+// PSD cones (coneops_psdtrianglecone.jl:8-27): the eigenvalues of mat(v)
+__global__ __launch_bounds__(256) void k_margins_psd(ConeDev C, const double* __restrict__ v, double* __restrict__ pmin,
+                                                    double* __restrict__ psum)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    __shared__ double sh[256];
+    const int c = C.psd_list[blockIdx.x];
+    const int k = C.psd_dim[c], off = C.off[c];
+    if (k == 0) { if (threadIdx.x == 0) { pmin[blockIdx.x] = DBL_MAX; psum[blockIdx.x] = 0.0; } return; }
+    psd_load_mat(smem, v + off, 1.0, k);
+    __syncthreads();
+    sym_jacobi_eig(smem, k, sh);
+    if (threadIdx.x == 0) {
+        double mn = DBL_MAX, sum = 0.0;
+        for (int i = 0; i < k; ++i) {
+            const double e = smem[i + i * k];
+            mn = fmin(mn, e);
+            if (e > 0.0) sum += e;
+        }
+        pmin[blockIdx.x] = mn;
+        psum[blockIdx.x] = sum;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_margins_finish(const double* __restrict__ pmin, const double* __restrict__ psum,
+                                                        int np, double* __restrict__ rec, Publish P)
+{
+    __shared__ double sh[256];
+    double mn = DBL_MAX, sum = 0.0;
+    for (int i = threadIdx.x; i < np; i += 256) { mn = fmin(mn, pmin[i]); sum += psum[i]; }
+    mn = block_reduce_256(mn, sh, OpMin{});
+    sum = block_reduce_256(sum, sh, OpSum{});
+    if (threadIdx.x == 0) {
+        rec[0] = mn;
+        rec[1] = sum;
+        if (P.dst) st_publish(P);
+    }
+}
+
+// scaled_unit_shift! of every cone: v += a e (nonnegative: every element, coneops_nncone.jl:42-52; second-order: element 0,
+// coneops_socone.jl:26-37; PSD: the diagonal entries, coneops_psdtrianglecone.jl:30-44), a zero cone's rows set to 0 for the
+// primal cone.  two: a second shift a2 applied AFTER the first, not their sum (variables.jl:190-191).
+__global__ __launch_bounds__(256) void k_unit_shift(ConeDev C, double* __restrict__ v, double a1, double a2, int two, int primal,
+                                                    int m)
+{
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) {
+        const int c = C.elem_cone[i];
+        const int kind = C.kind[c];
+        bool hit;
+        if (kind == 0) { if (primal) v[i] = 0.0; continue; }
+        else if (kind == 1) hit = true;
+        else if (kind == 2) hit = i == C.off[c];
+        else {
+            int r, cl;
+            st_svec_index(i - C.off[c], r, cl);
+            hit = r == cl;
+        }
+        if (!hit) continue;
+        double x = v[i] + a1;
+        if (two) x = x + a2;
+        v[i] = x;
+    }
+}
+
+inline int step_grid(int m)
+{
+    int64_t g = ((int64_t)m + 255) / 256;
+    if (g < 1) g = 1;
+    if (g > kStepGridCap) g = kStepGridCap;
+    return (int)g;
+}
+
+inline size_t step_psd_lds(const ConeDev& C) { return (size_t)4 * C.psd_kmax * C.psd_kmax * sizeof(double); }
+
+}  // namespace
+
+void launch_step_ds(const ConeDev& C, const ConeState& S, double* out, const double* step_z, const double* step_s,
+                    double sigma_mu, double m_corr, int m, bool combined, hipStream_t st)
+{
+    if (m <= 0) return;
+    if (C.npsd > 0) {
+        static PerDeviceOnce once;
+        once.run([]() { return set_max_lds(k_step_ds_psd, 150 * 1024); });
+        hipLaunchKernelGGL(k_step_ds_psd, dim3(C.npsd), dim3(256), combined ? step_psd_lds(C) : 0, st, C, S, out, step_z, step_s,
+                           sigma_mu, m_corr, combined ? 1 : 0);
+    }
+    const int ge = step_grid(m), gs = (C.nsoc + 3) / 4;
+    hipLaunchKernelGGL(k_step_ds, dim3(ge + gs), dim3(256), 0, st, C, S, out, step_z, step_s, sigma_mu, m_corr, m,
+                       combined ? 1 : 0, ge);
+}
+
+void launch_step_length(const ConeDev& C, const ConeState& S, const double* dz, const double* ds, const double* z,
+                        const double* s, double step_tau, double step_kappa, double tau, double kappa, double* partial,
+                        double* rec, const Publish& pub, int m, hipStream_t st)
+{
+    const int ge = step_grid(m), gs = (C.nsoc + 3) / 4;
+    if (C.npsd > 0) {
+        static PerDeviceOnce once;
+        once.run([]() { return set_max_lds(k_step_length_psd, 150 * 1024); });
+        hipLaunchKernelGGL(k_step_length_psd, dim3(C.npsd), dim3(256), step_psd_lds(C), st, C, S, dz, ds, partial + ge + C.nsoc);
+    }
+    hipLaunchKernelGGL(k_step_length, dim3(ge + gs), dim3(256), 0, st, C, dz, ds, z, s, m, partial, ge);
+    hipLaunchKernelGGL(k_step_length_finish, dim3(1), dim3(256), 0, st, partial, ge + C.nsoc + C.npsd, step_tau, step_kappa,
+                       tau, kappa, rec, pub);
+}
+
+void launch_margins(const ConeDev& C, const double* v, double* partial, double* rec, const Publish& pub, int m, hipStream_t st)
+{
+    const int ge = step_grid(m), gs = (C.nsoc + 3) / 4, np = step_partials(C);
+    double* pmin = partial;
+    double* psum = partial + np;
+    if (C.npsd > 0) {
+        static PerDeviceOnce once;
+        once.run([]() { return set_max_lds(k_margins_psd, 150 * 1024); });
+        hipLaunchKernelGGL(k_margins_psd, dim3(C.npsd), dim3(256), (size_t)C.psd_kmax * C.psd_kmax * sizeof(double), st, C, v,
+                           pmin + ge + C.nsoc, psum + ge + C.nsoc);
+    }
+    hipLaunchKernelGGL(k_margins, dim3(ge + gs), dim3(256), 0, st, C, v, m, pmin, psum, ge);
+    hipLaunchKernelGGL(k_margins_finish, dim3(1), dim3(256), 0, st, pmin, psum, ge + C.nsoc + C.npsd, rec, pub);
+}
+
+void launch_unit_shift(const ConeDev& C, double* v, double a1, double a2, bool two, bool primal, int m, hipStream_t st)
+{
+    if (m <= 0) return;
+    hipLaunchKernelGGL(k_unit_shift, dim3(step_grid(m)), dim3(256), 0, st, C, v, a1, a2, two ? 1 : 0, primal ? 1 : 0, m);
+}
+
+}  // namespace hipkkt

@@ -1,0 +1,229 @@
+"""The interior-point loop of `ipm.solve` with the iterate resident in HBM.
+
+`solve_device` is `ipm.solve` for symmetric cone lists (zero, nonnegative, second-order, PSD side <= 48), line for line,
+with x, s, z, the steps, the right-hand sides and the residual vectors held as torch device tensors for the whole
+solve.  Level C of the C ABI does everything KKT-shaped (init, initial point, kkt_update!, the two kkt_solve!) and --
+through hipkkt_kkt_system_affine_ds / _combined_ds / _step_length / _shift_to_interior -- everything cone-shaped; torch
+does the plumbing between them (the residual mat-vecs with fp64 CSR tensors, dots, norms, axpy).  After
+`system.init` nothing of length n or m crosses the bus until the final solution: per iteration only scalars do (one
+batch of dot products and norms, alpha twice, (dtau, dkappa) twice, the solves' status).
+
+    residuals, mu, termination, sigma = (1 - alpha)^3, m = alpha on the first iteration and 1 afterwards,
+    post-processing                       as ipm.solve (solver.jl:189-380, info.jl, variables.jl:107-190)
+
+One difference in bookkeeping: a cone point that is not interior is reported by kkt_update! itself (the device scales
+the cones inside it), so `iterations` counts that last, failed iteration, where `ipm.solve` with host cones stops one
+line earlier.  The status is NUMERICAL_ERROR either way.
+"""
+import warnings
+
+import numpy as np
+import scipy.sparse as sp
+
+from .cones import ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT
+from .ipm import (IPMSettings, IPMResult, HipSystemBackend, SOLVED, PRIMAL_INFEASIBLE, DUAL_INFEASIBLE, MAX_ITERATIONS,
+                  NUMERICAL_ERROR, INSUFFICIENT_PROGRESS, UNSOLVED, ALMOST_SOLVED)
+
+PSD_MAX_SIDE = 48          # kPsdMaxDim of the device kernels
+
+
+class _Csr:
+    """y = M x on the device for a scipy matrix: an fp64 CSR tensor; where the installed torch has no fp64 CSR mat-vec
+    on the GPU, the COO product written with index_add_ (mode tells which)."""
+
+    def __init__(self, M, dev):
+        import torch
+        M = sp.csr_matrix(M)
+        M.sort_indices()
+        self.shape = M.shape
+        self.torch = torch
+        val = torch.from_numpy(np.ascontiguousarray(M.data, dtype=np.float64)).to(dev)
+        self.mode = "csr"
+        try:
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")          # ("sparse CSR tensor support is in beta state")
+                self.M = torch.sparse_csr_tensor(torch.from_numpy(M.indptr.astype(np.int64)).to(dev),
+                                                 torch.from_numpy(M.indices.astype(np.int64)).to(dev), val, size=M.shape)
+            self.M @ torch.zeros(M.shape[1], dtype=torch.float64, device=dev)
+        except (RuntimeError, NotImplementedError, ValueError, IndexError):
+            self.mode = "coo"
+            coo = M.tocoo()
+            self.row = torch.from_numpy(coo.row.astype(np.int64)).to(dev)
+            self.col = torch.from_numpy(coo.col.astype(np.int64)).to(dev)
+            self.val = torch.from_numpy(np.ascontiguousarray(coo.data, dtype=np.float64)).to(dev)
+        self.dev = dev
+
+    def mv(self, x):
+        if self.mode == "csr":
+            return self.M @ x
+        y = self.torch.zeros(self.shape[0], dtype=self.torch.float64, device=self.dev)
+        return y.index_add_(0, self.row, self.val * x[self.col])
+
+
+def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None):
+    """Clarabel.solve! restated with device-resident vectors -> IPMResult (numpy x, z, s).
+
+    inspect (optional): called once per iteration with (dict of the tensors the loop holds, the HipSystemBackend) --
+    for tests that check residency."""
+    import torch
+    st = settings or IPMSettings()
+    cone_specs = list(cone_specs)
+    for c in cone_specs:
+        if not isinstance(c, (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT)):
+            raise ValueError("solve_device covers the symmetric cones only (zero, nonnegative, second-order, PSD); "
+                             f"got {type(c).__name__}: use ipm.solve")
+        if isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE:
+            raise ValueError(f"solve_device covers PSD cones up to side {PSD_MAX_SIDE}")
+    P = sp.csc_matrix(P)
+    Pt = sp.triu(P, format="csc")
+    Pfull_h = (Pt + sp.triu(Pt, 1).T).tocsr()
+    A_h = sp.csr_matrix(A)
+    q, b = np.asarray(q, float), np.asarray(b, float)
+    n, m = Pfull_h.shape[0], A_h.shape[0]
+    degree = sum(c.dim if isinstance(c, (NonnegativeConeT, PSDTriangleConeT)) else 1 if isinstance(c, SecondOrderConeT) else 0
+                 for c in cone_specs)
+    normq = np.abs(q).max() if n else 0.0
+    normb = np.abs(b).max() if m else 0.0
+
+    backend = HipSystemBackend(P, A, cone_specs)
+    ks, system = backend.ks, backend.system
+    dev = system._devstr
+    ks.set_stream(torch.cuda.current_stream(torch.device(dev)).cuda_stream)     # torch's kernels and the library's: one queue
+    Pfull, Ad, At = _Csr(Pfull_h, dev), _Csr(A_h, dev), _Csr(A_h.T, dev)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    new = lambda k: torch.zeros(max(k, 1), dtype=torch.float64, device=dev)[:k]
+    qd, bd = up(q), up(b)
+    p = lambda t: t.data_ptr()
+    ir_total = 0
+
+    # ---- default start: solver.jl:383-404
+    x, s, z = new(n), new(m), new(m)
+    dx, ds, dz = new(n), new(m), new(m)
+    aff_s, rhs_s = new(m), new(m)
+    system.init(q, b)
+    backend.update_identity()
+    system.solve_constant_rhs()
+    system.solve_initial_point_dev(p(x), p(s), p(z))
+    system.shift_to_interior_dev(p(s), True)             # variables.jl:213-237
+    system.shift_to_interior_dev(p(z), False)
+    tau, kappa = 1.0, 1.0
+
+    it, alpha, sigma = 0, 0.0, 1.0
+    status = UNSOLVED
+    prev = None
+    hist = []
+    prev_vars = None
+    nrm = torch.linalg.vector_norm
+    while True:
+        # ---- residuals (residuals.jl:1-37); the scalars in ONE read-back
+        Px = Pfull.mv(x)
+        rx_inf = -At.mv(z)
+        rz_inf = Ad.mv(x) + s
+        rx = rx_inf - Px - qd * tau
+        rz = rz_inf - bd * tau
+        qx, bz, sz, xPx, nx, nz, ns, n_rxi, n_Px, n_rzi, n_rz, n_rx = torch.stack(
+            [qd @ x, bd @ z, s @ z, x @ Px, nrm(x), nrm(z), nrm(s), nrm(rx_inf), nrm(Px), nrm(rz_inf), nrm(rz), nrm(rx)]).tolist()
+        rtau = qx + bz + kappa + xPx / tau
+        mu = (sz + tau * kappa) / (degree + 1)
+        if inspect is not None:
+            inspect(dict(x=x, s=s, z=z, dx=dx, ds=ds, dz=dz, aff_s=aff_s, rhs_s=rhs_s, rx=rx, rz=rz, rx_inf=rx_inf,
+                         rz_inf=rz_inf, Px=Px, q=qd, b=bd), backend)
+        # ---- info_update! (info.jl:1-63), no equilibration
+        tinv = 1.0 / tau
+        cost_p = qx * tinv + xPx * tinv * tinv / 2
+        cost_d = -bz * tinv - xPx * tinv * tinv / 2
+        res_pinf = n_rxi / max(1.0, nz)
+        res_dinf = max(n_Px / max(1.0, nx), n_rzi / max(1.0, nx + ns))
+        nx, nz, ns = nx * tinv, nz * tinv, ns * tinv
+        res_p = n_rz * tinv / max(1.0, normb + nx + ns)
+        res_d = n_rx * tinv / max(1.0, normq + nx + nz)
+        gap_abs = abs(cost_p - cost_d)
+        gap_rel = gap_abs / max(1.0, min(abs(cost_p), abs(cost_d)))
+        kt = kappa * tinv
+        hist.append(dict(iter=it, pcost=cost_p, dcost=cost_d, gap=gap_abs, pres=res_p, dres=res_d, kt=kt, mu=mu,
+                         step=alpha))
+        # ---- termination (info.jl:65-120, 270-330)
+        status = UNSOLVED
+        if kt <= 1 and (gap_abs < st.tol_gap_abs or gap_rel < st.tol_gap_rel) and res_p < st.tol_feas and res_d < st.tol_feas:
+            status = SOLVED
+        elif kt > 1000.0 / st.tol_ktratio:
+            if bz < -st.tol_infeas_abs and res_pinf < -st.tol_infeas_rel * bz:
+                status = PRIMAL_INFEASIBLE
+            elif qx < -st.tol_infeas_abs and res_dinf < -st.tol_infeas_rel * qx:
+                status = DUAL_INFEASIBLE
+        if status == UNSOLVED and it > 1 and prev is not None and (res_d > prev["res_d"] or res_p > prev["res_p"]):
+            if kt < 100 * np.finfo(float).eps and (prev["gap_abs"] < st.tol_gap_abs or prev["gap_rel"] < st.tol_gap_rel):
+                status = INSUFFICIENT_PROGRESS
+            if kt < 1 and ((res_d > 100 * st.tol_feas and res_d > 100 * prev["res_d"]) or
+                           (res_p > 100 * st.tol_feas and res_p > 100 * prev["res_p"])):
+                status = INSUFFICIENT_PROGRESS
+        if status == UNSOLVED and it == st.max_iter:
+            status = MAX_ITERATIONS
+        if status != UNSOLVED:
+            if status == INSUFFICIENT_PROGRESS and prev_vars is not None:
+                x, s, z, tau, kappa = prev_vars
+            break
+        # ---- kkt_update!: cone scaling from (s, z), refactor, constant-RHS solve (solver.jl:258-280)
+        it += 1
+        ok = system.update_dev(p(s), p(z))
+        if ok:
+            # ---- affine step (solver.jl:282-295)
+            system.affine_ds_dev(p(aff_s))
+            ok, dtau, dkappa = system.solve_dev((p(dx), p(ds), p(dz)), (p(rx), p(aff_s), p(rz)), rtau, tau * kappa,
+                                                (p(x), p(s), p(z)), tau, kappa, True)
+            ir_total += backend.last_ir_iterations
+        if ok:
+            # ---- combined step (solver.jl:297-323)
+            alpha = system.step_length_dev(p(dz), p(ds), p(z), p(s), dtau, dkappa, tau, kappa)
+            sigma = (1 - alpha) ** 3
+            mcorr = 1.0 if it > 1 else alpha
+            system.combined_ds_dev(p(rhs_s), p(dz), p(ds), sigma * mu, mcorr)
+            rhs_x, rhs_z = (1 - sigma) * rx, (1 - sigma) * rz
+            ok, dtau, dkappa = system.solve_dev((p(dx), p(ds), p(dz)), (p(rhs_x), p(rhs_s), p(rhs_z)), (1 - sigma) * rtau,
+                                                -sigma * mu + mcorr * dtau * dkappa + tau * kappa,
+                                                (p(x), p(s), p(z)), tau, kappa, False)
+            ir_total += backend.last_ir_iterations
+        if not ok:
+            alpha = 0.0
+            status = NUMERICAL_ERROR
+            break
+        alpha = system.step_length_dev(p(dz), p(ds), p(z), p(s), dtau, dkappa, tau, kappa) * st.max_step_fraction
+        if alpha <= max(0.0, st.min_terminate_step_length):
+            status = INSUFFICIENT_PROGRESS
+            alpha = 0.0
+            break
+        prev = dict(res_p=res_p, res_d=res_d, gap_abs=gap_abs, gap_rel=gap_rel)
+        prev_vars = (x.clone(), s.clone(), z.clone(), tau, kappa)
+        x.add_(dx, alpha=alpha)
+        s.add_(ds, alpha=alpha)
+        z.add_(dz, alpha=alpha)
+        tau += alpha * dtau
+        kappa += alpha * dkappa
+
+    # ---- info_post_process! (info.jl:196-211): after an error / limit exit, accept an iterate that meets the reduced
+    #      tolerances as ALMOST_SOLVED
+    if status in (NUMERICAL_ERROR, INSUFFICIENT_PROGRESS, MAX_ITERATIONS):
+        tinv = 1.0 / tau
+        Px = Pfull.mv(x)
+        qx, bz, xPx, nx, nz, ns, n_rz, n_rx = torch.stack(
+            [qd @ x, bd @ z, x @ Px, nrm(x), nrm(z), nrm(s), nrm(Ad.mv(x) + s - bd * tau), nrm(-At.mv(z) - Px - qd * tau)]).tolist()
+        cp = qx * tinv + xPx * tinv * tinv / 2
+        cd = -bz * tinv - xPx * tinv * tinv / 2
+        nx, nz, ns = nx * tinv, nz * tinv, ns * tinv
+        rp = n_rz * tinv / max(1.0, normb + nx + ns)
+        rd = n_rx * tinv / max(1.0, normq + nx + nz)
+        ga = abs(cp - cd)
+        gr = ga / max(1.0, min(abs(cp), abs(cd)))
+        if kappa * tinv <= 1 and (ga < st.reduced_tol_gap_abs or gr < st.reduced_tol_gap_rel) and \
+                rp < st.reduced_tol_feas and rd < st.reduced_tol_feas:
+            status = ALMOST_SOLVED
+    # ---- solution_post_process!: unscale by tau (kappa for certificates); the one copy of length n / m to the host
+    infeasible = status in (PRIMAL_INFEASIBLE, DUAL_INFEASIBLE)
+    sc = 1.0 / (kappa if infeasible else tau)
+    torch.cuda.synchronize()
+    xo, zo, so = (x * sc).cpu().numpy(), (z * sc).cpu().numpy(), (s * sc).cpu().numpy()
+    objp = q @ xo + 0.5 * xo @ (Pfull_h @ xo)
+    objd = -b @ zo - 0.5 * xo @ (Pfull_h @ xo)
+    if infeasible:
+        objp = objd = float("nan")
+    return IPMResult(status, xo, zo, so, objp, objd, it, ir_total, hist)

@@ -357,6 +357,32 @@ class HipKKTSystem:
             0 if affine else 1), "hipkkt_kkt_system_solve")
         return ok, tk[0], tk[1]
 
+    # ---- the cone operations between the solves, on device vectors (raw pointers, like solve_dev)
+    def affine_ds_dev(self, d_out):
+        """out = lambda o lambda (affine_ds!)."""
+        return check(_lib.lib().hipkkt_kkt_system_affine_ds(self.ks._h, C.c_void_p(d_out)), "hipkkt_kkt_system_affine_ds")
+
+    def combined_ds_dev(self, d_out, d_step_z, d_step_s, sigma_mu, m_corr):
+        """out = lambda o lambda + m_corr (W^-T step_s) o (W step_z) - sigma_mu e: d.s of the combined right-hand side."""
+        return check(_lib.lib().hipkkt_kkt_system_combined_ds(self.ks._h, C.c_void_p(d_out), C.c_void_p(d_step_z),
+                                                               C.c_void_p(d_step_s), float(sigma_mu), float(m_corr)),
+                     "hipkkt_kkt_system_combined_ds")
+
+    def step_length_dev(self, d_step_z, d_step_s, d_z, d_s, step_tau, step_kappa, tau, kappa):
+        """variables_calc_step_length without the max_step_fraction factor -> alpha (a host float)."""
+        out = np.zeros(1)
+        check(_lib.lib().hipkkt_kkt_system_step_length(self.ks._h, C.c_void_p(d_step_z), C.c_void_p(d_step_s), C.c_void_p(d_z),
+                                                       C.c_void_p(d_s), float(step_tau), float(step_kappa), float(tau),
+                                                       float(kappa), ptr(out)), "hipkkt_kkt_system_step_length")
+        return float(out[0])
+
+    def shift_to_interior_dev(self, d_v, primal):
+        """_shift_to_cone_interior! in place -> (min_margin, pos_margin) as found before the shift."""
+        out = np.zeros(2)
+        check(_lib.lib().hipkkt_kkt_system_shift_to_interior(self.ks._h, C.c_void_p(d_v), 1 if primal else 0, ptr(out)),
+              "hipkkt_kkt_system_shift_to_interior")
+        return float(out[0]), float(out[1])
+
     def prepared(self, d_lhs, d_rhs, rhs_tau, rhs_kappa, d_var, var_tau, var_kappa):
         """(update, solve_affine, solve_combined) closures over pre-converted ctypes arguments for a caller that issues the
         same three calls on the same resident buffers every iteration (bench.py): the per-call argument marshalling of

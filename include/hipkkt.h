@@ -283,6 +283,43 @@ int hipkkt_kkt_system_update_and_solve_affine(hipkkt_kkt_t h, double *d_lhs_x, d
                                               const double *d_var_x, const double *d_var_s, const double *d_var_z,
                                               double var_tau, double var_kappa);
 
+/* The cone operations an interior-point loop performs BETWEEN its kkt_solve! calls (solver.jl:258-351), on the caller's
+ * DEVICE vectors, so that an iterate kept in HBM never leaves it: per call only scalars cross the bus.  All vectors are
+ * device pointers of length m on the handle's device; all work goes on the handle's stream (in lazy mode simply behind
+ * the pending update).  They need hipkkt_kkt_system_init and -- except hipkkt_kkt_system_shift_to_interior -- the cone
+ * scaling of a hipkkt_kkt_system_update* call.  Inputs are never modified (the reference uses step.z / step.s as work
+ * space; these do not); d_out must not alias an input.  Symmetric cones only (zero, nonnegative, second-order, PSD side
+ * <= 48): on a handle that holds an exponential, power or generalized power cone, or a larger PSD cone, and on a
+ * deferred-status handle, every one of them returns HIPKKT_ERR_ARG (see hipkkt_last_error) and enqueues nothing.
+ * Results are reproducible bit for bit: every reduction has a fixed layout and there are no floating-point atomics. */
+/* affine_ds! over all cones (coneops_compositecone.jl:153-165; nncone :117-126, socone :219-228 via circ_op! :376-392,
+ * psdtrianglecone :189-205, zero cone: 0): out = lambda o lambda */
+int hipkkt_kkt_system_affine_ds(hipkkt_kkt_t h, double *d_out);
+
+/* d.s of variables_combined_step_rhs! (variables.jl:124-162) in one pass:
+ *   out = lambda o lambda + m_corr * (W^{-T} step_s) o (W step_z) - sigma_mu * e
+ * (_combined_ds_shift_symmetric!, coneops_symmetric_common.jl:1-35; mul_W!/mul_Winv!: nncone :196-227, socone :313-359,
+ * psdtrianglecone :298-333, :409-437; e = the cone's unit; zero cone rows: 0).  m_corr is the reference's `m`, which
+ * scales step.z before the product -- the product is bilinear, so it multiplies the circ term. */
+int hipkkt_kkt_system_combined_ds(hipkkt_kkt_t h, double *d_out, const double *d_step_z, const double *d_step_s,
+                                  double sigma_mu, double m_corr);
+
+/* variables_calc_step_length (variables.jl:14-43) WITHOUT the max_step_fraction factor (the caller multiplies):
+ *   alpha = min(1, -tau/step_tau if step_tau < 0, -kappa/step_kappa if step_kappa < 0, every cone's alpha_z, alpha_s)
+ * (composite :205-243; nncone :151-170; socone :271-285 + _step_length_soc_component :443-512, every branch;
+ * psdtrianglecone :230-254 + step_length_psd_component :439-466).  Every cone's limit has the form min(alpha_max, f(cone)),
+ * so the reference's sequential tightening of alpha_max is an order-free minimum and the result does not depend on the
+ * order of the reduction; where nothing binds it is alpha_max itself.  Synchronises; *alpha_out is a host double. */
+int hipkkt_kkt_system_step_length(hipkkt_kkt_t h, const double *d_step_z, const double *d_step_s,
+                                  const double *d_z, const double *d_s, double step_tau, double step_kappa,
+                                  double tau, double kappa, double *alpha_out);
+
+/* _shift_to_cone_interior! (variables.jl:180-208): margins (composite :49-63; zero :27-39, nncone :19-39,
+ * socone :13-23, psdtrianglecone :8-27), then the one or two scaled_unit_shift! calls of its three branches, in place.
+ * primal = 1: a zero cone's rows are set to 0; primal = 0: they are left alone.  degree = sum of cone degrees.
+ * margins_out (host, 2, may be NULL) receives (min_margin, pos_margin) as found BEFORE the shift.  Synchronises. */
+int hipkkt_kkt_system_shift_to_interior(hipkkt_kkt_t h, double *d_v, int primal, double *margins_out);
+
 /* Lazy constant-RHS solve: the same pairing reached through the reference's own TWO calls, so that solver.jl:278-295
  * stays as it is.  With lazy = 1, kkt_update! (hipkkt_kkt_system_update / _update_cones) scales, scatters and
  * refactors, returns the factorisation's status and only NOTES that (x2, z2) = K \ (-q, b) is due
