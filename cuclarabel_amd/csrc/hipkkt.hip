@@ -25,6 +25,7 @@
 #include "symbolic.hpp"
 #include "knobs.hpp"
 #include "schedule.hpp"
+#include "iterate_rows.hpp"
 
 namespace hipkkt {
 
@@ -1857,7 +1858,7 @@ static void fill_info(const Symbolic& S, hipkkt_info* info)
 
 struct PinnedScalars {
     double* h = nullptr;
-    PinnedScalars() { HIP_CHECK(hipHostMalloc((void**)&h, 64 * sizeof(double))); }   // [8..11] update status, [16..35] refinement read-back, [40..47] sticky
+    PinnedScalars() { HIP_CHECK(hipHostMalloc((void**)&h, 72 * sizeof(double))); }   // [8..11] update status, [16..35] refinement read-back, [40..47] sticky, [52..64] step / residual record
     ~PinnedScalars() { if (h) (void)hipHostFree(h); }
 };
 
@@ -1958,6 +1959,12 @@ struct hipkkt_kkt_s {
     int nlong = 0, nchunks = 0;
     size_t long_partial_cols = 0;
     int lanes_per_row = 8;
+    // the prefixes the iterate-residual pass walks (iterate_rows.hpp; kernels.hpp: IterDev), its slots and long-row sums
+    DBuf<int64_t> it_rend, it_long_chunk_ptr, it_chunk_q;
+    DBuf<int> it_long_rows;
+    DBuf<double> it_long_partial, it_partial;
+    int it_nlong = 0, it_nchunks = 0;
+    bool it_prefix_ok = true;
     // vectors
     DBuf<double> b, x, e, dx, rx, rz, sbuf, zbuf, ybuf;
     double *cur_x = nullptr, *cur_dx = nullptr;
@@ -2000,7 +2007,7 @@ struct hipkkt_kkt_s {
     DBuf<double> lam;                                        // scaled point, m
     DBuf<double> sq, snegq, sb, sx2, sz2, sworkx, sworkz, sconic, spa, spb, spc;
     DBuf<double> sys_partial, sys_dots, sys_cached, sys_in;
-    DBuf<double> step_partial, step_rec;                     // step length / margins: partial slots and the 2-double result record
+    DBuf<double> step_partial, step_rec;                     // step length / margins: partial slots and the result record (12 doubles)
     bool sys_ready = false;
     bool sys_lazy = false;           // hipkkt_kkt_system_set_lazy: kkt_update! leaves (x2, z2) = K \ (-q, b) to the affine kkt_solve!
     bool sys_const_pending = false;  // ... and that solve is still due
@@ -2502,6 +2509,20 @@ int hipkkt_kkt_create_ex2(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t
                 for (int64_t i = 0; i < K.n; ++i)
                     pend[(size_t)i] = std::lower_bound(col.begin() + ptr[(size_t)i], col.begin() + ptr[(size_t)i + 1], (int)K.n) - col.begin();
                 h->fpend.upload(pend);
+            }
+            {
+                // ... and what hipkkt_kkt_system_residuals walks: whole x rows, the A prefix of the z rows
+                const IterateRows R = plan_iterate_rows(K.n, K.m, ptr.data(), col.data(), kLongRow, kLongChunk);
+                h->it_prefix_ok = R.prefix_ok;
+                h->it_rend.upload(R.rend);
+                h->it_nlong = (int)R.long_rows.size();
+                h->it_nchunks = (int)(R.chunk_q.size() / 2);
+                if (h->it_nlong) {
+                    h->it_long_rows.upload(R.long_rows);
+                    h->it_long_chunk_ptr.upload(R.long_chunk_ptr);
+                    h->it_chunk_q.upload(R.chunk_q);
+                    h->it_long_partial.alloc((size_t)2 * h->it_nchunks);
+                }
             }
             h->fval.alloc(vmap.size());
             {
@@ -3716,10 +3737,8 @@ static void step_guard(hipkkt_kkt_t h, const char* who, bool need_scaling)
     if (need_scaling && !h->scaling_valid)
         throw ArgError(std::string(who) + ": needs the cone scaling of hipkkt_kkt_system_update");
     HIP_CHECK(hipSetDevice(h->device));
-    if (!h->step_rec.p) {
-        h->step_partial.alloc((size_t)2 * step_partials(h->cone_dev()));
-        h->step_rec.alloc(2);
-    }
+    if (!h->step_partial.p) h->step_partial.alloc((size_t)2 * step_partials(h->cone_dev()));
+    if (!h->step_rec.p) h->step_rec.alloc(12);        // (shared with hipkkt_kkt_system_residuals' twelve scalars)
 }
 
 // the record of a finishing kernel (nrec doubles) on the host: published by that kernel into the pinned block and
@@ -3800,6 +3819,85 @@ int hipkkt_kkt_system_shift_to_interior(hipkkt_kkt_t h, double* d_v, int primal,
         else if (min_margin < target) launch_unit_shift(C, d_v, target - min_margin, 0.0, false, primal == 1, h->K.m, h->stream);
         else launch_unit_shift(C, d_v, 0.0, 0.0, false, primal == 1, h->K.m, h->stream);
         HIP_CHECK(hipStreamSynchronize(h->stream));
+        return HIPKKT_OK;
+    });
+}
+
+// ---- residuals and termination scalars of a device-resident iterate (iterate_kernels.hip), and the two elementwise
+// steps around them.  They read K's image, q and b: no cone scaling, no factorisation, any cone kind.
+static void iterate_guard(hipkkt_kkt_t h)
+{
+    if (!h) throw ArgError("null handle");
+    if (!h->sys_ready) throw ArgError("hipkkt_kkt_system_*: call hipkkt_kkt_system_init first");
+    if (h->deferred) throw ArgError("hipkkt_kkt_system_*: level C reads its scalars back (deferred status is for level B)");
+    HIP_CHECK(hipSetDevice(h->device));
+}
+
+int hipkkt_kkt_system_residuals(hipkkt_kkt_t h, const double* d_x, const double* d_s, const double* d_z, double tau,
+                                double* d_rx, double* d_rz, double* d_rx_inf, double* d_rz_inf, double* d_Px,
+                                const double* d_d, const double* d_dinv, const double* d_e, const double* d_einv, double out[12])
+{
+    return guarded([&]() {
+        iterate_guard(h);
+        const int n = h->K.n, m = h->K.m;
+        if (!out || (n && (!d_x || !d_rx || !d_rx_inf || !d_Px)) || (m && (!d_s || !d_z || !d_rz || !d_rz_inf)))
+            throw ArgError("hipkkt_kkt_system_residuals: bad argument");
+        const int given = (d_d ? 1 : 0) + (d_dinv ? 1 : 0) + (d_e ? 1 : 0) + (d_einv ? 1 : 0);
+        if (given != 0 && given != 4)
+            throw ArgError("hipkkt_kkt_system_residuals: the equilibration vectors d, dinv, e, einv are all NULL or all given");
+        {
+            const void* outs[5] = {d_rx, d_rz, d_rx_inf, d_rz_inf, d_Px};
+            const void* ins[7] = {d_x, d_s, d_z, d_d, d_dinv, d_e, d_einv};
+            for (int i = 0; i < 5; ++i) {
+                if (!outs[i]) continue;
+                for (int j = 0; j < 7; ++j)
+                    if (outs[i] == ins[j]) throw ArgError("hipkkt_kkt_system_residuals: an output aliases an input");
+                for (int j = i + 1; j < 5; ++j)
+                    if (outs[i] == outs[j]) throw ArgError("hipkkt_kkt_system_residuals: two outputs alias");
+            }
+        }
+        if (!h->it_prefix_ok) throw std::runtime_error("hipkkt_kkt_system_residuals: the rows of A are not a prefix of K's z rows");
+        if (!h->it_partial.p) h->it_partial.alloc(iterate_partials());
+        if (!h->step_rec.p) h->step_rec.alloc(12);
+        const SpmvDev A = kkt_spmv(h);                   // (gathers the image's values first where P or A changed: fval_dirty)
+        IterDev I;
+        I.rend = h->it_rend.p;
+        I.nlong = h->it_nlong; I.nchunks = h->it_nchunks; I.long_rows = h->it_long_rows.p;
+        I.long_chunk_ptr = h->it_long_chunk_ptr.p; I.chunk_q = h->it_chunk_q.p; I.long_partial = h->it_long_partial.p;
+        IterVecs V;
+        V.x = d_x; V.s = d_s; V.z = d_z; V.q = h->sq.p; V.b = h->sb.p; V.tau = tau;
+        V.rx = d_rx; V.rz = d_rz; V.rx_inf = d_rx_inf; V.rz_inf = d_rz_inf; V.Px = d_Px;
+        V.d = d_d; V.dinv = d_dinv; V.e = d_e; V.einv = d_einv;
+        const double* rec = step_read_record(h, 12, [&](const Publish& pub) {
+            launch_iterate_residuals(A, I, V, n, m, h->it_partial.p, h->step_rec.p, pub, h->stream);
+        });
+        for (int i = 0; i < 12; ++i) out[i] = rec[i];
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_combined_rhs(hipkkt_kkt_t h, double* d_rhs_x, double* d_rhs_z, const double* d_rx, const double* d_rz,
+                                   double sigma)
+{
+    return guarded([&]() {
+        iterate_guard(h);
+        if ((h->K.n && (!d_rhs_x || !d_rx)) || (h->K.m && (!d_rhs_z || !d_rz)))
+            throw ArgError("hipkkt_kkt_system_combined_rhs: bad argument");
+        launch_iterate_scale(d_rhs_x, d_rhs_z, d_rx, d_rz, 1.0 - sigma, h->K.n, h->K.m, h->stream);
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_add_step(hipkkt_kkt_t h, double* d_x, double* d_s, double* d_z, const double* d_dx, const double* d_ds,
+                               const double* d_dz, double alpha)
+{
+    return guarded([&]() {
+        iterate_guard(h);
+        if ((h->K.n && (!d_x || !d_dx)) || (h->K.m && (!d_s || !d_z || !d_ds || !d_dz)))
+            throw ArgError("hipkkt_kkt_system_add_step: bad argument");
+        if ((d_x && d_x == d_dx) || (d_s && (d_s == d_ds || d_s == d_dz)) || (d_z && (d_z == d_dz || d_z == d_ds)) || (d_s && d_s == d_z))
+            throw ArgError("hipkkt_kkt_system_add_step: bad argument (a step must not alias the vector it is added to)");
+        launch_iterate_add_step(d_x, d_s, d_z, d_dx, d_ds, d_dz, alpha, h->K.n, h->K.m, h->stream);
         return HIPKKT_OK;
     });
 }

@@ -349,8 +349,7 @@ struct SpmvDev {
     const int64_t* chunk_q;      // nchunks + 1 would not do (rows are not adjacent): 2 per chunk, [begin, end)
     double* long_partial;        // nchunks per right-hand side
 };
-constexpr int kLongRow = 4096;
-constexpr int kLongChunk = 2048;
+// (kLongRow, kLongChunk: launch_shapes.hpp)
 // norm_out[j] = ||e_j||_inf (not finite if any entry is non-finite).  nrhs > 1: column j of b, x, e
 // at stride ld; `partial` then needs nrhs * (kNormParts + 1) doubles
 constexpr int kNormParts = 2048;   // partial needs nrhs * (kNormParts + 1) doubles
@@ -568,6 +567,39 @@ void launch_step_length(const ConeDev& C, const ConeState& S, const double* dz, 
 void launch_margins(const ConeDev& C, const double* v, double* partial, double* rec, const Publish& pub, int m, hipStream_t st);
 // scaled_unit_shift! over all cones: v += a1 e, then (two) += a2 e; a primal zero cone's rows are set to 0
 void launch_unit_shift(const ConeDev& C, double* v, double a1, double a2, bool two, bool primal, int m, hipStream_t st);
+
+// ---- residuals and termination scalars of a device-resident iterate (iterate_kernels.hip)
+// What the pass walks of the image besides SpmvDev: the end of each row's walked prefix and the long ones among those
+// prefixes (iterate_rows.hpp, computed on the host); long_partial: two doubles per chunk.
+struct IterDev {
+    const int64_t* rend;             // n + m
+    int nlong, nchunks;
+    const int* long_rows;
+    const int64_t* long_chunk_ptr;
+    const int64_t* chunk_q;
+    double* long_partial;
+};
+// d == null: the four equilibration vectors read as ones
+struct IterVecs {
+    const double *x, *s, *z, *q, *b;
+    double tau;
+    double *rx, *rz, *rx_inf, *rz_inf, *Px;
+    const double *d, *dinv, *e, *einv;
+};
+constexpr int kIterValues = 28;                      // four dot products, and three sums of squares for each of eight norms
+constexpr int kIterGridCap = 2048;                   // workgroups of 32 rows (grid-stride beyond)
+constexpr int kIterStride = kIterGridCap + 1;        // slots per value: one per workgroup and the long rows' one
+inline size_t iterate_partials() { return (size_t)kIterValues * kIterStride; }
+int iterate_grid(int n, int m);
+// rec[0..11] = {q.x, b.z, s.z, x.Px, |d x|, |e z|, |einv s|, |dinv rx_inf|, |dinv Px|, |einv rz_inf|, |einv rz|, |dinv rx|}
+// (2-norms), handed to the host through `pub` by the finishing kernel; A.val must be current (kkt_spmv)
+void launch_iterate_residuals(const SpmvDev& A, const IterDev& I, const IterVecs& V, int n, int m, double* partial, double* rec,
+                              const Publish& pub, hipStream_t st);
+// ox = f rx (n), oz = f rz (m) in one launch; outputs may alias inputs
+void launch_iterate_scale(double* ox, double* oz, const double* rx, const double* rz, double f, int n, int m, hipStream_t st);
+// x += alpha dx (n); s += alpha ds, z += alpha dz (m) in one launch
+void launch_iterate_add_step(double* x, double* s, double* z, const double* dx, const double* ds, const double* dz, double alpha,
+                             int n, int m, hipStream_t st);
 
 
 // ---- Ruiz equilibration of (P, A, q, b) (problemdata.jl:133-221, mathutils.jl:129-269), all vectors on the device

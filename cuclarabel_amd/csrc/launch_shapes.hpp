@@ -10,6 +10,11 @@ namespace hipkkt {
 // LDS a workgroup may ask for: a CU's 160 KB less what the runtime keeps
 constexpr size_t kLdsCap = 160 * 1024 - 512;
 
+// rows of the full-CSR image longer than kLongRow entries are cut into chunks of kLongChunk entries, one workgroup each
+// (kernels.hpp: SpmvDev; iterate_rows.hpp for the prefixes the iterate-residual kernel walks)
+constexpr int kLongRow = 4096;
+constexpr int kLongChunk = 2048;
+
 // one-wave fronts (a wave per front in the factorisation and the sweeps)
 constexpr int kSmallFrontMax = 64;         // f <= 64 ...
 constexpr int kSmallSliceMax = 1536;       // ... and f*nc + nb*nb <= this many doubles of LDS per wave

@@ -4,7 +4,8 @@
 with x, s, z, the steps, the right-hand sides and the residual vectors held as torch device tensors for the whole
 solve.  Level C of the C ABI does everything KKT-shaped (init, initial point, kkt_update!, the two kkt_solve!) and --
 through hipkkt_kkt_system_affine_ds / _combined_ds / _step_length / _shift_to_interior -- everything cone-shaped; torch
-does the plumbing between them (the residual mat-vecs with fp64 CSR tensors, dots, norms, axpy).  After
+does the plumbing between them (the residual mat-vecs with fp64 CSR tensors, dots, norms, axpy) -- or, with
+plumbing="device", the library does that too (hipkkt_kkt_system_residuals / _combined_rhs / _add_step).  After
 `system.init` nothing of length n or m crosses the bus until the final solution: per iteration only scalars do (one
 batch of dot products and norms, alpha twice, (dtau, dkappa) twice, the solves' status).
 
@@ -60,12 +61,19 @@ class _Csr:
         return y.index_add_(0, self.row, self.val * x[self.col])
 
 
-def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None):
+def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None, plumbing="torch"):
     """Clarabel.solve! restated with device-resident vectors -> IPMResult (numpy x, z, s).
 
     inspect (optional): called once per iteration with (dict of the tensors the loop holds, the HipSystemBackend) --
-    for tests that check residency."""
+    for tests that check residency.
+    plumbing: "torch" (the default) -- the residual mat-vecs, dots, norms and axpys between the library's calls are torch
+    expressions over fp64 CSR copies of P, A and A'; "device" -- they are the library's own
+    hipkkt_kkt_system_residuals / _combined_rhs / _add_step over the P, A the handle already holds: no second copy of the
+    matrices, and torch only allocates (and clones the previous iterate)."""
     import torch
+    if plumbing not in ("torch", "device"):
+        raise ValueError(f"plumbing must be 'torch' or 'device', got {plumbing!r}")
+    native = plumbing == "device"
     st = settings or IPMSettings()
     cone_specs = list(cone_specs)
     for c in cone_specs:
@@ -77,9 +85,8 @@ def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None):
     P = sp.csc_matrix(P)
     Pt = sp.triu(P, format="csc")
     Pfull_h = (Pt + sp.triu(Pt, 1).T).tocsr()
-    A_h = sp.csr_matrix(A)
     q, b = np.asarray(q, float), np.asarray(b, float)
-    n, m = Pfull_h.shape[0], A_h.shape[0]
+    n, m = Pfull_h.shape[0], sp.csc_matrix(A).shape[0]      # (Pfull_h: the objective of the final solution, on the host)
     degree = sum(c.dim if isinstance(c, (NonnegativeConeT, PSDTriangleConeT)) else 1 if isinstance(c, SecondOrderConeT) else 0
                  for c in cone_specs)
     normq = np.abs(q).max() if n else 0.0
@@ -89,7 +96,9 @@ def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None):
     ks, system = backend.ks, backend.system
     dev = system._devstr
     ks.set_stream(torch.cuda.current_stream(torch.device(dev)).cuda_stream)     # torch's kernels and the library's: one queue
-    Pfull, Ad, At = _Csr(Pfull_h, dev), _Csr(A_h, dev), _Csr(A_h.T, dev)
+    if not native:
+        A_h = sp.csr_matrix(A)
+        Pfull, Ad, At = _Csr(Pfull_h, dev), _Csr(A_h, dev), _Csr(A_h.T, dev)
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
     new = lambda k: torch.zeros(max(k, 1), dtype=torch.float64, device=dev)[:k]
     qd, bd = up(q), up(b)
@@ -100,6 +109,9 @@ def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None):
     x, s, z = new(n), new(m), new(m)
     dx, ds, dz = new(n), new(m), new(m)
     aff_s, rhs_s = new(m), new(m)
+    if native:
+        rx, rx_inf, Px, rhs_x = new(n), new(n), new(n), new(n)
+        rz, rz_inf, rhs_z = new(m), new(m), new(m)
     system.init(q, b)
     backend.update_identity()
     system.solve_constant_rhs()
@@ -116,13 +128,17 @@ def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None):
     nrm = torch.linalg.vector_norm
     while True:
         # ---- residuals (residuals.jl:1-37); the scalars in ONE read-back
-        Px = Pfull.mv(x)
-        rx_inf = -At.mv(z)
-        rz_inf = Ad.mv(x) + s
-        rx = rx_inf - Px - qd * tau
-        rz = rz_inf - bd * tau
-        qx, bz, sz, xPx, nx, nz, ns, n_rxi, n_Px, n_rzi, n_rz, n_rx = torch.stack(
-            [qd @ x, bd @ z, s @ z, x @ Px, nrm(x), nrm(z), nrm(s), nrm(rx_inf), nrm(Px), nrm(rz_inf), nrm(rz), nrm(rx)]).tolist()
+        if native:
+            qx, bz, sz, xPx, nx, nz, ns, n_rxi, n_Px, n_rzi, n_rz, n_rx = system.residuals_dev(
+                p(x), p(s), p(z), tau, p(rx), p(rz), p(rx_inf), p(rz_inf), p(Px)).tolist()
+        else:
+            Px = Pfull.mv(x)
+            rx_inf = -At.mv(z)
+            rz_inf = Ad.mv(x) + s
+            rx = rx_inf - Px - qd * tau
+            rz = rz_inf - bd * tau
+            qx, bz, sz, xPx, nx, nz, ns, n_rxi, n_Px, n_rzi, n_rz, n_rx = torch.stack(
+                [qd @ x, bd @ z, s @ z, x @ Px, nrm(x), nrm(z), nrm(s), nrm(rx_inf), nrm(Px), nrm(rz_inf), nrm(rz), nrm(rx)]).tolist()
         rtau = qx + bz + kappa + xPx / tau
         mu = (sz + tau * kappa) / (degree + 1)
         if inspect is not None:
@@ -178,7 +194,10 @@ def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None):
             sigma = (1 - alpha) ** 3
             mcorr = 1.0 if it > 1 else alpha
             system.combined_ds_dev(p(rhs_s), p(dz), p(ds), sigma * mu, mcorr)
-            rhs_x, rhs_z = (1 - sigma) * rx, (1 - sigma) * rz
+            if native:
+                system.combined_rhs_dev(p(rhs_x), p(rhs_z), p(rx), p(rz), sigma)
+            else:
+                rhs_x, rhs_z = (1 - sigma) * rx, (1 - sigma) * rz
             ok, dtau, dkappa = system.solve_dev((p(dx), p(ds), p(dz)), (p(rhs_x), p(rhs_s), p(rhs_z)), (1 - sigma) * rtau,
                                                 -sigma * mu + mcorr * dtau * dkappa + tau * kappa,
                                                 (p(x), p(s), p(z)), tau, kappa, False)
@@ -194,9 +213,12 @@ def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None):
             break
         prev = dict(res_p=res_p, res_d=res_d, gap_abs=gap_abs, gap_rel=gap_rel)
         prev_vars = (x.clone(), s.clone(), z.clone(), tau, kappa)
-        x.add_(dx, alpha=alpha)
-        s.add_(ds, alpha=alpha)
-        z.add_(dz, alpha=alpha)
+        if native:
+            system.add_step_dev(p(x), p(s), p(z), p(dx), p(ds), p(dz), alpha)
+        else:
+            x.add_(dx, alpha=alpha)
+            s.add_(ds, alpha=alpha)
+            z.add_(dz, alpha=alpha)
         tau += alpha * dtau
         kappa += alpha * dkappa
 
@@ -204,9 +226,13 @@ def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None):
     #      tolerances as ALMOST_SOLVED
     if status in (NUMERICAL_ERROR, INSUFFICIENT_PROGRESS, MAX_ITERATIONS):
         tinv = 1.0 / tau
-        Px = Pfull.mv(x)
-        qx, bz, xPx, nx, nz, ns, n_rz, n_rx = torch.stack(
-            [qd @ x, bd @ z, x @ Px, nrm(x), nrm(z), nrm(s), nrm(Ad.mv(x) + s - bd * tau), nrm(-At.mv(z) - Px - qd * tau)]).tolist()
+        if native:
+            o = system.residuals_dev(p(x), p(s), p(z), tau, p(rx), p(rz), p(rx_inf), p(rz_inf), p(Px))
+            qx, bz, xPx, nx, nz, ns, n_rz, n_rx = (float(o[i]) for i in (0, 1, 3, 4, 5, 6, 10, 11))
+        else:
+            Px = Pfull.mv(x)
+            qx, bz, xPx, nx, nz, ns, n_rz, n_rx = torch.stack(
+                [qd @ x, bd @ z, x @ Px, nrm(x), nrm(z), nrm(s), nrm(Ad.mv(x) + s - bd * tau), nrm(-At.mv(z) - Px - qd * tau)]).tolist()
         cp = qx * tinv + xPx * tinv * tinv / 2
         cd = -bz * tinv - xPx * tinv * tinv / 2
         nx, nz, ns = nx * tinv, nz * tinv, ns * tinv

@@ -383,6 +383,31 @@ class HipKKTSystem:
               "hipkkt_kkt_system_shift_to_interior")
         return float(out[0]), float(out[1])
 
+    # ---- residuals and termination scalars of a device-resident iterate, and the elementwise steps around them
+    def residuals_dev(self, d_x, d_s, d_z, tau, d_rx, d_rz, d_rx_inf, d_rz_inf, d_Px, d_equil=None):
+        """residuals_update! and the scalars info_update! reads, in one pass over K's image -> numpy array of 12:
+        q.x, b.z, s.z, x.Px, |d x|, |e z|, |einv s|, |dinv rx_inf|, |dinv Px|, |einv rz_inf|, |einv rz|, |dinv rx|.
+        d_equil: (d, dinv, e, einv) device pointers, or None for ones."""
+        out = np.zeros(12)
+        eq = (None,) * 4 if d_equil is None else tuple(d_equil)
+        check(_lib.lib().hipkkt_kkt_system_residuals(
+            self.ks._h, C.c_void_p(d_x), C.c_void_p(d_s), C.c_void_p(d_z), float(tau), C.c_void_p(d_rx), C.c_void_p(d_rz),
+            C.c_void_p(d_rx_inf), C.c_void_p(d_rz_inf), C.c_void_p(d_Px), C.c_void_p(eq[0]), C.c_void_p(eq[1]),
+            C.c_void_p(eq[2]), C.c_void_p(eq[3]), ptr(out)), "hipkkt_kkt_system_residuals")
+        return out
+
+    def combined_rhs_dev(self, d_rhs_x, d_rhs_z, d_rx, d_rz, sigma):
+        """rhs_x = (1 - sigma) rx, rhs_z = (1 - sigma) rz: the x and z parts of the combined right-hand side."""
+        return check(_lib.lib().hipkkt_kkt_system_combined_rhs(self.ks._h, C.c_void_p(d_rhs_x), C.c_void_p(d_rhs_z),
+                                                                C.c_void_p(d_rx), C.c_void_p(d_rz), float(sigma)),
+                     "hipkkt_kkt_system_combined_rhs")
+
+    def add_step_dev(self, d_x, d_s, d_z, d_dx, d_ds, d_dz, alpha):
+        """x += alpha dx, s += alpha ds, z += alpha dz (variables_add_step!) as one launch."""
+        return check(_lib.lib().hipkkt_kkt_system_add_step(self.ks._h, C.c_void_p(d_x), C.c_void_p(d_s), C.c_void_p(d_z),
+                                                            C.c_void_p(d_dx), C.c_void_p(d_ds), C.c_void_p(d_dz), float(alpha)),
+                     "hipkkt_kkt_system_add_step")
+
     def prepared(self, d_lhs, d_rhs, rhs_tau, rhs_kappa, d_var, var_tau, var_kappa):
         """(update, solve_affine, solve_combined) closures over pre-converted ctypes arguments for a caller that issues the
         same three calls on the same resident buffers every iteration (bench.py): the per-call argument marshalling of

@@ -320,6 +320,46 @@ int hipkkt_kkt_system_step_length(hipkkt_kkt_t h, const double *d_step_z, const 
  * margins_out (host, 2, may be NULL) receives (min_margin, pos_margin) as found BEFORE the shift.  Synchronises. */
 int hipkkt_kkt_system_shift_to_interior(hipkkt_kkt_t h, double *d_v, int primal, double *margins_out);
 
+/* The first step of every iteration on an iterate kept in HBM: residuals_update! (residuals.jl:1-37) and the scalars
+ * info_update! reads (the four dot products and the eight norm_scaled calls of info.jl:33-51), from the P, A the handle
+ * holds inside K and the q, b of hipkkt_kkt_system_init -- the caller needs no copy of the matrices and no sparse mat-vec
+ * of its own, and after hipkkt_kkt_update_P / _update_A the residuals are those of the new values (also in lazy mode
+ * with an update pending: the call simply queues on the handle's stream).  One pass over rows 0 .. n+m-1 of K:
+ *   Px = Symmetric(P) x     rx_inf = -A'z              rz_inf = A x + s
+ *   rx = rx_inf - Px - q tau                           rz = rz_inf - b tau
+ * d_x, d_rx, d_rx_inf, d_Px, d_d, d_dinv: device, length n; d_s, d_z, d_rz, d_rz_inf, d_e, d_einv: device, length m (a
+ * pointer of length 0 may be NULL).  out (host, 12):
+ *   q.x, b.z, s.z, x.Px, |d o x|, |e o z|, |einv o s|, |dinv o rx_inf|, |dinv o Px|, |einv o rz_inf|, |einv o rz|, |dinv o rx|
+ * (2-norms; x.Px and |.. rx| use the Px and rx that were stored).  The four equilibration vectors are ALL NULL (read as
+ * ones) or all given, anything else is HIPKKT_ERR_ARG; the scalar c and 1/tau are the caller's to apply, and
+ * r_tau = q.x + b.z + kappa + x.Px / tau its to form.  The norms survive the range norm_scaled survives
+ * (mathutils.jl:57-80): entries of 1e200 do not give inf, entries of 1e-200 do not give 0, a zero vector gives exactly 0;
+ * a non-finite entry gives a non-finite scalar.  Needs hipkkt_kkt_system_init and nothing else -- no cone scaling, no
+ * factorisation -- and works with every cone kind (the residuals do not depend on the cones; nothing behind a row's A
+ * entries is read).  The five outputs must not alias an input or each other (HIPKKT_ERR_ARG where the pointers are equal).
+ * A deferred-status handle is refused with HIPKKT_ERR_ARG, nothing enqueued, nothing written.  Synchronises: one
+ * read-back per call.  Reproducible bit for bit (fixed reduction layout, no floating-point atomics). */
+int hipkkt_kkt_system_residuals(hipkkt_kkt_t h, const double *d_x, const double *d_s, const double *d_z, double tau,
+                                double *d_rx, double *d_rz, double *d_rx_inf, double *d_rz_inf, double *d_Px,
+                                const double *d_d, const double *d_dinv, const double *d_e, const double *d_einv,
+                                double out[12]);
+
+/* The x and z parts of variables_combined_step_rhs! (variables.jl:124-162): rhs_x = (1 - sigma) rx (n),
+ * rhs_z = (1 - sigma) rz (m); the s part is hipkkt_kkt_system_combined_ds.  One launch on the handle's stream, no
+ * synchronisation.  Outputs may alias inputs.  A pointer to a vector of length 0 (n = 0 or m = 0) may be NULL, any other
+ * NULL is HIPKKT_ERR_ARG.  Needs hipkkt_kkt_system_init; refused on a deferred-status handle (HIPKKT_ERR_ARG, nothing
+ * enqueued). */
+int hipkkt_kkt_system_combined_rhs(hipkkt_kkt_t h, double *d_rhs_x, double *d_rhs_z, const double *d_rx,
+                                   const double *d_rz, double sigma);
+
+/* variables_add_step! (variables.jl:107-122) for the vector part: x += alpha dx (n), s += alpha ds, z += alpha dz (m),
+ * each element fl(v + fl(alpha d)), as one launch on the handle's stream, no synchronisation (tau and kappa are the
+ * caller's scalars).  A step must not alias the vector it is added to, and d_s must not be d_z (HIPKKT_ERR_ARG where the
+ * pointers are equal).  A pointer to a vector of length 0 may be NULL, any other NULL is HIPKKT_ERR_ARG.  Needs
+ * hipkkt_kkt_system_init; refused on a deferred-status handle (HIPKKT_ERR_ARG, nothing enqueued). */
+int hipkkt_kkt_system_add_step(hipkkt_kkt_t h, double *d_x, double *d_s, double *d_z, const double *d_dx,
+                               const double *d_ds, const double *d_dz, double alpha);
+
 /* Lazy constant-RHS solve: the same pairing reached through the reference's own TWO calls, so that solver.jl:278-295
  * stays as it is.  With lazy = 1, kkt_update! (hipkkt_kkt_system_update / _update_cones) scales, scatters and
  * refactors, returns the factorisation's status and only NOTES that (x2, z2) = K \ (-q, b) is due
