@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <cfloat>
 #include <chrono>
+#include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -2007,6 +2008,7 @@ struct hipkkt_kkt_s {
     DBuf<double> lam;                                        // scaled point, m
     DBuf<double> sq, snegq, sb, sx2, sz2, sworkx, sworkz, sconic, spa, spb, spc;
     DBuf<double> sys_partial, sys_dots, sys_cached, sys_in;
+    DBuf<double> ns_partial;                                 // ... of the *_ns entry points and the barrier (2 * barrier_partials)
     DBuf<double> step_partial, step_rec;                     // step length / margins: partial slots and the result record (12 doubles)
     bool sys_ready = false;
     bool sys_lazy = false;           // hipkkt_kkt_system_set_lazy: kkt_update! leaves (x2, z2) = K \ (-q, b) to the affine kkt_solve!
@@ -3726,12 +3728,14 @@ int hipkkt_kkt_system_solve(hipkkt_kkt_t h, double* d_lhs_x, double* d_lhs_s, do
 
 // ---- the cone operations between the solves (step_kernels.hip): affine_ds!, the combined step's d.s, step_length,
 // _shift_to_cone_interior! on the caller's device vectors
-static void step_guard(hipkkt_kkt_t h, const char* who, bool need_scaling)
+static void step_guard(hipkkt_kkt_t h, const char* who, bool need_scaling, bool nonsym_entry = false)
 {
     if (!h) throw ArgError("null handle");
     if (!h->sys_ready) throw ArgError("hipkkt_kkt_system_*: call hipkkt_kkt_system_init first");
     if (h->deferred) throw ArgError("hipkkt_kkt_system_*: level C reads its scalars back (deferred status is for level B)");
-    if (h->K.nnonsym > 0 || h->K.ngenpow > 0)
+    if (nonsym_entry && h->K.ngenpow > 0)
+        throw ArgError(std::string(who) + ": generalized power cones are not covered");
+    if (!nonsym_entry && (h->K.nnonsym > 0 || h->K.ngenpow > 0))
         throw ArgError(std::string(who) + ": symmetric cones only (the handle holds an exponential, power or generalized power cone)");
     if (h->psd_too_big) throw ArgError(std::string(who) + ": PSD cones with side > 48 are not covered");
     if (need_scaling && !h->scaling_valid)
@@ -3739,6 +3743,7 @@ static void step_guard(hipkkt_kkt_t h, const char* who, bool need_scaling)
     HIP_CHECK(hipSetDevice(h->device));
     if (!h->step_partial.p) h->step_partial.alloc((size_t)2 * step_partials(h->cone_dev()));
     if (!h->step_rec.p) h->step_rec.alloc(12);        // (shared with hipkkt_kkt_system_residuals' twelve scalars)
+    if (nonsym_entry && !h->ns_partial.p) h->ns_partial.alloc((size_t)2 * barrier_partials(h->cone_dev()));
 }
 
 // the record of a finishing kernel (nrec doubles) on the host: published by that kernel into the pinned block and
@@ -3819,6 +3824,82 @@ int hipkkt_kkt_system_shift_to_interior(hipkkt_kkt_t h, double* d_v, int primal,
         else if (min_margin < target) launch_unit_shift(C, d_v, target - min_margin, 0.0, false, primal == 1, h->K.m, h->stream);
         else launch_unit_shift(C, d_v, 0.0, 0.0, false, primal == 1, h->K.m, h->stream);
         HIP_CHECK(hipStreamSynchronize(h->stream));
+        return HIPKKT_OK;
+    });
+}
+
+// ---- the same for cone lists that hold exponential / power cones, and the two operations only such lists need (the
+// unit start and the barrier of the dual-scaling line search).  New entry points: the four above keep refusing such handles.
+int hipkkt_kkt_system_unit_initialization(hipkkt_kkt_t h, double* d_s, double* d_z)
+{
+    return guarded([&]() {
+        step_guard(h, "hipkkt_kkt_system_unit_initialization", false, true);
+        if (h->K.m && (!d_s || !d_z || d_s == d_z)) throw ArgError("hipkkt_kkt_system_unit_initialization: bad argument");
+        launch_unit_initialization(h->cone_dev(), d_s, d_z, h->K.m, h->stream);
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_affine_ds_ns(hipkkt_kkt_t h, double* d_out, const double* d_s)
+{
+    return guarded([&]() {
+        step_guard(h, "hipkkt_kkt_system_affine_ds_ns", true, true);
+        if (h->K.m && (!d_out || !d_s || d_out == d_s))
+            throw ArgError("hipkkt_kkt_system_affine_ds_ns: bad argument (d_out must not alias an input)");
+        launch_step_ds_ns(h->cone_dev(), h->cone_state(), d_out, nullptr, nullptr, d_s, nullptr, 0.0, 0.0, h->K.m, false, h->stream);
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_combined_ds_ns(hipkkt_kkt_t h, double* d_out, const double* d_step_z, const double* d_step_s,
+                                     const double* d_s, const double* d_z, double sigma_mu, double m_corr)
+{
+    return guarded([&]() {
+        step_guard(h, "hipkkt_kkt_system_combined_ds_ns", true, true);
+        if (h->K.m && (!d_out || !d_step_z || !d_step_s || !d_s || !d_z || d_out == d_step_z || d_out == d_step_s || d_out == d_s ||
+                       d_out == d_z))
+            throw ArgError("hipkkt_kkt_system_combined_ds_ns: bad argument (d_out must not alias an input)");
+        launch_step_ds_ns(h->cone_dev(), h->cone_state(), d_out, d_step_z, d_step_s, d_s, d_z, sigma_mu, m_corr, h->K.m, true,
+                          h->stream);
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_step_length_ns(hipkkt_kkt_t h, const double* d_step_z, const double* d_step_s, const double* d_z,
+                                     const double* d_s, double step_tau, double step_kappa, double tau, double kappa,
+                                     double backtrack_step, double alpha_min, double* alpha_out)
+{
+    return guarded([&]() {
+        step_guard(h, "hipkkt_kkt_system_step_length_ns", true, true);
+        if ((h->K.m && (!d_step_z || !d_step_s || !d_z || !d_s)) || !alpha_out)
+            throw ArgError("hipkkt_kkt_system_step_length_ns: bad argument");
+        if (!(backtrack_step > 0.0 && backtrack_step < 1.0) || !(alpha_min > 0.0))
+            throw ArgError("hipkkt_kkt_system_step_length_ns: backtrack_step must lie in (0, 1) and alpha_min be positive");
+        // the search starts at a0 <= 1 - sqrt(eps) and visits a0 step^j while that is >= alpha_min: at most
+        // floor(log(alpha_min) / log(step)) + 1 points; one more trip absorbs the rounding of the two logarithms
+        const double trips = std::log(alpha_min) / std::log(backtrack_step);
+        const int cap = !(trips > 0.0) ? 2 : trips >= 2.0e9 ? INT_MAX : (int)trips + 2;
+        const double* rec = step_read_record(h, 1, [&](const Publish& pub) {
+            launch_step_length_ns(h->cone_dev(), h->cone_state(), d_step_z, d_step_s, d_z, d_s, step_tau, step_kappa, tau, kappa,
+                                  backtrack_step, alpha_min, cap, h->step_partial.p, h->ns_partial.p, h->step_rec.p, pub, h->K.m,
+                                  h->stream);
+        });
+        *alpha_out = rec[0];
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_barrier(hipkkt_kkt_t h, const double* d_z, const double* d_s, const double* d_step_z,
+                              const double* d_step_s, double alpha, double out[2])
+{
+    return guarded([&]() {
+        step_guard(h, "hipkkt_kkt_system_barrier", true, true);
+        if ((h->K.m && (!d_z || !d_s || !d_step_z || !d_step_s)) || !out) throw ArgError("hipkkt_kkt_system_barrier: bad argument");
+        const double* rec = step_read_record(h, 2, [&](const Publish& pub) {
+            launch_barrier(h->cone_dev(), d_z, d_s, d_step_z, d_step_s, alpha, h->ns_partial.p, h->step_rec.p, pub, h->K.m, h->stream);
+        });
+        out[0] = rec[0];
+        out[1] = rec[1];
         return HIPKKT_OK;
     });
 }

@@ -568,6 +568,26 @@ void launch_margins(const ConeDev& C, const double* v, double* partial, double* 
 // scaled_unit_shift! over all cones: v += a1 e, then (two) += a2 e; a primal zero cone's rows are set to 0
 void launch_unit_shift(const ConeDev& C, double* v, double a1, double a2, bool two, bool primal, int m, hipStream_t st);
 
+// ---- the same for handles that also hold exponential / power cones (three rows each; one lane per cone through
+// exp_list / pow_list): the symmetric rows by the kernels above, unchanged
+// slots of the barrier partials: elementwise workgroups, second-order cones, PSD cones, workgroups of the lane-per-cone part
+inline int barrier_partials(const ConeDev& C) { return 2 * kStepGridCap + C.nsoc + C.npsd; }
+// unit_initialization! of every cone (solver.jl:383-404, the asymmetric start) into s and z: one launch
+void launch_unit_initialization(const ConeDev& C, double* s, double* z, int m, hipStream_t st);
+// launch_step_ds, then the exponential / power rows: a copy of s, and with `combined`
+//       s + sigma_mu grad f*(z) - eta(step_s, m_corr step_z); z: the point the scaling was computed from
+void launch_step_ds_ns(const ConeDev& C, const ConeState& S, double* out, const double* step_z, const double* step_s,
+                       const double* s, const double* z, double sigma_mu, double m_corr, int m, bool combined, hipStream_t st);
+// launch_step_length (its record stays on the device), min(., 1 - sqrt(eps)), then every exponential / power cone's
+// backtrack_search from that common start; ns_partial: kStepGridCap doubles
+void launch_step_length_ns(const ConeDev& C, const ConeState& S, const double* dz, const double* ds, const double* z,
+                           const double* s, double step_tau, double step_kappa, double tau, double kappa, double backtrack_step,
+                           double alpha_min, int trip_cap, double* partial, double* ns_partial, double* rec, const Publish& pub,
+                           int m, hipStream_t st);
+// rec[0..1] = (sum of compute_barrier over the cones, <z + alpha dz, s + alpha ds>); partial: 2 * barrier_partials(C) doubles
+void launch_barrier(const ConeDev& C, const double* z, const double* s, const double* dz, const double* ds, double alpha,
+                    double* partial, double* rec, const Publish& pub, int m, hipStream_t st);
+
 // ---- residuals and termination scalars of a device-resident iterate (iterate_kernels.hip)
 // What the pass walks of the image besides SpmvDev: the end of each row's walked prefix and the long ones among those
 // prefixes (iterate_rows.hpp, computed on the host); long_partial: two doubles per chunk.

@@ -7,9 +7,13 @@
 // workgroup per PSD cone with its matrices in LDS.  Compiled without FMA contraction: the exact-zero branches of the
 // second-order step length are tested on products and differences formed as the reference forms them.
 //
+// The exponential and the power cone (three rows each) ride behind them for handles that hold one: one lane per cone
+// through the handle's lists of such cones, see "exponential and power cones between the solves" below.
+//
 // Every reduction has a fixed layout (a slot per workgroup / wave / cone in a partials array, folded by one workgroup in
 // a fixed order) and there is no floating-point atomic: the same call on the same data gives the same bits.
 #include "kernels.hpp"
+#include "nonsym_cone.hpp"
 #include <cfloat>
 #include <cmath>
 
@@ -517,6 +521,379 @@ __global__ __launch_bounds__(256) void k_unit_shift(ConeDev C, double* __restric
     }
 }
 
+// =====================================================================================================================
+//  Exponential and power cones between the solves (coneops_nonsymmetric_common.jl, coneops_expcone.jl,
+//  coneops_powcone.jl).  One LANE per cone: lane j takes the handle's j-th exponential cone, lanes from nexp on its
+//  power cones, so that neighbouring lanes run the same branch; a cone is three rows and a few dozen to a few hundred
+//  scalar fp64 operations (log / exp / pow cost ~100 instructions each and dominate; there is nothing to share between
+//  lanes).  Lanes that backtrack or iterate different numbers of times diverge.  Per-workgroup minima and sums go to
+//  slots that one workgroup folds in a fixed order.
+// =====================================================================================================================
+constexpr double kSqrtEps = 1.4901161193847656e-08;                    // sqrt(eps(Float64)) = 2^-26
+
+__device__ inline int ns_lane_cone(const ConeDev& C, int j, bool& is_pow)
+{
+    is_pow = j >= C.nexp;
+    return is_pow ? C.pow_list[j - C.nexp] : C.exp_list[j];
+}
+
+// cholesky_3x3_explicit_factor! (mathutils.jl:427-451) of a row-major symmetric A; L = (l00, l10, l11, l20, l21, l22)
+__device__ inline bool ns_chol3_factor(const double* A, double* L)
+{
+    double t = A[0];
+    if (!(t > 0.0)) return false;
+    L[0] = sqrt(t);
+    L[1] = A[3] / L[0];
+    t = A[4] - L[1] * L[1];
+    if (!(t > 0.0)) return false;
+    L[2] = sqrt(t);
+    L[3] = A[6] / L[0];
+    L[4] = (A[7] - L[1] * L[3]) / L[2];
+    t = A[8] - L[3] * L[3] - L[4] * L[4];
+    if (!(t > 0.0)) return false;
+    L[5] = sqrt(t);
+    return true;
+}
+
+// cholesky_3x3_explicit_solve! (mathutils.jl:455-466)
+__device__ inline void ns_chol3_solve(const double* L, const double* b, double* x)
+{
+    const double l00 = L[0], l10 = L[1], l11 = L[2], l20 = L[3], l21 = L[4], l22 = L[5];
+    const double c1 = b[0] / l00;
+    const double c2 = (b[1] * l00 - b[0] * l10) / (l00 * l11);
+    const double c3 = (b[2] * l00 * l11 - b[1] * l00 * l21 + b[0] * l10 * l21 - b[0] * l11 * l20) / (l00 * l11 * l22);
+    x[0] = (c1 * l11 * l22 - c2 * l10 * l22 + c3 * l10 * l21 - c3 * l11 * l20) / (l00 * l11 * l22);
+    x[1] = (c2 * l22 - c3 * l21) / (l11 * l22);
+    x[2] = c3 / l22;
+}
+
+// higher_correction! of the exponential cone (coneops_expcone.jl:319-366): eta = +1/2 D^3 f*(z)[u, v], u = H*^{-1} ds, which
+// combined_ds_shift! subtracts
+__device__ inline void ns_exp_higher_correction(const double* z, const double* u, const double* v, double* eta)
+{
+    eta[1] = 1.0;
+    eta[2] = -z[0] / z[2];
+    eta[0] = ns_logsafe(eta[2]);
+    const double psi = z[0] * eta[0] - z[0] + z[1];
+    const double dpu = eta[0] * u[0] + eta[1] * u[1] + eta[2] * u[2];
+    const double dpv = eta[0] * v[0] + eta[1] * v[1] + eta[2] * v[2];
+    const double coef = ((u[0] * (v[0] / z[0] - v[2] / z[2]) + u[2] * (z[0] * v[2] / z[2] - v[0]) / z[2]) * psi - 2.0 * dpu * dpv)
+                        / (psi * psi * psi);
+    for (int i = 0; i < 3; ++i) eta[i] *= coef;
+    const double ip2 = 1.0 / psi / psi;
+    eta[0] += (1.0 / psi - 2.0 / z[0]) * u[0] * v[0] / (z[0] * z[0]) - u[2] * v[2] / (z[2] * z[2]) / psi
+              + dpu * ip2 * (v[0] / z[0] - v[2] / z[2]) + dpv * ip2 * (u[0] / z[0] - u[2] / z[2]);
+    eta[2] += 2.0 * (z[0] / psi - 1.0) * u[2] * v[2] / (z[2] * z[2] * z[2]) - (u[2] * v[0] + u[0] * v[2]) / (z[2] * z[2]) / psi
+              + dpu * ip2 * (z[0] * v[2] / (z[2] * z[2]) - v[0] / z[2]) + dpv * ip2 * (z[0] * u[2] / (z[2] * z[2]) - u[0] / z[2]);
+    for (int i = 0; i < 3; ++i) eta[i] /= 2.0;
+}
+
+// ... of the power cone (coneops_powcone.jl:329-404)
+__device__ inline void ns_pow_higher_correction(const double* z, double a, const double* u, const double* v, double* out)
+{
+    const double phi = pow(z[0] / a, 2.0 * a) * pow(z[1] / (1.0 - a), 2.0 - 2.0 * a);
+    const double psi = phi - z[2] * z[2];
+    const double eta[3] = {2.0 * a * phi / z[0], 2.0 * (1.0 - a) * phi / z[1], -2.0 * z[2]};
+    const double H11 = 2.0 * a * (2.0 * a - 1.0) * phi / (z[0] * z[0]);
+    const double H12 = 4.0 * a * (1.0 - a) * phi / (z[0] * z[1]);
+    const double H22 = 2.0 * (1.0 - a) * (1.0 - 2.0 * a) * phi / (z[1] * z[1]);
+    const double dpu = eta[0] * u[0] + eta[1] * u[1] + eta[2] * u[2];
+    const double dpv = eta[0] * v[0] + eta[1] * v[1] + eta[2] * v[2];
+    const double Hv[3] = {H11 * v[0] + H12 * v[1], H12 * v[0] + H22 * v[1], -2.0 * v[2]};
+    const double coef = ((u[0] * Hv[0] + u[1] * Hv[1] + u[2] * Hv[2]) * psi - 2.0 * dpu * dpv) / (psi * psi * psi);
+    const double coef2 = 4.0 * a * (2.0 * a - 1.0) * (1.0 - a) * phi * (u[0] / z[0] - u[1] / z[1]) * (v[0] / z[0] - v[1] / z[1]) / psi;
+    const double ip2 = 1.0 / psi / psi;
+    const double e0 = coef * eta[0] - 2.0 * (1.0 - a) * u[0] * v[0] / (z[0] * z[0] * z[0]) + coef2 / z[0] + Hv[0] * dpu * ip2;
+    const double e1 = coef * eta[1] - 2.0 * a * u[1] * v[1] / (z[1] * z[1] * z[1]) - coef2 / z[1] + Hv[1] * dpu * ip2;
+    const double e2 = coef * eta[2] + Hv[2] * dpu * ip2;
+    const double Hu[3] = {H11 * u[0] + H12 * u[1], H12 * u[0] + H22 * u[1], -2.0 * u[2]};
+    out[0] = (e0 + Hu[0] * dpv * ip2) / 2.0;
+    out[1] = (e1 + Hu[1] * dpv * ip2) / 2.0;
+    out[2] = (e2 + Hu[2] * dpv * ip2) / 2.0;
+}
+
+// affine_ds! (coneops_expcone.jl:117-127, coneops_powcone.jl:120-130: a copy of s) and, with `combined`, the cone's d.s of the combined step:
+// s + sigma_mu grad f*(z) - eta(step_s, m_corr step_z), grad and H*(z) as the scaling kernel stored them; eta = 0 where
+// the 3 x 3 factorisation fails
+__global__ __launch_bounds__(256) void k_ns_ds(ConeDev C, ConeState S, double* __restrict__ out, const double* __restrict__ dz,
+                                               const double* __restrict__ ds, const double* __restrict__ s,
+                                               const double* __restrict__ z, double sigma_mu, double m_corr, int combined)
+{
+    const int nns = C.nexp + C.npow;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < nns; j += gridDim.x * 256) {
+        bool is_pow;
+        const int c = ns_lane_cone(C, j, is_pow);
+        const int off = C.off[c];
+        const double sv[3] = {s[off], s[off + 1], s[off + 2]};
+        if (!combined) {
+            for (int i = 0; i < 3; ++i) out[off + i] = sv[i];
+            continue;
+        }
+        const int k = C.ns_index[c];
+        const double* grad = S.ns_grad + 3 * k;
+        double H[9], L[6], eta[3] = {0.0, 0.0, 0.0};
+        for (int i = 0; i < 9; ++i) H[i] = S.ns_H[9 * k + i];
+        if (ns_chol3_factor(H, L)) {
+            const double zv[3] = {z[off], z[off + 1], z[off + 2]};
+            const double dsv[3] = {ds[off], ds[off + 1], ds[off + 2]};
+            const double v[3] = {m_corr * dz[off], m_corr * dz[off + 1], m_corr * dz[off + 2]};
+            double u[3];
+            ns_chol3_solve(L, dsv, u);
+            if (is_pow) ns_pow_higher_correction(zv, C.param[c], u, v, eta);
+            else ns_exp_higher_correction(zv, u, v, eta);
+        }
+        for (int i = 0; i < 3; ++i) out[off + i] = sv[i] + (grad[i] * sigma_mu - eta[i]);
+    }
+}
+
+// is_primal_feasible / is_dual_feasible (coneops_expcone.jl:253-281, coneops_powcone.jl:256-286); a NaN point fails
+// every comparison: it is not in the cone
+__device__ inline bool ns_exp_primal_feasible(const double* s)
+{
+    return s[2] > 0.0 && s[1] > 0.0 && s[1] * ns_logsafe(s[2] / s[1]) - s[0] > 0.0;
+}
+__device__ inline bool ns_exp_dual_feasible(const double* z)
+{
+    return z[2] > 0.0 && z[0] < 0.0 && z[1] - z[0] - z[0] * ns_logsafe(-z[2] / z[0]) > 0.0;
+}
+__device__ inline bool ns_pow_primal_feasible(const double* s, double a)
+{
+    return s[0] > 0.0 && s[1] > 0.0 && exp(2.0 * a * ns_logsafe(s[0]) + 2.0 * (1.0 - a) * ns_logsafe(s[1])) - s[2] * s[2] > 0.0;
+}
+__device__ inline bool ns_pow_dual_feasible(const double* z, double a)
+{
+    return z[0] > 0.0 && z[1] > 0.0
+           && exp(2.0 * a * ns_logsafe(z[0] / a) + 2.0 * (1.0 - a) * ns_logsafe(z[1] / (1.0 - a))) - z[2] * z[2] > 0.0;
+}
+
+// backtrack_search (coneops_nonsymmetric_common.jl:5-34) from alpha = a: the values visited are a step^j by repeated
+// multiplication.  `cap` bounds the trips whatever the input (a NaN alpha never drops below alpha_min): the result is then 0.
+template <class F>
+__device__ inline double ns_backtrack(const double* q, const double* dq, double a, double amin, double step, int cap, F in_cone)
+{
+    for (int trip = 0; trip < cap; ++trip) {
+        const double p[3] = {q[0] + a * dq[0], q[1] + a * dq[1], q[2] + a * dq[2]};
+        if (in_cone(p)) return a;
+        a *= step;
+        if (a < amin) return 0.0;
+    }
+    return 0.0;
+}
+
+// Stage 2 and 3 of the composite step length (coneops_compositecone.jl:205-243): every cone backtracks on z and on s
+// from the common start a0 = min(rec[0], 1 - sqrt(eps)), rec[0] being what k_step_length_finish left on the device.
+__global__ __launch_bounds__(256) void k_ns_step_length(ConeDev C, const double* __restrict__ dz, const double* __restrict__ ds,
+                                                        const double* __restrict__ z, const double* __restrict__ s,
+                                                        const double* __restrict__ rec, double step, double amin, int cap,
+                                                        double* __restrict__ partial)
+{
+    __shared__ double sh[256];
+    const double a0 = fmin(rec[0], 1.0 - kSqrtEps);
+    const int nns = C.nexp + C.npow;
+    double amine = a0;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < nns; j += gridDim.x * 256) {
+        bool is_pow;
+        const int c = ns_lane_cone(C, j, is_pow);
+        const int off = C.off[c];
+        const double zv[3] = {z[off], z[off + 1], z[off + 2]}, dzv[3] = {dz[off], dz[off + 1], dz[off + 2]};
+        const double sv[3] = {s[off], s[off + 1], s[off + 2]}, dsv[3] = {ds[off], ds[off + 1], ds[off + 2]};
+        double az, as;
+        if (is_pow) {
+            const double a = C.param[c];
+            az = ns_backtrack(zv, dzv, a0, amin, step, cap, [a](const double* p) { return ns_pow_dual_feasible(p, a); });
+            as = ns_backtrack(sv, dsv, a0, amin, step, cap, [a](const double* p) { return ns_pow_primal_feasible(p, a); });
+        } else {
+            az = ns_backtrack(zv, dzv, a0, amin, step, cap, [](const double* p) { return ns_exp_dual_feasible(p); });
+            as = ns_backtrack(sv, dsv, a0, amin, step, cap, [](const double* p) { return ns_exp_primal_feasible(p); });
+        }
+        amine = fmin(amine, fmin(az, as));
+    }
+    amine = block_reduce_256(amine, sh, OpMin{});
+    if (threadIdx.x == 0) partial[blockIdx.x] = amine;
+}
+
+__global__ __launch_bounds__(256) void k_ns_step_length_finish(const double* __restrict__ partial, int np, double* __restrict__ rec,
+                                                               Publish P)
+{
+    __shared__ double sh[256];
+    double v = DBL_MAX;
+    for (int i = threadIdx.x; i < np; i += 256) v = fmin(v, partial[i]);
+    v = block_reduce_256(v, sh, OpMin{});
+    if (threadIdx.x == 0) {
+        rec[0] = fmin(fmin(rec[0], 1.0 - kSqrtEps), v);
+        if (P.dst) st_publish(P);
+    }
+}
+
+// ---- compute_barrier at (z + alpha dz, s + alpha ds)
+// barrier_dual + barrier_primal (coneops_expcone.jl:189-251, coneops_powcone.jl:193-254)
+__device__ inline double ns_exp_barrier(const double* z, const double* s)
+{
+    const double l = ns_logsafe(-z[2] / z[0]);
+    const double dual = -ns_logsafe(-z[2] * z[0]) - ns_logsafe(z[1] - z[0] - z[0] * l);
+    double w = ns_wright_omega(1.0 - s[0] / s[1] - ns_logsafe(s[1] / s[2]));
+    w = (w - 1.0) * (w - 1.0) / w;
+    const double primal = -ns_logsafe(w) - 2.0 * ns_logsafe(s[1]) - ns_logsafe(s[2]) - 3.0;
+    return dual + primal;
+}
+__device__ inline double ns_pow_barrier(const double* z, const double* s, double a)
+{
+    const double dual = -ns_logsafe(pow(z[0] / a, 2.0 * a) * pow(z[1] / (1.0 - a), 2.0 - 2.0 * a) - z[2] * z[2])
+                        - (1.0 - a) * ns_logsafe(z[0]) - a * ns_logsafe(z[1]);
+    double g[3];
+    ns_pow_gradient_primal(s, a, g);
+    const double primal = ns_logsafe(pow(-g[0] / a, 2.0 * a) * pow(-g[1] / (1.0 - a), 2.0 - 2.0 * a) - g[2] * g[2])
+                          + (1.0 - a) * ns_logsafe(-g[0]) + a * ns_logsafe(-g[1]) - 3.0;
+    return dual + primal;
+}
+
+// Workgroups below ge: <z + alpha dz, s + alpha ds> over ALL rows and the nonnegative cones' barrier
+// (coneops_nncone.jl:172-189); behind them one wave per second-order cone (coneops_socone.jl:287-305).
+__global__ __launch_bounds__(256) void k_barrier(ConeDev C, const double* __restrict__ z, const double* __restrict__ s,
+                                                 const double* __restrict__ dz, const double* __restrict__ ds, double alpha, int m,
+                                                 double* __restrict__ pbar, double* __restrict__ pdot, int ge)
+{
+    __shared__ double sh[256];
+    const int bx = blockIdx.x;
+    if (bx < ge) {
+        double bar = 0.0, dot = 0.0;
+        for (int i = bx * 256 + threadIdx.x; i < m; i += ge * 256) {
+            const double zi = z[i] + alpha * dz[i], si = s[i] + alpha * ds[i];
+            dot += zi * si;
+            if (C.kind[C.elem_cone[i]] == 1) bar -= ns_logsafe(si * zi);
+        }
+        bar = block_reduce_256(bar, sh, OpSum{});
+        dot = block_reduce_256(dot, sh, OpSum{});
+        if (threadIdx.x == 0) { pbar[bx] = bar; pdot[bx] = dot; }
+        return;
+    }
+    const int ci = (bx - ge) * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (ci >= C.nsoc) return;
+    const int c = C.soc_list[ci];
+    const int off = C.off[c], n = C.numel[c];
+    double sq_s = 0.0, sq_z = 0.0;
+    for (int i = 1 + lane; i < n; i += 64) {
+        const double zi = z[off + i] + alpha * dz[off + i], si = s[off + i] + alpha * ds[off + i];
+        sq_z += zi * zi;
+        sq_s += si * si;
+    }
+    sq_z = sqrt(st_wave_sum(sq_z));
+    sq_s = sqrt(st_wave_sum(sq_s));
+    if (lane == 0) {
+        const double z0 = z[off] + alpha * dz[off], s0 = s[off] + alpha * ds[off];
+        const double rz = (z0 - sq_z) * (z0 + sq_z), rs = (s0 - sq_s) * (s0 + sq_s);        // _soc_residual, :415-419
+        pbar[ge + ci] = (rs > 0.0 && rz > 0.0) ? -ns_logsafe(rs * rz) / 2.0 : HUGE_VAL;
+    }
+}
+
+// PSD cones (coneops_psdtrianglecone.jl:256-295): -logdet of mat(z + alpha dz) and of mat(s + alpha ds) by a right-looking
+// Cholesky factorisation in LDS (k x k doubles), +inf where one fails
+__global__ __launch_bounds__(256) void k_barrier_psd(ConeDev C, const double* __restrict__ z, const double* __restrict__ s,
+                                                     const double* __restrict__ dz, const double* __restrict__ ds, double alpha,
+                                                     double* __restrict__ slots)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    __shared__ int sh_fail;
+    const int tid = threadIdx.x;
+    const int c = C.psd_list[blockIdx.x];
+    const int k = C.psd_dim[c], off = C.off[c], t = k * (k + 1) / 2;
+    if (k == 0) { if (tid == 0) slots[blockIdx.x] = 0.0; return; }
+    double* X = smem;
+    if (tid == 0) sh_fail = 0;
+    double bar = 0.0;                                                  // (thread 0's)
+    for (int comp = 0; comp < 2; ++comp) {
+        const double* x = (comp == 0 ? z : s) + off;
+        const double* dx = (comp == 0 ? dz : ds) + off;
+        for (int idx = tid; idx < t; idx += 256) {
+            int r, cl;
+            st_svec_index(idx, r, cl);
+            const double v = (x[idx] + alpha * dx[idx]) * (r == cl ? 1.0 : kIs2);
+            X[r + cl * k] = v;
+            X[cl + r * k] = v;
+        }
+        __syncthreads();
+        for (int j = 0; j < k; ++j) {
+            const double d = X[j + j * k];
+            if (!(d > 0.0)) { if (tid == 0) sh_fail = 1; }
+            __syncthreads();
+            if (sh_fail) break;
+            const double sd = sqrt(d);
+            for (int i = j + 1 + tid; i < k; i += 256) X[i + j * k] /= sd;
+            if (tid == 0) { X[j + j * k] = sd; bar -= 2.0 * log(sd); }
+            __syncthreads();
+            const int w = k - j - 1;
+            for (int idx = tid; idx < w * w; idx += 256) {
+                const int a = j + 1 + idx / w, b = j + 1 + idx % w;
+                if (a >= b) X[a + b * k] -= X[a + j * k] * X[b + j * k];
+            }
+            __syncthreads();
+        }
+        if (sh_fail) break;
+    }
+    if (tid == 0) slots[blockIdx.x] = sh_fail ? HUGE_VAL : bar;
+}
+
+__global__ __launch_bounds__(256) void k_barrier_ns(ConeDev C, const double* __restrict__ z, const double* __restrict__ s,
+                                                    const double* __restrict__ dz, const double* __restrict__ ds, double alpha,
+                                                    double* __restrict__ slots)
+{
+    __shared__ double sh[256];
+    const int nns = C.nexp + C.npow;
+    double bar = 0.0;
+    for (int j = blockIdx.x * 256 + threadIdx.x; j < nns; j += gridDim.x * 256) {
+        bool is_pow;
+        const int c = ns_lane_cone(C, j, is_pow);
+        const int off = C.off[c];
+        const double zv[3] = {z[off] + alpha * dz[off], z[off + 1] + alpha * dz[off + 1], z[off + 2] + alpha * dz[off + 2]};
+        const double sv[3] = {s[off] + alpha * ds[off], s[off + 1] + alpha * ds[off + 1], s[off + 2] + alpha * ds[off + 2]};
+        bar += is_pow ? ns_pow_barrier(zv, sv, C.param[c]) : ns_exp_barrier(zv, sv);
+    }
+    bar = block_reduce_256(bar, sh, OpSum{});
+    if (threadIdx.x == 0) slots[blockIdx.x] = bar;
+}
+
+// rec = (sum of the nbar barrier slots, sum of the first ndot dot-product slots), each lane its strided slots in ascending
+// order, then the fixed tree
+__global__ __launch_bounds__(256) void k_barrier_finish(const double* __restrict__ pbar, int nbar, const double* __restrict__ pdot,
+                                                        int ndot, double* __restrict__ rec, Publish P)
+{
+    __shared__ double sh[256];
+    double bar = 0.0, dot = 0.0;
+    for (int i = threadIdx.x; i < nbar; i += 256) bar += pbar[i];
+    for (int i = threadIdx.x; i < ndot; i += 256) dot += pdot[i];
+    bar = block_reduce_256(bar, sh, OpSum{});
+    dot = block_reduce_256(dot, sh, OpSum{});
+    if (threadIdx.x == 0) {
+        rec[0] = bar;
+        rec[1] = dot;
+        if (P.dst) st_publish(P);
+    }
+}
+
+// unit_initialization! of every cone into s and z (zero: 0; nonnegative: 1; second-order: e_1; PSD: svec(I);
+// exponential: coneops_expcone.jl:36-52; power: coneops_powcone.jl:36-54)
+__global__ __launch_bounds__(256) void k_unit_initialization(ConeDev C, double* __restrict__ s, double* __restrict__ z, int m)
+{
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) {
+        const int c = C.elem_cone[i];
+        const int kind = C.kind[c], j = i - C.off[c];
+        double v = 0.0;
+        if (kind == 1) v = 1.0;
+        else if (kind == 2) v = j == 0 ? 1.0 : 0.0;
+        else if (kind == 3) {
+            int r, cl;
+            st_svec_index(j, r, cl);
+            v = r == cl ? 1.0 : 0.0;
+        } else if (kind == 4) v = j == 0 ? -1.051383945322714 : j == 1 ? 0.556409619469370 : 1.258967884768947;
+        else if (kind == 5) {
+            const double a = C.param[c];
+            v = j == 0 ? sqrt(1.0 + a) : j == 1 ? sqrt(1.0 + (1.0 - a)) : 0.0;
+        }
+        s[i] = v;
+        z[i] = v;
+    }
+}
+
 inline int step_grid(int m)
 {
     int64_t g = ((int64_t)m + 255) / 256;
@@ -578,6 +955,49 @@ void launch_unit_shift(const ConeDev& C, double* v, double a1, double a2, bool t
 {
     if (m <= 0) return;
     hipLaunchKernelGGL(k_unit_shift, dim3(step_grid(m)), dim3(256), 0, st, C, v, a1, a2, two ? 1 : 0, primal ? 1 : 0, m);
+}
+
+void launch_unit_initialization(const ConeDev& C, double* s, double* z, int m, hipStream_t st)
+{
+    if (m <= 0) return;
+    hipLaunchKernelGGL(k_unit_initialization, dim3(step_grid(m)), dim3(256), 0, st, C, s, z, m);
+}
+
+void launch_step_ds_ns(const ConeDev& C, const ConeState& S, double* out, const double* step_z, const double* step_s,
+                       const double* s, const double* z, double sigma_mu, double m_corr, int m, bool combined, hipStream_t st)
+{
+    launch_step_ds(C, S, out, step_z, step_s, sigma_mu, m_corr, m, combined, st);
+    const int nns = C.nexp + C.npow;
+    if (nns > 0)
+        hipLaunchKernelGGL(k_ns_ds, dim3(step_grid(nns)), dim3(256), 0, st, C, S, out, step_z, step_s, s, z, sigma_mu, m_corr,
+                           combined ? 1 : 0);
+}
+
+void launch_step_length_ns(const ConeDev& C, const ConeState& S, const double* dz, const double* ds, const double* z,
+                           const double* s, double step_tau, double step_kappa, double tau, double kappa, double backtrack_step,
+                           double alpha_min, int trip_cap, double* partial, double* ns_partial, double* rec, const Publish& pub,
+                           int m, hipStream_t st)
+{
+    launch_step_length(C, S, dz, ds, z, s, step_tau, step_kappa, tau, kappa, partial, rec, Publish{}, m, st);
+    const int nns = C.nexp + C.npow, gn = nns > 0 ? step_grid(nns) : 0;
+    if (gn > 0)
+        hipLaunchKernelGGL(k_ns_step_length, dim3(gn), dim3(256), 0, st, C, dz, ds, z, s, rec, backtrack_step, alpha_min, trip_cap,
+                           ns_partial);
+    hipLaunchKernelGGL(k_ns_step_length_finish, dim3(1), dim3(256), 0, st, ns_partial, gn, rec, pub);
+}
+
+void launch_barrier(const ConeDev& C, const double* z, const double* s, const double* dz, const double* ds, double alpha,
+                    double* partial, double* rec, const Publish& pub, int m, hipStream_t st)
+{
+    const int ge = step_grid(m), gs = (C.nsoc + 3) / 4, nns = C.nexp + C.npow, gn = nns > 0 ? step_grid(nns) : 0;
+    double* pbar = partial;
+    double* pdot = partial + barrier_partials(C);
+    if (C.npsd > 0)
+        hipLaunchKernelGGL(k_barrier_psd, dim3(C.npsd), dim3(256), (size_t)C.psd_kmax * C.psd_kmax * sizeof(double), st, C, z, s, dz,
+                           ds, alpha, pbar + ge + C.nsoc);
+    hipLaunchKernelGGL(k_barrier, dim3(ge + gs), dim3(256), 0, st, C, z, s, dz, ds, alpha, m, pbar, pdot, ge);
+    if (gn > 0) hipLaunchKernelGGL(k_barrier_ns, dim3(gn), dim3(256), 0, st, C, z, s, dz, ds, alpha, pbar + ge + C.nsoc + C.npsd);
+    hipLaunchKernelGGL(k_barrier_finish, dim3(1), dim3(256), 0, st, pbar, ge + C.nsoc + C.npsd + gn, pdot, ge, rec, pub);
 }
 
 }  // namespace hipkkt

@@ -15,15 +15,24 @@ batch of dot products and norms, alpha twice, (dtau, dkappa) twice, the solves' 
 One difference in bookkeeping: a cone point that is not interior is reported by kkt_update! itself (the device scales
 the cones inside it), so `iterations` counts that last, failed iteration, where `ipm.solve` with host cones stops one
 line earlier.  The status is NUMERICAL_ERROR either way.
+
+`solve_device_nonsymmetric` is the same loop for cone lists that hold exponential or power cones (the non-symmetric
+branch of `ipm.solve`): the unit start, `set_nonsymmetric_scaling(strategy, mu)` before every update, the three strategy
+checkpoints, and the barrier line search under the dual strategy -- the cone operations through
+hipkkt_kkt_system_unit_initialization / _affine_ds_ns / _combined_ds_ns / _step_length_ns / _barrier.  Per iteration
+the same scalars cross the bus, plus two per barrier evaluation.  There the bookkeeping difference has one more
+consequence: kkt_update! does not say WHY it failed, so a failed scaling under the primal-dual strategy passes through
+the numerical-error checkpoint (one more iteration under the dual strategy, where it fails again) before the loop
+ends with NUMERICAL_ERROR.
 """
 import warnings
 
 import numpy as np
 import scipy.sparse as sp
 
-from .cones import ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT
+from .cones import ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT, ExponentialConeT, PowerConeT
 from .ipm import (IPMSettings, IPMResult, HipSystemBackend, SOLVED, PRIMAL_INFEASIBLE, DUAL_INFEASIBLE, MAX_ITERATIONS,
-                  NUMERICAL_ERROR, INSUFFICIENT_PROGRESS, UNSOLVED, ALMOST_SOLVED)
+                  NUMERICAL_ERROR, INSUFFICIENT_PROGRESS, UNSOLVED, ALMOST_SOLVED, PRIMAL_DUAL, DUAL, _logsafe)
 
 PSD_MAX_SIDE = 48          # kPsdMaxDim of the device kernels
 
@@ -70,25 +79,48 @@ def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None, plumbing="
     expressions over fp64 CSR copies of P, A and A'; "device" -- they are the library's own
     hipkkt_kkt_system_residuals / _combined_rhs / _add_step over the P, A the handle already holds: no second copy of the
     matrices, and torch only allocates (and clones the previous iterate)."""
-    import torch
     if plumbing not in ("torch", "device"):
         raise ValueError(f"plumbing must be 'torch' or 'device', got {plumbing!r}")
-    native = plumbing == "device"
-    st = settings or IPMSettings()
     cone_specs = list(cone_specs)
     for c in cone_specs:
         if not isinstance(c, (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT)):
             raise ValueError("solve_device covers the symmetric cones only (zero, nonnegative, second-order, PSD); "
-                             f"got {type(c).__name__}: use ipm.solve")
+                             f"got {type(c).__name__}: use solve_device_nonsymmetric for exponential and power cones, "
+                             "ipm.solve for anything else")
         if isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE:
             raise ValueError(f"solve_device covers PSD cones up to side {PSD_MAX_SIDE}")
+    return _solve(P, q, A, b, cone_specs, settings, inspect, plumbing == "device", False)
+
+
+def solve_device_nonsymmetric(P, q, A, b, cone_specs, settings=None, inspect=None, plumbing="device"):
+    """`solve_device` for cone lists with exponential and power cones among the symmetric ones (any order): the
+    non-symmetric branch of Clarabel.solve! with device-resident vectors -> IPMResult.  Generalized power cones are not
+    covered (use ipm.solve).  `inspect` and `plumbing` as in solve_device; settings.min_terminate_step_length must be
+    positive and linesearch_backtrack_step lie in (0, 1) (the device's backtracking search refuses anything else)."""
+    if plumbing not in ("torch", "device"):
+        raise ValueError(f"plumbing must be 'torch' or 'device', got {plumbing!r}")
+    cone_specs = list(cone_specs)
+    for c in cone_specs:
+        if not isinstance(c, (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT, ExponentialConeT, PowerConeT)):
+            raise ValueError("solve_device_nonsymmetric covers zero, nonnegative, second-order, PSD, exponential and power "
+                             f"cones; got {type(c).__name__}: use ipm.solve")
+        if isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE:
+            raise ValueError(f"solve_device_nonsymmetric covers PSD cones up to side {PSD_MAX_SIDE}")
+    return _solve(P, q, A, b, cone_specs, settings, inspect, plumbing == "device", True)
+
+
+def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym):
+    """The loop both entry points share.  nonsym: the reference's path for a list that does not allow the symmetric
+    start (solver.jl:383-404) -- every line that differs sits under `if nonsym`."""
+    import torch
+    st = settings or IPMSettings()
     P = sp.csc_matrix(P)
     Pt = sp.triu(P, format="csc")
     Pfull_h = (Pt + sp.triu(Pt, 1).T).tocsr()
     q, b = np.asarray(q, float), np.asarray(b, float)
     n, m = Pfull_h.shape[0], sp.csc_matrix(A).shape[0]      # (Pfull_h: the objective of the final solution, on the host)
-    degree = sum(c.dim if isinstance(c, (NonnegativeConeT, PSDTriangleConeT)) else 1 if isinstance(c, SecondOrderConeT) else 0
-                 for c in cone_specs)
+    degree = sum(c.dim if isinstance(c, (NonnegativeConeT, PSDTriangleConeT)) else 1 if isinstance(c, SecondOrderConeT)
+                 else 3 if isinstance(c, (ExponentialConeT, PowerConeT)) else 0 for c in cone_specs)
     normq = np.abs(q).max() if n else 0.0
     normb = np.abs(b).max() if m else 0.0
 
@@ -113,12 +145,36 @@ def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None, plumbing="
         rx, rx_inf, Px, rhs_x = new(n), new(n), new(n), new(n)
         rz, rz_inf, rhs_z = new(m), new(m), new(m)
     system.init(q, b)
-    backend.update_identity()
-    system.solve_constant_rhs()
-    system.solve_initial_point_dev(p(x), p(s), p(z))
-    system.shift_to_interior_dev(p(s), True)             # variables.jl:213-237
-    system.shift_to_interior_dev(p(z), False)
+    strategy = PRIMAL_DUAL                               # the reference's `scaling` (solver.jl:221); read under nonsym only
+    bt_step, bt_min = st.linesearch_backtrack_step, st.min_terminate_step_length
+    if nonsym:
+        system.unit_initialization_dev(p(s), p(z))       # variables_unit_initialization!: x = 0, no solve
+    else:
+        backend.update_identity()
+        system.solve_constant_rhs()
+        system.solve_initial_point_dev(p(x), p(s), p(z))
+        system.shift_to_interior_dev(p(s), True)         # variables.jl:213-237
+        system.shift_to_interior_dev(p(z), False)
     tau, kappa = 1.0, 1.0
+
+    def step_length_ns(combined):                        # solver_get_step_length (solver.jl:407-442) on a non-symmetric list
+        a = system.step_length_ns_dev(p(dz), p(ds), p(z), p(s), dtau, dkappa, tau, kappa, bt_step, bt_min)
+        if not combined:
+            return a
+        a *= st.max_step_fraction
+        if strategy == DUAL:                             # solver_backtrack_step_to_barrier
+            for _ in range(50):
+                if barrier(a) < 1.0:
+                    break
+                a *= bt_step
+        return a
+
+    def barrier(a):                                      # variables_barrier (variables.jl:46-72): two scalars per call
+        cone_barrier, dot = system.barrier_dev(p(z), p(s), p(dz), p(ds), a)
+        ct, ck = tau + a * dtau, kappa + a * dkappa
+        with np.errstate(all="ignore"):
+            mu_a = (dot + ct * ck) / (degree + 1)
+            return (degree + 1) * _logsafe(mu_a) - _logsafe(ct) - _logsafe(ck) + cone_barrier
 
     it, alpha, sigma = 0, 0.0, 1.0
     status = UNSOLVED
@@ -178,22 +234,35 @@ def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None, plumbing="
         if status != UNSOLVED:
             if status == INSUFFICIENT_PROGRESS and prev_vars is not None:
                 x, s, z, tau, kappa = prev_vars
+            if status == INSUFFICIENT_PROGRESS and nonsym and strategy == PRIMAL_DUAL:
+                # _strategy_checkpoint_insufficient_progress: go on from the previous iterate with dual scaling
+                strategy, status = DUAL, UNSOLVED
+                continue
             break
         # ---- kkt_update!: cone scaling from (s, z), refactor, constant-RHS solve (solver.jl:258-280)
         it += 1
+        if nonsym:
+            ks.set_nonsymmetric_scaling(strategy, mu)    # host-only; the update below picks it up
         ok = system.update_dev(p(s), p(z))
         if ok:
             # ---- affine step (solver.jl:282-295)
-            system.affine_ds_dev(p(aff_s))
+            if nonsym:
+                system.affine_ds_ns_dev(p(aff_s), p(s))
+            else:
+                system.affine_ds_dev(p(aff_s))
             ok, dtau, dkappa = system.solve_dev((p(dx), p(ds), p(dz)), (p(rx), p(aff_s), p(rz)), rtau, tau * kappa,
                                                 (p(x), p(s), p(z)), tau, kappa, True)
             ir_total += backend.last_ir_iterations
         if ok:
             # ---- combined step (solver.jl:297-323)
-            alpha = system.step_length_dev(p(dz), p(ds), p(z), p(s), dtau, dkappa, tau, kappa)
+            alpha = step_length_ns(False) if nonsym else \
+                system.step_length_dev(p(dz), p(ds), p(z), p(s), dtau, dkappa, tau, kappa)
             sigma = (1 - alpha) ** 3
             mcorr = 1.0 if it > 1 else alpha
-            system.combined_ds_dev(p(rhs_s), p(dz), p(ds), sigma * mu, mcorr)
+            if nonsym:
+                system.combined_ds_ns_dev(p(rhs_s), p(dz), p(ds), p(s), p(z), sigma * mu, mcorr)
+            else:
+                system.combined_ds_dev(p(rhs_s), p(dz), p(ds), sigma * mu, mcorr)
             if native:
                 system.combined_rhs_dev(p(rhs_x), p(rhs_z), p(rx), p(rz), sigma)
             else:
@@ -204,9 +273,18 @@ def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None, plumbing="
             ir_total += backend.last_ir_iterations
         if not ok:
             alpha = 0.0
+            if nonsym and strategy == PRIMAL_DUAL:       # _strategy_checkpoint_numerical_error
+                strategy = DUAL
+                continue
             status = NUMERICAL_ERROR
             break
-        alpha = system.step_length_dev(p(dz), p(ds), p(z), p(s), dtau, dkappa, tau, kappa) * st.max_step_fraction
+        if nonsym:
+            alpha = step_length_ns(True)
+            if strategy == PRIMAL_DUAL and alpha < st.min_switch_step_length:
+                strategy, alpha = DUAL, 0.0              # _strategy_checkpoint_small_step
+                continue
+        else:
+            alpha = system.step_length_dev(p(dz), p(ds), p(z), p(s), dtau, dkappa, tau, kappa) * st.max_step_fraction
         if alpha <= max(0.0, st.min_terminate_step_length):
             status = INSUFFICIENT_PROGRESS
             alpha = 0.0

@@ -383,6 +383,42 @@ class HipKKTSystem:
               "hipkkt_kkt_system_shift_to_interior")
         return float(out[0]), float(out[1])
 
+    # ---- the same for cone lists with exponential / power cones (zero, nonnegative, second-order, PSD <= 48, exponential
+    #      and power cones in any order; a generalized power cone is refused)
+    def unit_initialization_dev(self, d_s, d_z):
+        """Every cone's unit_initialization! into s and z (the asymmetric start): one launch, no scaling needed."""
+        return check(_lib.lib().hipkkt_kkt_system_unit_initialization(self.ks._h, C.c_void_p(d_s), C.c_void_p(d_z)),
+                     "hipkkt_kkt_system_unit_initialization")
+
+    def affine_ds_ns_dev(self, d_out, d_s):
+        """out = lambda o lambda on symmetric rows, a copy of s on exponential / power rows (affine_ds!)."""
+        return check(_lib.lib().hipkkt_kkt_system_affine_ds_ns(self.ks._h, C.c_void_p(d_out), C.c_void_p(d_s)),
+                     "hipkkt_kkt_system_affine_ds_ns")
+
+    def combined_ds_ns_dev(self, d_out, d_step_z, d_step_s, d_s, d_z, sigma_mu, m_corr):
+        """d.s of the combined right-hand side; exponential / power rows: s + sigma_mu grad f*(z) - eta(step_s, m_corr
+        step_z).  d_z must be the z the current scaling was computed from."""
+        return check(_lib.lib().hipkkt_kkt_system_combined_ds_ns(self.ks._h, C.c_void_p(d_out), C.c_void_p(d_step_z),
+                                                                  C.c_void_p(d_step_s), C.c_void_p(d_s), C.c_void_p(d_z),
+                                                                  float(sigma_mu), float(m_corr)),
+                     "hipkkt_kkt_system_combined_ds_ns")
+
+    def step_length_ns_dev(self, d_step_z, d_step_s, d_z, d_s, step_tau, step_kappa, tau, kappa, backtrack_step, alpha_min):
+        """The composite step length of a list with exponential / power cones, without max_step_fraction -> alpha."""
+        out = np.zeros(1)
+        check(_lib.lib().hipkkt_kkt_system_step_length_ns(self.ks._h, C.c_void_p(d_step_z), C.c_void_p(d_step_s),
+                                                          C.c_void_p(d_z), C.c_void_p(d_s), float(step_tau), float(step_kappa),
+                                                          float(tau), float(kappa), float(backtrack_step), float(alpha_min),
+                                                          ptr(out)), "hipkkt_kkt_system_step_length_ns")
+        return float(out[0])
+
+    def barrier_dev(self, d_z, d_s, d_step_z, d_step_s, alpha):
+        """(sum of the cones' compute_barrier, <z + alpha dz, s + alpha ds>) at the stepped point, as host floats."""
+        out = np.zeros(2)
+        check(_lib.lib().hipkkt_kkt_system_barrier(self.ks._h, C.c_void_p(d_z), C.c_void_p(d_s), C.c_void_p(d_step_z),
+                                                   C.c_void_p(d_step_s), float(alpha), ptr(out)), "hipkkt_kkt_system_barrier")
+        return float(out[0]), float(out[1])
+
     # ---- residuals and termination scalars of a device-resident iterate, and the elementwise steps around them
     def residuals_dev(self, d_x, d_s, d_z, tau, d_rx, d_rz, d_rx_inf, d_rz_inf, d_Px, d_equil=None):
         """residuals_update! and the scalars info_update! reads, in one pass over K's image -> numpy array of 12:

@@ -320,6 +320,74 @@ int hipkkt_kkt_system_step_length(hipkkt_kkt_t h, const double *d_step_z, const 
  * margins_out (host, 2, may be NULL) receives (min_margin, pos_margin) as found BEFORE the shift.  Synchronises. */
 int hipkkt_kkt_system_shift_to_interior(hipkkt_kkt_t h, double *d_v, int primal, double *margins_out);
 
+/* The same operations for cone lists that hold an exponential or a power cone, and the two that only such lists need
+ * (the unit start and the barrier of the dual-scaling line search), so that their iterate stays in HBM too.  They are
+ * entry points of their own: the four above keep refusing such handles.  Covered: zero, nonnegative, second-order, PSD
+ * (side <= 48), exponential and power cones in any order.  Same rules as above: they need hipkkt_kkt_system_init and --
+ * except hipkkt_kkt_system_unit_initialization -- the cone scaling of a hipkkt_kkt_system_update* call; on a handle that
+ * holds a generalized power cone or a PSD cone of side > 48, and on a deferred-status handle, each returns
+ * HIPKKT_ERR_ARG and enqueues nothing.  Inputs are never modified, outputs must not alias inputs, all work goes on the
+ * handle's stream, results are reproducible bit for bit (fixed reduction layout, no floating-point atomics).  On the
+ * rows of the symmetric cones each gives, bit for bit, what its counterpart above gives on a handle with those cones
+ * alone (the same kernels run); the exponential / power rows take one lane per cone. */
+/* variables_unit_initialization! (variables.jl:213-226; the asymmetric start of solver.jl:383-404): every cone's
+ * unit_initialization! into s and z -- zero: 0; nonnegative: 1; second-order: e_1; PSD: svec(I); exponential
+ * (coneops_expcone.jl:36-52): (-1.051383945322714, 0.556409619469370, 1.258967884768947); power
+ * (coneops_powcone.jl:36-54): (sqrt(1 + alpha), sqrt(1 + (1 - alpha)), 0).  One launch, no synchronisation; d_s != d_z. */
+int hipkkt_kkt_system_unit_initialization(hipkkt_kkt_t h, double *d_s, double *d_z);
+
+/* affine_ds! over all cones (coneops_compositecone.jl:153-165): lambda o lambda on the symmetric rows as
+ * hipkkt_kkt_system_affine_ds, a copy of s on the exponential / power rows (coneops_expcone.jl:117-127,
+ * coneops_powcone.jl:120-130). */
+int hipkkt_kkt_system_affine_ds_ns(hipkkt_kkt_t h, double *d_out, const double *d_s);
+
+/* The whole d.s of variables_combined_step_rhs! (variables.jl:124-162).  Symmetric rows: as
+ * hipkkt_kkt_system_combined_ds.  Exponential / power rows (combined_ds_shift!: coneops_expcone.jl:130-147,
+ * coneops_powcone.jl:132-149):
+ *   out = s + sigma_mu * grad f*(z) - eta(step_s, m_corr * step_z)
+ * with grad f*(z) as the scaling stored it and eta what higher_correction! returns, +1/2 D^3 f*(z)[H*^{-1} step_s, m_corr
+ * step_z] (the negative of the method's third-order correction, which this subtraction restores; coneops_expcone.jl:319-366, coneops_powcone.jl:329-404; the 3 x 3 Cholesky factor and
+ * solve of H*(z) as mathutils.jl:427-466; eta = 0 where that factorisation fails).  d_z MUST be the z the current
+ * scaling was computed from (the z of the last hipkkt_kkt_system_update*): the stored gradient and Hessian belong to
+ * it, and the correction's closed form reads z itself. */
+int hipkkt_kkt_system_combined_ds_ns(hipkkt_kkt_t h, double *d_out, const double *d_step_z, const double *d_step_s,
+                                     const double *d_s, const double *d_z, double sigma_mu, double m_corr);
+
+/* step_length of the composite cone for lists that hold an exponential or power cone (coneops_compositecone.jl:205-243),
+ * WITHOUT the max_step_fraction factor:
+ *   1. a = min(1, tau limit, kappa limit, every symmetric cone's limit), as hipkkt_kkt_system_step_length;
+ *   2. a0 = min(a, 1 - sqrt(eps));
+ *   3. every exponential / power cone's backtrack_search (coneops_nonsymmetric_common.jl:5-34) on z with
+ *      is_dual_feasible and on s with is_primal_feasible: alpha <- alpha * backtrack_step until the point is in the
+ *      cone, 0 once alpha < alpha_min.
+ * The reference tightens alpha cone after cone; here every cone backtracks independently from the common start a0 and
+ * the results are folded by a minimum.  The values any search visits are a0 * backtrack_step^j formed by repeated
+ * multiplication -- the same doubles whichever cone's search a value is reached in -- and the feasible set along a ray
+ * out of an interior point of a convex cone is an interval [0, t), so a cone accepts a visited value exactly if it
+ * accepts every smaller one: the sequential result is the largest visited value every cone accepts, which is the
+ * minimum of the independent results (0 included: a search that gives up makes both 0).
+ * Stage 2 is applied whether or not the list holds such a cone -- which is the composite's rule only for lists that do:
+ * this entry point is FOR those lists; use hipkkt_kkt_system_step_length for symmetric ones.
+ * The start a0 is read by the lane-per-cone kernel from the device record the symmetric stage left: one synchronisation
+ * per call.  The call ends on any input: backtrack_step outside (0, 1) or alpha_min <= 0 (or NaN) is HIPKKT_ERR_ARG; the
+ * search has a hard trip cap of floor(log(alpha_min) / log(backtrack_step)) + 2 after which it gives 0; a NaN point is
+ * not in the cone.  *alpha_out is a host double. */
+int hipkkt_kkt_system_step_length_ns(hipkkt_kkt_t h, const double *d_step_z, const double *d_step_s,
+                                     const double *d_z, const double *d_s, double step_tau, double step_kappa,
+                                     double tau, double kappa, double backtrack_step, double alpha_min,
+                                     double *alpha_out);
+
+/* The cone part of variables_barrier (variables.jl:46-72) at (z + alpha step_z, s + alpha step_s):
+ *   out[0] = sum over the cones of compute_barrier -- zero: 0; nonnegative: coneops_nncone.jl:172-189; second-order:
+ *            coneops_socone.jl:287-305; PSD: coneops_psdtrianglecone.jl:256-295 (log-determinants by Cholesky in LDS, one
+ *            workgroup per cone); exponential / power: barrier_dual + barrier_primal
+ *            (coneops_expcone.jl:189-251, coneops_powcone.jl:193-254);
+ *   out[1] = <z + alpha step_z, s + alpha step_s> over all rows.
+ * The caller forms mu_a and the tau / kappa terms from out[1].  A point outside a cone gives +inf or NaN in out[0]: a
+ * result, not an error (HIPKKT_OK).  Synchronises: one read-back per call.  out: host, 2 doubles. */
+int hipkkt_kkt_system_barrier(hipkkt_kkt_t h, const double *d_z, const double *d_s, const double *d_step_z,
+                              const double *d_step_s, double alpha, double out[2]);
+
 /* The first step of every iteration on an iterate kept in HBM: residuals_update! (residuals.jl:1-37) and the scalars
  * info_update! reads (the four dot products and the eight norm_scaled calls of info.jl:33-51), from the P, A the handle
  * holds inside K and the q, b of hipkkt_kkt_system_init -- the caller needs no copy of the matrices and no sparse mat-vec
