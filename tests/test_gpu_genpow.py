@@ -217,6 +217,7 @@ def test_level_b_solve_against_the_reduced_dense_system():
 @pytest.mark.parametrize("mode,affine", [("eager", True), ("eager", False), ("lazy", True), ("lazy", False),
                                          ("batched", True), ("torch", True), ("torch", False)])
 def test_level_c_solve_in_every_mode_against_the_reduced_dense_system(mode, affine):
+    """(The symmetric cones' step is held to its defining equations at rounding level in tests/test_gpu_system_step.py.)"""
     P, A, s, z = G.mixed_problem(13, G.MIXED)
     rng = np.random.default_rng(7)
     n, m = P.shape[0], A.shape[0]
