@@ -116,6 +116,12 @@ SYMBOLS = {
     "hipkkt_kkt_system_step_length_ns": (C.c_int, [_P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,
                                                    C.c_double, C.c_double, _P]),
     "hipkkt_kkt_system_barrier": (C.c_int, [_P, _P, _P, _P, _P, C.c_double, _P]),
+    "hipkkt_kkt_system_unit_initialization_gp": (C.c_int, [_P, _P, _P]),
+    "hipkkt_kkt_system_affine_ds_gp": (C.c_int, [_P, _P, _P]),
+    "hipkkt_kkt_system_combined_ds_gp": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_double, C.c_double]),
+    "hipkkt_kkt_system_step_length_gp": (C.c_int, [_P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                   C.c_double, C.c_double, _P]),
+    "hipkkt_kkt_system_barrier_gp": (C.c_int, [_P, _P, _P, _P, _P, C.c_double, _P]),
     "hipkkt_kkt_system_residuals": (C.c_int, [_P, _P, _P, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hipkkt_kkt_system_combined_rhs": (C.c_int, [_P, _P, _P, _P, _P, C.c_double]),
     "hipkkt_kkt_system_add_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_double]),

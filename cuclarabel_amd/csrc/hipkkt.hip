@@ -3728,13 +3728,13 @@ int hipkkt_kkt_system_solve(hipkkt_kkt_t h, double* d_lhs_x, double* d_lhs_s, do
 
 // ---- the cone operations between the solves (step_kernels.hip): affine_ds!, the combined step's d.s, step_length,
 // _shift_to_cone_interior! on the caller's device vectors
-static void step_guard(hipkkt_kkt_t h, const char* who, bool need_scaling, bool nonsym_entry = false)
+static void step_guard(hipkkt_kkt_t h, const char* who, bool need_scaling, bool nonsym_entry = false, bool genpow_entry = false)
 {
     if (!h) throw ArgError("null handle");
     if (!h->sys_ready) throw ArgError("hipkkt_kkt_system_*: call hipkkt_kkt_system_init first");
     if (h->deferred) throw ArgError("hipkkt_kkt_system_*: level C reads its scalars back (deferred status is for level B)");
-    if (nonsym_entry && h->K.ngenpow > 0)
-        throw ArgError(std::string(who) + ": generalized power cones are not covered");
+    if (nonsym_entry && !genpow_entry && h->K.ngenpow > 0)
+        throw ArgError(std::string(who) + ": generalized power cones are not covered (the _gp entry points are)");
     if (!nonsym_entry && (h->K.nnonsym > 0 || h->K.ngenpow > 0))
         throw ArgError(std::string(who) + ": symmetric cones only (the handle holds an exponential, power or generalized power cone)");
     if (h->psd_too_big) throw ArgError(std::string(who) + ": PSD cones with side > 48 are not covered");
@@ -3897,6 +3897,81 @@ int hipkkt_kkt_system_barrier(hipkkt_kkt_t h, const double* d_z, const double* d
         if ((h->K.m && (!d_z || !d_s || !d_step_z || !d_step_s)) || !out) throw ArgError("hipkkt_kkt_system_barrier: bad argument");
         const double* rec = step_read_record(h, 2, [&](const Publish& pub) {
             launch_barrier(h->cone_dev(), d_z, d_s, d_step_z, d_step_s, alpha, h->ns_partial.p, h->step_rec.p, pub, h->K.m, h->stream);
+        });
+        out[0] = rec[0];
+        out[1] = rec[1];
+        return HIPKKT_OK;
+    });
+}
+
+// ---- the same five for cone lists that hold generalized power cones as well (coneops_genpowcone.jl).  Entry points of
+// their own: the nine above keep refusing what they refuse.  The _ns launches run first, unchanged; the generalized power
+// cones' rows and terms follow, one wave or one workgroup per cone.
+int hipkkt_kkt_system_unit_initialization_gp(hipkkt_kkt_t h, double* d_s, double* d_z)
+{
+    return guarded([&]() {
+        step_guard(h, "hipkkt_kkt_system_unit_initialization_gp", false, true, true);
+        if (h->K.m && (!d_s || !d_z || d_s == d_z)) throw ArgError("hipkkt_kkt_system_unit_initialization_gp: bad argument");
+        launch_unit_initialization_gp(h->cone_dev(), h->cone_state(), d_s, d_z, h->K.m, h->stream);
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_affine_ds_gp(hipkkt_kkt_t h, double* d_out, const double* d_s)
+{
+    return guarded([&]() {
+        step_guard(h, "hipkkt_kkt_system_affine_ds_gp", true, true, true);
+        if (h->K.m && (!d_out || !d_s || d_out == d_s))
+            throw ArgError("hipkkt_kkt_system_affine_ds_gp: bad argument (d_out must not alias an input)");
+        launch_step_ds_gp(h->cone_dev(), h->cone_state(), d_out, nullptr, nullptr, d_s, nullptr, 0.0, 0.0, h->K.m, false, h->stream);
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_combined_ds_gp(hipkkt_kkt_t h, double* d_out, const double* d_step_z, const double* d_step_s,
+                                     const double* d_s, const double* d_z, double sigma_mu, double m_corr)
+{
+    return guarded([&]() {
+        step_guard(h, "hipkkt_kkt_system_combined_ds_gp", true, true, true);
+        if (h->K.m && (!d_out || !d_step_z || !d_step_s || !d_s || !d_z || d_out == d_step_z || d_out == d_step_s || d_out == d_s ||
+                       d_out == d_z))
+            throw ArgError("hipkkt_kkt_system_combined_ds_gp: bad argument (d_out must not alias an input)");
+        launch_step_ds_gp(h->cone_dev(), h->cone_state(), d_out, d_step_z, d_step_s, d_s, d_z, sigma_mu, m_corr, h->K.m, true,
+                          h->stream);
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_step_length_gp(hipkkt_kkt_t h, const double* d_step_z, const double* d_step_s, const double* d_z,
+                                     const double* d_s, double step_tau, double step_kappa, double tau, double kappa,
+                                     double backtrack_step, double alpha_min, double* alpha_out)
+{
+    return guarded([&]() {
+        step_guard(h, "hipkkt_kkt_system_step_length_gp", true, true, true);
+        if ((h->K.m && (!d_step_z || !d_step_s || !d_z || !d_s)) || !alpha_out)
+            throw ArgError("hipkkt_kkt_system_step_length_gp: bad argument");
+        if (!(backtrack_step > 0.0 && backtrack_step < 1.0) || !(alpha_min > 0.0))
+            throw ArgError("hipkkt_kkt_system_step_length_gp: backtrack_step must lie in (0, 1) and alpha_min be positive");
+        const double trips = std::log(alpha_min) / std::log(backtrack_step);         // (as hipkkt_kkt_system_step_length_ns)
+        const int cap = !(trips > 0.0) ? 2 : trips >= 2.0e9 ? INT_MAX : (int)trips + 2;
+        const double* rec = step_read_record(h, 1, [&](const Publish& pub) {
+            launch_step_length_gp(h->cone_dev(), h->cone_state(), d_step_z, d_step_s, d_z, d_s, step_tau, step_kappa, tau, kappa,
+                                  backtrack_step, alpha_min, cap, h->step_partial.p, h->ns_partial.p, h->step_rec.p, pub, h->K.m,
+                                  h->stream);
+        });
+        *alpha_out = rec[0];
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_barrier_gp(hipkkt_kkt_t h, const double* d_z, const double* d_s, const double* d_step_z,
+                                 const double* d_step_s, double alpha, double out[2])
+{
+    return guarded([&]() {
+        step_guard(h, "hipkkt_kkt_system_barrier_gp", true, true, true);
+        if ((h->K.m && (!d_z || !d_s || !d_step_z || !d_step_s)) || !out) throw ArgError("hipkkt_kkt_system_barrier_gp: bad argument");
+        const double* rec = step_read_record(h, 2, [&](const Publish& pub) {
+            launch_barrier_gp(h->cone_dev(), d_z, d_s, d_step_z, d_step_s, alpha, h->ns_partial.p, h->step_rec.p, pub, h->K.m, h->stream);
         });
         out[0] = rec[0];
         out[1] = rec[1];

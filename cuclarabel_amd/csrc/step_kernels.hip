@@ -8,7 +8,9 @@
 // second-order step length are tested on products and differences formed as the reference forms them.
 //
 // The exponential and the power cone (three rows each) ride behind them for handles that hold one: one lane per cone
-// through the handle's lists of such cones, see "exponential and power cones between the solves" below.
+// through the handle's lists of such cones, see "exponential and power cones between the solves" below.  Generalized
+// power cones ride behind those: one wave or one workgroup per cone, as the scaling kernel splits them, see "generalized
+// power cones between the solves".
 //
 // Every reduction has a fixed layout (a slot per workgroup / wave / cone in a partials array, folded by one workgroup in
 // a fixed order) and there is no floating-point atomic: the same call on the same data gives the same bits.
@@ -894,6 +896,237 @@ __global__ __launch_bounds__(256) void k_unit_initialization(ConeDev C, double* 
     }
 }
 
+// =====================================================================================================================
+//  Generalized power cones between the solves (coneops_genpowcone.jl), with the scaling kernel's work split
+//  (kernels.hip, cone_genpow_body): NT = 64, one wave per cone of gp_small, four to a workgroup; NT = 256, one workgroup
+//  per cone of gp_big.  Every sum is reduced in a fixed order -- a lane its strided rows in ascending order, a butterfly
+//  over the lanes, the waves left to right through LDS -- and every thread of the cone's wave / workgroup receives the
+//  same bits, so the data-dependent loops below (backtracking, Newton) take the same turn in every thread: no barrier
+//  sits under a branch that can differ between the threads of a workgroup.  DESIGN.md 4.4b.
+// =====================================================================================================================
+constexpr double kEps = 2.220446049250313e-16;
+constexpr int kGpRedMax = 6;                                           // values per reduction; LDS: 4 waves x kGpRedMax
+
+// v[0..N) summed over the cone's threads (v[0] multiplied where PROD0).  NT = 256: two barriers, so that a caller's loop
+// may come back before a slow wave has read the slots.
+template <int NT, int N, bool PROD0>
+__device__ inline void gpst_reduce(double (&v)[N], double* sh)
+{
+    static_assert(N <= kGpRedMax, "LDS slots");
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const double t = __shfl_xor(v[j], o, 64);
+            v[j] = (PROD0 && j == 0) ? v[j] * t : v[j] + t;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) v[j] = __shfl(v[j], 0, 64);              // (the butterfly's sums commute: the same bits already)
+    if (NT > 64) {
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        if (lane == 0)
+            for (int j = 0; j < N; ++j) sh[N * wave + j] = v[j];
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+            v[j] = (PROD0 && j == 0) ? (sh[j] * sh[N + j]) * (sh[2 * N + j] * sh[3 * N + j])
+                                     : (sh[j] + sh[N + j]) + (sh[2 * N + j] + sh[3 * N + j]);
+        __syncthreads();
+    }
+}
+
+struct GpCone { int off, n, d1; const double* al; int g; };
+__device__ inline GpCone gp_cone_of(const ConeDev& C, int k)
+{
+    const int c = C.gp_cone[k];
+    return GpCone{C.off[c], C.numel[c], C.gp_dim1[k], C.gp_alpha + C.gp_off[k], C.gp_off[k]};
+}
+
+// mode 0: unit_initialization! (:34-53) into out and out2; 1: affine_ds! (:137-147), a copy of s; 2: the combined step's
+// d.s (:149-168), s + sigma_mu grad f*(z) with the gradient the scaling kernel stored (no higher-order correction)
+template <int NT>
+__device__ inline void gp_rows_body(const ConeDev& C, const ConeState& S, int k, int tid, int mode, double* __restrict__ out,
+                                    double* __restrict__ out2, const double* __restrict__ s, double sigma_mu)
+{
+    const GpCone G = gp_cone_of(C, k);
+    for (int i = tid; i < G.n; i += NT) {
+        if (mode == 0) {
+            const double v = i < G.d1 ? sqrt(1.0 + G.al[i]) : 0.0;
+            out[G.off + i] = v;
+            out2[G.off + i] = v;
+        } else if (mode == 1) out[G.off + i] = s[G.off + i];
+        else out[G.off + i] = s[G.off + i] + sigma_mu * S.gp_grad[G.g + i];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_gp_rows(ConeDev C, ConeState S, int mode, double* __restrict__ out, double* __restrict__ out2,
+                                                 const double* __restrict__ s, double sigma_mu)
+{
+    const int gq = (C.ngp_small + 3) / 4, bx = (int)blockIdx.x;
+    if (bx < gq) {
+        const int i = bx * 4 + (int)(threadIdx.x >> 6);
+        if (i < C.ngp_small) gp_rows_body<64>(C, S, C.gp_small[i], threadIdx.x & 63, mode, out, out2, s, sigma_mu);
+        return;
+    }
+    gp_rows_body<256>(C, S, C.gp_big[bx - gq], threadIdx.x, mode, out, out2, s, sigma_mu);
+}
+
+// backtrack_search (coneops_nonsymmetric_common.jl:5-34) of one cone from a with is_dual_feasible (scaled, :272-292) or
+// is_primal_feasible (:249-269): the first dim1 entries > 0 and exp(sum 2 alpha_i logsafe(v_i [/ alpha_i])) - ||v[dim1:]||^2 > 0.
+// A NaN entry fails its comparison: the point is not in the cone.  At most `cap` trips.
+template <int NT>
+__device__ inline double gp_backtrack(const GpCone& G, const double* __restrict__ q, const double* __restrict__ dq, double a,
+                                      double amin, double step, int cap, bool scaled, int tid, double* sh)
+{
+    for (int trip = 0; trip < cap; ++trip) {
+        double v[3] = {0.0, 0.0, 0.0};                                 // sum of logs, sum of squares, entries not > 0
+        for (int i = tid; i < G.n; i += NT) {
+            const double x = q[G.off + i] + a * dq[G.off + i];
+            if (i < G.d1) {
+                const double al = G.al[i];
+                if (!(x > 0.0)) v[2] += 1.0;
+                v[0] += 2.0 * al * ns_logsafe(scaled ? x / al : x);
+            } else v[1] += x * x;
+        }
+        gpst_reduce<NT, 3, false>(v, sh);
+        if (v[2] == 0.0 && exp(v[0]) - v[1] > 0.0) return a;
+        a *= step;
+        if (a < amin) return 0.0;
+    }
+    return 0.0;
+}
+
+template <int NT>
+__device__ inline void gp_step_length_body(const ConeDev& C, int k, int tid, const double* __restrict__ dz,
+                                           const double* __restrict__ ds, const double* __restrict__ z, const double* __restrict__ s,
+                                           double a0, double step, double amin, int cap, double* __restrict__ slot, double* sh)
+{
+    const GpCone G = gp_cone_of(C, k);
+    const double az = gp_backtrack<NT>(G, z, dz, a0, amin, step, cap, true, tid, sh);
+    const double as = gp_backtrack<NT>(G, s, ds, a0, amin, step, cap, false, tid, sh);
+    if (tid == 0) *slot = fmin(az, as);
+}
+
+// slot k (the cone's index among the generalized power cones) = the cone's limit, from the common start a0 (k_ns_step_length)
+__global__ __launch_bounds__(256) void k_gp_step_length(ConeDev C, const double* __restrict__ dz, const double* __restrict__ ds,
+                                                        const double* __restrict__ z, const double* __restrict__ s,
+                                                        const double* __restrict__ rec, double step, double amin, int cap,
+                                                        double* __restrict__ slots)
+{
+    __shared__ double sh[4 * kGpRedMax];
+    const double a0 = fmin(rec[0], 1.0 - kSqrtEps);
+    const int gq = (C.ngp_small + 3) / 4, bx = (int)blockIdx.x;
+    if (bx < gq) {
+        const int i = bx * 4 + (int)(threadIdx.x >> 6);
+        if (i < C.ngp_small) {
+            const int k = C.gp_small[i];
+            gp_step_length_body<64>(C, k, threadIdx.x & 63, dz, ds, z, s, a0, step, amin, cap, slots + k, nullptr);
+        }
+        return;
+    }
+    const int k = C.gp_big[bx - gq];
+    gp_step_length_body<256>(C, k, threadIdx.x, dz, ds, z, s, a0, step, amin, cap, slots + k, sh);
+}
+
+// compute_barrier (:209-234) of one cone at (z + alpha dz, s + alpha ds): barrier_dual(z') (:313-333) +
+// barrier_primal(s') = -barrier_dual(-g(s')) - (dim1 + 1), g = gradient_primal! (:393-426) with the one-dimensional Newton
+// iteration of ipm._newton_raphson_genpowcone (:437-472; the start halved at most 64 times until f0 > 0, then at most 100
+// one-sided steps with the three stop tests of coneops_nonsymmetric_common.jl:170-193).  Every comparison that keeps a
+// loop running is false for NaN.
+template <int NT>
+__device__ inline void gp_barrier_body(const ConeDev& C, int k, int tid, const double* __restrict__ z, const double* __restrict__ s,
+                                       const double* __restrict__ dz, const double* __restrict__ ds, double alpha,
+                                       double* __restrict__ slot, double* sh)
+{
+    const GpCone G = gp_cone_of(C, k);
+    // one pass: the dual barrier's three sums, and of s': phi = prod s_i^(2 alpha_i), ||r||^2, sum alpha_i^2
+    double v[6] = {1.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int i = tid; i < G.n; i += NT) {
+        const double zi = z[G.off + i] + alpha * dz[G.off + i], si = s[G.off + i] + alpha * ds[G.off + i];
+        if (i < G.d1) {
+            const double al = G.al[i];
+            v[0] *= pow(si, 2.0 * al);
+            v[1] += 2.0 * al * ns_logsafe(zi / al);
+            v[2] += (1.0 - al) * ns_logsafe(zi);
+            v[5] += al * al;
+        } else {
+            v[3] += zi * zi;
+            v[4] += si * si;
+        }
+    }
+    gpst_reduce<NT, 6, true>(v, sh);
+    const double dual = -ns_logsafe(exp(v[1]) - v[3]) - v[2];
+    const double phi = v[0], nr = sqrt(v[4]), psi = 1.0 / v[5];
+    double g1 = 0.0;
+    const bool newton = nr > kEps;
+    if (newton) {
+        double x = -1.0 / nr + (psi * nr + sqrt((phi / nr / nr + psi * psi - 1.0) * phi)) / (phi - nr * nr);
+        double f[2];
+        // f0(x) and f1(x) in one pass
+        auto eval = [&](double y) {
+            f[0] = 0.0; f[1] = 0.0;
+            for (int i = tid; i < G.d1; i += NT) {
+                const double al = G.al[i], pi = s[G.off + i] + alpha * ds[G.off + i];
+                const double t = (1.0 + al) / al;
+                f[0] += 2.0 * al * (ns_logsafe(y * nr + t) - ns_logsafe(pi));
+                f[1] += 2.0 * al * nr / (nr * y + t);
+            }
+            gpst_reduce<NT, 2, false>(f, sh);
+            f[0] = -ns_logsafe(2.0 * y / nr + y * y) + f[0];
+            f[1] = -(2.0 * y + 2.0 / nr) / (y * y + 2.0 * y / nr) + f[1];
+        };
+        eval(x);
+        for (int h = 0; h < 64 && f[0] <= 0.0; ++h) {
+            x *= 0.5;
+            eval(x);
+        }
+        for (int iter = 0; iter < 100; ++iter) {
+            const double dfdx = f[1];
+            const double dx = -f[0] / dfdx;
+            if (!(dx >= kEps) || !(fabs(dx / x) >= kSqrtEps) || !(fabs(dfdx) >= kEps)) break;
+            x += dx;
+            if (iter + 1 < 100) eval(x);
+        }
+        g1 = x;
+    }
+    // barrier_dual(-g): -g_i = (1 + alpha_i + alpha_i g1 ||r||) / p_i, -g_w = -g1 r / ||r||
+    double w[3] = {0.0, 0.0, 0.0};
+    for (int i = tid; i < G.n; i += NT) {
+        const double si = s[G.off + i] + alpha * ds[G.off + i];
+        if (i < G.d1) {
+            const double al = G.al[i];
+            const double g = newton ? -(1.0 + al + al * g1 * nr) / si : -(1.0 + al) / si;
+            w[0] += 2.0 * al * ns_logsafe(-g / al);
+            w[2] += (1.0 - al) * ns_logsafe(-g);
+        } else {
+            const double g = newton ? g1 * si / nr : 0.0;
+            w[1] += g * g;
+        }
+    }
+    gpst_reduce<NT, 3, false>(w, sh);
+    const double primal = -(-ns_logsafe(exp(w[0]) - w[1]) - w[2]) - (double)(G.d1 + 1);
+    if (tid == 0) *slot = dual + primal;
+}
+
+__global__ __launch_bounds__(256) void k_gp_barrier(ConeDev C, const double* __restrict__ z, const double* __restrict__ s,
+                                                    const double* __restrict__ dz, const double* __restrict__ ds, double alpha,
+                                                    double* __restrict__ slots)
+{
+    __shared__ double sh[4 * kGpRedMax];
+    const int gq = (C.ngp_small + 3) / 4, bx = (int)blockIdx.x;
+    if (bx < gq) {
+        const int i = bx * 4 + (int)(threadIdx.x >> 6);
+        if (i < C.ngp_small) {
+            const int k = C.gp_small[i];
+            gp_barrier_body<64>(C, k, threadIdx.x & 63, z, s, dz, ds, alpha, slots + k, nullptr);
+        }
+        return;
+    }
+    const int k = C.gp_big[bx - gq];
+    gp_barrier_body<256>(C, k, threadIdx.x, z, s, dz, ds, alpha, slots + k, sh);
+}
+
 inline int step_grid(int m)
 {
     int64_t g = ((int64_t)m + 255) / 256;
@@ -973,23 +1206,49 @@ void launch_step_ds_ns(const ConeDev& C, const ConeState& S, double* out, const 
                            combined ? 1 : 0);
 }
 
+// stages 1 to 3 of the composite step length; gp: the generalized power cones' searches too, their slots behind the
+// lane-per-cone workgroups' (without them the launches are those of launch_step_length_ns, kernel for kernel)
+static void step_length_nonsym(const ConeDev& C, const ConeState& S, const double* dz, const double* ds, const double* z,
+                               const double* s, double step_tau, double step_kappa, double tau, double kappa, double backtrack_step,
+                               double alpha_min, int trip_cap, double* partial, double* ns_partial, double* rec, const Publish& pub,
+                               int m, bool gp, hipStream_t st)
+{
+    launch_step_length(C, S, dz, ds, z, s, step_tau, step_kappa, tau, kappa, partial, rec, Publish{}, m, st);
+    const int nns = C.nexp + C.npow, gn = nns > 0 ? step_grid(nns) : 0;
+    const int ngp = gp ? C.ngp_small + C.ngp_big : 0;
+    if (gn > 0)
+        hipLaunchKernelGGL(k_ns_step_length, dim3(gn), dim3(256), 0, st, C, dz, ds, z, s, rec, backtrack_step, alpha_min, trip_cap,
+                           ns_partial);
+    if (ngp > 0)
+        hipLaunchKernelGGL(k_gp_step_length, dim3((C.ngp_small + 3) / 4 + C.ngp_big), dim3(256), 0, st, C, dz, ds, z, s, rec,
+                           backtrack_step, alpha_min, trip_cap, ns_partial + gn);
+    hipLaunchKernelGGL(k_ns_step_length_finish, dim3(1), dim3(256), 0, st, ns_partial, gn + ngp, rec, pub);
+}
+
 void launch_step_length_ns(const ConeDev& C, const ConeState& S, const double* dz, const double* ds, const double* z,
                            const double* s, double step_tau, double step_kappa, double tau, double kappa, double backtrack_step,
                            double alpha_min, int trip_cap, double* partial, double* ns_partial, double* rec, const Publish& pub,
                            int m, hipStream_t st)
 {
-    launch_step_length(C, S, dz, ds, z, s, step_tau, step_kappa, tau, kappa, partial, rec, Publish{}, m, st);
-    const int nns = C.nexp + C.npow, gn = nns > 0 ? step_grid(nns) : 0;
-    if (gn > 0)
-        hipLaunchKernelGGL(k_ns_step_length, dim3(gn), dim3(256), 0, st, C, dz, ds, z, s, rec, backtrack_step, alpha_min, trip_cap,
-                           ns_partial);
-    hipLaunchKernelGGL(k_ns_step_length_finish, dim3(1), dim3(256), 0, st, ns_partial, gn, rec, pub);
+    step_length_nonsym(C, S, dz, ds, z, s, step_tau, step_kappa, tau, kappa, backtrack_step, alpha_min, trip_cap, partial, ns_partial,
+                       rec, pub, m, false, st);
 }
 
-void launch_barrier(const ConeDev& C, const double* z, const double* s, const double* dz, const double* ds, double alpha,
-                    double* partial, double* rec, const Publish& pub, int m, hipStream_t st)
+void launch_step_length_gp(const ConeDev& C, const ConeState& S, const double* dz, const double* ds, const double* z,
+                           const double* s, double step_tau, double step_kappa, double tau, double kappa, double backtrack_step,
+                           double alpha_min, int trip_cap, double* partial, double* ns_partial, double* rec, const Publish& pub,
+                           int m, hipStream_t st)
+{
+    step_length_nonsym(C, S, dz, ds, z, s, step_tau, step_kappa, tau, kappa, backtrack_step, alpha_min, trip_cap, partial, ns_partial,
+                       rec, pub, m, true, st);
+}
+
+// gp: the generalized power cones' terms too, in slots behind the lane-per-cone workgroups'
+static void barrier_all(const ConeDev& C, const double* z, const double* s, const double* dz, const double* ds, double alpha,
+                        double* partial, double* rec, const Publish& pub, int m, bool gp, hipStream_t st)
 {
     const int ge = step_grid(m), gs = (C.nsoc + 3) / 4, nns = C.nexp + C.npow, gn = nns > 0 ? step_grid(nns) : 0;
+    const int ngp = gp ? C.ngp_small + C.ngp_big : 0;
     double* pbar = partial;
     double* pdot = partial + barrier_partials(C);
     if (C.npsd > 0)
@@ -997,7 +1256,42 @@ void launch_barrier(const ConeDev& C, const double* z, const double* s, const do
                            ds, alpha, pbar + ge + C.nsoc);
     hipLaunchKernelGGL(k_barrier, dim3(ge + gs), dim3(256), 0, st, C, z, s, dz, ds, alpha, m, pbar, pdot, ge);
     if (gn > 0) hipLaunchKernelGGL(k_barrier_ns, dim3(gn), dim3(256), 0, st, C, z, s, dz, ds, alpha, pbar + ge + C.nsoc + C.npsd);
-    hipLaunchKernelGGL(k_barrier_finish, dim3(1), dim3(256), 0, st, pbar, ge + C.nsoc + C.npsd + gn, pdot, ge, rec, pub);
+    if (ngp > 0)
+        hipLaunchKernelGGL(k_gp_barrier, dim3((C.ngp_small + 3) / 4 + C.ngp_big), dim3(256), 0, st, C, z, s, dz, ds, alpha,
+                           pbar + ge + C.nsoc + C.npsd + gn);
+    hipLaunchKernelGGL(k_barrier_finish, dim3(1), dim3(256), 0, st, pbar, ge + C.nsoc + C.npsd + gn + ngp, pdot, ge, rec, pub);
+}
+
+void launch_barrier(const ConeDev& C, const double* z, const double* s, const double* dz, const double* ds, double alpha,
+                    double* partial, double* rec, const Publish& pub, int m, hipStream_t st)
+{
+    barrier_all(C, z, s, dz, ds, alpha, partial, rec, pub, m, false, st);
+}
+
+void launch_barrier_gp(const ConeDev& C, const double* z, const double* s, const double* dz, const double* ds, double alpha,
+                       double* partial, double* rec, const Publish& pub, int m, hipStream_t st)
+{
+    barrier_all(C, z, s, dz, ds, alpha, partial, rec, pub, m, true, st);
+}
+
+static void launch_gp_rows(const ConeDev& C, const ConeState& S, int mode, double* out, double* out2, const double* s, double sigma_mu,
+                           hipStream_t st)
+{
+    const int g = (C.ngp_small + 3) / 4 + C.ngp_big;
+    if (g > 0) hipLaunchKernelGGL(k_gp_rows, dim3(g), dim3(256), 0, st, C, S, mode, out, out2, s, sigma_mu);
+}
+
+void launch_unit_initialization_gp(const ConeDev& C, const ConeState& S, double* s, double* z, int m, hipStream_t st)
+{
+    launch_unit_initialization(C, s, z, m, st);            // (a generalized power cone's rows: 0)
+    launch_gp_rows(C, S, 0, s, z, nullptr, 0.0, st);
+}
+
+void launch_step_ds_gp(const ConeDev& C, const ConeState& S, double* out, const double* step_z, const double* step_s,
+                       const double* s, const double* z, double sigma_mu, double m_corr, int m, bool combined, hipStream_t st)
+{
+    launch_step_ds_ns(C, S, out, step_z, step_s, s, z, sigma_mu, m_corr, m, combined, st);
+    launch_gp_rows(C, S, combined ? 2 : 1, out, nullptr, s, sigma_mu, st);
 }
 
 }  // namespace hipkkt

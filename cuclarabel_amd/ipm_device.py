@@ -24,13 +24,20 @@ the same scalars cross the bus, plus two per barrier evaluation.  There the book
 consequence: kkt_update! does not say WHY it failed, so a failed scaling under the primal-dual strategy passes through
 the numerical-error checkpoint (one more iteration under the dual strategy, where it fails again) before the loop
 ends with NUMERICAL_ERROR.
+
+`solve_device_genpow` is that loop again for cone lists that hold generalized power cones (any of the other six kinds
+beside them), through hipkkt_kkt_system_unit_initialization_gp / _affine_ds_gp / _combined_ds_gp / _step_length_gp /
+_barrier_gp.  A generalized power cone has degree dim1 + 1 and dual scaling only; the loop still starts under
+PRIMAL_DUAL, as `ipm.solve` does for such lists, so that the two are comparable.  The combined d.s uses the gradient the
+device's own scaling kernel stored, so nothing of the scaling is read back.
 """
 import warnings
 
 import numpy as np
 import scipy.sparse as sp
 
-from .cones import ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT, ExponentialConeT, PowerConeT
+from .cones import (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT, ExponentialConeT, PowerConeT,
+                    GenPowerConeT)
 from .ipm import (IPMSettings, IPMResult, HipSystemBackend, SOLVED, PRIMAL_INFEASIBLE, DUAL_INFEASIBLE, MAX_ITERATIONS,
                   NUMERICAL_ERROR, INSUFFICIENT_PROGRESS, UNSOLVED, ALMOST_SOLVED, PRIMAL_DUAL, DUAL, _logsafe)
 
@@ -86,7 +93,7 @@ def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None, plumbing="
         if not isinstance(c, (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT)):
             raise ValueError("solve_device covers the symmetric cones only (zero, nonnegative, second-order, PSD); "
                              f"got {type(c).__name__}: use solve_device_nonsymmetric for exponential and power cones, "
-                             "ipm.solve for anything else")
+                             "solve_device_genpow for generalized power cones")
         if isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE:
             raise ValueError(f"solve_device covers PSD cones up to side {PSD_MAX_SIDE}")
     return _solve(P, q, A, b, cone_specs, settings, inspect, plumbing == "device", False)
@@ -95,7 +102,7 @@ def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None, plumbing="
 def solve_device_nonsymmetric(P, q, A, b, cone_specs, settings=None, inspect=None, plumbing="device"):
     """`solve_device` for cone lists with exponential and power cones among the symmetric ones (any order): the
     non-symmetric branch of Clarabel.solve! with device-resident vectors -> IPMResult.  Generalized power cones are not
-    covered (use ipm.solve).  `inspect` and `plumbing` as in solve_device; settings.min_terminate_step_length must be
+    covered (use solve_device_genpow).  `inspect` and `plumbing` as in solve_device; settings.min_terminate_step_length must be
     positive and linesearch_backtrack_step lie in (0, 1) (the device's backtracking search refuses anything else)."""
     if plumbing not in ("torch", "device"):
         raise ValueError(f"plumbing must be 'torch' or 'device', got {plumbing!r}")
@@ -103,15 +110,32 @@ def solve_device_nonsymmetric(P, q, A, b, cone_specs, settings=None, inspect=Non
     for c in cone_specs:
         if not isinstance(c, (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT, ExponentialConeT, PowerConeT)):
             raise ValueError("solve_device_nonsymmetric covers zero, nonnegative, second-order, PSD, exponential and power "
-                             f"cones; got {type(c).__name__}: use ipm.solve")
+                             f"cones; got {type(c).__name__}: use solve_device_genpow")
         if isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE:
             raise ValueError(f"solve_device_nonsymmetric covers PSD cones up to side {PSD_MAX_SIDE}")
     return _solve(P, q, A, b, cone_specs, settings, inspect, plumbing == "device", True)
 
 
-def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym):
-    """The loop both entry points share.  nonsym: the reference's path for a list that does not allow the symmetric
-    start (solver.jl:383-404) -- every line that differs sits under `if nonsym`."""
+def solve_device_genpow(P, q, A, b, cone_specs, settings=None, inspect=None, plumbing="device"):
+    """`solve_device_nonsymmetric` for cone lists that hold a generalized power cone, with any of the other six kinds
+    beside it (any order) -> IPMResult.  The cone operations go through the library's _gp entry points; `inspect`,
+    `plumbing` and the two settings constraints as in solve_device_nonsymmetric."""
+    if plumbing not in ("torch", "device"):
+        raise ValueError(f"plumbing must be 'torch' or 'device', got {plumbing!r}")
+    cone_specs = list(cone_specs)
+    for c in cone_specs:
+        if not isinstance(c, (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT, ExponentialConeT, PowerConeT,
+                              GenPowerConeT)):
+            raise ValueError(f"solve_device_genpow: unknown cone type {type(c).__name__}")
+        if isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE:
+            raise ValueError(f"solve_device_genpow covers PSD cones up to side {PSD_MAX_SIDE}")
+    return _solve(P, q, A, b, cone_specs, settings, inspect, plumbing == "device", True, True)
+
+
+def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym, genpow=False):
+    """The loop the entry points share.  nonsym: the reference's path for a list that does not allow the symmetric
+    start (solver.jl:383-404) -- every line that differs sits under `if nonsym`.  genpow (with nonsym): the cone
+    operations are the _gp calls, which cover generalized power cones as well."""
     import torch
     st = settings or IPMSettings()
     P = sp.csc_matrix(P)
@@ -120,12 +144,21 @@ def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym):
     q, b = np.asarray(q, float), np.asarray(b, float)
     n, m = Pfull_h.shape[0], sp.csc_matrix(A).shape[0]      # (Pfull_h: the objective of the final solution, on the host)
     degree = sum(c.dim if isinstance(c, (NonnegativeConeT, PSDTriangleConeT)) else 1 if isinstance(c, SecondOrderConeT)
-                 else 3 if isinstance(c, (ExponentialConeT, PowerConeT)) else 0 for c in cone_specs)
+                 else 3 if isinstance(c, (ExponentialConeT, PowerConeT))
+                 else len(c.alpha) + 1 if isinstance(c, GenPowerConeT) else 0 for c in cone_specs)
     normq = np.abs(q).max() if n else 0.0
     normb = np.abs(b).max() if m else 0.0
 
     backend = HipSystemBackend(P, A, cone_specs)
     ks, system = backend.ks, backend.system
+    if genpow:                                           # the five cone operations of a non-symmetric list
+        unit_initialization, affine_ds_ns, combined_ds_ns, step_length_ns_dev, barrier_dev = (
+            system.unit_initialization_gp_dev, system.affine_ds_gp_dev, system.combined_ds_gp_dev, system.step_length_gp_dev,
+            system.barrier_gp_dev)
+    else:
+        unit_initialization, affine_ds_ns, combined_ds_ns, step_length_ns_dev, barrier_dev = (
+            system.unit_initialization_dev, system.affine_ds_ns_dev, system.combined_ds_ns_dev, system.step_length_ns_dev,
+            system.barrier_dev)
     dev = system._devstr
     ks.set_stream(torch.cuda.current_stream(torch.device(dev)).cuda_stream)     # torch's kernels and the library's: one queue
     if not native:
@@ -148,7 +181,7 @@ def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym):
     strategy = PRIMAL_DUAL                               # the reference's `scaling` (solver.jl:221); read under nonsym only
     bt_step, bt_min = st.linesearch_backtrack_step, st.min_terminate_step_length
     if nonsym:
-        system.unit_initialization_dev(p(s), p(z))       # variables_unit_initialization!: x = 0, no solve
+        unit_initialization(p(s), p(z))                  # variables_unit_initialization!: x = 0, no solve
     else:
         backend.update_identity()
         system.solve_constant_rhs()
@@ -158,7 +191,7 @@ def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym):
     tau, kappa = 1.0, 1.0
 
     def step_length_ns(combined):                        # solver_get_step_length (solver.jl:407-442) on a non-symmetric list
-        a = system.step_length_ns_dev(p(dz), p(ds), p(z), p(s), dtau, dkappa, tau, kappa, bt_step, bt_min)
+        a = step_length_ns_dev(p(dz), p(ds), p(z), p(s), dtau, dkappa, tau, kappa, bt_step, bt_min)
         if not combined:
             return a
         a *= st.max_step_fraction
@@ -170,7 +203,7 @@ def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym):
         return a
 
     def barrier(a):                                      # variables_barrier (variables.jl:46-72): two scalars per call
-        cone_barrier, dot = system.barrier_dev(p(z), p(s), p(dz), p(ds), a)
+        cone_barrier, dot = barrier_dev(p(z), p(s), p(dz), p(ds), a)
         ct, ck = tau + a * dtau, kappa + a * dkappa
         with np.errstate(all="ignore"):
             mu_a = (dot + ct * ck) / (degree + 1)
@@ -247,7 +280,7 @@ def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym):
         if ok:
             # ---- affine step (solver.jl:282-295)
             if nonsym:
-                system.affine_ds_ns_dev(p(aff_s), p(s))
+                affine_ds_ns(p(aff_s), p(s))
             else:
                 system.affine_ds_dev(p(aff_s))
             ok, dtau, dkappa = system.solve_dev((p(dx), p(ds), p(dz)), (p(rx), p(aff_s), p(rz)), rtau, tau * kappa,
@@ -260,7 +293,7 @@ def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym):
             sigma = (1 - alpha) ** 3
             mcorr = 1.0 if it > 1 else alpha
             if nonsym:
-                system.combined_ds_ns_dev(p(rhs_s), p(dz), p(ds), p(s), p(z), sigma * mu, mcorr)
+                combined_ds_ns(p(rhs_s), p(dz), p(ds), p(s), p(z), sigma * mu, mcorr)
             else:
                 system.combined_ds_dev(p(rhs_s), p(dz), p(ds), sigma * mu, mcorr)
             if native:

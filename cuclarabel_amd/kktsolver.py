@@ -419,6 +419,41 @@ class HipKKTSystem:
                                                    C.c_void_p(d_step_s), float(alpha), ptr(out)), "hipkkt_kkt_system_barrier")
         return float(out[0]), float(out[1])
 
+    # ---- the same for cone lists that hold generalized power cones as well (any of the seven kinds, in any order)
+    def unit_initialization_gp_dev(self, d_s, d_z):
+        """unit_initialization_dev with the generalized power cones' start: sqrt(1 + alpha_i) on the first dim1 rows, 0 behind."""
+        return check(_lib.lib().hipkkt_kkt_system_unit_initialization_gp(self.ks._h, C.c_void_p(d_s), C.c_void_p(d_z)),
+                     "hipkkt_kkt_system_unit_initialization_gp")
+
+    def affine_ds_gp_dev(self, d_out, d_s):
+        """affine_ds_ns_dev, and a copy of s on the generalized power rows."""
+        return check(_lib.lib().hipkkt_kkt_system_affine_ds_gp(self.ks._h, C.c_void_p(d_out), C.c_void_p(d_s)),
+                     "hipkkt_kkt_system_affine_ds_gp")
+
+    def combined_ds_gp_dev(self, d_out, d_step_z, d_step_s, d_s, d_z, sigma_mu, m_corr):
+        """combined_ds_ns_dev, and s + sigma_mu grad f*(z) (the stored gradient, no higher-order correction) on the
+        generalized power rows.  d_z must be the z the current scaling was computed from."""
+        return check(_lib.lib().hipkkt_kkt_system_combined_ds_gp(self.ks._h, C.c_void_p(d_out), C.c_void_p(d_step_z),
+                                                                  C.c_void_p(d_step_s), C.c_void_p(d_s), C.c_void_p(d_z),
+                                                                  float(sigma_mu), float(m_corr)),
+                     "hipkkt_kkt_system_combined_ds_gp")
+
+    def step_length_gp_dev(self, d_step_z, d_step_s, d_z, d_s, step_tau, step_kappa, tau, kappa, backtrack_step, alpha_min):
+        """step_length_ns_dev with every generalized power cone's backtracking search in the minimum -> alpha."""
+        out = np.zeros(1)
+        check(_lib.lib().hipkkt_kkt_system_step_length_gp(self.ks._h, C.c_void_p(d_step_z), C.c_void_p(d_step_s),
+                                                          C.c_void_p(d_z), C.c_void_p(d_s), float(step_tau), float(step_kappa),
+                                                          float(tau), float(kappa), float(backtrack_step), float(alpha_min),
+                                                          ptr(out)), "hipkkt_kkt_system_step_length_gp")
+        return float(out[0])
+
+    def barrier_gp_dev(self, d_z, d_s, d_step_z, d_step_s, alpha):
+        """barrier_dev with every generalized power cone's barrier_dual + barrier_primal in the sum."""
+        out = np.zeros(2)
+        check(_lib.lib().hipkkt_kkt_system_barrier_gp(self.ks._h, C.c_void_p(d_z), C.c_void_p(d_s), C.c_void_p(d_step_z),
+                                                      C.c_void_p(d_step_s), float(alpha), ptr(out)), "hipkkt_kkt_system_barrier_gp")
+        return float(out[0]), float(out[1])
+
     # ---- residuals and termination scalars of a device-resident iterate, and the elementwise steps around them
     def residuals_dev(self, d_x, d_s, d_z, tau, d_rx, d_rz, d_rx_inf, d_rz_inf, d_Px, d_equil=None):
         """residuals_update! and the scalars info_update! reads, in one pass over K's image -> numpy array of 12:

@@ -388,6 +388,70 @@ int hipkkt_kkt_system_step_length_ns(hipkkt_kkt_t h, const double *d_step_z, con
 int hipkkt_kkt_system_barrier(hipkkt_kkt_t h, const double *d_z, const double *d_s, const double *d_step_z,
                               const double *d_step_s, double alpha, double out[2]);
 
+/* The same five operations for cone lists that hold a generalized power cone as well (coneops_genpowcone.jl), so that
+ * the iterate of such a problem stays in HBM too.  Entry points of their own: the nine above keep refusing what they
+ * refuse.  Covered: zero, nonnegative, second-order, PSD (side <= 48), exponential, power and generalized power cones in
+ * any order.  Same rules as the _ns block: they need hipkkt_kkt_system_init and -- except the unit start -- the cone
+ * scaling of a hipkkt_kkt_system_update* call; on a deferred-status handle or one with a PSD cone of side > 48 each
+ * returns HIPKKT_ERR_ARG with nothing enqueued and nothing written.  Inputs are never modified, outputs must not alias
+ * inputs, all work goes on the handle's stream.  On every row that is not a generalized power cone's each call gives,
+ * bit for bit, what its _ns counterpart gives on a handle with those cones alone: the same kernels are launched first,
+ * and on a handle without a generalized power cone the five calls ARE the _ns calls.  A generalized power cone of up to
+ * 512 rows is taken by one wave (four cones to a workgroup), a larger one by a workgroup of 256; every reduction has a
+ * fixed order (a lane its strided rows ascending, a butterfly over the lanes, the waves left to right) and there is no
+ * floating-point atomic, so two runs give the same bits. */
+/* unit_initialization! with the generalized power cones' start (coneops_genpowcone.jl:34-53): s_i = z_i =
+ * sqrt(1 + alpha_i) on the first dim1 rows of such a cone and 0 on the dim2 rows behind them; every other cone as
+ * hipkkt_kkt_system_unit_initialization.  Needs no cone scaling.  Two launches on the handle's stream, no
+ * synchronisation; d_s and d_z are outputs and must not alias each other. */
+int hipkkt_kkt_system_unit_initialization_gp(hipkkt_kkt_t h, double *d_s, double *d_z);
+
+/* affine_ds! over all cones: as hipkkt_kkt_system_affine_ds_ns, and a copy of s on the rows of a generalized power cone
+ * (coneops_genpowcone.jl:137-147).  d_out must not alias d_s; d_s is not modified; no synchronisation -- the result is
+ * ordered on the handle's stream like every other launch of the call's kernels. */
+int hipkkt_kkt_system_affine_ds_gp(hipkkt_kkt_t h, double *d_out, const double *d_s);
+
+/* The whole d.s of the combined step: as hipkkt_kkt_system_combined_ds_ns, and on the rows of a generalized power cone
+ * (combined_ds_shift!, coneops_genpowcone.jl:149-168)
+ *   out_i = s_i + sigma_mu * grad_i
+ * with grad = grad f*(z) as the scaling kernel stored it (what hipkkt_kkt_get_genpow returns).  There is no higher-order
+ * correction for this cone (the reference has it commented out): d_step_z, d_step_s and m_corr are read on the other
+ * cones' rows only.  d_z must be the z of the last hipkkt_kkt_system_update*.  d_out must not alias an input; no
+ * synchronisation. */
+int hipkkt_kkt_system_combined_ds_gp(hipkkt_kkt_t h, double *d_out, const double *d_step_z, const double *d_step_s,
+                                     const double *d_s, const double *d_z, double sigma_mu, double m_corr);
+
+/* step_length of the composite cone, WITHOUT max_step_fraction: stages 1 and 2 as hipkkt_kkt_system_step_length_ns
+ * (a = min(1, tau limit, kappa limit, symmetric limits); a0 = min(a, 1 - sqrt(eps))); stage 3 folds the minimum over every
+ * exponential, power AND generalized power cone's independent backtrack_search from a0 (coneops_genpowcone.jl:186-207):
+ * on z with is_dual_feasible (:272-292), on s with is_primal_feasible (:249-269) -- the first dim1 entries all > 0 and
+ *   exp(sum_i 2 alpha_i logsafe(v_i [/ alpha_i])) - ||v[dim1:]||^2 > 0.
+ * The order-free argument of the _ns call carries over: every search visits the same doubles a0 * backtrack_step^j, and
+ * the feasible set along a ray is an interval.  A trip of a search is one three-value reduction over the cone's rows (sum
+ * of logs, sum of squares, count of non-positive entries) that every thread of the cone's wave / workgroup receives, so
+ * the loop is uniform.  backtrack_step outside (0, 1) or alpha_min <= 0 (or NaN) is HIPKKT_ERR_ARG; the trip cap is
+ * floor(log(alpha_min) / log(backtrack_step)) + 2, after which the search gives 0; a NaN point is not in the cone.
+ * Inputs are not modified (nothing to alias: the result is the host double *alpha_out).  Synchronises once. */
+int hipkkt_kkt_system_step_length_gp(hipkkt_kkt_t h, const double *d_step_z, const double *d_step_s,
+                                     const double *d_z, const double *d_s, double step_tau, double step_kappa,
+                                     double tau, double kappa, double backtrack_step, double alpha_min,
+                                     double *alpha_out);
+
+/* The cone part of variables_barrier at (z', s') = (z + alpha step_z, s + alpha step_s): as hipkkt_kkt_system_barrier,
+ * with every generalized power cone's compute_barrier (coneops_genpowcone.jl:209-234) added to out[0]:
+ *   barrier_dual(z') (:313-333) = -logsafe(exp(sum 2 alpha_i logsafe(z'_i / alpha_i)) - ||z'[dim1:]||^2)
+ *                                 - sum (1 - alpha_i) logsafe(z'_i)
+ *   barrier_primal(s') = -barrier_dual(-g(s')) - (dim1 + 1), g = gradient_primal! (:393-426): for ||s'[dim1:]|| > eps
+ *   the root of the one-dimensional equation by _newton_raphson_genpowcone (:437-472, psi = 1 / (alpha . alpha)) --
+ *   the start is halved at most 64 times while f0 > 0 fails (the guard ipm._newton_raphson_genpowcone has; the reference
+ *   has it for the 3-row power cone only), then at most 100 one-sided Newton steps with the three stop tests of
+ *   coneops_nonsymmetric_common.jl:170-193; otherwise the closed form g_i = -(1 + alpha_i) / s'_i, g[dim1:] = 0.
+ * A Newton trip reduces f0 and f1 in one pass; a NaN leaves every loop.  out[1] = <z', s'> over all rows.  A point
+ * outside a cone gives +inf or NaN in out[0] and HIPKKT_OK.  Inputs are not modified (nothing to alias: out is a host
+ * array of 2 doubles).  Synchronises once. */
+int hipkkt_kkt_system_barrier_gp(hipkkt_kkt_t h, const double *d_z, const double *d_s, const double *d_step_z,
+                                 const double *d_step_s, double alpha, double out[2]);
+
 /* The first step of every iteration on an iterate kept in HBM: residuals_update! (residuals.jl:1-37) and the scalars
  * info_update! reads (the four dot products and the eight norm_scaled calls of info.jl:33-51), from the P, A the handle
  * holds inside K and the q, b of hipkkt_kkt_system_init -- the caller needs no copy of the matrices and no sparse mat-vec
