@@ -85,34 +85,6 @@ void launch_scale(double* K, const int* idx, double scale, int64_t n, hipStream_
     hipLaunchKernelGGL(k_scale, dim3(grid_for(n, 256)), dim3(256), 0, st, K, idx, scale, n);
 }
 
-// sparse second-order cones: K[u] = u*(-eta2), K[v] = v*(-eta2), D = (-eta2, +eta2)
-// (directldl_datamaps.jl:61-79: update then scale, which is the single product written here)
-__global__ void k_soc_columns(double* __restrict__ K, const int* __restrict__ mapU, const int* __restrict__ mapV,
-                              const int* __restrict__ mapD, const double* __restrict__ u,
-                              const double* __restrict__ v, const double* __restrict__ eta2,
-                              const int* __restrict__ soc_of_entry, int sparse_len, int nsparse)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < sparse_len) {
-        const double e2 = eta2[soc_of_entry[i]];
-        K[mapU[i]] = u[i] * (-e2);
-        K[mapV[i]] = v[i] * (-e2);
-    }
-    if (i < nsparse) {
-        K[mapD[2 * i]] = -eta2[i];
-        K[mapD[2 * i + 1]] = eta2[i];
-    }
-}
-void launch_soc_columns(double* K, const int* mapU, const int* mapV, const int* mapD, const double* u,
-                        const double* v, const double* eta2, const int* soc_of_entry, int sparse_len,
-                        int nsparse, hipStream_t st)
-{
-    int n = sparse_len > nsparse ? sparse_len : nsparse;
-    if (n <= 0) return;
-    hipLaunchKernelGGL(k_soc_columns, dim3((n + 255) / 256), dim3(256), 0, st, K, mapU, mapV, mapD, u, v, eta2,
-                       soc_of_entry, sparse_len, nsparse);
-}
-
 // ---- reductions: block max -> partial[], then one small block finishes
 __device__ inline double block_max_256(double v, double* sh)
 {

@@ -324,10 +324,6 @@ inline int chain_seg_wgs(const ChainSeg& s) { return chain_seg_wgs(s.nblock, s.n
 // ---- KKT value updates (kktsolver_directldl.jl:130-188, 211-245, 374-386)
 void launch_scatter(double* Kval, const int* idx, const double* vals, int64_t n, double scale, hipStream_t st);
 void launch_scale(double* Kval, const int* idx, double scale, int64_t n, hipStream_t st);
-// per sparse SOC t: K[mapU] = u * (-eta2), K[mapV] = v * (-eta2), K[mapD] = (-eta2, +eta2)
-void launch_soc_columns(double* Kval, const int* mapU, const int* mapV, const int* mapD,
-                        const double* u, const double* v, const double* eta2, const int* soc_of_entry,
-                        int sparse_len, int nsparse, hipStream_t st);
 // eps = c0 + c1 * max_i |Kval[diag[i]]|  (kktsolver_directldl.jl:297-310) -> *eps_out
 void launch_regularizer(const double* Kval, const int* diag, int N, double c0, double c1,
                         double* partial, double* eps_out, hipStream_t st);
