@@ -120,7 +120,9 @@ __global__ __launch_bounds__(256) void k_front_wave(FactorArgs A, int begin, int
     double* P = smem + (size_t)wv * slice;       // f x nc, ld f
     double* Us = P + f * nc;                     // nb x nb, ld nb
 
-    for (int i = lane; i < f * nc + nb * nb; i += 64) P[i] = 0.0;
+    // a pulled leaf (FrontDesc::pad bit 1; schedule.hpp: FactorLists) has no update block: its parent forms the entries
+    const bool pulled_leaf = (fd.pad & 2) != 0;
+    for (int i = lane; i < f * nc + (pulled_leaf ? 0 : nb * nb); i += 64) P[i] = 0.0;
     WAVE_FENCE();
     {   // K entries
         const int64_t e0 = fd.kptr;
@@ -210,7 +212,7 @@ __global__ __launch_bounds__(256) void k_front_wave(FactorArgs A, int begin, int
         if (r >= j) F[i] = P[i];
     }
     // update block: U(a,b) = Us(a,b) - sum_k L(a,k) d_k L(b,k), lane = row a
-    if (lane < nb) {
+    if (lane < nb && !pulled_leaf) {
         const int a = lane;
         for (int b = 0; b <= a; ++b) {
             double acc = 0.0;
@@ -241,7 +243,8 @@ __global__ __launch_bounds__(256) void k_front_tiny(FactorArgs A, int begin, int
     double* P = smem_t + grp * kTinySlice;        // f x nc, ld f
     double* Us = P + f * nc;                      // nb x nb, ld nb
 
-    for (int i = sub; i < f * nc + nb * nb; i += 8) P[i] = 0.0;
+    const bool pulled_leaf = (fd.pad & 2) != 0;         // (as in k_front_wave: no update block)
+    for (int i = sub; i < f * nc + (pulled_leaf ? 0 : nb * nb); i += 8) P[i] = 0.0;
     WAVE_FENCE();
     {
         const int64_t e0 = fd.kptr;
@@ -297,7 +300,7 @@ __global__ __launch_bounds__(256) void k_front_tiny(FactorArgs A, int begin, int
         const int j = i / f, r = i - j * f;
         if (r >= j) F[i] = P[i];
     }
-    if (sub < nb) {
+    if (sub < nb && !pulled_leaf) {
         const int a = sub;
         for (int b = 0; b <= a; ++b) {
             double acc = 0.0;
@@ -344,6 +347,71 @@ __device__ inline int64_t uniform_i64(int64_t v)
     const int hi = __builtin_amdgcn_readfirstlane((int)(v >> 32));
     return ((int64_t)hi << 32) | (uint32_t)lo;
 }
+// The pulled leaves' terms of one wave (schedule.hpp: FactorLists), chunks [c0, c1) of 64 terms, lane = term: the entry
+// U(a, b) = 0 - fma(l_a d, l_b, 0) of the leaf's update block -- the operations and roundings with which k_front_wave /
+// k_front_tiny form a one-column front's block, so the entry has the value it had as a stored number -- is formed from
+// the leaf's panel [d, l_0, l_1, ...] in the front store (one 64-byte line for a leaf of up to seven rows) and added to
+// dst[target].  Terms of one target sit in neighbouring lanes (a run, in child order); where a chunk has such runs (its
+// lane 0 says how many doubling steps the longest needs) they are summed in registers first -- a segmented scan over
+// the lanes, its order fixed by the lanes alone -- and the run's last lane adds the sum: no two lanes of an LDS add
+// instruction address one target, and every target's sum is a fixed function of the list.
+// kPullPF chunks in flight; the term loads run one group ahead of the gathers (the first group: `first`, which the
+// panel kernel fetches before it zeroes its panel).
+// Visibility: a pulled leaf sits in a one-wave launch, which has ENDED before any block-class launch above it begins
+// (the same stream, or the tile stream behind its fork event) -- plain loads, no scope qualifiers, in overlap mode too.
+constexpr int kPullPF = 4;
+struct PullGroup { uint32_t off[kPullPF], tg[kPullPF]; };
+__device__ __forceinline__ PullGroup pull_fetch(const PullTerm* __restrict__ terms, int c, int c1, int lane)
+{
+    PullGroup g;
+#pragma unroll
+    for (int q = 0; q < kPullPF; ++q) {
+        const PullTerm t = terms[((int64_t)min(c + q, c1 - 1) << 6) + lane];      // (c < c1)
+        g.off[q] = t.leaf_off;
+        g.tg[q] = (c + q < c1) ? t.tgt_ab : kPullNone;
+    }
+    return g;
+}
+__device__ __forceinline__ void apply_pulled(const PullTerm* __restrict__ terms, const double* __restrict__ fronts, double* dst,
+                                             int c0, int c1, int lane, PullGroup g)
+{
+    for (int c = c0; c < c1; c += kPullPF) {
+        double d[kPullPF], la[kPullPF], lb[kPullPF];
+#pragma unroll
+        for (int q = 0; q < kPullPF; ++q) {
+            const bool ok = g.tg[q] != kPullNone;
+            const double* __restrict__ L = fronts + g.off[q];
+            const int a = (g.tg[q] >> 15) & 63, b = (g.tg[q] >> 21) & 63;
+            d[q] = ok ? L[0] : 0.0;
+            la[q] = ok ? L[1 + a] : 0.0;
+            lb[q] = ok ? L[1 + b] : 0.0;
+        }
+        PullGroup gn = g;
+        if (c + kPullPF < c1) gn = pull_fetch(terms, c + kPullPF, c1, lane);
+#pragma unroll
+        for (int q = 0; q < kPullPF; ++q) {
+            if (c + q >= c1) break;                                                  // (uniform)
+            const bool ok = g.tg[q] != kPullNone;
+            double v = 0.0 - fma(la[q] * d[q], lb[q], 0.0);
+            const int nsteps = (__builtin_amdgcn_readfirstlane((int)g.tg[q]) >> 27) & 7;      // (lane 0 of a chunk always holds a term)
+            const int target = ok ? (int)(g.tg[q] & 0x7fff) : 0x8000 + lane;        // (an empty lane: a run of its own)
+            bool last = ok;
+            if (nsteps > 0) {
+                const int prev = __shfl_up(target, 1);
+                const unsigned long long heads = __ballot(lane == 0 || prev != target);
+                const int start = 63 - __builtin_clzll(heads & (~0ull >> (63 - lane)));      // first lane of this lane's run
+                for (int st = 0, dd = 1; st < nsteps; ++st, dd <<= 1) {
+                    const double vv = __shfl_up(v, dd);
+                    if (lane - dd >= start) v += vv;
+                }
+                last = ok && (lane == 63 || ((heads >> (lane + 1)) & 1ull));
+            }
+            if (last) lds_add(dst + target, v);
+        }
+        g = gn;
+    }
+}
+
 // SLICED: the workgroup holds the top nc rows and the front rows [r_lo, r_lo + rs) only (local row nc + r - r_lo)
 template <bool SLICED, bool COH>
 __device__ inline void apply_items_panel(const TreeDev& T, const double* __restrict__ upd, double* P, int f,
@@ -454,6 +522,8 @@ __global__ __launch_bounds__(BS) void k_panel(FactorArgs A, int begin)
     // this wave's slice of the children's extend-add items (host-cut, 16 slices) and its first 64 descriptors: issued
     // now, used in phase 3
     int64_t it0 = 0, it1 = 0;
+    int pt0 = 0, pt1 = 0;              // ... and of its pulled leaves' term chunks (whole fronts only: a sliced parent pulls
+    PullGroup pt_first{};              //     nothing) with the first group of terms
     ExtItem it_first{};
     {
         const int64_t* __restrict__ wc = T.wave_cut + (int64_t)(SLICED ? T.nsuper + begin + (int)blockIdx.x : s) * 17;
@@ -462,6 +532,13 @@ __global__ __launch_bounds__(BS) void k_panel(FactorArgs A, int begin)
             it0 = wc[wv * SPW];
             it1 = wc[min(16, (wv + 1) * SPW)];
             if (it1 > it0) it_first = T.items[min(it0 + lane, it1 - 1)];
+            if (!SLICED) {
+                pt0 = T.pwave_cut[(int64_t)s * 17 + wv * SPW];
+                pt1 = T.pwave_cut[(int64_t)s * 17 + min(16, (wv + 1) * SPW)];
+                pt0 = __builtin_amdgcn_readfirstlane(pt0);
+                pt1 = __builtin_amdgcn_readfirstlane(pt1);
+                if (pt1 > pt0) pt_first = pull_fetch(T.pterms, pt0, pt1, lane);
+            }
         }
     }
     // ---- 1. zero the panel (and fetch the pivot signs: the serial diagonal step must not wait for global memory)
@@ -546,6 +623,7 @@ __global__ __launch_bounds__(BS) void k_panel(FactorArgs A, int begin)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         A.stamps[A.stamp_row * 16 + 6] = wall_clock64();
     }
+    if (!SLICED && pt1 > pt0) apply_pulled(T.pterms, A.fronts, P, pt0, pt1, lane, pt_first);      // (before the regular pieces: a fixed order)
     if (it1 > it0) apply_items_panel<SLICED, OV>(T, A.upd, P, f, it0, it1, lane, nc, r_lo, rs, it_first,
                                              (A.stamps && blockIdx.x == 0 && wv == 0) ? A.stamps + A.stamp_row * 16 + 15 : nullptr);
     if (A.stamps && blockIdx.x == 0 && tid == 0) A.stamps[A.stamp_row * 16 + 7] = wall_clock64();
@@ -861,6 +939,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OV ? 3 : 4)
     // takes descriptor l, ONE vector load round -- so that after the product only (rel, value) load rounds remain
     const int64_t* __restrict__ tc = T.tile_cut + 5 * (int64_t)(tile_begin + tix);
     const int64_t i0 = tc[wv], i1 = tc[wv + 1];
+    const int pt0 = __builtin_amdgcn_readfirstlane(T.ptile_cut[5 * (int64_t)(tile_begin + tix) + wv]);
+    const int pt1 = __builtin_amdgcn_readfirstlane(T.ptile_cut[5 * (int64_t)(tile_begin + tix) + wv + 1]);
     static_assert(sizeof(SubItem) == 16, "SubItem is read as an int4");
     const int4* __restrict__ sit4 = reinterpret_cast<const int4*>(T.sitems);
     int4 mine = (i0 < i1) ? sit4[min(i0 + lane, i1 - 1)] : make_int4(0, 0, 0, 0);
@@ -870,6 +950,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OV ? 3 : 4)
         constexpr int PT = 16;
         const int rlo = nc + r0;
         double* ct = &Ct[0][0];
+        if (pt1 > pt0) apply_pulled(T.pterms, A.fronts, ct, pt0, pt1, lane, pull_fetch(T.pterms, pt0, pt1, lane));      // the pulled leaves' terms first (a fixed order)
         for (int64_t base = i0; base < i1; base += 64) {
             if (base > i0) mine = sit4[min(base + lane, i1 - 1)];
             const int n = (int)min((int64_t)64, i1 - base);

@@ -156,10 +156,10 @@ public:
             if (overlap_wanted()) for (size_t q = sch.ov_first; q < sch.launches.size(); ++q) ov_slices += sch.launches[q].slice_count;
             std::fprintf(stderr, "[hipkkt] N %d, %d supernodes in %zu levels (%zu launches), %d block-class fronts, %d of them in "
                          "%zu row slices; persistent solve set: last %zu launches, %d fronts on %d workgroups, %d (front, slice) tasks; "
-                         "factorisation overlap: last %zu launches (%d row slices in them)\n",
+                         "factorisation overlap: last %zu launches (%d row slices in them); pulled leaves: %lld (%lld terms)\n",
                          S.N, S.nsuper, S.levels.size(), sch.launches.size(), nblock, nsl_fronts, sch.slice_list.size(), sch.top_launches,
                          sch.top_count, sch.top_ntask > 0 ? sch.top_sgrid : sch.top_grid, sch.top_ntask, overlap_wanted() ? sch.launches.size() - sch.ov_first : (size_t)0,
-                         ov_slices);
+                         ov_slices, (long long)n_factor_pulled, (long long)n_factor_terms);
             {
                 int ntall_all = 0;
                 for (const Launch& L : sch.launches) ntall_all += L.ntall;
@@ -1215,6 +1215,9 @@ private:
     DBuf<int64_t> d_wave_cut;
     DBuf<int64_t> d_sitems;      // SubItem = 2 x int64
     DBuf<int64_t> d_tile_cut;
+    DBuf<int64_t> d_pterms;      // PullTerm = one int64
+    DBuf<int> d_pwave_cut, d_ptile_cut;
+    int64_t n_factor_pulled = 0, n_factor_terms = 0;
     DBuf<int64_t> d_desc;        // FrontDesc = 8 x int64
     DBuf<int64_t> d_sdesc;       // FrontDesc per row slice of the sliced panels
     std::vector<int64_t> slice_kptr;              // per slice: its K scatter list in ksrc / kdst
@@ -1250,7 +1253,8 @@ private:
         t.dense_off = d_dense_off.p; t.item_ptr = d_item_ptr.p; t.items = (const ExtItem*)d_items.p; t.gl_ptr = d_item_ptr.p; t.gl_src = d_gl_src.p; t.udst = d_udst.p;
         t.glm_ptr = d_glm_ptr.p; t.udst_m = d_udst_m.p; t.hp_col = d_hp_col.p; t.hp_row = d_hp_row.p; t.hp_lidx = d_hp_lidx.p; t.pr_ptr = d_pr_ptr.p; t.pr_slot = d_pr_slot.p;
         t.cut_ptr = d_cut_ptr.p; t.cuts = d_cuts.p; t.wave_cut = d_wave_cut.p; t.tinv_off = d_tinv_off.p;
-        t.sitems = (const SubItem*)d_sitems.p; t.tile_cut = d_tile_cut.p; t.desc = (const FrontDesc*)d_desc.p; t.sdesc = (const FrontDesc*)d_sdesc.p;
+        t.sitems = (const SubItem*)d_sitems.p; t.tile_cut = d_tile_cut.p;
+        t.pterms = (const PullTerm*)d_pterms.p; t.pwave_cut = d_pwave_cut.p; t.ptile_cut = d_ptile_cut.p; t.desc = (const FrontDesc*)d_desc.p; t.sdesc = (const FrontDesc*)d_sdesc.p;
         t.spos = d_spos.p; t.sn_parent = d_sn_parent.p;
         return t;
     }
@@ -1313,6 +1317,9 @@ private:
 
     void upload(const std::vector<int>& dsigns)
     {
+        // the factorisation's extend-add work lists and which leaves their parents pull (schedule.cpp)
+        FactorLists fl = build_factor_lists(S, sch);
+        n_factor_pulled = fl.n_pulled; n_factor_terms = fl.n_terms;
         // leaves with one column and a short row list, pulled by their parents in the many-column sweeps (see the gather
         // lists below; HIPKKT_PULL_LEAVES=0: none)
         const bool pull_on = knobs().pull_leaves;
@@ -1437,7 +1444,7 @@ private:
                 d.front_off = S.front_off[s]; d.upd_off = S.upd_off[s]; d.w_off = toff[s]; d.rp = S.rowptr[s];
                 d.kptr = S.kptr[s]; d.s = s; d.c0 = S.sn_start[s]; d.nc = S.sn_start[s + 1] - S.sn_start[s];
                 d.nb = (int)(S.rowptr[s + 1] - S.rowptr[s]); d.nk = (int)(S.kptr[s + 1] - S.kptr[s]);
-                d.pad = pulled[(size_t)s] ? 1 : 0;          // (launch records: bit 0 = a pulled leaf of the many-column sweeps, see below)
+                d.pad = (pulled[(size_t)s] ? 1 : 0) | (fl.pulled[(size_t)s] ? 2 : 0);     // (launch records: bit 0 = a pulled leaf of the many-column sweeps, see below; bit 1 = of the factorisation)
                 desc[q] = d;
             }
             std::vector<int64_t> rawd(desc.size() * 8);
@@ -1532,120 +1539,16 @@ private:
                              hist[0], hist[1], hist[2], hist[3], hist[4], hist[5], (long long)gmax, fronts_over8, fronts_over12, nf);
             }
             d_item_ptr.upload(ptr);
-            // extend-add items of the PANEL columns (the update-block columns go through the Schur sub-items):
-            // one record per child update column and 64-row piece of it, grouped by the (global, permuted) panel
-            // column it lands in, children in fixed order -- a wave handles eight pieces at a time, all of them
-            // a single load round, however long the child's column is
+            // extend-add items of the PANEL columns and Schur sub-items of the update-block columns: schedule.cpp
             static_assert(sizeof(ExtItem) == 32, "ExtItem layout");
-            // DENSE CHILD: a child whose update block IS its parent's whole front (same rows in the same order: the
-            // previous panel of a supernode that was cut into panels, the lower front of a chain) needs no work lists at
-            // all -- parent entry (r, j) receives child entry (r, j).  The panel kernel and the Schur tiles add it as a
-            // dense block (coalesced loads, no descriptors, no row lookups); its pieces stay out of both lists.
-            std::vector<int> dense_child((size_t)S.nsuper, -1);
-            std::vector<int64_t> dense_off((size_t)S.nsuper, -1);
-            const bool dense_on = knobs().dense_child;
-            int64_t n_dense = 0;
-            for (int p = 0; dense_on && p < S.nsuper; ++p) {
-                if (sch.tile_base[p] < 0) continue;                              // block-class parents only
-                const int fp = front_size(p);
-                for (int e = S.child_ptr[p]; e < S.child_ptr[p + 1]; ++e) {
-                    const int c = S.child_idx[e];
-                    const int nbc = (int)(S.rowptr[c + 1] - S.rowptr[c]);
-                    if (nbc != fp) continue;
-                    bool ident = true;
-                    for (int q = 0; ident && q < nbc; ++q) ident = S.rel[S.rowptr[c] + q] == q;
-                    if (!ident) continue;
-                    dense_child[(size_t)p] = c;
-                    dense_off[(size_t)p] = S.upd_off[c];
-                    ++n_dense;
-                    break;
-                }
-            }
-            d_dense_off.upload(dense_off);
-            if (knobs().verbose) std::fprintf(stderr, "[hipkkt] dense children: %lld\n", (long long)n_dense);
-            std::vector<int64_t> pptr((size_t)S.N + 1, 0);
-            for (int c = 0; c < S.nsuper; ++c) {
-                int p = S.sn_parent[c];
-                if (p < 0 || dense_child[(size_t)p] == c) continue;
-                const int pnc = S.sn_start[p + 1] - S.sn_start[p];
-                const int nbc = (int)(S.rowptr[c + 1] - S.rowptr[c]);
-                for (int b = 0; b < nbc; ++b) {
-                    const int r = S.rel[S.rowptr[c] + b];
-                    if (r >= pnc) break;                                   // rel ascends: the rest lands in U
-                    pptr[(size_t)S.sn_start[p] + r + 1] += (nbc - b + 63) / 64;
-                }
-            }
-            for (int i = 0; i < S.N; ++i) pptr[i + 1] += pptr[i];
-            std::vector<ExtItem> items((size_t)pptr[S.N]);
-            {
-                std::vector<int64_t> nxt(pptr.begin(), pptr.end() - 1);
-                for (int p = 0; p < S.nsuper; ++p) {
-                    const int pnc = S.sn_start[p + 1] - S.sn_start[p];
-                    for (int e = S.child_ptr[p]; e < S.child_ptr[p + 1]; ++e) {
-                        int c = S.child_idx[e];
-                        if (dense_child[(size_t)p] == c) continue;
-                        int nbc = (int)(S.rowptr[c + 1] - S.rowptr[c]);
-                        for (int b = 0; b < nbc; ++b) {
-                            int64_t q = S.rowptr[c] + b;
-                            const int r = S.rel[q];
-                            if (r >= pnc) break;
-                            for (int a = b; a < nbc; a += 64) {
-                                ExtItem it;
-                                it.uoff = S.upd_off[c] + (int64_t)b * nbc + a;
-                                it.relstart = (int)(S.rowptr[c] + a);
-                                it.cnt = std::min(64, nbc - a);
-                                it.rfirst = S.rel[S.rowptr[c] + a];
-                                it.rlast = S.rel[S.rowptr[c] + a + it.cnt - 1];
-                                it.tcol = r;
-                                it.pad = 0;
-                                items[(size_t)nxt[(size_t)S.sn_start[p] + r]++] = it;
-                            }
-                        }
-                    }
-                }
-            }
-            // 16 slices of each supernode's panel items, cut on column boundaries
-            std::vector<int64_t> wcut(((size_t)S.nsuper + sch.slice_list.size()) * 17, 0);
-            for (int s = 0; s < S.nsuper; ++s) {
-                const int nc = S.sn_start[s + 1] - S.sn_start[s];
-                const int64_t* cp = pptr.data() + S.sn_start[s];      // nc + 1 column pointers
-                const int64_t I0 = cp[0], I1 = cp[nc];
-                int j = 0;
-                for (int w = 0; w < 16; ++w) {
-                    const int64_t target = I0 + ((I1 - I0) * w) / 16;
-                    while (j < nc && cp[j] < target) ++j;
-                    wcut[(size_t)s * 17 + w] = cp[j];
-                }
-                wcut[(size_t)s * 17 + 16] = I1;
-            }
-            // A row slice of a sliced front gets an item list of its own: the pieces that reach its rows or the top block,
-            // in the same order, cut into 16 wave slices of whole columns again -- instead of every slice walking the whole
-            // front's list in rounds that are mostly skipped pieces.
-            for (size_t q = 0; q < sch.slice_list.size(); ++q) {
-                const int s = sch.slice_list[q][0], sl = sch.slice_list[q][1], nsl = sch.slice_list[q][2];
-                const int ff = front_size(s), nc = S.sn_start[s + 1] - S.sn_start[s], nb = ff - nc;
-                const int rsmax = (nb + nsl - 1) / nsl, r_lo = nc + sl * rsmax;
-                const int rs = std::max(0, std::min(rsmax, ff - r_lo));
-                const int64_t* cp = pptr.data() + S.sn_start[s];
-                std::vector<int64_t> scp((size_t)nc + 1);
-                for (int j = 0; j < nc; ++j) {
-                    scp[(size_t)j] = (int64_t)items.size();
-                    for (int64_t it = cp[j]; it < cp[j + 1]; ++it) {
-                        const ExtItem e = items[(size_t)it];
-                        if (e.rfirst >= nc && (e.rlast < r_lo || e.rfirst >= r_lo + rs)) continue;
-                        items.push_back(e);
-                    }
-                }
-                scp[(size_t)nc] = (int64_t)items.size();
-                const int64_t I0 = scp[0], I1 = scp[(size_t)nc];
-                int j = 0;
-                int64_t* w = wcut.data() + ((size_t)S.nsuper + q) * 17;
-                for (int k = 0; k < 16; ++k) {
-                    const int64_t target = I0 + ((I1 - I0) * k) / 16;
-                    while (j < nc && scp[(size_t)j] < target) ++j;
-                    w[k] = scp[(size_t)j];
-                }
-                w[16] = I1;
+            const std::vector<ExtItem>& items = fl.items;
+            const std::vector<int64_t>& wcut = fl.wcut;
+            d_dense_off.upload(fl.dense_off);
+            if (knobs().verbose) {
+                int64_t n_dense = 0;
+                for (int c : fl.dense_child) n_dense += c >= 0;
+                std::fprintf(stderr, "[hipkkt] dense children: %lld\n", (long long)n_dense);
+                std::fprintf(stderr, "[hipkkt] pulled leaves' terms: %zu chunks of 64, deepest stack %d\n", fl.pterms.size() / 64, fl.max_depth);
             }
             std::vector<int64_t> raw(std::max<size_t>(items.size(), 1) * 4);
             std::memcpy(raw.data(), items.data(), items.size() * sizeof(ExtItem));
@@ -1665,63 +1568,10 @@ private:
                     }
                 }
             }
-            // Schur sub-items: every child update column that lands in a U column, cut at the parent's
-            // 64-row tile boundaries, grouped by (tile, tile column), children in fixed order
             static_assert(sizeof(SubItem) == 16, "SubItem layout");
-            const int64_t ntile = (int64_t)sch.tiles.size();
-            std::vector<int64_t> cnt((size_t)ntile * 64 + 1, 0);
-            auto for_each_sub = [&](auto&& fn) {
-                for (int p = 0; p < S.nsuper; ++p) {
-                    if (sch.tile_base[p] < 0) continue;
-                    const int pnc = S.sn_start[p + 1] - S.sn_start[p];
-                    for (int e = S.child_ptr[p]; e < S.child_ptr[p + 1]; ++e) {
-                        const int c = S.child_idx[e];
-                        if (dense_child[(size_t)p] == c) continue;
-                        const int nbc = (int)(S.rowptr[c + 1] - S.rowptr[c]);
-                        const int* rl = S.rel.data() + S.rowptr[c];
-                        for (int b = 0; b < nbc; ++b) {
-                            if (rl[b] < pnc) continue;
-                            const int j = rl[b] - pnc, tj = j >> 6;
-                            int a = b;
-                            while (a < nbc) {
-                                const int ti = (rl[a] - pnc) >> 6;
-                                int a2 = a;
-                                while (a2 < nbc && ((rl[a2] - pnc) >> 6) == ti) ++a2;
-                                const int64_t tile = sch.tile_base[p] + (int64_t)ti * (ti + 1) / 2 + tj;
-                                fn(tile, j & 63, c, b, a, a2 - a, nbc);
-                                a = a2;
-                            }
-                        }
-                    }
-                }
-            };
-            for_each_sub([&](int64_t tile, int q, int, int, int, int, int) { cnt[tile * 64 + q + 1]++; });
-            for (size_t i = 0; i + 1 < cnt.size(); ++i) cnt[i + 1] += cnt[i];
-            std::vector<SubItem> sit((size_t)cnt.back());
-            {
-                std::vector<int64_t> nx(cnt.begin(), cnt.end() - 1);
-                for_each_sub([&](int64_t tile, int q, int c, int b, int a, int n, int nbc) {
-                    SubItem si;
-                    si.uoff = S.upd_off[c] + (int64_t)b * nbc + a;
-                    si.relstart = (int)(S.rowptr[c] + a);
-                    si.cnt = (unsigned char)n;
-                    si.qcol = (unsigned char)q;
-                    si.pad = 0;
-                    sit[(size_t)nx[tile * 64 + q]++] = si;
-                });
-            }
-            std::vector<int64_t> tcut((size_t)ntile * 5 + 5, 0);
-            for (int64_t t = 0; t < ntile; ++t) {
-                const int64_t* cp = cnt.data() + t * 64;       // 65 column pointers of this tile
-                const int64_t I0 = cp[0], I1 = cp[64];
-                int q = 0;
-                for (int w = 0; w < 4; ++w) {
-                    const int64_t target = I0 + ((I1 - I0) * w) / 4;
-                    while (q < 64 && cp[q] < target) ++q;
-                    tcut[t * 5 + w] = cp[q];
-                }
-                tcut[t * 5 + 4] = I1;
-            }
+            const std::vector<SubItem>& sit = fl.sit;
+            std::vector<int64_t>& tcut = fl.tcut;
+            std::vector<int>& ptcut = fl.ptcut;
             std::vector<int64_t> tiles_up(sch.tiles);       // (the tiles in the order they are launched in)
             {
                 // XCD-aware launch order of a wide level's tiles (HIPKKT_TILE_XCD=n: launches with at least n fronts;
@@ -1735,6 +1585,7 @@ private:
                 const int tile_xcd = knobs().tile_xcd;
                 if (tile_xcd > 0) {
                     std::vector<int64_t> nc2(tcut);
+                    std::vector<int> pc2(ptcut);
                     for (const Launch& L : sch.launches) {
                         if (L.small || L.count < tile_xcd || L.ntiles <= 0) continue;
                         // the launch's fronts and their (contiguous) logical tile ranges
@@ -1757,12 +1608,14 @@ private:
                                         const int64_t from = rng[x].first + j;
                                         tiles_up[(size_t)pos] = sch.tiles[(size_t)from];
                                         for (int w = 0; w < 5; ++w) nc2[(size_t)pos * 5 + w] = tcut[(size_t)from * 5 + w];
+                                        for (int w = 0; w < 5; ++w) pc2[(size_t)pos * 5 + w] = ptcut[(size_t)from * 5 + w];
                                         ++pos;
                                     }
                         }
                         if (pos != (int64_t)L.tile_begin + L.ntiles) throw std::runtime_error("tile permutation lost a tile");
                     }
                     tcut.swap(nc2);
+                    ptcut.swap(pc2);
                 }
             }
             d_tiles.upload(tiles_up);
@@ -1770,6 +1623,25 @@ private:
             std::memcpy(raw2.data(), sit.data(), sit.size() * sizeof(SubItem));
             d_sitems.upload(raw2);
             d_tile_cut.upload(tcut);
+#ifdef HIPKKT_EXPERIMENTS
+            // EXPERIMENT (timing only, WRONG RESULTS; never in the default build): the pulled leaves' items and sub-items are
+            // gone and their update blocks are not stored, but nobody forms their terms either -- what the factorisation
+            // would take if the leaves' extend-add cost nothing: the ceiling of HIPKKT_PULL_FACTOR_LEAVES
+            if (std::getenv("HIPKKT_EXPERIMENT_DROP_LEAF_UPDATES")) {
+                fl.pterms.clear();
+                std::fill(fl.pwcut.begin(), fl.pwcut.end(), 0);
+                std::fill(ptcut.begin(), ptcut.end(), 0);
+            }
+#endif
+            {   // the pulled leaves' terms (PullTerm = one int64) and their chunk ranges per wave slice / tile wave
+                static_assert(sizeof(PullTerm) == 8, "PullTerm layout");
+                std::vector<int64_t> rawp(std::max<size_t>(fl.pterms.size(), 1), 0);
+                std::memcpy(rawp.data(), fl.pterms.data(), fl.pterms.size() * sizeof(PullTerm));
+                d_pterms.upload(rawp);
+                if (fl.pwcut.empty()) fl.pwcut.push_back(0);
+                d_pwave_cut.upload(fl.pwcut);
+                d_ptile_cut.upload(ptcut);
+            }
             d_gl_src.upload(gsrc);
             build_records(ptr, gsrc);
             // where each contribution entry sits in its receiver's gather list (solve_multi's layout)
@@ -2156,6 +2028,14 @@ int hipkkt_symbolic_analyse(int64_t N, const int64_t* colptr, const int64_t* row
                              "upd %.2f MB flops %.1f M | panels by LDS <=52K %d, <=79K %d, more %d\n", l, cnt, n8, n64, fmax, ncmax, cols, panel * 8e-6,
                              upd * 8e-6, flops * 1e-6, lds3, lds2, lds1);
             }
+        }
+        if (knobs().dump_levels) {          // ... and the extend-add pieces per parent level, for the schedule of a 256-CU device
+            DeviceLimits dev;
+            dev.top_solve_capacity = [](size_t, bool) { return 240; };
+            dev.top_solve_capacity_nr = [](size_t, int) { return 240; };
+            dev.top_solve_sliced_capacity = [](size_t, int) { return 240; };
+            const Schedule sch = build_schedule(S, dev, opt.panel_cap, std::max(1, opt.panel_max_slices));
+            std::fputs(describe_pieces(S, sch, build_factor_lists(S, sch)).c_str(), stderr);
         }
         if (knobs().dump_subtrees) {        // diagnostic: what the subtrees below a cut level look like (host only)
             {

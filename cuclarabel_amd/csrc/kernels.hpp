@@ -49,23 +49,7 @@ inline hipError_t set_max_lds(K kernel, int bytes)
     return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
 }
 
-struct ExtItem {                 // a piece (<= 64 rows) of one child update column that lands in a panel column; 32 bytes
-    int64_t uoff;                // offset in the update store of the piece's first entry U_c(a, b)
-    int relstart;                // index into rel[] of the child's row a
-    int cnt;                     // rows in the piece
-    int rfirst, rlast;           // parent-local target rows of the piece's first and last entry (row slices skip
-                                 // pieces that miss their row range without touching rel[])
-    int tcol;                    // parent-local column this item lands in
-    int pad;
-};
-
-struct SubItem {                 // a child update column restricted to one 64-row tile of the parent's U; 16 bytes
-    int64_t uoff;                // offset in the update store of the first entry
-    int relstart;                // index into rel[] of the first row
-    unsigned char cnt;           // rows (1..64)
-    unsigned char qcol;          // column inside the tile (0..63)
-    unsigned short pad;
-};
+// (ExtItem, SubItem -- the extend-add work lists' records, built by schedule.cpp -- and PullTerm: launch_shapes.hpp)
 
 struct FrontDesc {               // everything a kernel needs to know about one front, in launch order; 64 bytes
     int64_t front_off;           // panel store offset
@@ -161,6 +145,12 @@ struct TreeDev {                 // device copies of the symbolic structure
     // wave w of the tile's workgroup takes [tile_cut[5t+w], tile_cut[5t+w+1]) -- whole columns
     const SubItem* sitems;
     const int64_t* tile_cut;     // 5 per tile
+    // the factorisation's pulled leaves (schedule.hpp: FactorLists; FrontDesc::pad bit 1 marks such a leaf): chunks of 64
+    // terms; wave slice w of front s walks chunks [pwave_cut[17 s + w], pwave_cut[17 s + w + 1]), wave w of the tile at
+    // launch position t chunks [ptile_cut[5 t + w], ptile_cut[5 t + w + 1])
+    const PullTerm* pterms;
+    const int* pwave_cut;
+    const int* ptile_cut;
 };
 
 struct FactorArgs {

@@ -40,6 +40,7 @@ namespace hipkkt {
     FLAG_ON(dense_child, "HIPKKT_DENSE_CHILD")              /* a child whose update block is its parent's whole front is added as a dense block */ \
     KNOB(int, tile_xcd, "HIPKKT_TILE_XCD", 150)             /* launches of at least this many fronts deal a front's tiles to one XCD (0: off) */ \
     FLAG_ON(pull_leaves, "HIPKKT_PULL_LEAVES")              /* many-column sweeps: one-column leaves are pulled by their parents */     \
+    FLAG_ON(pull_factor_leaves, "HIPKKT_PULL_FACTOR_LEAVES") /* factorisation: block-class parents form their one-column leaves' update entries themselves (schedule.hpp: FactorLists); 0: stored update blocks */ \
     FLAG_ON(packed, "HIPKKT_PACKED")                        /* packed sweep records (kernels.hpp: SolveHdr); 0: the legacy layout */    \
     KNOB(long long, packed_max_mb, "HIPKKT_PACKED_MAX_MB", 4096) /* ... unless they would exceed this many MB */                      \
     /* ---- factorisation */                                                                                                           \

@@ -39,6 +39,40 @@ inline size_t solve_lds_bytes(int fmax, int ncmax)
     return (fwd > bwd ? fwd : bwd) * sizeof(double);
 }
 
+// ---- the factorisation's extend-add work lists (built on the host: schedule.cpp, build_factor_lists; walked by
+// factor_kernels.hip)
+struct ExtItem {                 // a piece (<= 64 rows) of one child update column that lands in a panel column; 32 bytes
+    int64_t uoff;                // offset in the update store of the piece's first entry U_c(a, b)
+    int relstart;                // index into rel[] of the child's row a
+    int cnt;                     // rows in the piece
+    int rfirst, rlast;           // parent-local target rows of the piece's first and last entry (row slices skip
+                                 // pieces that miss their row range without touching rel[])
+    int tcol;                    // parent-local column this item lands in
+    int pad;
+};
+
+struct SubItem {                 // a child update column restricted to one 64-row tile of the parent's U; 16 bytes
+    int64_t uoff;                // offset in the update store of the first entry
+    int relstart;                // index into rel[] of the first row
+    unsigned char cnt;           // rows (1..64)
+    unsigned char qcol;          // column inside the tile (0..63)
+    unsigned short pad;
+};
+
+// A PULLED LEAF (schedule.cpp: build_factor_lists) stores no update block: its parent forms the entries it needs,
+// U(a, b) = -(l_a d) l_b, from the leaf's panel in the front store ([d, l_0 .. l_nb-1], one column).  One term per entry,
+// eight bytes: the leaf's offset in the front store and target | a << 15 | b << 21, the target being the entry's place
+// in the parent's LDS image (the panel's trapezoid index, or qcol * 65 + row of a Schur tile; below 2^15: a CU's LDS
+// holds 20 480 doubles).  Terms come in chunks of 64, lane = term; the terms of one target are neighbours (a run).  Lane 0
+// of a chunk carries in bits 27..29 the doubling steps that sum the chunk's longest run (0: no two terms share a
+// target).  tgt_ab = kPullNone: the lane has no term.
+struct PullTerm {
+    uint32_t leaf_off;
+    uint32_t tgt_ab;
+};
+constexpr uint32_t kPullNone = 0xffffffffu;
+static_assert(sizeof(PullTerm) == 8, "PullTerm layout");
+
 // most fronts the persistent top-of-tree kernel takes (every workgroup resident: solve_kernels.hip, k_top_solve)
 constexpr int kTopMaxFronts = 480;
 

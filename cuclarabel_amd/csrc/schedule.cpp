@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <stdexcept>
+#include <unordered_map>
 
 namespace hipkkt {
 
@@ -552,6 +553,381 @@ std::string describe_launches(const SweepPlan& p, const Schedule& sch)
         }
         out += buf;
     }
+    return out;
+}
+
+// ---- the factorisation's extend-add work lists (schedule.hpp: FactorLists)
+namespace {
+// parts + 1 cut positions (column indices) of n columns whose pieces start at cp[0 .. n] and which hold tp[j] pulled
+// terms each: equal shares of 64 x pieces + terms.  Without terms: the cut on pieces alone, as it has always been.
+void cut_columns(const int64_t* cp, const int64_t* tp, int n, int parts, int* col_out)
+{
+    int64_t nterms = 0;
+    for (int j = 0; tp && j < n; ++j) nterms += tp[j];
+    const int64_t I0 = cp[0], I1 = cp[n];
+    int j = 0;
+    if (nterms == 0) {
+        for (int w = 0; w < parts; ++w) {
+            const int64_t target = I0 + ((I1 - I0) * w) / parts;
+            while (j < n && cp[j] < target) ++j;
+            col_out[w] = j;
+        }
+    } else {
+        const int64_t total = 64 * (I1 - I0) + nterms;
+        int64_t before = 0;                                  // weight of columns [0, j)
+        for (int w = 0; w < parts; ++w) {
+            const int64_t target = (total * w) / parts;
+            while (j < n && before < target) { before += 64 * (cp[j + 1] - cp[j]) + tp[j]; ++j; }
+            col_out[w] = j;
+        }
+    }
+    col_out[parts] = n;
+}
+struct RawTerm { uint32_t leaf_off, tgt_ab; };
+// the terms of one owner (the wave slices of a panel that one wave walks, a wave of a tile), in child order -> chunks of
+// 64 behind `out`: sorted by target (a target's terms stay in child order), packed densely
+void emit_runs(const RawTerm* t, int n, std::vector<PullTerm>& out, int64_t& n_stacked, int& max_depth)
+{
+    if (n == 0) return;
+    std::vector<int> order((size_t)n);
+    for (int i = 0; i < n; ++i) order[(size_t)i] = i;
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return (t[a].tgt_ab & 0x7fff) < (t[b].tgt_ab & 0x7fff); });
+    const size_t first = out.size();
+    int depth = 0;
+    for (int q = 0; q < n; ++q) {
+        const RawTerm& r = t[order[(size_t)q]];
+        const bool same = q > 0 && (t[order[(size_t)q - 1]].tgt_ab & 0x7fff) == (r.tgt_ab & 0x7fff);
+        depth = same ? depth + 1 : 1;
+        n_stacked += same;
+        max_depth = std::max(max_depth, depth);
+        out.push_back(PullTerm{r.leaf_off, r.tgt_ab});
+    }
+    while (out.size() % 64) out.push_back(PullTerm{0u, kPullNone});
+    for (size_t c = first; c < out.size(); c += 64) {        // the doubling steps of the chunk's longest run, into lane 0
+        int longest = 1, run = 1;
+        for (size_t l = 1; l < 64 && out[c + l].tgt_ab != kPullNone; ++l) {
+            run = (out[c + l].tgt_ab & 0x7fff) == (out[c + l - 1].tgt_ab & 0x7fff) ? run + 1 : 1;
+            longest = std::max(longest, run);
+        }
+        uint32_t steps = 0;
+        while ((1 << steps) < longest) ++steps;
+        out[c].tgt_ab |= steps << 27;
+    }
+}
+}  // namespace
+
+FactorLists build_factor_lists(const Symbolic& S, const Schedule& sch)
+{
+    FactorLists fl;
+    const size_t ns = (size_t)S.nsuper;
+    auto fsize = [&](int s) { return front_size(S, s); };
+    // DENSE CHILD: a child whose update block IS its parent's whole front (same rows in the same order: the
+    // previous panel of a supernode that was cut into panels, the lower front of a chain) needs no work lists at
+    // all -- parent entry (r, j) receives child entry (r, j).  The panel kernel and the Schur tiles add it as a
+    // dense block (coalesced loads, no descriptors, no row lookups); its pieces stay out of both lists.
+    std::vector<int>& dense_child = fl.dense_child;
+    dense_child.assign(ns, -1);
+    fl.dense_off.assign(ns, -1);
+    const bool dense_on = knobs().dense_child;
+    for (int p = 0; dense_on && p < S.nsuper; ++p) {
+        if (sch.tile_base[p] < 0) continue;                              // block-class parents only
+        const int fp = fsize(p);
+        for (int e = S.child_ptr[p]; e < S.child_ptr[p + 1]; ++e) {
+            const int c = S.child_idx[e];
+            const int nbc = (int)(S.rowptr[c + 1] - S.rowptr[c]);
+            if (nbc != fp) continue;
+            bool ident = true;
+            for (int q = 0; ident && q < nbc; ++q) ident = S.rel[S.rowptr[c] + q] == q;
+            if (!ident) continue;
+            dense_child[(size_t)p] = c;
+            fl.dense_off[(size_t)p] = S.upd_off[c];
+            break;
+        }
+    }
+    // PULLED LEAVES (the rule: schedule.hpp)
+    std::vector<char>& pulled = fl.pulled;
+    pulled.assign(ns, 0);
+    if (knobs().pull_factor_leaves && S.front_store < ((int64_t)1 << 32)) {      // (a term keeps the leaf's offset in 32 bits)
+        std::vector<char> in_small(ns, 0), sliced(ns, 0);
+        for (const Launch& L : sch.launches)
+            if (L.small) for (int t = L.begin; t < L.begin + L.count; ++t) in_small[(size_t)sch.sched[(size_t)t]] = 1;
+        for (const auto& sl : sch.slice_list) sliced[(size_t)sl[0]] = 1;
+        for (int c = 0; c < S.nsuper; ++c) {
+            const int p = S.sn_parent[c];
+            const int nb = (int)(S.rowptr[c + 1] - S.rowptr[c]);
+            if (p < 0 || S.sn_start[c + 1] - S.sn_start[c] != 1 || S.child_ptr[c + 1] != S.child_ptr[c] || !in_small[(size_t)c]) continue;
+            if (nb < 1 || nb > 63 || sch.tile_base[p] < 0 || sliced[(size_t)p] || dense_child[(size_t)p] == c) continue;
+            pulled[(size_t)c] = 1;
+            ++fl.n_pulled;
+        }
+    }
+    auto listed = [&](int p, int c) { return dense_child[(size_t)p] != c && !pulled[(size_t)c]; };
+    // ---- panel items: one record per child update column and 64-row piece of it, grouped by the (global, permuted) panel
+    // column it lands in, children in fixed order -- a wave handles sixteen pieces at a time, all of them a single load
+    // round, however long the child's column is
+    std::vector<int64_t>& pptr = fl.pptr;
+    pptr.assign((size_t)S.N + 1, 0);
+    std::vector<int64_t> pterm_col((size_t)S.N, 0);          // pulled terms per panel column
+    for (int c = 0; c < S.nsuper; ++c) {
+        const int p = S.sn_parent[c];
+        if (p < 0 || dense_child[(size_t)p] == c) continue;
+        const int pnc = S.sn_start[p + 1] - S.sn_start[p];
+        const int nbc = (int)(S.rowptr[c + 1] - S.rowptr[c]);
+        for (int b = 0; b < nbc; ++b) {
+            const int r = S.rel[S.rowptr[c] + b];
+            if (r >= pnc) break;                                   // rel ascends: the rest lands in U
+            if (pulled[(size_t)c]) pterm_col[(size_t)S.sn_start[p] + r] += nbc - b;
+            else pptr[(size_t)S.sn_start[p] + r + 1] += (nbc - b + 63) / 64;
+        }
+    }
+    for (int i = 0; i < S.N; ++i) pptr[(size_t)i + 1] += pptr[(size_t)i];
+    std::vector<ExtItem>& items = fl.items;
+    items.resize((size_t)pptr[(size_t)S.N]);
+    {
+        std::vector<int64_t> nxt(pptr.begin(), pptr.end() - 1);
+        for (int p = 0; p < S.nsuper; ++p) {
+            const int pnc = S.sn_start[p + 1] - S.sn_start[p];
+            for (int e = S.child_ptr[p]; e < S.child_ptr[p + 1]; ++e) {
+                const int c = S.child_idx[e];
+                if (!listed(p, c)) continue;
+                const int nbc = (int)(S.rowptr[c + 1] - S.rowptr[c]);
+                for (int b = 0; b < nbc; ++b) {
+                    const int64_t q = S.rowptr[c] + b;
+                    const int r = S.rel[q];
+                    if (r >= pnc) break;
+                    for (int a = b; a < nbc; a += 64) {
+                        ExtItem it;
+                        it.uoff = S.upd_off[c] + (int64_t)b * nbc + a;
+                        it.relstart = (int)(S.rowptr[c] + a);
+                        it.cnt = std::min(64, nbc - a);
+                        it.rfirst = S.rel[S.rowptr[c] + a];
+                        it.rlast = S.rel[S.rowptr[c] + a + it.cnt - 1];
+                        it.tcol = r;
+                        it.pad = 0;
+                        items[(size_t)nxt[(size_t)S.sn_start[p] + r]++] = it;
+                    }
+                }
+            }
+        }
+    }
+    // 16 slices of each supernode's panel work, cut on column boundaries
+    fl.wcut.assign((ns + sch.slice_list.size()) * 17, 0);
+    std::vector<int>& wcol = fl.wcol;                        // ... and the columns they are cut at
+    wcol.assign(ns * 17, 0);
+    for (int s = 0; s < S.nsuper; ++s) {
+        const int nc = S.sn_start[s + 1] - S.sn_start[s];
+        const int64_t* cp = pptr.data() + S.sn_start[s];      // nc + 1 column pointers
+        int* col = wcol.data() + (size_t)s * 17;
+        cut_columns(cp, pterm_col.data() + S.sn_start[s], nc, 16, col);
+        for (int w = 0; w <= 16; ++w) fl.wcut[(size_t)s * 17 + w] = cp[col[w]];
+    }
+    // A row slice of a sliced front gets an item list of its own: the pieces that reach its rows or the top block,
+    // in the same order, cut into 16 wave slices of whole columns again -- instead of every slice walking the whole
+    // front's list in rounds that are mostly skipped pieces.  (No pulled terms here: a sliced parent pulls nothing.)
+    for (size_t q = 0; q < sch.slice_list.size(); ++q) {
+        const int s = sch.slice_list[q][0], sl = sch.slice_list[q][1], nsl = sch.slice_list[q][2];
+        const int ff = fsize(s), nc = S.sn_start[s + 1] - S.sn_start[s], nb = ff - nc;
+        const int rsmax = (nb + nsl - 1) / nsl, r_lo = nc + sl * rsmax;
+        const int rs = std::max(0, std::min(rsmax, ff - r_lo));
+        const int64_t* cp = pptr.data() + S.sn_start[s];
+        std::vector<int64_t> scp((size_t)nc + 1);
+        for (int j = 0; j < nc; ++j) {
+            scp[(size_t)j] = (int64_t)items.size();
+            for (int64_t it = cp[j]; it < cp[j + 1]; ++it) {
+                const ExtItem e = items[(size_t)it];
+                if (e.rfirst >= nc && (e.rlast < r_lo || e.rfirst >= r_lo + rs)) continue;
+                items.push_back(e);
+            }
+        }
+        scp[(size_t)nc] = (int64_t)items.size();
+        int col[17];
+        cut_columns(scp.data(), nullptr, nc, 16, col);
+        for (int k = 0; k <= 16; ++k) fl.wcut[(ns + q) * 17 + (size_t)k] = scp[(size_t)col[k]];
+    }
+    // ---- Schur sub-items: every child update column that lands in a U column, cut at the parent's
+    // 64-row tile boundaries, grouped by (tile, tile column), children in fixed order
+    const int64_t ntile = (int64_t)sch.tiles.size();
+    std::vector<int64_t>& cnt = fl.tptr;
+    cnt.assign((size_t)ntile * 64 + 1, 0);
+    std::vector<int64_t> pterm_tcol((size_t)ntile * 64, 0);   // pulled terms per tile column
+    auto for_each_sub = [&](bool of_pulled, auto&& fn) {
+        for (int p = 0; p < S.nsuper; ++p) {
+            if (sch.tile_base[p] < 0) continue;
+            const int pnc = S.sn_start[p + 1] - S.sn_start[p];
+            for (int e = S.child_ptr[p]; e < S.child_ptr[p + 1]; ++e) {
+                const int c = S.child_idx[e];
+                if (dense_child[(size_t)p] == c || (pulled[(size_t)c] != 0) != of_pulled) continue;
+                const int nbc = (int)(S.rowptr[c + 1] - S.rowptr[c]);
+                const int* rl = S.rel.data() + S.rowptr[c];
+                for (int b = 0; b < nbc; ++b) {
+                    if (rl[b] < pnc) continue;
+                    const int j = rl[b] - pnc, tj = j >> 6;
+                    int a = b;
+                    while (a < nbc) {
+                        const int ti = (rl[a] - pnc) >> 6;
+                        int a2 = a;
+                        while (a2 < nbc && ((rl[a2] - pnc) >> 6) == ti) ++a2;
+                        const int64_t tile = sch.tile_base[p] + (int64_t)ti * (ti + 1) / 2 + tj;
+                        fn(tile, j & 63, c, b, a, a2 - a, nbc);
+                        a = a2;
+                    }
+                }
+            }
+        }
+    };
+    for_each_sub(false, [&](int64_t tile, int q, int, int, int, int, int) { cnt[(size_t)(tile * 64 + q + 1)]++; });
+    if (fl.n_pulled) for_each_sub(true, [&](int64_t tile, int q, int, int, int, int n, int) { pterm_tcol[(size_t)(tile * 64 + q)] += n; });
+    for (size_t i = 0; i + 1 < cnt.size(); ++i) cnt[i + 1] += cnt[i];
+    fl.sit.resize((size_t)cnt.back());
+    {
+        std::vector<int64_t> nx(cnt.begin(), cnt.end() - 1);
+        for_each_sub(false, [&](int64_t tile, int q, int c, int b, int a, int n, int nbc) {
+            SubItem si;
+            si.uoff = S.upd_off[c] + (int64_t)b * nbc + a;
+            si.relstart = (int)(S.rowptr[c] + a);
+            si.cnt = (unsigned char)n;
+            si.qcol = (unsigned char)q;
+            si.pad = 0;
+            fl.sit[(size_t)nx[(size_t)(tile * 64 + q)]++] = si;
+        });
+    }
+    fl.tcut.assign((size_t)ntile * 5 + 5, 0);
+    std::vector<int>& tcol = fl.tcol;
+    tcol.assign((size_t)ntile * 5 + 5, 0);
+    for (int64_t t = 0; t < ntile; ++t) {
+        const int64_t* cp = cnt.data() + t * 64;       // 65 column pointers of this tile
+        int* col = tcol.data() + t * 5;
+        cut_columns(cp, pterm_tcol.data() + t * 64, 64, 4, col);
+        for (int w = 0; w <= 4; ++w) fl.tcut[(size_t)(t * 5 + w)] = cp[col[w]];
+    }
+    // ---- the pulled leaves' terms, by owner: wave slice w of front s is owner 16 s + w, wave w of tile t owner 16 nsuper + 4 t + w
+    fl.pwcut.assign(ns * 17, 0);
+    fl.ptcut.assign((size_t)ntile * 5 + 5, 0);
+    // A panel kernel of NW < 16 waves gives every wave 16 / NW consecutive slices: their terms form ONE list (at the first
+    // of the slices; the others' ranges are empty).  Launches of the overlap region count as 16 waves -- their panels may go
+    // out in a merged 1024-thread kernel, and a kernel of fewer waves walks consecutive lists, which is as good.
+    fl.spw.assign(ns, 1);
+    for (size_t q = 0; q < sch.launches.size() && q < sch.ov_first; ++q) {
+        const Launch& L = sch.launches[q];
+        if (L.small) continue;
+        for (int t = L.begin; t < L.begin + L.count; ++t) fl.spw[(size_t)sch.sched[(size_t)t]] = std::max(1, 16 / std::max(1, L.bs_panel / 64));
+    }
+    if (fl.n_pulled == 0) return fl;
+    const size_t nown = ns * 16 + (size_t)ntile * 4;
+    std::vector<int64_t> optr(nown + 1, 0);
+    auto slice_of = [](const int* col, int parts, int j) { int w = 0; while (w + 1 < parts && col[w + 1] <= j) ++w; return w; };
+    auto for_each_term = [&](auto&& fn) {
+        for (int p = 0; p < S.nsuper; ++p) {
+            if (sch.tile_base[p] < 0) continue;
+            const int pnc = S.sn_start[p + 1] - S.sn_start[p], fp = fsize(p);
+            for (int e = S.child_ptr[p]; e < S.child_ptr[p + 1]; ++e) {
+                const int c = S.child_idx[e];
+                if (!pulled[(size_t)c]) continue;
+                const int nbc = (int)(S.rowptr[c + 1] - S.rowptr[c]);
+                const int* rl = S.rel.data() + S.rowptr[c];
+                for (int b = 0; b < nbc; ++b)
+                    for (int a = b; a < nbc; ++a) {
+                        const int ra = rl[a], rb = rl[b];
+                        size_t owner;
+                        int target;
+                        if (rb < pnc) {
+                            const int w = slice_of(wcol.data() + (size_t)p * 17, 16, rb);
+                            owner = (size_t)p * 16 + (size_t)(w - w % fl.spw[(size_t)p]);     // the first slice of the wave that owns w
+                            target = ra + (int)(((int64_t)rb * (2 * fp - 1 - rb)) >> 1);        // the panel's trapezoid (pcol)
+                        } else {
+                            const int j = rb - pnc, i = ra - pnc;
+                            const int64_t tile = sch.tile_base[p] + (int64_t)(i >> 6) * ((i >> 6) + 1) / 2 + (j >> 6);
+                            owner = ns * 16 + (size_t)tile * 4 + (size_t)slice_of(tcol.data() + tile * 5, 4, j & 63);
+                            target = (j & 63) * 65 + (i & 63);                                   // Ct[qcol][row], ld TS + 1
+                        }
+                        if (target > 0x7fff) throw std::runtime_error("pulled leaf: target beyond 15 bits");
+                        fn(owner, RawTerm{(uint32_t)S.front_off[c], (uint32_t)target | ((uint32_t)a << 15) | ((uint32_t)b << 21)});
+                    }
+            }
+        }
+    };
+    for_each_term([&](size_t owner, const RawTerm&) { ++optr[owner + 1]; });
+    for (size_t o = 0; o < nown; ++o) optr[o + 1] += optr[o];
+    fl.n_terms = optr[nown];
+    std::vector<RawTerm> raw((size_t)fl.n_terms);
+    {
+        std::vector<int64_t> nx(optr.begin(), optr.end() - 1);
+        for_each_term([&](size_t owner, const RawTerm& t) { raw[(size_t)nx[owner]++] = t; });
+    }
+    for (size_t o = 0; o < nown; ++o) {
+        const int chunk = (int)(fl.pterms.size() / 64);
+        if (o < ns * 16) fl.pwcut[(o / 16) * 17 + o % 16] = chunk;
+        else fl.ptcut[((o - ns * 16) / 4) * 5 + (o - ns * 16) % 4] = chunk;
+        emit_runs(raw.data() + optr[o], (int)(optr[o + 1] - optr[o]), fl.pterms, fl.n_stacked, fl.max_depth);
+        const int end = (int)(fl.pterms.size() / 64);
+        if (o < ns * 16) { if (o % 16 == 15) fl.pwcut[(o / 16) * 17 + 16] = end; }
+        else if ((o - ns * 16) % 4 == 3) fl.ptcut[((o - ns * 16) / 4) * 5 + 4] = end;
+        if (fl.pterms.size() / 64 > (size_t)0x7fffff00) throw std::runtime_error("pulled leaves: too many term chunks");
+    }
+    return fl;
+}
+
+std::string describe_pieces(const Symbolic& S, const Schedule& sch, const FactorLists& fl)
+{
+    struct Row {
+        int64_t tile_pieces = 0, tile_entries = 0, tile_len[3] = {0, 0, 0};      // pieces of <= 4, 5..16, 17..64 entries
+        int64_t panel_pieces = 0, panel_entries = 0;
+        int64_t pulled_tile_pieces = 0, pulled_panel_pieces = 0, terms = 0, stacked = 0;
+        int depth = 0;
+    };
+    std::vector<Row> rows(S.levels.size());
+    std::unordered_map<uint64_t, int> hit;                   // per entry (ra >= rb) of the parent's front
+    for (int p = 0; p < S.nsuper; ++p) {
+        if (sch.tile_base[p] < 0) continue;
+        Row& R = rows[(size_t)S.sn_level[p]];
+        const int pnc = S.sn_start[p + 1] - S.sn_start[p];
+        hit.clear();
+        for (int e = S.child_ptr[p]; e < S.child_ptr[p + 1]; ++e) {
+            const int c = S.child_idx[e];
+            if (fl.dense_child[(size_t)p] == c) continue;
+            const bool pl = fl.pulled[(size_t)c] != 0;
+            const int nbc = (int)(S.rowptr[c + 1] - S.rowptr[c]);
+            const int* rl = S.rel.data() + S.rowptr[c];
+            for (int b = 0; b < nbc; ++b) {
+                if (rl[b] < pnc) {
+                    const int64_t np = (nbc - b + 63) / 64;
+                    if (pl) R.pulled_panel_pieces += np; else { R.panel_pieces += np; R.panel_entries += nbc - b; }
+                } else {
+                    int a = b;
+                    while (a < nbc) {
+                        const int ti = (rl[a] - pnc) >> 6;
+                        int a2 = a;
+                        while (a2 < nbc && ((rl[a2] - pnc) >> 6) == ti) ++a2;
+                        const int n = a2 - a;
+                        if (pl) ++R.pulled_tile_pieces;
+                        else { ++R.tile_pieces; R.tile_entries += n; ++R.tile_len[n <= 4 ? 0 : n <= 16 ? 1 : 2]; }
+                        a = a2;
+                    }
+                }
+                if (pl) for (int a = b; a < nbc; ++a) {
+                    const uint64_t key = (uint64_t)rl[a] << 32 | (uint32_t)rl[b];
+                    ++R.terms;
+                    if (hit[key]++ > 0) ++R.stacked;
+                    R.depth = std::max(R.depth, hit[key]);
+                }
+            }
+        }
+    }
+    std::string out;
+    char buf[512];
+    for (size_t l = 0; l < rows.size(); ++l) {
+        const Row& R = rows[l];
+        if (R.tile_pieces + R.panel_pieces + R.terms == 0) continue;
+        std::snprintf(buf, sizeof buf, "[pieces] parent level %2zu: tile pieces %lld (%lld entries; <=4: %lld, 5-16: %lld, 17-64: %lld), panel pieces %lld "
+                      "(%lld entries) | pulled leaves took out %lld tile and %lld panel pieces: %lld terms, %lld stacked, deepest %d\n", l,
+                      (long long)R.tile_pieces, (long long)R.tile_entries, (long long)R.tile_len[0], (long long)R.tile_len[1], (long long)R.tile_len[2],
+                      (long long)R.panel_pieces, (long long)R.panel_entries, (long long)R.pulled_tile_pieces, (long long)R.pulled_panel_pieces,
+                      (long long)R.terms, (long long)R.stacked, R.depth);
+        out += buf;
+    }
+    std::snprintf(buf, sizeof buf, "[pieces] pulled leaves %lld, terms %lld in %zu chunks of 64 (%lld onto an earlier term's target, deepest stack %d)\n",
+                  (long long)fl.n_pulled, (long long)fl.n_terms, fl.pterms.size() / 64, (long long)fl.n_stacked, fl.max_depth);
+    out += buf;
     return out;
 }
 

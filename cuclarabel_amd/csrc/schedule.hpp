@@ -105,6 +105,48 @@ struct Schedule {
 // Today's whole schedule of one structure.  Throws std::runtime_error where a front fits no kernel.
 Schedule build_schedule(const Symbolic& S, const DeviceLimits& dev, int64_t panel_cap, int panel_max_slices);
 
+// ---- the factorisation's extend-add work lists (walked by k_panel and k_schur; the records: launch_shapes.hpp)
+// Panel items: the pieces of child update columns that land in a panel column, grouped by column, children in fixed
+// order, cut into 16 wave slices of whole columns per front (wcut).  Schur sub-items: the same for the columns of U, per
+// (tile, tile column), cut into four wave slices per tile (tcut).  A dense child (HIPKKT_DENSE_CHILD) is in neither list.
+//
+// PULLED LEAVES (HIPKKT_PULL_FACTOR_LEAVES, default on).  A front is a pulled leaf iff it has one column, no children
+// and a parent, sits in a one-wave launch (k_front_wave / k_front_tiny factorise it), and its parent is a block-class
+// front that is not cut into row slices.  Such a leaf stores no update block and has no items or sub-items: the parent
+// forms U(a, b) = -(l_a d) l_b itself, one PullTerm per entry a >= b.  The terms one wave walks -- those of its wave
+// slices of the panel, or of its share of a tile's columns -- are sorted by target, a target's terms in child order,
+// and packed into chunks of 64 lanes.  Many leaves hit one entry (cfg2: stacks of up to 53), so the kernel sums a run of
+// equal targets in registers first (a segmented scan over the lanes) and the run's last lane adds the sum to LDS:
+// no two lanes of one LDS add instruction address the same target, and the order of additions into every target is a
+// fixed function of the list -- within a chunk the scan's tree over the run, chunk after chunk in list order.
+// (Neither of the two plainer layouts: "round k holds every target's k-th term" was built first and measured -- 1.62 M
+// terms took 224 k chunks, seven terms per wave-wide load, and a panel wave behind a stack of 49 walked 49 of them;
+// "one lane sums its target's terms in a loop" has the same number of load rounds.  Runs fill the lanes.)
+// wcut / tcut balance 64 x pieces + terms per column; a front or tile without pulled terms is cut exactly as before.
+struct FactorLists {
+    std::vector<char> pulled;            // per supernode: a pulled leaf
+    std::vector<int> dense_child;        // per supernode: its dense child, -1: none
+    std::vector<int64_t> dense_off;      // ... and that child's update-block offset
+    std::vector<int64_t> pptr;           // N + 1: first item of every (permuted) panel column
+    std::vector<ExtItem> items;          // whole fronts first, then the row slices' own lists (sch.slice_list order)
+    std::vector<int64_t> wcut;           // (nsuper + row slices) x 17
+    std::vector<int> wcol;               // nsuper x 17: the panel columns the whole fronts' slices are cut at (slice w: columns [wcol[w], wcol[w + 1]))
+    std::vector<int64_t> tptr;           // tiles x 64 + 1: first sub-item of every tile column (sch.tiles order)
+    std::vector<SubItem> sit;
+    std::vector<int64_t> tcut;           // tiles x 5 (+ 5)
+    std::vector<int> tcol;               // tiles x 5 (+ 5): the tile columns the waves are cut at
+    std::vector<PullTerm> pterms;        // chunks of 64: the fronts' wave slices in (supernode, slice) order, then the tiles' waves
+    std::vector<int> spw;                // per supernode: wave slices per wave of the panel kernel its launch uses (1, 2 or 4): their terms are one list
+    std::vector<int> pwcut;              // nsuper x 17: chunk range of wave slice w of front s is [pwcut[17 s + w], pwcut[17 s + w + 1])
+    std::vector<int> ptcut;              // tiles x 5 (+ 5): the same per tile wave
+    int64_t n_pulled = 0, n_terms = 0, n_stacked = 0;     // leaves, terms, terms onto a target another term already hit
+    int max_depth = 0;                                     // deepest stack of terms on one target
+};
+FactorLists build_factor_lists(const Symbolic& S, const Schedule& sch);
+// diagnostic (HIPKKT_DUMP_LEVELS): the "[pieces]" lines -- per parent level the tile and panel pieces, their entries and
+// lengths, what the pulled leaves took out of them and how deep their terms stack
+std::string describe_pieces(const Symbolic& S, const Schedule& sch, const FactorLists& fl);
+
 // Packed sweep records (kernels.hpp: SolveHdr / RecSeg): per launch and size class one record size, so that a
 // kernel finds a front's record from its place in the launch and fetches header and row slots in one round of loads.
 // HIPKKT_PACKED=0, or more than HIPKKT_PACKED_MAX_MB (4096) of records -- a wide level with one very tall front pays
