@@ -3608,14 +3608,17 @@ int hipkkt_kkt_system_solve(hipkkt_kkt_t h, double* d_lhs_x, double* d_lhs_s, do
 
 // ---- the cone operations between the solves (step_kernels.hip): affine_ds!, the combined step's d.s, step_length,
 // _shift_to_cone_interior! on the caller's device vectors
-static void step_guard(hipkkt_kkt_t h, const char* who, bool need_scaling, bool nonsym_entry = false, bool genpow_entry = false)
+// the family of an entry point: what its name promises to cover (the symmetric four, the _ns five, the _gp five)
+enum class StepFamily { Symmetric, Nonsym, Genpow };
+
+static void step_guard(hipkkt_kkt_t h, const char* who, StepFamily fam, bool need_scaling)
 {
     if (!h) throw ArgError("null handle");
     if (!h->sys_ready) throw ArgError("hipkkt_kkt_system_*: call hipkkt_kkt_system_init first");
     if (h->deferred) throw ArgError("hipkkt_kkt_system_*: level C reads its scalars back (deferred status is for level B)");
-    if (nonsym_entry && !genpow_entry && h->K.ngenpow > 0)
+    if (fam == StepFamily::Nonsym && h->K.ngenpow > 0)
         throw ArgError(std::string(who) + ": generalized power cones are not covered (the _gp entry points are)");
-    if (!nonsym_entry && (h->K.nnonsym > 0 || h->K.ngenpow > 0))
+    if (fam == StepFamily::Symmetric && (h->K.nnonsym > 0 || h->K.ngenpow > 0))
         throw ArgError(std::string(who) + ": symmetric cones only (the handle holds an exponential, power or generalized power cone)");
     if (h->psd_too_big) throw ArgError(std::string(who) + ": PSD cones with side > 48 are not covered");
     if (need_scaling && !h->scaling_valid)
@@ -3623,7 +3626,7 @@ static void step_guard(hipkkt_kkt_t h, const char* who, bool need_scaling, bool 
     HIP_CHECK(hipSetDevice(h->device));
     if (!h->step_partial.p) h->step_partial.alloc((size_t)2 * step_partials(h->cone_dev()));
     if (!h->step_rec.p) h->step_rec.alloc(12);        // (shared with hipkkt_kkt_system_residuals' twelve scalars)
-    if (nonsym_entry && !h->ns_partial.p) h->ns_partial.alloc((size_t)2 * barrier_partials(h->cone_dev()));
+    if (fam != StepFamily::Symmetric && !h->ns_partial.p) h->ns_partial.alloc((size_t)2 * barrier_partials(h->cone_dev()));
 }
 
 // the record of a finishing kernel (nrec doubles) on the host: published by that kernel into the pinned block and
@@ -3648,7 +3651,7 @@ static const double* step_read_record(hipkkt_kkt_t h, int nrec, const std::funct
 int hipkkt_kkt_system_affine_ds(hipkkt_kkt_t h, double* d_out)
 {
     return guarded([&]() {
-        step_guard(h, "hipkkt_kkt_system_affine_ds", true);
+        step_guard(h, "hipkkt_kkt_system_affine_ds", StepFamily::Symmetric, true);
         if (h->K.m && !d_out) throw ArgError("hipkkt_kkt_system_affine_ds: bad argument");
         launch_step_ds(h->cone_dev(), h->cone_state(), d_out, nullptr, nullptr, 0.0, 0.0, h->K.m, false, h->stream);
         return HIPKKT_OK;
@@ -3659,7 +3662,7 @@ int hipkkt_kkt_system_combined_ds(hipkkt_kkt_t h, double* d_out, const double* d
                                   double sigma_mu, double m_corr)
 {
     return guarded([&]() {
-        step_guard(h, "hipkkt_kkt_system_combined_ds", true);
+        step_guard(h, "hipkkt_kkt_system_combined_ds", StepFamily::Symmetric, true);
         if (h->K.m && (!d_out || !d_step_z || !d_step_s || d_out == d_step_z || d_out == d_step_s))
             throw ArgError("hipkkt_kkt_system_combined_ds: bad argument (d_out must not alias an input)");
         launch_step_ds(h->cone_dev(), h->cone_state(), d_out, d_step_z, d_step_s, sigma_mu, m_corr, h->K.m, true, h->stream);
@@ -3672,7 +3675,7 @@ int hipkkt_kkt_system_step_length(hipkkt_kkt_t h, const double* d_step_z, const 
                                   double* alpha_out)
 {
     return guarded([&]() {
-        step_guard(h, "hipkkt_kkt_system_step_length", true);
+        step_guard(h, "hipkkt_kkt_system_step_length", StepFamily::Symmetric, true);
         if ((h->K.m && (!d_step_z || !d_step_s || !d_z || !d_s)) || !alpha_out)
             throw ArgError("hipkkt_kkt_system_step_length: bad argument");
         const double* rec = step_read_record(h, 1, [&](const Publish& pub) {
@@ -3687,7 +3690,7 @@ int hipkkt_kkt_system_step_length(hipkkt_kkt_t h, const double* d_step_z, const 
 int hipkkt_kkt_system_shift_to_interior(hipkkt_kkt_t h, double* d_v, int primal, double* margins_out)
 {
     return guarded([&]() {
-        step_guard(h, "hipkkt_kkt_system_shift_to_interior", false);
+        step_guard(h, "hipkkt_kkt_system_shift_to_interior", StepFamily::Symmetric, false);
         if ((h->K.m && !d_v) || (primal != 0 && primal != 1)) throw ArgError("hipkkt_kkt_system_shift_to_interior: bad argument");
         const ConeDev C = h->cone_dev();
         const double* rec = step_read_record(h, 2, [&](const Publish& pub) {
@@ -3708,53 +3711,54 @@ int hipkkt_kkt_system_shift_to_interior(hipkkt_kkt_t h, double* d_v, int primal,
     });
 }
 
-// ---- the same for cone lists that hold exponential / power cones, and the two operations only such lists need (the
-// unit start and the barrier of the dual-scaling line search).  New entry points: the four above keep refusing such handles.
-int hipkkt_kkt_system_unit_initialization(hipkkt_kkt_t h, double* d_s, double* d_z)
+// ---- the same for cone lists that hold exponential / power cones (the _ns entry points) and generalized power cones as
+// well (the _gp ones, coneops_genpowcone.jl), and the two operations only such lists need (the unit start and the barrier
+// of the dual-scaling line search).  Entry points of their own: each family keeps refusing what its name does not cover.
+// One body per operation: the family decides what step_guard refuses, the handle's cone list which kernels run.
+static int step_unit_initialization(hipkkt_kkt_t h, StepFamily fam, const char* who, double* d_s, double* d_z)
 {
     return guarded([&]() {
-        step_guard(h, "hipkkt_kkt_system_unit_initialization", false, true);
-        if (h->K.m && (!d_s || !d_z || d_s == d_z)) throw ArgError("hipkkt_kkt_system_unit_initialization: bad argument");
-        launch_unit_initialization(h->cone_dev(), d_s, d_z, h->K.m, h->stream);
+        step_guard(h, who, fam, false);
+        if (h->K.m && (!d_s || !d_z || d_s == d_z)) throw ArgError(std::string(who) + ": bad argument");
+        launch_unit_initialization(h->cone_dev(), h->cone_state(), d_s, d_z, h->K.m, h->stream);
         return HIPKKT_OK;
     });
 }
 
-int hipkkt_kkt_system_affine_ds_ns(hipkkt_kkt_t h, double* d_out, const double* d_s)
+static int step_affine_ds(hipkkt_kkt_t h, StepFamily fam, const char* who, double* d_out, const double* d_s)
 {
     return guarded([&]() {
-        step_guard(h, "hipkkt_kkt_system_affine_ds_ns", true, true);
+        step_guard(h, who, fam, true);
         if (h->K.m && (!d_out || !d_s || d_out == d_s))
-            throw ArgError("hipkkt_kkt_system_affine_ds_ns: bad argument (d_out must not alias an input)");
+            throw ArgError(std::string(who) + ": bad argument (d_out must not alias an input)");
         launch_step_ds_ns(h->cone_dev(), h->cone_state(), d_out, nullptr, nullptr, d_s, nullptr, 0.0, 0.0, h->K.m, false, h->stream);
         return HIPKKT_OK;
     });
 }
 
-int hipkkt_kkt_system_combined_ds_ns(hipkkt_kkt_t h, double* d_out, const double* d_step_z, const double* d_step_s,
-                                     const double* d_s, const double* d_z, double sigma_mu, double m_corr)
+static int step_combined_ds(hipkkt_kkt_t h, StepFamily fam, const char* who, double* d_out, const double* d_step_z,
+                            const double* d_step_s, const double* d_s, const double* d_z, double sigma_mu, double m_corr)
 {
     return guarded([&]() {
-        step_guard(h, "hipkkt_kkt_system_combined_ds_ns", true, true);
+        step_guard(h, who, fam, true);
         if (h->K.m && (!d_out || !d_step_z || !d_step_s || !d_s || !d_z || d_out == d_step_z || d_out == d_step_s || d_out == d_s ||
                        d_out == d_z))
-            throw ArgError("hipkkt_kkt_system_combined_ds_ns: bad argument (d_out must not alias an input)");
+            throw ArgError(std::string(who) + ": bad argument (d_out must not alias an input)");
         launch_step_ds_ns(h->cone_dev(), h->cone_state(), d_out, d_step_z, d_step_s, d_s, d_z, sigma_mu, m_corr, h->K.m, true,
                           h->stream);
         return HIPKKT_OK;
     });
 }
 
-int hipkkt_kkt_system_step_length_ns(hipkkt_kkt_t h, const double* d_step_z, const double* d_step_s, const double* d_z,
-                                     const double* d_s, double step_tau, double step_kappa, double tau, double kappa,
-                                     double backtrack_step, double alpha_min, double* alpha_out)
+static int step_length_backtrack(hipkkt_kkt_t h, StepFamily fam, const char* who, const double* d_step_z, const double* d_step_s,
+                                 const double* d_z, const double* d_s, double step_tau, double step_kappa, double tau, double kappa,
+                                 double backtrack_step, double alpha_min, double* alpha_out)
 {
     return guarded([&]() {
-        step_guard(h, "hipkkt_kkt_system_step_length_ns", true, true);
-        if ((h->K.m && (!d_step_z || !d_step_s || !d_z || !d_s)) || !alpha_out)
-            throw ArgError("hipkkt_kkt_system_step_length_ns: bad argument");
+        step_guard(h, who, fam, true);
+        if ((h->K.m && (!d_step_z || !d_step_s || !d_z || !d_s)) || !alpha_out) throw ArgError(std::string(who) + ": bad argument");
         if (!(backtrack_step > 0.0 && backtrack_step < 1.0) || !(alpha_min > 0.0))
-            throw ArgError("hipkkt_kkt_system_step_length_ns: backtrack_step must lie in (0, 1) and alpha_min be positive");
+            throw ArgError(std::string(who) + ": backtrack_step must lie in (0, 1) and alpha_min be positive");
         // the search starts at a0 <= 1 - sqrt(eps) and visits a0 step^j while that is >= alpha_min: at most
         // floor(log(alpha_min) / log(step)) + 1 points; one more trip absorbs the rounding of the two logarithms
         const double trips = std::log(alpha_min) / std::log(backtrack_step);
@@ -3769,12 +3773,12 @@ int hipkkt_kkt_system_step_length_ns(hipkkt_kkt_t h, const double* d_step_z, con
     });
 }
 
-int hipkkt_kkt_system_barrier(hipkkt_kkt_t h, const double* d_z, const double* d_s, const double* d_step_z,
-                              const double* d_step_s, double alpha, double out[2])
+static int step_barrier(hipkkt_kkt_t h, StepFamily fam, const char* who, const double* d_z, const double* d_s,
+                        const double* d_step_z, const double* d_step_s, double alpha, double out[2])
 {
     return guarded([&]() {
-        step_guard(h, "hipkkt_kkt_system_barrier", true, true);
-        if ((h->K.m && (!d_z || !d_s || !d_step_z || !d_step_s)) || !out) throw ArgError("hipkkt_kkt_system_barrier: bad argument");
+        step_guard(h, who, fam, true);
+        if ((h->K.m && (!d_z || !d_s || !d_step_z || !d_step_s)) || !out) throw ArgError(std::string(who) + ": bad argument");
         const double* rec = step_read_record(h, 2, [&](const Publish& pub) {
             launch_barrier(h->cone_dev(), d_z, d_s, d_step_z, d_step_s, alpha, h->ns_partial.p, h->step_rec.p, pub, h->K.m, h->stream);
         });
@@ -3784,79 +3788,66 @@ int hipkkt_kkt_system_barrier(hipkkt_kkt_t h, const double* d_z, const double* d
     });
 }
 
-// ---- the same five for cone lists that hold generalized power cones as well (coneops_genpowcone.jl).  Entry points of
-// their own: the nine above keep refusing what they refuse.  The _ns launches run first, unchanged; the generalized power
-// cones' rows and terms follow, one wave or one workgroup per cone.
+int hipkkt_kkt_system_unit_initialization(hipkkt_kkt_t h, double* d_s, double* d_z)
+{
+    return step_unit_initialization(h, StepFamily::Nonsym, "hipkkt_kkt_system_unit_initialization", d_s, d_z);
+}
+
+int hipkkt_kkt_system_affine_ds_ns(hipkkt_kkt_t h, double* d_out, const double* d_s)
+{
+    return step_affine_ds(h, StepFamily::Nonsym, "hipkkt_kkt_system_affine_ds_ns", d_out, d_s);
+}
+
+int hipkkt_kkt_system_combined_ds_ns(hipkkt_kkt_t h, double* d_out, const double* d_step_z, const double* d_step_s,
+                                     const double* d_s, const double* d_z, double sigma_mu, double m_corr)
+{
+    return step_combined_ds(h, StepFamily::Nonsym, "hipkkt_kkt_system_combined_ds_ns", d_out, d_step_z, d_step_s, d_s, d_z, sigma_mu,
+                            m_corr);
+}
+
+int hipkkt_kkt_system_step_length_ns(hipkkt_kkt_t h, const double* d_step_z, const double* d_step_s, const double* d_z,
+                                     const double* d_s, double step_tau, double step_kappa, double tau, double kappa,
+                                     double backtrack_step, double alpha_min, double* alpha_out)
+{
+    return step_length_backtrack(h, StepFamily::Nonsym, "hipkkt_kkt_system_step_length_ns", d_step_z, d_step_s, d_z, d_s, step_tau,
+                                 step_kappa, tau, kappa, backtrack_step, alpha_min, alpha_out);
+}
+
+int hipkkt_kkt_system_barrier(hipkkt_kkt_t h, const double* d_z, const double* d_s, const double* d_step_z,
+                              const double* d_step_s, double alpha, double out[2])
+{
+    return step_barrier(h, StepFamily::Nonsym, "hipkkt_kkt_system_barrier", d_z, d_s, d_step_z, d_step_s, alpha, out);
+}
+
 int hipkkt_kkt_system_unit_initialization_gp(hipkkt_kkt_t h, double* d_s, double* d_z)
 {
-    return guarded([&]() {
-        step_guard(h, "hipkkt_kkt_system_unit_initialization_gp", false, true, true);
-        if (h->K.m && (!d_s || !d_z || d_s == d_z)) throw ArgError("hipkkt_kkt_system_unit_initialization_gp: bad argument");
-        launch_unit_initialization_gp(h->cone_dev(), h->cone_state(), d_s, d_z, h->K.m, h->stream);
-        return HIPKKT_OK;
-    });
+    return step_unit_initialization(h, StepFamily::Genpow, "hipkkt_kkt_system_unit_initialization_gp", d_s, d_z);
 }
 
 int hipkkt_kkt_system_affine_ds_gp(hipkkt_kkt_t h, double* d_out, const double* d_s)
 {
-    return guarded([&]() {
-        step_guard(h, "hipkkt_kkt_system_affine_ds_gp", true, true, true);
-        if (h->K.m && (!d_out || !d_s || d_out == d_s))
-            throw ArgError("hipkkt_kkt_system_affine_ds_gp: bad argument (d_out must not alias an input)");
-        launch_step_ds_gp(h->cone_dev(), h->cone_state(), d_out, nullptr, nullptr, d_s, nullptr, 0.0, 0.0, h->K.m, false, h->stream);
-        return HIPKKT_OK;
-    });
+    return step_affine_ds(h, StepFamily::Genpow, "hipkkt_kkt_system_affine_ds_gp", d_out, d_s);
 }
 
 int hipkkt_kkt_system_combined_ds_gp(hipkkt_kkt_t h, double* d_out, const double* d_step_z, const double* d_step_s,
                                      const double* d_s, const double* d_z, double sigma_mu, double m_corr)
 {
-    return guarded([&]() {
-        step_guard(h, "hipkkt_kkt_system_combined_ds_gp", true, true, true);
-        if (h->K.m && (!d_out || !d_step_z || !d_step_s || !d_s || !d_z || d_out == d_step_z || d_out == d_step_s || d_out == d_s ||
-                       d_out == d_z))
-            throw ArgError("hipkkt_kkt_system_combined_ds_gp: bad argument (d_out must not alias an input)");
-        launch_step_ds_gp(h->cone_dev(), h->cone_state(), d_out, d_step_z, d_step_s, d_s, d_z, sigma_mu, m_corr, h->K.m, true,
-                          h->stream);
-        return HIPKKT_OK;
-    });
+    return step_combined_ds(h, StepFamily::Genpow, "hipkkt_kkt_system_combined_ds_gp", d_out, d_step_z, d_step_s, d_s, d_z, sigma_mu,
+                            m_corr);
 }
 
 int hipkkt_kkt_system_step_length_gp(hipkkt_kkt_t h, const double* d_step_z, const double* d_step_s, const double* d_z,
                                      const double* d_s, double step_tau, double step_kappa, double tau, double kappa,
                                      double backtrack_step, double alpha_min, double* alpha_out)
 {
-    return guarded([&]() {
-        step_guard(h, "hipkkt_kkt_system_step_length_gp", true, true, true);
-        if ((h->K.m && (!d_step_z || !d_step_s || !d_z || !d_s)) || !alpha_out)
-            throw ArgError("hipkkt_kkt_system_step_length_gp: bad argument");
-        if (!(backtrack_step > 0.0 && backtrack_step < 1.0) || !(alpha_min > 0.0))
-            throw ArgError("hipkkt_kkt_system_step_length_gp: backtrack_step must lie in (0, 1) and alpha_min be positive");
-        const double trips = std::log(alpha_min) / std::log(backtrack_step);         // (as hipkkt_kkt_system_step_length_ns)
-        const int cap = !(trips > 0.0) ? 2 : trips >= 2.0e9 ? INT_MAX : (int)trips + 2;
-        const double* rec = step_read_record(h, 1, [&](const Publish& pub) {
-            launch_step_length_gp(h->cone_dev(), h->cone_state(), d_step_z, d_step_s, d_z, d_s, step_tau, step_kappa, tau, kappa,
-                                  backtrack_step, alpha_min, cap, h->step_partial.p, h->ns_partial.p, h->step_rec.p, pub, h->K.m,
-                                  h->stream);
-        });
-        *alpha_out = rec[0];
-        return HIPKKT_OK;
-    });
+    return step_length_backtrack(h, StepFamily::Genpow, "hipkkt_kkt_system_step_length_gp", d_step_z, d_step_s, d_z, d_s, step_tau,
+                                 step_kappa, tau, kappa, backtrack_step, alpha_min, alpha_out);
 }
 
 int hipkkt_kkt_system_barrier_gp(hipkkt_kkt_t h, const double* d_z, const double* d_s, const double* d_step_z,
                                  const double* d_step_s, double alpha, double out[2])
 {
-    return guarded([&]() {
-        step_guard(h, "hipkkt_kkt_system_barrier_gp", true, true, true);
-        if ((h->K.m && (!d_z || !d_s || !d_step_z || !d_step_s)) || !out) throw ArgError("hipkkt_kkt_system_barrier_gp: bad argument");
-        const double* rec = step_read_record(h, 2, [&](const Publish& pub) {
-            launch_barrier_gp(h->cone_dev(), d_z, d_s, d_step_z, d_step_s, alpha, h->ns_partial.p, h->step_rec.p, pub, h->K.m, h->stream);
-        });
-        out[0] = rec[0];
-        out[1] = rec[1];
-        return HIPKKT_OK;
-    });
+    return step_barrier(h, StepFamily::Genpow, "hipkkt_kkt_system_barrier_gp", d_z, d_s, d_step_z, d_step_s, alpha, out);
 }
 
 // ---- residuals and termination scalars of a device-resident iterate (iterate_kernels.hip), and the two elementwise

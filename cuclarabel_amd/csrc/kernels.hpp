@@ -555,42 +555,31 @@ void launch_margins(const ConeDev& C, const double* v, double* partial, double* 
 void launch_unit_shift(const ConeDev& C, double* v, double a1, double a2, bool two, bool primal, int m, hipStream_t st);
 
 // ---- the same for handles that also hold exponential / power cones (three rows each; one lane per cone through
-// exp_list / pow_list): the symmetric rows by the kernels above, unchanged
+// exp_list / pow_list) and generalized power cones (coneops_genpowcone.jl): the symmetric rows by the
+// kernels above, unchanged; then the lane-per-cone kernel where C.nexp + C.npow > 0; then, where C.ngp_small + C.ngp_big > 0,
+// one wave per cone of gp_small / one workgroup per cone of gp_big, as the scaling kernel splits them
 // slots of the barrier partials: elementwise workgroups, second-order cones, PSD cones, workgroups of the lane-per-cone part
-// and a slot per generalized power cone (the *_gp launches below; the step length's per-cone minima fit in the same array)
+// and a slot per generalized power cone (the step length's per-cone minima fit in the same array)
 inline int barrier_partials(const ConeDev& C) { return 2 * kStepGridCap + C.nsoc + C.npsd + C.ngp_small + C.ngp_big; }
-// unit_initialization! of every cone (solver.jl:383-404, the asymmetric start) into s and z: one launch
-void launch_unit_initialization(const ConeDev& C, double* s, double* z, int m, hipStream_t st);
+// unit_initialization! of every cone (solver.jl:383-404, the asymmetric start) into s and z; a generalized power cone
+// (coneops_genpowcone.jl:34-53): s_i = z_i = sqrt(1 + alpha_i) on its first dim1 rows, 0 behind
+void launch_unit_initialization(const ConeDev& C, const ConeState& S, double* s, double* z, int m, hipStream_t st);
 // launch_step_ds, then the exponential / power rows: a copy of s, and with `combined`
 //       s + sigma_mu grad f*(z) - eta(step_s, m_corr step_z); z: the point the scaling was computed from
+// the generalized power rows: a copy of s (coneops_genpowcone.jl:137-147), with `combined` s + sigma_mu grad f*(z), the
+// stored gradient (:149-168)
 void launch_step_ds_ns(const ConeDev& C, const ConeState& S, double* out, const double* step_z, const double* step_s,
                        const double* s, const double* z, double sigma_mu, double m_corr, int m, bool combined, hipStream_t st);
-// launch_step_length (its record stays on the device), min(., 1 - sqrt(eps)), then every exponential / power cone's
-// backtrack_search from that common start; ns_partial: kStepGridCap doubles
+// launch_step_length (its record stays on the device), min(., 1 - sqrt(eps)), then every exponential / power / generalized
+// power cone's backtrack_search (coneops_genpowcone.jl:186-207) from that common start; ns_partial: 2 * barrier_partials(C) doubles
 void launch_step_length_ns(const ConeDev& C, const ConeState& S, const double* dz, const double* ds, const double* z,
                            const double* s, double step_tau, double step_kappa, double tau, double kappa, double backtrack_step,
                            double alpha_min, int trip_cap, double* partial, double* ns_partial, double* rec, const Publish& pub,
                            int m, hipStream_t st);
-// rec[0..1] = (sum of compute_barrier over the cones, <z + alpha dz, s + alpha ds>); partial: 2 * barrier_partials(C) doubles
+// rec[0..1] = (sum of compute_barrier over the cones -- a generalized power cone's barrier_dual + barrier_primal,
+// coneops_genpowcone.jl:209-234 --, <z + alpha dz, s + alpha ds>); partial: 2 * barrier_partials(C) doubles
 void launch_barrier(const ConeDev& C, const double* z, const double* s, const double* dz, const double* ds, double alpha,
                     double* partial, double* rec, const Publish& pub, int m, hipStream_t st);
-
-// ---- and for handles that hold generalized power cones as well (coneops_genpowcone.jl): the launches
-// above first, unchanged, then one wave per cone of gp_small / one workgroup per cone of gp_big, as the scaling kernel
-// splits them.  ns_partial / partial: 2 * barrier_partials(C) doubles as above.
-// :34-53: s_i = z_i = sqrt(1 + alpha_i) on the first dim1 rows of such a cone, 0 behind
-void launch_unit_initialization_gp(const ConeDev& C, const ConeState& S, double* s, double* z, int m, hipStream_t st);
-// their rows: a copy of s (:137-147), with `combined` s + sigma_mu grad f*(z), the stored gradient (:149-168)
-void launch_step_ds_gp(const ConeDev& C, const ConeState& S, double* out, const double* step_z, const double* step_s,
-                       const double* s, const double* z, double sigma_mu, double m_corr, int m, bool combined, hipStream_t st);
-// every such cone's backtrack_search (:186-207) from the common start joins the minimum
-void launch_step_length_gp(const ConeDev& C, const ConeState& S, const double* dz, const double* ds, const double* z,
-                           const double* s, double step_tau, double step_kappa, double tau, double kappa, double backtrack_step,
-                           double alpha_min, int trip_cap, double* partial, double* ns_partial, double* rec, const Publish& pub,
-                           int m, hipStream_t st);
-// their barrier_dual + barrier_primal (:209-234) joins the sum
-void launch_barrier_gp(const ConeDev& C, const double* z, const double* s, const double* dz, const double* ds, double alpha,
-                       double* partial, double* rec, const Publish& pub, int m, hipStream_t st);
 
 // ---- residuals and termination scalars of a device-resident iterate (iterate_kernels.hip)
 // What the pass walks of the image besides SpmvDev: the end of each row's walked prefix and the long ones among those

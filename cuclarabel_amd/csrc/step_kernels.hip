@@ -1190,10 +1190,19 @@ void launch_unit_shift(const ConeDev& C, double* v, double a1, double a2, bool t
     hipLaunchKernelGGL(k_unit_shift, dim3(step_grid(m)), dim3(256), 0, st, C, v, a1, a2, two ? 1 : 0, primal ? 1 : 0, m);
 }
 
-void launch_unit_initialization(const ConeDev& C, double* s, double* z, int m, hipStream_t st)
+// the generalized power cones' rows (mode 0: the unit start into out and out2; 1: a copy of s; 2: s + sigma_mu grad f*(z))
+static void launch_gp_rows(const ConeDev& C, const ConeState& S, int mode, double* out, double* out2, const double* s, double sigma_mu,
+                           hipStream_t st)
+{
+    const int g = (C.ngp_small + 3) / 4 + C.ngp_big;
+    if (g > 0) hipLaunchKernelGGL(k_gp_rows, dim3(g), dim3(256), 0, st, C, S, mode, out, out2, s, sigma_mu);
+}
+
+void launch_unit_initialization(const ConeDev& C, const ConeState& S, double* s, double* z, int m, hipStream_t st)
 {
     if (m <= 0) return;
-    hipLaunchKernelGGL(k_unit_initialization, dim3(step_grid(m)), dim3(256), 0, st, C, s, z, m);
+    hipLaunchKernelGGL(k_unit_initialization, dim3(step_grid(m)), dim3(256), 0, st, C, s, z, m);   // (a generalized power cone's rows: 0)
+    launch_gp_rows(C, S, 0, s, z, nullptr, 0.0, st);
 }
 
 void launch_step_ds_ns(const ConeDev& C, const ConeState& S, double* out, const double* step_z, const double* step_s,
@@ -1204,18 +1213,19 @@ void launch_step_ds_ns(const ConeDev& C, const ConeState& S, double* out, const 
     if (nns > 0)
         hipLaunchKernelGGL(k_ns_ds, dim3(step_grid(nns)), dim3(256), 0, st, C, S, out, step_z, step_s, s, z, sigma_mu, m_corr,
                            combined ? 1 : 0);
+    launch_gp_rows(C, S, combined ? 2 : 1, out, nullptr, s, sigma_mu, st);
 }
 
-// stages 1 to 3 of the composite step length; gp: the generalized power cones' searches too, their slots behind the
-// lane-per-cone workgroups' (without them the launches are those of launch_step_length_ns, kernel for kernel)
-static void step_length_nonsym(const ConeDev& C, const ConeState& S, const double* dz, const double* ds, const double* z,
-                               const double* s, double step_tau, double step_kappa, double tau, double kappa, double backtrack_step,
-                               double alpha_min, int trip_cap, double* partial, double* ns_partial, double* rec, const Publish& pub,
-                               int m, bool gp, hipStream_t st)
+// stages 1 to 3 of the composite step length; the generalized power cones' searches keep their slots behind the
+// lane-per-cone workgroups'
+void launch_step_length_ns(const ConeDev& C, const ConeState& S, const double* dz, const double* ds, const double* z,
+                           const double* s, double step_tau, double step_kappa, double tau, double kappa, double backtrack_step,
+                           double alpha_min, int trip_cap, double* partial, double* ns_partial, double* rec, const Publish& pub,
+                           int m, hipStream_t st)
 {
     launch_step_length(C, S, dz, ds, z, s, step_tau, step_kappa, tau, kappa, partial, rec, Publish{}, m, st);
     const int nns = C.nexp + C.npow, gn = nns > 0 ? step_grid(nns) : 0;
-    const int ngp = gp ? C.ngp_small + C.ngp_big : 0;
+    const int ngp = C.ngp_small + C.ngp_big;
     if (gn > 0)
         hipLaunchKernelGGL(k_ns_step_length, dim3(gn), dim3(256), 0, st, C, dz, ds, z, s, rec, backtrack_step, alpha_min, trip_cap,
                            ns_partial);
@@ -1225,30 +1235,12 @@ static void step_length_nonsym(const ConeDev& C, const ConeState& S, const doubl
     hipLaunchKernelGGL(k_ns_step_length_finish, dim3(1), dim3(256), 0, st, ns_partial, gn + ngp, rec, pub);
 }
 
-void launch_step_length_ns(const ConeDev& C, const ConeState& S, const double* dz, const double* ds, const double* z,
-                           const double* s, double step_tau, double step_kappa, double tau, double kappa, double backtrack_step,
-                           double alpha_min, int trip_cap, double* partial, double* ns_partial, double* rec, const Publish& pub,
-                           int m, hipStream_t st)
-{
-    step_length_nonsym(C, S, dz, ds, z, s, step_tau, step_kappa, tau, kappa, backtrack_step, alpha_min, trip_cap, partial, ns_partial,
-                       rec, pub, m, false, st);
-}
-
-void launch_step_length_gp(const ConeDev& C, const ConeState& S, const double* dz, const double* ds, const double* z,
-                           const double* s, double step_tau, double step_kappa, double tau, double kappa, double backtrack_step,
-                           double alpha_min, int trip_cap, double* partial, double* ns_partial, double* rec, const Publish& pub,
-                           int m, hipStream_t st)
-{
-    step_length_nonsym(C, S, dz, ds, z, s, step_tau, step_kappa, tau, kappa, backtrack_step, alpha_min, trip_cap, partial, ns_partial,
-                       rec, pub, m, true, st);
-}
-
-// gp: the generalized power cones' terms too, in slots behind the lane-per-cone workgroups'
-static void barrier_all(const ConeDev& C, const double* z, const double* s, const double* dz, const double* ds, double alpha,
-                        double* partial, double* rec, const Publish& pub, int m, bool gp, hipStream_t st)
+// the generalized power cones' terms: in slots behind the lane-per-cone workgroups'
+void launch_barrier(const ConeDev& C, const double* z, const double* s, const double* dz, const double* ds, double alpha,
+                    double* partial, double* rec, const Publish& pub, int m, hipStream_t st)
 {
     const int ge = step_grid(m), gs = (C.nsoc + 3) / 4, nns = C.nexp + C.npow, gn = nns > 0 ? step_grid(nns) : 0;
-    const int ngp = gp ? C.ngp_small + C.ngp_big : 0;
+    const int ngp = C.ngp_small + C.ngp_big;
     double* pbar = partial;
     double* pdot = partial + barrier_partials(C);
     if (C.npsd > 0)
@@ -1260,38 +1252,6 @@ static void barrier_all(const ConeDev& C, const double* z, const double* s, cons
         hipLaunchKernelGGL(k_gp_barrier, dim3((C.ngp_small + 3) / 4 + C.ngp_big), dim3(256), 0, st, C, z, s, dz, ds, alpha,
                            pbar + ge + C.nsoc + C.npsd + gn);
     hipLaunchKernelGGL(k_barrier_finish, dim3(1), dim3(256), 0, st, pbar, ge + C.nsoc + C.npsd + gn + ngp, pdot, ge, rec, pub);
-}
-
-void launch_barrier(const ConeDev& C, const double* z, const double* s, const double* dz, const double* ds, double alpha,
-                    double* partial, double* rec, const Publish& pub, int m, hipStream_t st)
-{
-    barrier_all(C, z, s, dz, ds, alpha, partial, rec, pub, m, false, st);
-}
-
-void launch_barrier_gp(const ConeDev& C, const double* z, const double* s, const double* dz, const double* ds, double alpha,
-                       double* partial, double* rec, const Publish& pub, int m, hipStream_t st)
-{
-    barrier_all(C, z, s, dz, ds, alpha, partial, rec, pub, m, true, st);
-}
-
-static void launch_gp_rows(const ConeDev& C, const ConeState& S, int mode, double* out, double* out2, const double* s, double sigma_mu,
-                           hipStream_t st)
-{
-    const int g = (C.ngp_small + 3) / 4 + C.ngp_big;
-    if (g > 0) hipLaunchKernelGGL(k_gp_rows, dim3(g), dim3(256), 0, st, C, S, mode, out, out2, s, sigma_mu);
-}
-
-void launch_unit_initialization_gp(const ConeDev& C, const ConeState& S, double* s, double* z, int m, hipStream_t st)
-{
-    launch_unit_initialization(C, s, z, m, st);            // (a generalized power cone's rows: 0)
-    launch_gp_rows(C, S, 0, s, z, nullptr, 0.0, st);
-}
-
-void launch_step_ds_gp(const ConeDev& C, const ConeState& S, double* out, const double* step_z, const double* step_s,
-                       const double* s, const double* z, double sigma_mu, double m_corr, int m, bool combined, hipStream_t st)
-{
-    launch_step_ds_ns(C, S, out, step_z, step_s, s, z, sigma_mu, m_corr, m, combined, st);
-    launch_gp_rows(C, S, combined ? 2 : 1, out, nullptr, s, sigma_mu, st);
 }
 
 }  // namespace hipkkt

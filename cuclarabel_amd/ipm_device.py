@@ -77,6 +77,22 @@ class _Csr:
         return y.index_add_(0, self.row, self.val * x[self.col])
 
 
+_SYMMETRIC = (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT)
+_NONSYMMETRIC = _SYMMETRIC + (ExponentialConeT, PowerConeT)
+
+
+def _check_cones(who, cone_specs, allowed, hint):
+    """The entry points' argument check -> the cone list.  hint: the refusal of a kind outside `allowed`, with {} for
+    that kind's name."""
+    cone_specs = list(cone_specs)
+    for c in cone_specs:
+        if not isinstance(c, allowed):
+            raise ValueError(hint.format(type(c).__name__))
+        if isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE:
+            raise ValueError(f"{who} covers PSD cones up to side {PSD_MAX_SIDE}")
+    return cone_specs
+
+
 def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None, plumbing="torch"):
     """Clarabel.solve! restated with device-resident vectors -> IPMResult (numpy x, z, s).
 
@@ -88,14 +104,10 @@ def solve_device(P, q, A, b, cone_specs, settings=None, inspect=None, plumbing="
     matrices, and torch only allocates (and clones the previous iterate)."""
     if plumbing not in ("torch", "device"):
         raise ValueError(f"plumbing must be 'torch' or 'device', got {plumbing!r}")
-    cone_specs = list(cone_specs)
-    for c in cone_specs:
-        if not isinstance(c, (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT)):
-            raise ValueError("solve_device covers the symmetric cones only (zero, nonnegative, second-order, PSD); "
-                             f"got {type(c).__name__}: use solve_device_nonsymmetric for exponential and power cones, "
-                             "solve_device_genpow for generalized power cones")
-        if isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE:
-            raise ValueError(f"solve_device covers PSD cones up to side {PSD_MAX_SIDE}")
+    cone_specs = _check_cones("solve_device", cone_specs, _SYMMETRIC,
+                              "solve_device covers the symmetric cones only (zero, nonnegative, second-order, PSD); "
+                              "got {}: use solve_device_nonsymmetric for exponential and power cones, "
+                              "solve_device_genpow for generalized power cones")
     return _solve(P, q, A, b, cone_specs, settings, inspect, plumbing == "device", False)
 
 
@@ -106,13 +118,9 @@ def solve_device_nonsymmetric(P, q, A, b, cone_specs, settings=None, inspect=Non
     positive and linesearch_backtrack_step lie in (0, 1) (the device's backtracking search refuses anything else)."""
     if plumbing not in ("torch", "device"):
         raise ValueError(f"plumbing must be 'torch' or 'device', got {plumbing!r}")
-    cone_specs = list(cone_specs)
-    for c in cone_specs:
-        if not isinstance(c, (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT, ExponentialConeT, PowerConeT)):
-            raise ValueError("solve_device_nonsymmetric covers zero, nonnegative, second-order, PSD, exponential and power "
-                             f"cones; got {type(c).__name__}: use solve_device_genpow")
-        if isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE:
-            raise ValueError(f"solve_device_nonsymmetric covers PSD cones up to side {PSD_MAX_SIDE}")
+    cone_specs = _check_cones("solve_device_nonsymmetric", cone_specs, _NONSYMMETRIC,
+                              "solve_device_nonsymmetric covers zero, nonnegative, second-order, PSD, exponential and power "
+                              "cones; got {}: use solve_device_genpow")
     return _solve(P, q, A, b, cone_specs, settings, inspect, plumbing == "device", True)
 
 
@@ -122,13 +130,8 @@ def solve_device_genpow(P, q, A, b, cone_specs, settings=None, inspect=None, plu
     `plumbing` and the two settings constraints as in solve_device_nonsymmetric."""
     if plumbing not in ("torch", "device"):
         raise ValueError(f"plumbing must be 'torch' or 'device', got {plumbing!r}")
-    cone_specs = list(cone_specs)
-    for c in cone_specs:
-        if not isinstance(c, (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleConeT, ExponentialConeT, PowerConeT,
-                              GenPowerConeT)):
-            raise ValueError(f"solve_device_genpow: unknown cone type {type(c).__name__}")
-        if isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE:
-            raise ValueError(f"solve_device_genpow covers PSD cones up to side {PSD_MAX_SIDE}")
+    cone_specs = _check_cones("solve_device_genpow", cone_specs, _NONSYMMETRIC + (GenPowerConeT,),
+                              "solve_device_genpow: unknown cone type {}")
     return _solve(P, q, A, b, cone_specs, settings, inspect, plumbing == "device", True, True)
 
 

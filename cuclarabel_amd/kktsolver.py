@@ -383,76 +383,76 @@ class HipKKTSystem:
               "hipkkt_kkt_system_shift_to_interior")
         return float(out[0]), float(out[1])
 
-    # ---- the same for cone lists with exponential / power cones (zero, nonnegative, second-order, PSD <= 48, exponential
-    #      and power cones in any order; a generalized power cone is refused)
+    # ---- the same for cone lists with exponential / power cones (the _ns symbols) and with generalized power cones as
+    #      well (the _gp symbols): one marshalling helper per operation, the symbol's name chosen by the public method
+    def _unit_initialization(self, sym, d_s, d_z):
+        return check(getattr(_lib.lib(), sym)(self.ks._h, C.c_void_p(d_s), C.c_void_p(d_z)), sym)
+
+    def _affine_ds(self, sym, d_out, d_s):
+        return check(getattr(_lib.lib(), sym)(self.ks._h, C.c_void_p(d_out), C.c_void_p(d_s)), sym)
+
+    def _combined_ds(self, sym, d_out, d_step_z, d_step_s, d_s, d_z, sigma_mu, m_corr):
+        return check(getattr(_lib.lib(), sym)(self.ks._h, C.c_void_p(d_out), C.c_void_p(d_step_z), C.c_void_p(d_step_s),
+                                              C.c_void_p(d_s), C.c_void_p(d_z), float(sigma_mu), float(m_corr)), sym)
+
+    def _step_length_bt(self, sym, d_step_z, d_step_s, d_z, d_s, step_tau, step_kappa, tau, kappa, backtrack_step, alpha_min):
+        out = np.zeros(1)
+        check(getattr(_lib.lib(), sym)(self.ks._h, C.c_void_p(d_step_z), C.c_void_p(d_step_s), C.c_void_p(d_z), C.c_void_p(d_s),
+                                       float(step_tau), float(step_kappa), float(tau), float(kappa), float(backtrack_step),
+                                       float(alpha_min), ptr(out)), sym)
+        return float(out[0])
+
+    def _barrier(self, sym, d_z, d_s, d_step_z, d_step_s, alpha):
+        out = np.zeros(2)
+        check(getattr(_lib.lib(), sym)(self.ks._h, C.c_void_p(d_z), C.c_void_p(d_s), C.c_void_p(d_step_z), C.c_void_p(d_step_s),
+                                       float(alpha), ptr(out)), sym)
+        return float(out[0]), float(out[1])
+
+    # zero, nonnegative, second-order, PSD <= 48, exponential and power cones in any order; a generalized power cone is refused
     def unit_initialization_dev(self, d_s, d_z):
         """Every cone's unit_initialization! into s and z (the asymmetric start): one launch, no scaling needed."""
-        return check(_lib.lib().hipkkt_kkt_system_unit_initialization(self.ks._h, C.c_void_p(d_s), C.c_void_p(d_z)),
-                     "hipkkt_kkt_system_unit_initialization")
+        return self._unit_initialization("hipkkt_kkt_system_unit_initialization", d_s, d_z)
 
     def affine_ds_ns_dev(self, d_out, d_s):
         """out = lambda o lambda on symmetric rows, a copy of s on exponential / power rows (affine_ds!)."""
-        return check(_lib.lib().hipkkt_kkt_system_affine_ds_ns(self.ks._h, C.c_void_p(d_out), C.c_void_p(d_s)),
-                     "hipkkt_kkt_system_affine_ds_ns")
+        return self._affine_ds("hipkkt_kkt_system_affine_ds_ns", d_out, d_s)
 
     def combined_ds_ns_dev(self, d_out, d_step_z, d_step_s, d_s, d_z, sigma_mu, m_corr):
         """d.s of the combined right-hand side; exponential / power rows: s + sigma_mu grad f*(z) - eta(step_s, m_corr
         step_z).  d_z must be the z the current scaling was computed from."""
-        return check(_lib.lib().hipkkt_kkt_system_combined_ds_ns(self.ks._h, C.c_void_p(d_out), C.c_void_p(d_step_z),
-                                                                  C.c_void_p(d_step_s), C.c_void_p(d_s), C.c_void_p(d_z),
-                                                                  float(sigma_mu), float(m_corr)),
-                     "hipkkt_kkt_system_combined_ds_ns")
+        return self._combined_ds("hipkkt_kkt_system_combined_ds_ns", d_out, d_step_z, d_step_s, d_s, d_z, sigma_mu, m_corr)
 
     def step_length_ns_dev(self, d_step_z, d_step_s, d_z, d_s, step_tau, step_kappa, tau, kappa, backtrack_step, alpha_min):
         """The composite step length of a list with exponential / power cones, without max_step_fraction -> alpha."""
-        out = np.zeros(1)
-        check(_lib.lib().hipkkt_kkt_system_step_length_ns(self.ks._h, C.c_void_p(d_step_z), C.c_void_p(d_step_s),
-                                                          C.c_void_p(d_z), C.c_void_p(d_s), float(step_tau), float(step_kappa),
-                                                          float(tau), float(kappa), float(backtrack_step), float(alpha_min),
-                                                          ptr(out)), "hipkkt_kkt_system_step_length_ns")
-        return float(out[0])
+        return self._step_length_bt("hipkkt_kkt_system_step_length_ns", d_step_z, d_step_s, d_z, d_s, step_tau, step_kappa, tau,
+                                    kappa, backtrack_step, alpha_min)
 
     def barrier_dev(self, d_z, d_s, d_step_z, d_step_s, alpha):
         """(sum of the cones' compute_barrier, <z + alpha dz, s + alpha ds>) at the stepped point, as host floats."""
-        out = np.zeros(2)
-        check(_lib.lib().hipkkt_kkt_system_barrier(self.ks._h, C.c_void_p(d_z), C.c_void_p(d_s), C.c_void_p(d_step_z),
-                                                   C.c_void_p(d_step_s), float(alpha), ptr(out)), "hipkkt_kkt_system_barrier")
-        return float(out[0]), float(out[1])
+        return self._barrier("hipkkt_kkt_system_barrier", d_z, d_s, d_step_z, d_step_s, alpha)
 
-    # ---- the same for cone lists that hold generalized power cones as well (any of the seven kinds, in any order)
+    # any of the seven kinds, in any order
     def unit_initialization_gp_dev(self, d_s, d_z):
         """unit_initialization_dev with the generalized power cones' start: sqrt(1 + alpha_i) on the first dim1 rows, 0 behind."""
-        return check(_lib.lib().hipkkt_kkt_system_unit_initialization_gp(self.ks._h, C.c_void_p(d_s), C.c_void_p(d_z)),
-                     "hipkkt_kkt_system_unit_initialization_gp")
+        return self._unit_initialization("hipkkt_kkt_system_unit_initialization_gp", d_s, d_z)
 
     def affine_ds_gp_dev(self, d_out, d_s):
         """affine_ds_ns_dev, and a copy of s on the generalized power rows."""
-        return check(_lib.lib().hipkkt_kkt_system_affine_ds_gp(self.ks._h, C.c_void_p(d_out), C.c_void_p(d_s)),
-                     "hipkkt_kkt_system_affine_ds_gp")
+        return self._affine_ds("hipkkt_kkt_system_affine_ds_gp", d_out, d_s)
 
     def combined_ds_gp_dev(self, d_out, d_step_z, d_step_s, d_s, d_z, sigma_mu, m_corr):
         """combined_ds_ns_dev, and s + sigma_mu grad f*(z) (the stored gradient, no higher-order correction) on the
         generalized power rows.  d_z must be the z the current scaling was computed from."""
-        return check(_lib.lib().hipkkt_kkt_system_combined_ds_gp(self.ks._h, C.c_void_p(d_out), C.c_void_p(d_step_z),
-                                                                  C.c_void_p(d_step_s), C.c_void_p(d_s), C.c_void_p(d_z),
-                                                                  float(sigma_mu), float(m_corr)),
-                     "hipkkt_kkt_system_combined_ds_gp")
+        return self._combined_ds("hipkkt_kkt_system_combined_ds_gp", d_out, d_step_z, d_step_s, d_s, d_z, sigma_mu, m_corr)
 
     def step_length_gp_dev(self, d_step_z, d_step_s, d_z, d_s, step_tau, step_kappa, tau, kappa, backtrack_step, alpha_min):
         """step_length_ns_dev with every generalized power cone's backtracking search in the minimum -> alpha."""
-        out = np.zeros(1)
-        check(_lib.lib().hipkkt_kkt_system_step_length_gp(self.ks._h, C.c_void_p(d_step_z), C.c_void_p(d_step_s),
-                                                          C.c_void_p(d_z), C.c_void_p(d_s), float(step_tau), float(step_kappa),
-                                                          float(tau), float(kappa), float(backtrack_step), float(alpha_min),
-                                                          ptr(out)), "hipkkt_kkt_system_step_length_gp")
-        return float(out[0])
+        return self._step_length_bt("hipkkt_kkt_system_step_length_gp", d_step_z, d_step_s, d_z, d_s, step_tau, step_kappa, tau,
+                                    kappa, backtrack_step, alpha_min)
 
     def barrier_gp_dev(self, d_z, d_s, d_step_z, d_step_s, alpha):
         """barrier_dev with every generalized power cone's barrier_dual + barrier_primal in the sum."""
-        out = np.zeros(2)
-        check(_lib.lib().hipkkt_kkt_system_barrier_gp(self.ks._h, C.c_void_p(d_z), C.c_void_p(d_s), C.c_void_p(d_step_z),
-                                                      C.c_void_p(d_step_s), float(alpha), ptr(out)), "hipkkt_kkt_system_barrier_gp")
-        return float(out[0]), float(out[1])
+        return self._barrier("hipkkt_kkt_system_barrier_gp", d_z, d_s, d_step_z, d_step_s, alpha)
 
     # ---- residuals and termination scalars of a device-resident iterate, and the elementwise steps around them
     def residuals_dev(self, d_x, d_s, d_z, tau, d_rx, d_rz, d_rx_inf, d_rz_inf, d_Px, d_equil=None):
