@@ -88,6 +88,7 @@ SYMBOLS = {
     "hipkkt_kkt_update_cones": (C.c_int, [_P, _P, _P, _P, _P]),
     "hipkkt_kkt_update_from_sz": (C.c_int, [_P, _P, _P]),
     "hipkkt_kkt_update_from_sz_dev": (C.c_int, [_P, _P, _P]),
+    "hipkkt_kkt_enable_large_psd": (C.c_int, [_P, C.c_int]),
     "hipkkt_kkt_update_P": (C.c_int, [_P, _P]),
     "hipkkt_kkt_update_A": (C.c_int, [_P, _P]),
     "hipkkt_kkt_setrhs": (C.c_int, [_P, _P, _P]),

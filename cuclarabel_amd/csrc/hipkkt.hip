@@ -1864,6 +1864,12 @@ struct hipkkt_kkt_s {
     DBuf<int64_t> c_psdaoff;
     DBuf<double> psdA, psdR, psdRinv;
     bool has_psd = false, psd_too_big = false, scaling_valid = false;
+    // the big class (side > kPsdMaxDim; kernels.hpp, ConeDev): listed at creation, handed to the kernels only after
+    // hipkkt_kkt_enable_large_psd, which also allocates psd_work
+    DBuf<int> c_psdblist;
+    DBuf<double> psd_work;
+    int npsdb = 0, psdb_kmax = 1;
+    bool large_psd = false;
     double last_eps = 0;
     int64_t last_ir = 0;
     // refinement on the device (k_ir_round): state slots (4 doubles per round), a 5-double read-back record, the
@@ -1920,6 +1926,7 @@ struct hipkkt_kkt_s {
         C.gp_cone = gp_cone.p; C.gp_dim1 = gp_dim1.p; C.gp_off = gp_off.p; C.gp_alpha = gp_alpha.p;
         C.gp_small = gp_small.p; C.gp_big = gp_big.p; C.ngp_small = ngp_small; C.ngp_big = ngp_big;
         C.gp_mapP = gp_mapP.p; C.gp_mapQR = gp_mapQR.p; C.gp_mapD = gp_mapD.p; C.gp_mu = gp_mu;
+        C.psdb_list = c_psdblist.p; C.npsdb = large_psd ? npsdb : 0; C.psdb_kmax = psdb_kmax; C.psd_work = psd_work.p;
         return C;
     }
     ConeState cone_state()
@@ -2521,20 +2528,22 @@ int hipkkt_kkt_create_ex2(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t
                 for (double* q : {h->gp_grad.p, h->gp_d.p, h->gp_p.p, h->gp_qr.p}) HIP_CHECK(hipMemset(q, 0, gl * sizeof(double)));
             }
             {
-                std::vector<int> plist, pdim(nc, 0);
+                std::vector<int> plist, blist, pdim(nc, 0);
                 std::vector<int64_t> paoff(nc, 0);
                 int64_t ao = 0;
                 for (size_t c = 0; c < nc; ++c) {
                     const ConeInfo& ci = K.cones[c];
                     if (ci.kind != HIPKKT_CONE_PSD) continue;
-                    plist.push_back((int)c);
                     pdim[c] = ci.dim;
                     paoff[c] = ao;
                     ao += (int64_t)ci.dim * ci.dim;
-                    h->psd_kmax = std::max(h->psd_kmax, ci.dim);
+                    // two size classes, as gp_small / gp_big: the all-in-LDS kernels see sides <= kPsdMaxDim only
+                    if (ci.dim <= kPsdMaxDim) { plist.push_back((int)c); h->psd_kmax = std::max(h->psd_kmax, ci.dim); }
+                    else { blist.push_back((int)c); h->psdb_kmax = std::max(h->psdb_kmax, ci.dim); }
                 }
-                h->npsd = (int)plist.size();
+                h->npsd = (int)plist.size(); h->npsdb = (int)blist.size();
                 h->c_psdlist.upload(plist); h->c_psddim.upload(pdim); h->c_psdaoff.upload(paoff);
+                h->c_psdblist.upload(blist);
                 h->psdA.alloc((size_t)ao); h->psdR.alloc((size_t)ao); h->psdRinv.alloc((size_t)ao);
             }
             h->c_kind.upload(kind); h->c_off.upload(off); h->c_numel.upload(numel); h->c_boff.upload(boff);
@@ -2641,8 +2650,10 @@ static int kkt_update_from_sz_dev_impl(hipkkt_kkt_t h, const double* d_s, const 
 {
     return guarded([&]() {
         if (!h || (h->K.m > 0 && (!d_s || !d_z))) throw ArgError("hipkkt_kkt_update_from_sz: bad argument");
-        if (h->psd_too_big)
+        if (h->psd_too_big && !h->large_psd)
             throw ArgError("update_from_sz: PSD cones with side > 48 are scaled by the caller; use hipkkt_kkt_update_cones");
+        if (h->psdb_kmax > kPsdBigMaxDim)
+            throw ArgError("update_from_sz: PSD cones with side > 96 are scaled by the caller; use hipkkt_kkt_update_cones");
         HIP_CHECK(hipSetDevice(h->device));
         launch_zero_ints(h->fail.p, 1, h->stream);
         int pu = h->prof.begin(0, h->stream);
@@ -2653,6 +2664,26 @@ static int kkt_update_from_sz_dev_impl(hipkkt_kkt_t h, const double* d_s, const 
         return kkt_update_device(h, deferred);
     });
 }
+// Opt-in to the big PSD class (hipkkt.h).  The flag decides what cone_dev() hands to the launchers; a scaling made under
+// the other setting does not cover the same cones, so it stops being valid.
+int hipkkt_kkt_enable_large_psd(hipkkt_kkt_t h, int enable)
+{
+    return guarded([&]() {
+        if (!h) throw ArgError("null handle");
+        HIP_CHECK(hipSetDevice(h->device));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        const bool on = enable != 0;
+        if (on && h->npsdb > 0 && h->psdb_kmax <= kPsdBigMaxDim && !h->psd_work.p) {
+            const size_t n = (size_t)3 * h->psdb_kmax * h->psdb_kmax * h->npsdb;
+            h->psd_work.alloc(n);
+            HIP_CHECK(hipMemset(h->psd_work.p, 0, n * sizeof(double)));
+        }
+        if (on != h->large_psd && h->npsdb > 0) h->scaling_valid = false;
+        h->large_psd = on;
+        return HIPKKT_OK;
+    });
+}
+
 int hipkkt_kkt_update_from_sz_dev(hipkkt_kkt_t h, const double* d_s, const double* d_z)
 {
     return kkt_update_from_sz_dev_impl(h, d_s, d_z, h && h->deferred);
@@ -3620,13 +3651,16 @@ static void step_guard(hipkkt_kkt_t h, const char* who, StepFamily fam, bool nee
         throw ArgError(std::string(who) + ": generalized power cones are not covered (the _gp entry points are)");
     if (fam == StepFamily::Symmetric && (h->K.nnonsym > 0 || h->K.ngenpow > 0))
         throw ArgError(std::string(who) + ": symmetric cones only (the handle holds an exponential, power or generalized power cone)");
-    if (h->psd_too_big) throw ArgError(std::string(who) + ": PSD cones with side > 48 are not covered");
+    if (h->psd_too_big && !h->large_psd) throw ArgError(std::string(who) + ": PSD cones with side > 48 are not covered");
+    if (h->psdb_kmax > kPsdBigMaxDim) throw ArgError(std::string(who) + ": PSD cones with side > 96 are not covered");
     if (need_scaling && !h->scaling_valid)
         throw ArgError(std::string(who) + ": needs the cone scaling of hipkkt_kkt_system_update");
     HIP_CHECK(hipSetDevice(h->device));
-    if (!h->step_partial.p) h->step_partial.alloc((size_t)2 * step_partials(h->cone_dev()));
+    ConeDev Call = h->cone_dev();
+    Call.npsdb = h->npsdb;                            // (sized for the big PSD class whether or not it is enabled now)
+    if (!h->step_partial.p) h->step_partial.alloc((size_t)2 * step_partials(Call));
     if (!h->step_rec.p) h->step_rec.alloc(12);        // (shared with hipkkt_kkt_system_residuals' twelve scalars)
-    if (fam != StepFamily::Symmetric && !h->ns_partial.p) h->ns_partial.alloc((size_t)2 * barrier_partials(h->cone_dev()));
+    if (fam != StepFamily::Symmetric && !h->ns_partial.p) h->ns_partial.alloc((size_t)2 * barrier_partials(Call));
 }
 
 // the record of a finishing kernel (nrec doubles) on the host: published by that kernel into the pinned block and
@@ -3961,9 +3995,12 @@ int hipkkt_kkt_system_update_cones(hipkkt_kkt_t h, const double* Hs, const doubl
     if (rc != HIPKKT_OK) return rc;
     return guarded([&]() {
         const size_t m = (size_t)h->K.m, nc = h->K.cones.size();
-        if ((m && (!w || !lambda)) || (h->nsoc > 0 && !eta) || (h->npsd > 0 && (!psd_R || !psd_Rinv)))
+        if ((m && (!w || !lambda)) || (h->nsoc > 0 && !eta) || (h->npsd + h->npsdb > 0 && (!psd_R || !psd_Rinv)))
             throw ArgError("hipkkt_kkt_system_update_cones: missing scaling data");
-        if (h->psd_too_big) throw ArgError("hipkkt_kkt_system_*: PSD cones with side > 48 are not covered by level C");
+        if (h->psd_too_big && !h->large_psd)
+            throw ArgError("hipkkt_kkt_system_*: PSD cones with side > 48 are not covered by level C");
+        if (h->psdb_kmax > kPsdBigMaxDim)
+            throw ArgError("hipkkt_kkt_system_*: PSD cones with side > 96 are not covered by level C");
         HIP_CHECK(hipSetDevice(h->device));
         hipStream_t st = h->stream;
         if (m) {
@@ -3971,7 +4008,7 @@ int hipkkt_kkt_system_update_cones(hipkkt_kkt_t h, const double* Hs, const doubl
             HIP_CHECK(hipMemcpyAsync(h->lam.p, lambda, m * sizeof(double), hipMemcpyHostToDevice, st));
         }
         if (eta && nc) HIP_CHECK(hipMemcpyAsync(h->eta.p, eta, nc * sizeof(double), hipMemcpyHostToDevice, st));
-        if (h->npsd > 0) {
+        if (h->npsd + h->npsdb > 0) {
             HIP_CHECK(hipMemcpyAsync(h->psdR.p, psd_R, h->psdR.n * sizeof(double), hipMemcpyHostToDevice, st));
             HIP_CHECK(hipMemcpyAsync(h->psdRinv.p, psd_Rinv, h->psdRinv.n * sizeof(double), hipMemcpyHostToDevice, st));
             launch_psd_A_from_R(h->cone_dev(), h->cone_state(), st);       // A = R R' (mul_Hs!, coneops_psdtrianglecone.jl:164-187)
@@ -3993,9 +4030,12 @@ int hipkkt_kkt_system_update_scaling(hipkkt_kkt_t h, const double* w, const doub
     int rc = guarded([&]() {
         if (!h) throw ArgError("null handle");
         const size_t m = (size_t)h->K.m, nc = h->K.cones.size();
-        if ((m && (!w || !lambda)) || (h->nsoc > 0 && !eta) || (h->npsd > 0 && (!psd_R || !psd_Rinv)))
+        if ((m && (!w || !lambda)) || (h->nsoc > 0 && !eta) || (h->npsd + h->npsdb > 0 && (!psd_R || !psd_Rinv)))
             throw ArgError("hipkkt_kkt_system_update_scaling: missing scaling data");
-        if (h->psd_too_big) throw ArgError("hipkkt_kkt_system_*: PSD cones with side > 48 are not covered by level C");
+        if (h->psd_too_big && !h->large_psd)
+            throw ArgError("hipkkt_kkt_system_*: PSD cones with side > 48 are not covered by level C");
+        if (h->psdb_kmax > kPsdBigMaxDim)
+            throw ArgError("hipkkt_kkt_system_*: PSD cones with side > 96 are not covered by level C");
         if (h->K.nnonsym > 0)
             throw ArgError("hipkkt_kkt_system_update_scaling: (w, eta, lambda, R) cannot carry the 3 x 3 block of an exponential "
                            "or power cone; use hipkkt_kkt_system_update_cones");
@@ -4009,7 +4049,7 @@ int hipkkt_kkt_system_update_scaling(hipkkt_kkt_t h, const double* w, const doub
             HIP_CHECK(hipMemcpyAsync(h->lam.p, lambda, m * sizeof(double), hipMemcpyHostToDevice, st));
         }
         if (eta && nc) HIP_CHECK(hipMemcpyAsync(h->eta.p, eta, nc * sizeof(double), hipMemcpyHostToDevice, st));
-        if (h->npsd > 0) {
+        if (h->npsd + h->npsdb > 0) {
             HIP_CHECK(hipMemcpyAsync(h->psdR.p, psd_R, h->psdR.n * sizeof(double), hipMemcpyHostToDevice, st));
             HIP_CHECK(hipMemcpyAsync(h->psdRinv.p, psd_Rinv, h->psdRinv.n * sizeof(double), hipMemcpyHostToDevice, st));
         }

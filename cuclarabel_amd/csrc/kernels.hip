@@ -1244,9 +1244,288 @@ __global__ __launch_bounds__(256) void k_mul_Hs_psd(ConeDev C, ConeState S, doub
     }
 }
 
+// -------------------------------------------------------------------------------------
+//  PSD cones of side kPsdMaxDim < k <= kPsdBigMaxDim (C.psdb_list; hipkkt_kkt_enable_large_psd).  The same steps and the
+//  same arithmetic as k_cone_psd, one workgroup per cone, but only two k x k matrices stay in LDS: first S and Z for the
+//  two Cholesky factorisations, then the pair (M, V) that the one-sided Jacobi rotates.  L1, L2 and the product
+//  M = L2' L1 go through the cone's slice of C.psd_work, R and A through S.psdR / S.psdA themselves; a slice is read
+//  only by the workgroup that wrote it, behind a workgroup barrier.  512 threads = 64 groups of eight lanes, enough for
+//  the 48 column pairs of side 96.  Hs is formed by a launch of its own, k_psd_hs_big.
+// -------------------------------------------------------------------------------------
+constexpr int kPsdBigGroups = kPsdBigThreads / 8;
+static_assert((kPsdBigMaxDim + 1) / 2 <= kPsdBigGroups, "one group of eight lanes per column pair");
+
+__global__ __launch_bounds__(kPsdBigThreads) void k_cone_psd_big(ConeDev C, ConeState S, const double* __restrict__ s,
+                                                                 const double* __restrict__ z)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    __shared__ int sh_fail;
+    __shared__ double sh_off[kPsdBigGroups], sh_sv[kPsdBigMaxDim];
+    __shared__ int sh_rank[kPsdBigMaxDim];
+    constexpr int NT = kPsdBigThreads;
+    const int tid = threadIdx.x;
+    const int c = C.psdb_list[blockIdx.x];
+    const int k = C.psd_dim[c], off = C.off[c];
+    const int kk = k * k, t = k * (k + 1) / 2;
+    double* Sm = smem;            // S -> L1 (lower), then M = L2' L1 -> U diag(sv)
+    double* Zm = smem + kk;       // Z -> L2 (lower), then V
+    double* W = C.psd_work + (size_t)blockIdx.x * 3 * C.psdb_kmax * C.psdb_kmax;
+    double* L1 = W;
+    double* L2 = W + kk;
+    double* Mg = W + 2 * kk;
+    const double is2 = 0.70710678118654752440;
+    if (tid == 0) sh_fail = 0;
+    for (int idx = tid; idx < t; idx += NT) {
+        int r, cl;
+        svec_index(idx, r, cl);
+        const double sv = s[off + idx], zv = z[off + idx];
+        if (r == cl) { Sm[r + cl * k] = sv; Zm[r + cl * k] = zv; }
+        else {
+            Sm[r + cl * k] = Sm[cl + r * k] = sv * is2;
+            Zm[r + cl * k] = Zm[cl + r * k] = zv * is2;
+        }
+    }
+    __syncthreads();
+    // Cholesky of S and of Z, in place, right-looking (:97-104)
+    for (int pass = 0; pass < 2; ++pass) {
+        double* Mx = pass == 0 ? Sm : Zm;
+        for (int j = 0; j < k; ++j) {
+            const double d = Mx[j + j * k];
+            if (!(d > 0.0)) { if (tid == 0) sh_fail = 1; }
+            __syncthreads();
+            if (sh_fail) break;
+            const double sd = sqrt(d);
+            for (int i = j + 1 + tid; i < k; i += NT) Mx[i + j * k] /= sd;
+            if (tid == 0) Mx[j + j * k] = sd;
+            __syncthreads();
+            for (int idx = tid; idx < (k - j - 1) * (k - j - 1); idx += NT) {
+                const int a = j + 1 + idx / (k - j - 1), b = j + 1 + idx % (k - j - 1);
+                if (a >= b) Mx[a + b * k] -= Mx[a + j * k] * Mx[b + j * k];
+            }
+            __syncthreads();
+        }
+        if (sh_fail) break;
+    }
+    if (sh_fail) { if (tid == 0) *S.fail = 1; return; }
+    for (int idx = tid; idx < kk; idx += NT) {
+        const int r = idx % k, cl = idx / k;
+        if (r < cl) { Sm[idx] = 0.0; Zm[idx] = 0.0; }
+    }
+    __syncthreads();
+    // L1, L2 to the work area; M = L2' L1 (:113-114) beside them, since both its operands are still being read
+    for (int idx = tid; idx < kk; idx += NT) {
+        const int r = idx % k, cl = idx / k;
+        double acc = 0.0;
+        for (int q = (r > cl ? r : cl); q < k; ++q) acc = fma(Zm[q + r * k], Sm[q + cl * k], acc);
+        Mg[idx] = acc;
+        L1[idx] = Sm[idx];
+        L2[idx] = Zm[idx];
+    }
+    __syncthreads();
+    double* M = Sm;
+    double* V = Zm;
+    for (int idx = tid; idx < kk; idx += NT) {
+        M[idx] = Mg[idx];
+        V[idx] = (idx % k == idx / k) ? 1.0 : 0.0;
+    }
+    __syncthreads();
+    // one-sided Jacobi: rotate column pairs (p, q) of M (and of V) until all columns are mutually orthogonal
+    const int m = (k + 1) & ~1, npair = m / 2;          // k <= 96: at most 48 pairs, eight lanes each
+    const int grp = tid >> 3, sub = tid & 7;
+    for (int sweep = 0; sweep < 60; ++sweep) {
+        double myoff = 0.0;
+        for (int step = 0; step < m - 1; ++step) {
+            if (grp < npair) {
+                int p, q;
+                if (grp == 0) { p = m - 1; q = step; }
+                else { p = (step + grp) % (m - 1); q = (step - grp + (m - 1)) % (m - 1); }
+                if (p > q) { const int tmp = p; p = q; q = tmp; }
+                if (q < k) {                                           // (q == k: the dummy index of an odd k)
+                    double a = 0.0, b = 0.0, cc = 0.0;
+                    for (int i = sub; i < k; i += 8) {
+                        const double mp = M[i + p * k], mq = M[i + q * k];
+                        a = fma(mp, mp, a); b = fma(mq, mq, b); cc = fma(mp, mq, cc);
+                    }
+#pragma unroll
+                    for (int o = 4; o > 0; o >>= 1) {
+                        a += __shfl_xor(a, o, 8); b += __shfl_xor(b, o, 8); cc += __shfl_xor(cc, o, 8);
+                    }
+                    const double ab = sqrt(a) * sqrt(b);       // (sqrt(a * b) overflows / flushes for entries beyond ~2^+-256)
+                    if (!(fabs(cc) <= 1e-300 || fabs(cc) <= 1e-17 * ab)) {
+                        myoff = fmax(myoff, fabs(cc) / ab);
+                        const double zeta = (b - a) / (2.0 * cc);
+                        const double tt = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+                        const double cs = 1.0 / sqrt(1.0 + tt * tt), sn = cs * tt;
+                        for (int i = sub; i < k; i += 8) {
+                            const double mp = M[i + p * k], mq = M[i + q * k];
+                            M[i + p * k] = cs * mp - sn * mq;
+                            M[i + q * k] = sn * mp + cs * mq;
+                            const double vp = V[i + p * k], vq = V[i + q * k];
+                            V[i + p * k] = cs * vp - sn * vq;
+                            V[i + q * k] = sn * vp + cs * vq;
+                        }
+                    }
+                }
+            }
+            __syncthreads();               // the next step pairs the columns differently
+        }
+        if (sub == 0) sh_off[grp] = grp < npair ? myoff : 0.0;
+        __syncthreads();
+        double offn = 0.0;
+        for (int i = 0; i < npair; ++i) offn = fmax(offn, sh_off[i]);   // uniform: every thread reads the same words
+        __syncthreads();
+        if (offn < 1e-15) break;
+    }
+    // singular values = column norms; U = M with unit columns; descending order like LAPACK's
+    if (tid < k) {
+        double nrm = 0.0;
+        for (int i = 0; i < k; ++i) nrm = fma(M[i + tid * k], M[i + tid * k], nrm);
+        sh_sv[tid] = sqrt(nrm);
+    }
+    __syncthreads();
+    if (tid < k) {
+        const double mine = sh_sv[tid];
+        int rank = 0;
+        for (int i = 0; i < k; ++i) rank += (sh_sv[i] > mine || (sh_sv[i] == mine && i < tid)) ? 1 : 0;
+        sh_rank[tid] = rank;
+        if (S.lam) S.lam[off + rank] = mine;                   // lam occupies the first k of the cone's t slots
+    }
+    if (S.lam) for (int i = k + tid; i < t; i += NT) S.lam[off + i] = 0.0;
+    __syncthreads();
+    // R = L1 V Lam^{-1/2} (columns in sorted order), Rinv = Lam^{-1/2} U' L2' (rows in sorted order)
+    double* Rout = S.psdR + C.psd_aoff[c];
+    double* Riout = S.psdRinv + C.psd_aoff[c];
+    for (int idx = tid; idx < kk; idx += NT) {
+        const int r = idx % k, cl = idx / k;
+        double acc = 0.0;
+        for (int q = 0; q <= r; ++q) acc = fma(L1[r + q * k], V[q + cl * k], acc);
+        const double sc = 1.0 / sqrt(sh_sv[cl]);
+        Rout[r + sh_rank[cl] * k] = acc * sc;
+        // Rinv(row cl of the unsorted order, column r): (1/sqrt(s_cl)) (1/s_cl) sum_q M(q, cl) L2(r, q)
+        double acc2 = 0.0;
+        for (int q = 0; q <= r; ++q) acc2 = fma(M[q + cl * k], L2[r + q * k], acc2);
+        Riout[sh_rank[cl] + r * k] = acc2 * sc / sh_sv[cl];
+    }
+    __syncthreads();
+    double* Aout = S.psdA + C.psd_aoff[c];
+    for (int idx = tid; idx < kk; idx += NT) {
+        const int r = idx % k, cl = idx / k;
+        double acc = 0.0;
+        if (r <= cl) {                                           // upper triangle (syrk 'U'), mirrored: exactly symmetric
+            for (int q = 0; q < k; ++q) acc = fma(Rout[r + q * k], Rout[cl + q * k], acc);
+            Aout[r + cl * k] = acc; Aout[cl + r * k] = acc;
+        }
+    }
+}
+
+// (A cone whose S or Z is not positive definite leaves k_cone_psd_big before R and A are written; this launch, which
+// does not know, then still writes that cone's Hs block from whatever psdA held.  The small class leaves the block
+// untouched instead.  Either way the update reports the failure and the block's contents are unspecified: hipkkt.h.)
+// Hs = A (x)_s A of the big class, packed upper triangle: at side 96 the block has 10.8 M entries, so the columns of a
+// cone are dealt round-robin to gridDim.x workgroups (blockIdx.y = the cone), each with A in LDS.  (k, l) of a column is
+// found once; a thread's rows advance by 256, and (i, j) with them.  Each entry is the expression of k_cone_psd's tail.
+constexpr int kPsdBigHsChunks = 128;
+__global__ __launch_bounds__(256) void k_psd_hs_big(ConeDev C, ConeState S)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int tid = threadIdx.x;
+    const int c = C.psdb_list[blockIdx.y];
+    const int k = C.psd_dim[c], t = k * (k + 1) / 2;
+    double* Am = smem;
+    const double* A = S.psdA + C.psd_aoff[c];
+    for (int idx = tid; idx < k * k; idx += 256) Am[idx] = A[idx];
+    __syncthreads();
+    double* Hs = S.Hs + C.boff[c];
+    const double s2 = 1.41421356237309504880;
+    int i0, j0;
+    svec_index(tid, i0, j0);                                   // (t > 256: row tid exists)
+    for (int col = blockIdx.x; col < t; col += gridDim.x) {
+        int kq, l;
+        svec_index(col, kq, l);         // col <-> (k, l), k <= l
+        const bool kl = (kq == l);
+        double* Hc = Hs + (int64_t)col * (col + 1) / 2;
+        int i = i0, j = j0;             // row <-> (i, j), i <= j
+        for (int row = tid; row <= col; row += 256) {
+            double v;
+            const bool ij = (i == j);
+            if (!ij && !kl) v = Am[i + kq * k] * Am[j + l * k] + Am[i + l * k] * Am[j + kq * k];
+            else if (ij && !kl) v = s2 * Am[j + l * k] * Am[j + kq * k];
+            else if (!ij && kl) v = s2 * Am[i + l * k] * Am[j + kq * k];
+            else v = Am[j + l * k] * Am[j + l * k];
+            Hc[row] = v;
+            i += 256;
+            while (i > j) { i -= j + 1; ++j; }
+        }
+    }
+}
+
+// y = (A (x)_s A) x = svec(A X A) for the big class: X and A in LDS, T = X A through the work area and then in X's place.
+// (The round trip through HBM exists only to reuse X's space: T cannot be written over X while other threads still read
+// X's rows, and a third matrix does not fit LDS at side 96.  A thread copies back the entries it wrote itself.)
+__global__ __launch_bounds__(kPsdBigThreads) void k_mul_Hs_psd_big(ConeDev C, ConeState S, double* __restrict__ y,
+                                                                   const double* __restrict__ x,
+                                                                   const double* __restrict__ addend)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int NT = kPsdBigThreads;
+    const int tid = threadIdx.x;
+    const int c = C.psdb_list[blockIdx.x];
+    const int k = C.psd_dim[c], off = C.off[c], kk = k * k, t = k * (k + 1) / 2;
+    double* X = smem;
+    double* Am = smem + kk;
+    double* Tg = C.psd_work + (size_t)blockIdx.x * 3 * C.psdb_kmax * C.psdb_kmax;
+    const double is2 = 0.70710678118654752440;
+    const double* A = S.psdA + C.psd_aoff[c];
+    for (int idx = tid; idx < kk; idx += NT) Am[idx] = A[idx];
+    for (int idx = tid; idx < t; idx += NT) {
+        int r, cl;
+        svec_index(idx, r, cl);
+        const double v = x[off + idx];
+        if (r == cl) X[r + cl * k] = v;
+        else X[r + cl * k] = X[cl + r * k] = v * is2;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < kk; idx += NT) {
+        const int r = idx % k, cl = idx / k;
+        double acc = 0.0;
+        for (int q = 0; q < k; ++q) acc = fma(X[r + q * k], Am[q + cl * k], acc);
+        Tg[idx] = acc;
+    }
+    __syncthreads();
+    double* Tm = X;
+    for (int idx = tid; idx < kk; idx += NT) Tm[idx] = Tg[idx];
+    __syncthreads();
+    for (int idx = tid; idx < t; idx += NT) {
+        int r, cl;
+        svec_index(idx, r, cl);
+        double a1 = 0.0, a2 = 0.0;
+        for (int q = 0; q < k; ++q) { a1 = fma(Am[r + q * k], Tm[q + cl * k], a1); a2 = fma(Am[cl + q * k], Tm[q + r * k], a2); }
+        const double v = (r == cl) ? a1 : (a1 + a2) * is2;
+        y[off + idx] = addend ? -(v + addend[off + idx]) : v;
+    }
+}
+
+static void psd_big_set_lds()
+{
+    static PerDeviceOnce once;
+    once.run([]() {
+        const int one = kPsdBigMaxDim * kPsdBigMaxDim * (int)sizeof(double);
+        hipError_t e = set_max_lds(k_cone_psd_big, 2 * one);
+        if (e == hipSuccess) e = set_max_lds(k_psd_hs_big, one);
+        if (e == hipSuccess) e = set_max_lds(k_mul_Hs_psd_big, 2 * one);
+        return e;
+    });
+}
+
 void launch_cone_scaling(const ConeDev& C, const ConeState& S, const double* s, const double* z, int m,
                          hipStream_t st)
 {
+    if (C.npsdb > 0) {
+        psd_big_set_lds();
+        const size_t one = (size_t)C.psdb_kmax * C.psdb_kmax * sizeof(double);
+        hipLaunchKernelGGL(k_cone_psd_big, dim3(C.npsdb), dim3(kPsdBigThreads), 2 * one, st, C, S, s, z);
+        hipLaunchKernelGGL(k_psd_hs_big, dim3(kPsdBigHsChunks, C.npsdb), dim3(256), one, st, C, S);
+    }
     const int ge = m > 0 ? grid_for(m, 256) : 0, gs = (C.nsoc + 3) / 4;
     const int gx = (C.nexp + 255) / 256, gp = (C.npow + 255) / 256;
     const int gg = (C.ngp_small + 3) / 4 + C.ngp_big;
@@ -1341,9 +1620,8 @@ __global__ __launch_bounds__(256) void k_mul_Hs_gp(ConeDev C, ConeState S, doubl
     mul_Hs_genpow_body<256>(C, S, y, x, addend, C.gp_big[b0 - gq], threadIdx.x, sh);
 }
 // A = R R' per PSD cone, from a caller-supplied R (hipkkt_kkt_system_update_cones); one workgroup per cone
-__global__ __launch_bounds__(256) void k_psd_A_from_R(ConeDev C, ConeState S)
+__device__ inline void psd_A_from_R_body(const ConeDev& C, const ConeState& S, int c)
 {
-    const int c = C.psd_list[blockIdx.x];
     const int k = C.psd_dim[c];
     const double* R = S.psdR + C.psd_aoff[c];
     double* A = S.psdA + C.psd_aoff[c];
@@ -1354,9 +1632,13 @@ __global__ __launch_bounds__(256) void k_psd_A_from_R(ConeDev C, ConeState S)
         A[idx] = acc;
     }
 }
+__global__ __launch_bounds__(256) void k_psd_A_from_R(ConeDev C, ConeState S) { psd_A_from_R_body(C, S, C.psd_list[blockIdx.x]); }
+// ... and for the big class (nothing in LDS, so the side does not matter: only the list differs)
+__global__ __launch_bounds__(256) void k_psd_A_from_R_big(ConeDev C, ConeState S) { psd_A_from_R_body(C, S, C.psdb_list[blockIdx.x]); }
 void launch_psd_A_from_R(const ConeDev& C, const ConeState& S, hipStream_t st)
 {
     if (C.npsd > 0) hipLaunchKernelGGL(k_psd_A_from_R, dim3(C.npsd), dim3(256), 0, st, C, S);
+    if (C.npsdb > 0) hipLaunchKernelGGL(k_psd_A_from_R_big, dim3(C.npsdb), dim3(256), 0, st, C, S);
 }
 
 // ---- get_Hs! and the sparse second-order-cone vectors from a GIVEN scaling (w, eta; psdA = R R'): what a caller that
@@ -1451,12 +1733,18 @@ void launch_cone_from_scaling(const ConeDev& C, const ConeState& S, int m, hipSt
         const size_t lds = (size_t)C.psd_kmax * C.psd_kmax * sizeof(double);
         hipLaunchKernelGGL(k_psd_hs_from_A, dim3(C.npsd), dim3(256), lds, st, C, S);
     }
+    if (C.npsdb > 0) {
+        psd_big_set_lds();
+        hipLaunchKernelGGL(k_psd_A_from_R_big, dim3(C.npsdb), dim3(256), 0, st, C, S);
+        const size_t lds = (size_t)C.psdb_kmax * C.psdb_kmax * sizeof(double);
+        hipLaunchKernelGGL(k_psd_hs_big, dim3(kPsdBigHsChunks, C.npsdb), dim3(256), lds, st, C, S);
+    }
 }
 void launch_mul_Hs(const ConeDev& C, const ConeState& S, double* y, const double* x, int m, hipStream_t st, const double* addend,
                    const Publish& pub)
 {
     const int ge = m > 0 ? grid_for(m, 256) : 0, gs = (C.nsoc + 3) / 4;
-    const bool ride = ge + gs > 0 && C.npsd == 0;          // (the publication rides with the LAST kernel of the call)
+    const bool ride = ge + gs > 0 && C.npsd + C.npsdb == 0;   // (the publication rides with the LAST kernel of the call)
     const int gg = (C.ngp_small + 3) / 4 + C.ngp_big;
     if (gg > 0)
         hipLaunchKernelGGL(k_mul_Hs_gp, dim3(ge + gs + gg), dim3(256), 0, st, C, S, y, x, m, addend, ge, gs, ride ? pub : Publish{});
@@ -1464,6 +1752,11 @@ void launch_mul_Hs(const ConeDev& C, const ConeState& S, double* y, const double
     if (C.npsd > 0) {
         const size_t lds = (size_t)3 * C.psd_kmax * C.psd_kmax * sizeof(double);
         hipLaunchKernelGGL(k_mul_Hs_psd, dim3(C.npsd), dim3(256), lds, st, C, S, y, x, addend);
+    }
+    if (C.npsdb > 0) {
+        psd_big_set_lds();
+        const size_t lds = (size_t)2 * C.psdb_kmax * C.psdb_kmax * sizeof(double);
+        hipLaunchKernelGGL(k_mul_Hs_psd_big, dim3(C.npsdb), dim3(kPsdBigThreads), lds, st, C, S, y, x, addend);
     }
     if (!ride) launch_publish(pub, st);
 }
@@ -1578,6 +1871,53 @@ __global__ __launch_bounds__(256) void k_sys_offset_psd(ConeDev C, ConeState S, 
     }
 }
 
+// ... for the big class: X and R in LDS, Tm = X R' through the work area and then in X's place (as k_mul_Hs_psd_big)
+__global__ __launch_bounds__(kPsdBigThreads) void k_sys_offset_psd_big(ConeDev C, ConeState S, double* __restrict__ konst,
+                                                                       double* __restrict__ workz,
+                                                                       const double* __restrict__ ds,
+                                                                       const double* __restrict__ rhs_z)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int NT = kPsdBigThreads;
+    const int tid = threadIdx.x;
+    const int c = C.psdb_list[blockIdx.x];
+    const int k = C.psd_dim[c], off = C.off[c], kk = k * k, t = k * (k + 1) / 2;
+    double* X = smem;
+    double* Rm = smem + kk;
+    double* Tg = C.psd_work + (size_t)blockIdx.x * 3 * C.psdb_kmax * C.psdb_kmax;
+    const double is2 = 0.70710678118654752440;
+    const double* R = S.psdR + C.psd_aoff[c];
+    const double* lam = S.lam + off;
+    for (int idx = tid; idx < kk; idx += NT) Rm[idx] = R[idx];
+    for (int idx = tid; idx < t; idx += NT) {
+        int r, cl;
+        svec_index(idx, r, cl);
+        const double v = ds[off + idx] * (r == cl ? 1.0 : is2) * 2.0 / (lam[r] + lam[cl]);
+        X[r + cl * k] = v;
+        X[cl + r * k] = v;
+    }
+    __syncthreads();
+    for (int idx = tid; idx < kk; idx += NT) {           // Tm = X R'
+        const int r = idx % k, cl = idx / k;
+        double acc = 0.0;
+        for (int q = 0; q < k; ++q) acc = fma(X[r + q * k], Rm[cl + q * k], acc);
+        Tg[idx] = acc;
+    }
+    __syncthreads();
+    double* Tm = X;
+    for (int idx = tid; idx < kk; idx += NT) Tm[idx] = Tg[idx];
+    __syncthreads();
+    for (int idx = tid; idx < t; idx += NT) {            // Y = R Tm, svec
+        int r, cl;
+        svec_index(idx, r, cl);
+        double a1 = 0.0, a2 = 0.0;
+        for (int q = 0; q < k; ++q) { a1 = fma(Rm[r + q * k], Tm[q + cl * k], a1); a2 = fma(Rm[cl + q * k], Tm[q + r * k], a2); }
+        const double o = (r == cl) ? a1 : (a1 + a2) * is2;
+        konst[off + idx] = o;
+        workz[off + idx] = o - rhs_z[off + idx];
+    }
+}
+
 __global__ __launch_bounds__(256) void k_sys_offset(ConeDev C, ConeState S, double* __restrict__ konst, double* __restrict__ workz,
                                                     const double* __restrict__ ds, const double* __restrict__ z,
                                                     const double* __restrict__ rhs_z, int m, int affine, int ge)
@@ -1595,6 +1935,12 @@ bool launch_sys_offset(const ConeDev& C, const ConeState& S, double* konst, doub
         once.run([]() { return set_max_lds(k_sys_offset_psd, 150 * 1024); });
         const size_t lds = (size_t)3 * C.psd_kmax * C.psd_kmax * sizeof(double);
         hipLaunchKernelGGL(k_sys_offset_psd, dim3(C.npsd), dim3(256), lds, st, C, S, konst, workz, ds, rhs_z);
+    }
+    if (!affine && C.npsdb > 0) {
+        static PerDeviceOnce once;
+        once.run([]() { return set_max_lds(k_sys_offset_psd_big, 2 * kPsdBigMaxDim * kPsdBigMaxDim * (int)sizeof(double)); });
+        const size_t lds = (size_t)2 * C.psdb_kmax * C.psdb_kmax * sizeof(double);
+        hipLaunchKernelGGL(k_sys_offset_psd_big, dim3(C.npsdb), dim3(kPsdBigThreads), lds, st, C, S, konst, workz, ds, rhs_z);
     }
     const int ge = grid_for(m, 256), gs = affine ? 0 : (C.nsoc + 3) / 4;
     hipLaunchKernelGGL(k_sys_offset, dim3(ge + gs), dim3(256), 0, st, C, S, konst, workz, ds, z, rhs_z, m, affine ? 1 : 0, ge);

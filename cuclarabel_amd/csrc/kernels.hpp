@@ -454,6 +454,12 @@ struct ConeDev {
     const int* gp_mapD = nullptr;    // three per cone
     int ngp_small = 0, ngp_big = 0;
     double gp_mu = 0.0;
+    // PSD cones of side kPsdMaxDim < k <= kPsdBigMaxDim, listed only on a handle that has opted in
+    // (hipkkt_kkt_enable_large_psd); psd_list holds the sides <= kPsdMaxDim.  psd_work: 3 psdb_kmax^2 doubles per listed
+    // cone, in list order -- the matrices the big-class kernels stream instead of keeping them in LDS.
+    const int* psdb_list = nullptr;
+    int npsdb = 0, psdb_kmax = 1;
+    double* psd_work = nullptr;
 };
 // A generalized power cone of up to this many rows is scaled (and multiplied) by one wave, four cones to a workgroup: 8
 // rows per lane, all loads of a pass in flight at once.  A larger one takes a workgroup of 256 with an LDS stage.
@@ -483,6 +489,13 @@ struct ConeState {
     const int* kpos = nullptr;
 };
 constexpr int kPsdMaxDim = 48;   // largest PSD side handled by the in-LDS scaling kernel
+// Largest side of the big class.  Its scaling kernel keeps in LDS only the pair (M, V) that the one-sided Jacobi rotates,
+// 2 k^2 doubles: 147 456 B at k = 96, which leaves 16 KB of the CU's 160 KiB for the reduction arrays; at k = 100 the pair
+// takes 160 000 B and leaves 3 840 B.  96 is the last multiple of 16 that fits.  (= HIPKKT_PSD_MAX_SIDE_LARGE)
+constexpr int kPsdBigMaxDim = 96;
+// Workgroup of the big class: the Jacobi sweeps give a column pair eight lanes, and side 96 has 48 pairs, which 256
+// threads (32 groups of eight) cannot hold; 512 threads are 64 groups.
+constexpr int kPsdBigThreads = 512;
 void launch_cone_scaling(const ConeDev& C, const ConeState& S, const double* s, const double* z, int m,
                          hipStream_t st);
 // addend != null: y = -(W'W x + addend) (the Delta_s recovery of kkt_solve!, kktsystem.jl:206-212)
@@ -538,8 +551,10 @@ void launch_neg_copy(double* y, const double* a, int n, hipStream_t st);        
 // ---- the cone operations of the loop BETWEEN the solves, on device vectors (step_kernels.hip); symmetric cones only
 // (zero, nonnegative, second-order, PSD side <= kPsdMaxDim) -- the caller refuses other handles.
 constexpr int kStepGridCap = 2048;          // workgroups of the elementwise part (grid-stride beyond 2048 * 256 rows)
-// slots of the step-length partials (one per elementwise workgroup, second-order cone and PSD cone); margins needs twice as many
-inline int step_partials(const ConeDev& C) { return kStepGridCap + C.nsoc + C.npsd; }
+// slots of the step-length partials (one per elementwise workgroup, second-order cone and PSD cone); margins needs twice as many.
+// The big PSD class keeps its slots at the END of every partials array, so that the others' positions and the fold order
+// do not depend on it.
+inline int step_partials(const ConeDev& C) { return kStepGridCap + C.nsoc + C.npsd + C.npsdb; }
 // out = lambda o lambda (affine_ds!, coneops_compositecone.jl:153-165), and with `combined`
 //       + (W^{-T} step_s) o (W (m_corr step_z)) - sigma_mu e (_combined_ds_shift_symmetric!, coneops_symmetric_common.jl:1-35)
 void launch_step_ds(const ConeDev& C, const ConeState& S, double* out, const double* step_z, const double* step_s,
@@ -560,7 +575,7 @@ void launch_unit_shift(const ConeDev& C, double* v, double a1, double a2, bool t
 // one wave per cone of gp_small / one workgroup per cone of gp_big, as the scaling kernel splits them
 // slots of the barrier partials: elementwise workgroups, second-order cones, PSD cones, workgroups of the lane-per-cone part
 // and a slot per generalized power cone (the step length's per-cone minima fit in the same array)
-inline int barrier_partials(const ConeDev& C) { return 2 * kStepGridCap + C.nsoc + C.npsd + C.ngp_small + C.ngp_big; }
+inline int barrier_partials(const ConeDev& C) { return 2 * kStepGridCap + C.nsoc + C.npsd + C.ngp_small + C.ngp_big + C.npsdb; }
 // unit_initialization! of every cone (solver.jl:383-404, the asymmetric start) into s and z; a generalized power cone
 // (coneops_genpowcone.jl:34-53): s_i = z_i = sqrt(1 + alpha_i) on its first dim1 rows, 0 behind
 void launch_unit_initialization(const ConeDev& C, const ConeState& S, double* s, double* z, int m, hipStream_t st);

@@ -2,7 +2,8 @@
 //   affine_ds!, combined_ds_shift!      coneops_compositecone.jl:153-182
 //   step_length                         coneops_compositecone.jl:205-243
 //   margins, scaled_unit_shift!         coneops_compositecone.jl:49-76
-// for the symmetric cones (zero, nonnegative, second-order, PSD side <= kPsdMaxDim).  Launch shapes as k_sys_offset /
+// for the symmetric cones (zero, nonnegative, second-order, PSD side <= kPsdMaxDim; on an opted-in handle the big PSD
+// class up to kPsdBigMaxDim, whose kernels stand beside the small class's below).  Launch shapes as k_sys_offset /
 // k_sys_offset_psd: an elementwise grid-stride part with one wave per second-order cone riding behind it, one 256-thread
 // workgroup per PSD cone with its matrices in LDS.  Compiled without FMA contraction: the exact-zero branches of the
 // second-order step length are tested on products and differences formed as the reference forms them.
@@ -46,14 +47,14 @@ struct OpMin { __device__ double operator()(double a, double b) const { return f
 struct OpMax { __device__ double operator()(double a, double b) const { return fmax(a, b); } };
 struct OpSum { __device__ double operator()(double a, double b) const { return a + b; } };
 
-// fixed tree over the 256 threads of a workgroup; every thread gets the result
-template <class Op>
-__device__ inline double block_reduce_256(double v, double* sh, Op op)
+// fixed tree over the NT threads of a workgroup; every thread gets the result
+template <int NT, class Op>
+__device__ inline double block_reduce_n(double v, double* sh, Op op)
 {
     const int tid = threadIdx.x;
     sh[tid] = v;
     __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
+    for (int o = NT / 2; o > 0; o >>= 1) {
         if (tid < o) sh[tid] = op(sh[tid], sh[tid + o]);
         __syncthreads();
     }
@@ -61,6 +62,8 @@ __device__ inline double block_reduce_256(double v, double* sh, Op op)
     __syncthreads();
     return r;
 }
+template <class Op>
+__device__ inline double block_reduce_256(double v, double* sh, Op op) { return block_reduce_n<256>(v, sh, op); }
 
 __device__ inline void st_publish(const Publish& P)
 {
@@ -78,17 +81,19 @@ __device__ inline void st_publish(const Publish& P)
 //  The pairs of a step touch disjoint columns in 2 and disjoint rows in 3.  Unlike the one-sided sweep (an SVD) this
 //  keeps the signs, and its error in every eigenvalue is ABSOLUTE, a modest multiple of k u ||A|| -- what the step
 //  length needs of the smallest one (the reference calls LAPACK's syevr).  Rotations stop when a whole sweep saw no
-//  off-diagonal entry above 2^-60 ||A||_F.  On return the eigenvalues are the diagonal.  All 256 threads call.
+//  off-diagonal entry above 2^-60 ||A||_F.  On return the eigenvalues are the diagonal.  All NT threads call; NT / 8
+//  groups of eight lanes must cover the pairs: 256 threads up to side 64, kPsdBigThreads up to kPsdBigMaxDim.
 // ---------------------------------------------------------------------------------------------------------------------
+template <int NT = 256>
 __device__ inline void sym_jacobi_eig(double* A, int k, double* sh)
 {
     const int tid = threadIdx.x;
     double f = 0.0;
-    for (int idx = tid; idx < k * k; idx += 256) f += A[idx] * A[idx];
-    f = sqrt(block_reduce_256(f, sh, OpSum{}));
+    for (int idx = tid; idx < k * k; idx += NT) f += A[idx] * A[idx];
+    f = sqrt(block_reduce_n<NT>(f, sh, OpSum{}));
     if (!(f > 0.0) || !(f <= DBL_MAX)) return;          // the zero matrix (or a non-finite one: unspecified input)
     const double thr_conv = ldexp(f, -60), thr_skip = ldexp(f, -80);
-    const int mm = (k + 1) & ~1, npair = mm / 2;         // k <= 48: at most 24 pairs
+    const int mm = (k + 1) & ~1, npair = mm / 2;         // at most NT / 8 pairs
     const int grp = tid >> 3, sub = tid & 7;
     for (int sweep = 0; sweep < 40; ++sweep) {
         double myoff = 0.0;
@@ -136,16 +141,17 @@ __device__ inline void sym_jacobi_eig(double* A, int k, double* sh)
             }
             __syncthreads();
         }
-        const double offn = block_reduce_256(myoff, sh, OpMax{});
+        const double offn = block_reduce_n<NT>(myoff, sh, OpMax{});
         if (offn <= thr_conv) break;
     }
 }
 
 // X = mat(scale * x) of an svec vector (coneops_psdtrianglecone.jl:469-483), both triangles
+template <int NT = 256>
 __device__ inline void psd_load_mat(double* X, const double* __restrict__ x, double scale, int k)
 {
     const int t = k * (k + 1) / 2;
-    for (int idx = threadIdx.x; idx < t; idx += 256) {
+    for (int idx = threadIdx.x; idx < t; idx += NT) {
         int r, cl;
         st_svec_index(idx, r, cl);
         const double v = scale * x[idx] * (r == cl ? 1.0 : kIs2);
@@ -156,17 +162,19 @@ __device__ inline void psd_load_mat(double* X, const double* __restrict__ x, dou
 
 // M = G' X G for symmetric X, exactly symmetric (each pair (r, c) from both orders, averaged).  mul_W!(:N) is G = R
 // (R' X R, :409-437 with :N), mul_Winv!(:T) is G = Rinv' (Rinv X Rinv').  T: work matrix.  Ends with a barrier.
+// (The big class passes T, and where it can M, in its work area in HBM: the workgroup's own stores, read behind a barrier.)
+template <int NT = 256>
 __device__ inline void psd_congruence(double* M, double* T, const double* G, const double* X, int k)
 {
     const int tid = threadIdx.x, kk = k * k, t = k * (k + 1) / 2;
-    for (int idx = tid; idx < kk; idx += 256) {          // T = X G
+    for (int idx = tid; idx < kk; idx += NT) {           // T = X G
         const int r = idx % k, cl = idx / k;
         double acc = 0.0;
         for (int q = 0; q < k; ++q) acc = fma(X[r + q * k], G[q + cl * k], acc);
         T[idx] = acc;
     }
     __syncthreads();
-    for (int idx = tid; idx < t; idx += 256) {           // M = G' T
+    for (int idx = tid; idx < t; idx += NT) {            // M = G' T
         int r, cl;
         st_svec_index(idx, r, cl);
         double a1 = 0.0, a2 = 0.0;
@@ -179,9 +187,10 @@ __device__ inline void psd_congruence(double* M, double* T, const double* G, con
 }
 
 // G = R (transpose = 0) or Rinv' (transpose = 1) into LDS
+template <int NT = 256>
 __device__ inline void psd_load_G(double* G, const double* __restrict__ src, int k, int transpose)
 {
-    for (int idx = threadIdx.x; idx < k * k; idx += 256) {
+    for (int idx = threadIdx.x; idx < k * k; idx += NT) {
         const int r = idx % k, cl = idx / k;
         G[idx] = transpose ? src[cl + r * k] : src[idx];
     }
@@ -300,6 +309,51 @@ __global__ __launch_bounds__(256) void k_step_ds_psd(ConeDev C, ConeState S, dou
     }
 }
 
+// The big PSD class (C.psdb_list, side <= kPsdBigMaxDim): the same steps with kPsdBigThreads threads and two matrices
+// in LDS -- the operands G and X of a product; T and Z go through the cone's slice of C.psd_work.
+__global__ __launch_bounds__(kPsdBigThreads) void k_step_ds_psd_big(ConeDev C, ConeState S, double* __restrict__ out,
+                                                                    const double* __restrict__ dz,
+                                                                    const double* __restrict__ ds, double sigma_mu,
+                                                                    double m_corr, int combined)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    constexpr int NT = kPsdBigThreads;
+    const int tid = threadIdx.x;
+    const int c = C.psdb_list[blockIdx.x];
+    const int k = C.psd_dim[c], off = C.off[c], kk = k * k, t = k * (k + 1) / 2;
+    const double* lam = S.lam + off;
+    if (!combined) {
+        for (int idx = tid; idx < t; idx += NT) {
+            int r, cl;
+            st_svec_index(idx, r, cl);
+            out[off + idx] = r == cl ? lam[r] * lam[r] : 0.0;
+        }
+        return;
+    }
+    double* W = C.psd_work + (size_t)blockIdx.x * 3 * C.psdb_kmax * C.psdb_kmax;
+    double* G = smem;
+    double* X = smem + kk;          // mat(ds), then Y
+    double* T = W;
+    double* Z = W + kk;
+    psd_load_G<NT>(G, S.psdR + C.psd_aoff[c], k, 0);
+    psd_load_mat<NT>(X, dz + off, m_corr, k);
+    __syncthreads();
+    psd_congruence<NT>(Z, T, G, X, k);
+    psd_load_G<NT>(G, S.psdRinv + C.psd_aoff[c], k, 1);
+    psd_load_mat<NT>(X, ds + off, 1.0, k);
+    __syncthreads();
+    psd_congruence<NT>(X, T, G, X, k);                   // (the product X G is complete before X is overwritten)
+    const double* Y = X;
+    for (int idx = tid; idx < t; idx += NT) {
+        int r, cl;
+        st_svec_index(idx, r, cl);
+        double a1 = 0.0, a2 = 0.0;
+        for (int q = 0; q < k; ++q) { a1 = fma(Y[r + q * k], Z[q + cl * k], a1); a2 = fma(Z[r + q * k], Y[q + cl * k], a2); }
+        const double v = 0.5 * (a1 + a2);
+        out[off + idx] = r == cl ? lam[r] * lam[r] + (v - sigma_mu) : v * kS2;
+    }
+}
+
 // =====================================================================================================================
 //  step_length: every cone's limit is min(alpha_max, f(cone)), so the composite's sequential tightening of alpha_max
 //  (coneops_compositecone.jl:205-243) is an order-free minimum: each workgroup / wave / PSD cone leaves its f in a slot
@@ -407,6 +461,42 @@ __global__ __launch_bounds__(256) void k_step_length_psd(ConeDev C, ConeState S,
     if (tid == 0) slots[blockIdx.x] = alpha;
 }
 
+// ... of the big class: G and X in LDS, T through the work area, M in X's place, where the two-sided Jacobi then runs
+__global__ __launch_bounds__(kPsdBigThreads) void k_step_length_psd_big(ConeDev C, ConeState S, const double* __restrict__ dz,
+                                                                        const double* __restrict__ ds,
+                                                                        double* __restrict__ slots)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    __shared__ double sh[kPsdBigThreads];
+    constexpr int NT = kPsdBigThreads;
+    const int tid = threadIdx.x;
+    const int c = C.psdb_list[blockIdx.x];
+    const int k = C.psd_dim[c], off = C.off[c], kk = k * k;
+    double* G = smem;
+    double* X = smem + kk;
+    double* T = C.psd_work + (size_t)blockIdx.x * 3 * C.psdb_kmax * C.psdb_kmax;
+    double* M = X;
+    const double* lam = S.lam + off;
+    double alpha = DBL_MAX;
+    for (int comp = 0; comp < 2; ++comp) {
+        psd_load_G<NT>(G, (comp == 0 ? S.psdR : S.psdRinv) + C.psd_aoff[c], k, comp);
+        psd_load_mat<NT>(X, (comp == 0 ? dz : ds) + off, 1.0, k);
+        __syncthreads();
+        psd_congruence<NT>(M, T, G, X, k);               // (the product X G is complete before X is overwritten)
+        for (int idx = tid; idx < kk; idx += NT) {       // lrscale! with Lam^{-1/2} (symmetric entries get the same factors)
+            const int r = idx % k, cl = idx / k;
+            M[idx] = M[idx] * ((1.0 / sqrt(lam[r])) * (1.0 / sqrt(lam[cl])));
+        }
+        __syncthreads();
+        sym_jacobi_eig<NT>(M, k, sh);
+        double g = DBL_MAX;
+        for (int i = 0; i < k; ++i) g = fmin(g, M[i + i * k]);          // uniform: every thread reads the same words
+        if (g < 0.0) alpha = fmin(alpha, 1.0 / (-g));
+        __syncthreads();
+    }
+    if (tid == 0) slots[blockIdx.x] = alpha;
+}
+
 // variables_calc_step_length (variables.jl:14-43) without max_step_fraction: min(1, tau limit, kappa limit, cones)
 __global__ __launch_bounds__(256) void k_step_length_finish(const double* __restrict__ partial, int np, double step_tau,
                                                             double step_kappa, double tau, double kappa,
@@ -471,6 +561,28 @@ __global__ __launch_bounds__(256) void k_margins_psd(ConeDev C, const double* __
     psd_load_mat(smem, v + off, 1.0, k);
     __syncthreads();
     sym_jacobi_eig(smem, k, sh);
+    if (threadIdx.x == 0) {
+        double mn = DBL_MAX, sum = 0.0;
+        for (int i = 0; i < k; ++i) {
+            const double e = smem[i + i * k];
+            mn = fmin(mn, e);
+            if (e > 0.0) sum += e;
+        }
+        pmin[blockIdx.x] = mn;
+        psum[blockIdx.x] = sum;
+    }
+}
+
+__global__ __launch_bounds__(kPsdBigThreads) void k_margins_psd_big(ConeDev C, const double* __restrict__ v,
+                                                                    double* __restrict__ pmin, double* __restrict__ psum)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    __shared__ double sh[kPsdBigThreads];
+    const int c = C.psdb_list[blockIdx.x];
+    const int k = C.psd_dim[c], off = C.off[c];
+    psd_load_mat<kPsdBigThreads>(smem, v + off, 1.0, k);
+    __syncthreads();
+    sym_jacobi_eig<kPsdBigThreads>(smem, k, sh);
     if (threadIdx.x == 0) {
         double mn = DBL_MAX, sum = 0.0;
         for (int i = 0; i < k; ++i) {
@@ -835,6 +947,54 @@ __global__ __launch_bounds__(256) void k_barrier_psd(ConeDev C, const double* __
     if (tid == 0) slots[blockIdx.x] = sh_fail ? HUGE_VAL : bar;
 }
 
+// ... of the big class: the one matrix still fits LDS; kPsdBigThreads threads
+__global__ __launch_bounds__(kPsdBigThreads) void k_barrier_psd_big(ConeDev C, const double* __restrict__ z,
+                                                                    const double* __restrict__ s,
+                                                                    const double* __restrict__ dz,
+                                                                    const double* __restrict__ ds, double alpha,
+                                                                    double* __restrict__ slots)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    __shared__ int sh_fail;
+    constexpr int NT = kPsdBigThreads;
+    const int tid = threadIdx.x;
+    const int c = C.psdb_list[blockIdx.x];
+    const int k = C.psd_dim[c], off = C.off[c], t = k * (k + 1) / 2;
+    double* X = smem;
+    if (tid == 0) sh_fail = 0;
+    double bar = 0.0;                                                  // (thread 0's)
+    for (int comp = 0; comp < 2; ++comp) {
+        const double* x = (comp == 0 ? z : s) + off;
+        const double* dx = (comp == 0 ? dz : ds) + off;
+        for (int idx = tid; idx < t; idx += NT) {
+            int r, cl;
+            st_svec_index(idx, r, cl);
+            const double v = (x[idx] + alpha * dx[idx]) * (r == cl ? 1.0 : kIs2);
+            X[r + cl * k] = v;
+            X[cl + r * k] = v;
+        }
+        __syncthreads();
+        for (int j = 0; j < k; ++j) {
+            const double d = X[j + j * k];
+            if (!(d > 0.0)) { if (tid == 0) sh_fail = 1; }
+            __syncthreads();
+            if (sh_fail) break;
+            const double sd = sqrt(d);
+            for (int i = j + 1 + tid; i < k; i += NT) X[i + j * k] /= sd;
+            if (tid == 0) { X[j + j * k] = sd; bar -= 2.0 * log(sd); }
+            __syncthreads();
+            const int w = k - j - 1;
+            for (int idx = tid; idx < w * w; idx += NT) {
+                const int a = j + 1 + idx / w, b = j + 1 + idx % w;
+                if (a >= b) X[a + b * k] -= X[a + j * k] * X[b + j * k];
+            }
+            __syncthreads();
+        }
+        if (sh_fail) break;
+    }
+    if (tid == 0) slots[blockIdx.x] = sh_fail ? HUGE_VAL : bar;
+}
+
 __global__ __launch_bounds__(256) void k_barrier_ns(ConeDev C, const double* __restrict__ z, const double* __restrict__ s,
                                                     const double* __restrict__ dz, const double* __restrict__ ds, double alpha,
                                                     double* __restrict__ slots)
@@ -1136,6 +1296,20 @@ inline int step_grid(int m)
 }
 
 inline size_t step_psd_lds(const ConeDev& C) { return (size_t)4 * C.psd_kmax * C.psd_kmax * sizeof(double); }
+// the big PSD class: n matrices of its largest side; the attribute is set once for all four kernels
+inline size_t step_psdb_lds(const ConeDev& C, int n) { return (size_t)n * C.psdb_kmax * C.psdb_kmax * sizeof(double); }
+inline void step_psdb_set_lds()
+{
+    static PerDeviceOnce once;
+    once.run([]() {
+        const int one = kPsdBigMaxDim * kPsdBigMaxDim * (int)sizeof(double);
+        hipError_t e = set_max_lds(k_step_ds_psd_big, 2 * one);
+        if (e == hipSuccess) e = set_max_lds(k_step_length_psd_big, 2 * one);
+        if (e == hipSuccess) e = set_max_lds(k_margins_psd_big, one);
+        if (e == hipSuccess) e = set_max_lds(k_barrier_psd_big, one);
+        return e;
+    });
+}
 
 }  // namespace
 
@@ -1148,6 +1322,11 @@ void launch_step_ds(const ConeDev& C, const ConeState& S, double* out, const dou
         once.run([]() { return set_max_lds(k_step_ds_psd, 150 * 1024); });
         hipLaunchKernelGGL(k_step_ds_psd, dim3(C.npsd), dim3(256), combined ? step_psd_lds(C) : 0, st, C, S, out, step_z, step_s,
                            sigma_mu, m_corr, combined ? 1 : 0);
+    }
+    if (C.npsdb > 0) {
+        step_psdb_set_lds();
+        hipLaunchKernelGGL(k_step_ds_psd_big, dim3(C.npsdb), dim3(kPsdBigThreads), combined ? step_psdb_lds(C, 2) : 0, st, C, S,
+                           out, step_z, step_s, sigma_mu, m_corr, combined ? 1 : 0);
     }
     const int ge = step_grid(m), gs = (C.nsoc + 3) / 4;
     hipLaunchKernelGGL(k_step_ds, dim3(ge + gs), dim3(256), 0, st, C, S, out, step_z, step_s, sigma_mu, m_corr, m,
@@ -1164,9 +1343,14 @@ void launch_step_length(const ConeDev& C, const ConeState& S, const double* dz, 
         once.run([]() { return set_max_lds(k_step_length_psd, 150 * 1024); });
         hipLaunchKernelGGL(k_step_length_psd, dim3(C.npsd), dim3(256), step_psd_lds(C), st, C, S, dz, ds, partial + ge + C.nsoc);
     }
+    if (C.npsdb > 0) {
+        step_psdb_set_lds();
+        hipLaunchKernelGGL(k_step_length_psd_big, dim3(C.npsdb), dim3(kPsdBigThreads), step_psdb_lds(C, 2), st, C, S, dz, ds,
+                           partial + ge + C.nsoc + C.npsd);
+    }
     hipLaunchKernelGGL(k_step_length, dim3(ge + gs), dim3(256), 0, st, C, dz, ds, z, s, m, partial, ge);
-    hipLaunchKernelGGL(k_step_length_finish, dim3(1), dim3(256), 0, st, partial, ge + C.nsoc + C.npsd, step_tau, step_kappa,
-                       tau, kappa, rec, pub);
+    hipLaunchKernelGGL(k_step_length_finish, dim3(1), dim3(256), 0, st, partial, ge + C.nsoc + C.npsd + C.npsdb, step_tau,
+                       step_kappa, tau, kappa, rec, pub);
 }
 
 void launch_margins(const ConeDev& C, const double* v, double* partial, double* rec, const Publish& pub, int m, hipStream_t st)
@@ -1180,8 +1364,13 @@ void launch_margins(const ConeDev& C, const double* v, double* partial, double* 
         hipLaunchKernelGGL(k_margins_psd, dim3(C.npsd), dim3(256), (size_t)C.psd_kmax * C.psd_kmax * sizeof(double), st, C, v,
                            pmin + ge + C.nsoc, psum + ge + C.nsoc);
     }
+    if (C.npsdb > 0) {
+        step_psdb_set_lds();
+        hipLaunchKernelGGL(k_margins_psd_big, dim3(C.npsdb), dim3(kPsdBigThreads), step_psdb_lds(C, 1), st, C, v,
+                           pmin + ge + C.nsoc + C.npsd, psum + ge + C.nsoc + C.npsd);
+    }
     hipLaunchKernelGGL(k_margins, dim3(ge + gs), dim3(256), 0, st, C, v, m, pmin, psum, ge);
-    hipLaunchKernelGGL(k_margins_finish, dim3(1), dim3(256), 0, st, pmin, psum, ge + C.nsoc + C.npsd, rec, pub);
+    hipLaunchKernelGGL(k_margins_finish, dim3(1), dim3(256), 0, st, pmin, psum, ge + C.nsoc + C.npsd + C.npsdb, rec, pub);
 }
 
 void launch_unit_shift(const ConeDev& C, double* v, double a1, double a2, bool two, bool primal, int m, hipStream_t st)
@@ -1251,7 +1440,13 @@ void launch_barrier(const ConeDev& C, const double* z, const double* s, const do
     if (ngp > 0)
         hipLaunchKernelGGL(k_gp_barrier, dim3((C.ngp_small + 3) / 4 + C.ngp_big), dim3(256), 0, st, C, z, s, dz, ds, alpha,
                            pbar + ge + C.nsoc + C.npsd + gn);
-    hipLaunchKernelGGL(k_barrier_finish, dim3(1), dim3(256), 0, st, pbar, ge + C.nsoc + C.npsd + gn + ngp, pdot, ge, rec, pub);
+    if (C.npsdb > 0) {
+        step_psdb_set_lds();
+        hipLaunchKernelGGL(k_barrier_psd_big, dim3(C.npsdb), dim3(kPsdBigThreads), step_psdb_lds(C, 1), st, C, z, s, dz, ds, alpha,
+                           pbar + ge + C.nsoc + C.npsd + gn + ngp);
+    }
+    hipLaunchKernelGGL(k_barrier_finish, dim3(1), dim3(256), 0, st, pbar, ge + C.nsoc + C.npsd + gn + ngp + C.npsdb, pdot, ge, rec,
+                       pub);
 }
 
 }  // namespace hipkkt

@@ -1086,6 +1086,9 @@ def solve(P, q, A, b, cone_specs, backend, settings=None):
          update(s, z)                 -> bool     (kktsolver_update! after update_scaling!(s,z))
          kktsolver_setrhs(rx, rz); kktsolver_solve(x_out, z_out) -> bool
          last_ir_iterations
+       and may offer
+         psd_scaling()                -> [(R, Rinv, lambda) per PSD cone] of the scaling the last update(s, z) built K
+                                         from; the host's PSD cone objects then adopt it (one scaling per iteration)
     """
     st = settings or IPMSettings()
     P = sp.csc_matrix(P)
@@ -1258,6 +1261,12 @@ def solve(P, q, A, b, cone_specs, backend, settings=None):
                 adopt_device_scaling(cones, backend.ks.scaling()[1])
         else:
             ok = backend.update(s, z, mu=mu, strategy=strategy) if nonsym else backend.update(s, z)
+            # A backend that can say which PSD scaling its K was built from (psd_scaling() -> [(R, Rinv, lambda)]) is
+            # asked: ds = -(Hs dz + ...) formed with the host's own R does not belong to the dz that K gave, the
+            # two A = R R' differ by eps cond, and on the 1225-row blocks of a nearly complementary PSD(49) the primal
+            # residual then grows again from 1e-8 (as adopt_device_genpow's note says of the generalized power cone).
+            if ok and hasattr(backend, "psd_scaling") and any(isinstance(c, _PSD) and c.n for c in cones):
+                adopt_device_scaling(cones, backend.psd_scaling())
             if ok:
                 ok, x2, z2 = ksolve(-q, b)
 
@@ -1396,9 +1405,9 @@ def solve(P, q, A, b, cone_specs, backend, settings=None):
 class HipBackend:
     """The MI355X path: libhipkkt.so through HipKKTSolver (level B of the C ABI)."""
 
-    def __init__(self, P, A, cone_specs, settings=None):
+    def __init__(self, P, A, cone_specs, settings=None, large_psd=False):
         from .kktsolver import HipKKTSolver
-        self.ks = HipKKTSolver(P, A, cone_specs, settings=settings)
+        self.ks = HipKKTSolver(P, A, cone_specs, settings=settings, large_psd=large_psd)
         self.specs = list(cone_specs)
 
     def update_identity(self):
@@ -1424,8 +1433,9 @@ class HipSystemBackend(HipBackend):
     """As HipBackend, but the reduced-system layer (kktsystem.jl) runs on the device too (level C of the
     C ABI): the driver hands over iterates and right-hand sides and gets the step back."""
 
-    def __init__(self, P, A, cone_specs, settings=None, batch_affine=False, lazy=False, host_cones=False, staging="host"):
-        super().__init__(P, A, cone_specs, settings=settings)
+    def __init__(self, P, A, cone_specs, settings=None, batch_affine=False, lazy=False, host_cones=False, staging="host",
+                 large_psd=False):
+        super().__init__(P, A, cone_specs, settings=settings, large_psd=large_psd)
         from .kktsolver import HipKKTSystem
         self.system = HipKKTSystem(self.ks)
         self.system.staging = staging              # "host": the *_host entry points; "torch": device tensors + *_dev

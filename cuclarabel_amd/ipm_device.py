@@ -41,7 +41,9 @@ from .cones import (ZeroConeT, NonnegativeConeT, SecondOrderConeT, PSDTriangleCo
 from .ipm import (IPMSettings, IPMResult, HipSystemBackend, SOLVED, PRIMAL_INFEASIBLE, DUAL_INFEASIBLE, MAX_ITERATIONS,
                   NUMERICAL_ERROR, INSUFFICIENT_PROGRESS, UNSOLVED, ALMOST_SOLVED, PRIMAL_DUAL, DUAL, _logsafe)
 
-PSD_MAX_SIDE = 48          # kPsdMaxDim of the device kernels
+PSD_MAX_SIDE = 48          # kPsdMaxDim of the device kernels: the all-in-LDS class, what a handle covers by default
+PSD_MAX_SIDE_LARGE = 96    # kPsdBigMaxDim = HIPKKT_PSD_MAX_SIDE_LARGE: with hipkkt_kkt_enable_large_psd, which the entry
+#                            points below call themselves for a list that holds a side above PSD_MAX_SIDE
 
 
 class _Csr:
@@ -88,8 +90,8 @@ def _check_cones(who, cone_specs, allowed, hint):
     for c in cone_specs:
         if not isinstance(c, allowed):
             raise ValueError(hint.format(type(c).__name__))
-        if isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE:
-            raise ValueError(f"{who} covers PSD cones up to side {PSD_MAX_SIDE}")
+        if isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE_LARGE:
+            raise ValueError(f"{who} covers PSD cones up to side {PSD_MAX_SIDE_LARGE}")
     return cone_specs
 
 
@@ -152,7 +154,8 @@ def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym, genpow=Fal
     normq = np.abs(q).max() if n else 0.0
     normb = np.abs(b).max() if m else 0.0
 
-    backend = HipSystemBackend(P, A, cone_specs)
+    large_psd = any(isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE for c in cone_specs)
+    backend = HipSystemBackend(P, A, cone_specs, large_psd=large_psd)
     ks, system = backend.ks, backend.system
     if genpow:                                           # the five cone operations of a non-symmetric list
         unit_initialization, affine_ds_ns, combined_ds_ns, step_length_ns_dev, barrier_dev = (

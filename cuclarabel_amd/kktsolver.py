@@ -32,7 +32,7 @@ class HipKKTSolver:
     """DirectLDLKKTSolver on the MI355X: KKT assembly maps, value scatter, regularisation,
     numeric LDL', triangular solves and iterative refinement all run on the device."""
 
-    def __init__(self, P, A, cones, m=None, n=None, settings=None):
+    def __init__(self, P, A, cones, m=None, n=None, settings=None, large_psd=False):
         L = _lib.lib()
         P = sp.triu(sp.csc_matrix(P), format="csc")
         P.sort_indices()
@@ -65,6 +65,8 @@ class HipKKTSolver:
         self.info = info.as_dict()
         self.p = info.p
         self.N = info.N
+        if large_psd:
+            self.enable_large_psd(True)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -97,6 +99,11 @@ class HipKKTSolver:
     def kktsolver_update_from_sz_dev(self, d_s, d_z):
         return check(_lib.lib().hipkkt_kkt_update_from_sz_dev(self._h, C.c_void_p(d_s), C.c_void_p(d_z)),
                      "hipkkt_kkt_update_from_sz_dev")
+
+    def enable_large_psd(self, enable=True):
+        """Opt in to (or out of) the device path for PSD cones of side 49 ... 96 (hipkkt_kkt_enable_large_psd), at every
+        level: without it a handle with such a cone is refused as before."""
+        check(_lib.lib().hipkkt_kkt_enable_large_psd(self._h, int(bool(enable))), "hipkkt_kkt_enable_large_psd")
 
     def kktsolver_setrhs(self, rhsx, rhsz):
         rx, rz = f64(rhsx), f64(rhsz)

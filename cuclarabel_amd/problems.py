@@ -469,3 +469,33 @@ def generalized_power_mix(copies=4, seed=3101, shapes=GENPOW_MIX_SHAPES):
                         [np.concatenate([np.sqrt(1.0 + np.array(c.alpha)), np.zeros(c.dim2)]) for c in specs])
     return Problem(f"genpow_mix_{len(specs)}", P, q, A, b, cones, s0, s0.copy(), np.zeros(n),
                    meta=dict(seed=seed, copies=copies, ncones=len(specs)))
+
+
+def max_eigenvalue_sdp(C):
+    """The largest eigenvalue of a symmetric matrix C as an SDP with a known answer at any side:
+
+        minimise t   s.t.  t I - C  positive semidefinite
+
+    n = 1, one cone PSD(k): A = -svec(I), b = -svec(C), so that s = b - A t = svec(t I - C).  The optimum is
+    lambda_max(C) (numpy.linalg.eigvalsh).  (s0, z0) = svec(I), x0 = lambda_max's upper bound ||C||_F + 1."""
+    C = np.asarray(C, dtype=float)
+    k = C.shape[0]
+    if C.shape != (k, k) or not np.allclose(C, C.T):
+        raise ValueError("C must be square and symmetric")
+    eye = mat_to_svec(np.eye(k))
+    A = _csc(sp.csc_matrix(-eye.reshape(-1, 1)))
+    P = _triu_csc(sp.csc_matrix((1, 1)))
+    return Problem(f"max_eigenvalue_sdp_k{k}", P, np.ones(1), A, -mat_to_svec((C + C.T) / 2), [PSDTriangleConeT(k)],
+                   eye.copy(), eye.copy(), np.array([np.linalg.norm(C) + 1.0]), meta=dict(side=k))
+
+
+def sdp_large_cones(seed=1105, n=60, sides=(49, 50)):
+    """config5's construction with PSD cones of the given sides (any side; above 48 the device path is the opt-in big
+    class): A 3 nnz/row local window, P = 1e-3 I, b = A x0 + s0 with s0 interior, so the problem is strictly feasible."""
+    rng = np.random.default_rng(seed)
+    cones = [PSDTriangleConeT(int(k)) for k in sides]
+    m = total_numel(cones)
+    P = (1e-3 * sp.identity(n)).tocsc()
+    A = _local_window_A(m, n, 3, rng)
+    return _finish(f"sdp_large_cones_n{n}_" + "x".join(str(int(k)) for k in sides), P, A, cones, rng, seed=seed,
+                   meta=dict(sides=tuple(int(k) for k in sides)))

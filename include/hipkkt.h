@@ -213,6 +213,26 @@ int hipkkt_kkt_update_cones(hipkkt_kkt_t h, const double *Hsblocks, const double
  * point is not interior (update_scaling! returning false). */
 int hipkkt_kkt_update_from_sz(hipkkt_kkt_t h, const double *s, const double *z);
 int hipkkt_kkt_update_from_sz_dev(hipkkt_kkt_t h, const double *d_s, const double *d_z);
+/* PSD cones of side 49 ... HIPKKT_PSD_MAX_SIDE_LARGE on the device, opt-in per handle.  update_scaling! of a PSD cone
+ * (coneops_psdtrianglecone.jl:78-161: two Cholesky factors, the SVD of L2'L1, R, Rinv, Hs = RR' (x)_s RR') runs for
+ * sides <= 48 in one workgroup with all six k x k work matrices in LDS; that is the default, and without this call a
+ * handle with a larger PSD cone is refused by hipkkt_kkt_update_from_sz[_dev], by level C and by the cone operations
+ * between the solves ("side > 48") exactly as before.  With
+ * enable = 1 the cones of side 49 ... 96 are scaled by a second kernel class that keeps in LDS only the matrix pair
+ * (M, V) the one-sided Jacobi SVD rotates and streams the rest through a per-handle work area in HBM, which this call
+ * allocates; Hs is then formed by many workgroups per cone.  Why 96: 2 k^2 doubles are 147 456 B at k = 96, leaving
+ * 16 KB of a CU's 160 KiB of LDS for the reduction arrays; at k = 100 they are 160 000 B and leave 3 840 B; 96 is the
+ * last multiple of 16 that fits.  An enabled handle is taken by every entry point that takes side <= 48 without the
+ * call: hipkkt_kkt_update_from_sz[_dev], hipkkt_kkt_mul_Hs, hipkkt_kkt_get_Hs / _get_scaling / _get_scaling_w, all of
+ * level C (hipkkt_kkt_system_*) and the fourteen cone operations between the solves.  A cone of side > 96 stays
+ * refused by the same guards, with a message that says "side > 96".  Cones of side <= 48 and all other cones launch what they
+ * launch without the call and give the same bits.  May be called at any time between operations; it synchronises the
+ * handle's stream, and a device-side scaling made under the other setting stops being valid (hipkkt_kkt_mul_Hs and
+ * hipkkt_kkt_get_scaling then ask for a new hipkkt_kkt_update_from_sz).  hipkkt_kkt_update_cones, which takes any
+ * side, is unaffected.  After an update that reports a cone point outside its cone, the Hs block of that cone is
+ * unspecified (the small class leaves it as it was, the big class overwrites it).  Returns HIPKKT_OK, HIPKKT_ERR_ARG for a null handle, or a HIP error. */
+#define HIPKKT_PSD_MAX_SIDE_LARGE 96
+int hipkkt_kkt_enable_large_psd(hipkkt_kkt_t h, int enable);
 /* kktsolver_update_P! / kktsolver_update_A! (kktsolver_directldl.jl:374-386) */
 int hipkkt_kkt_update_P(hipkkt_kkt_t h, const double *Pnzval);
 int hipkkt_kkt_update_A(hipkkt_kkt_t h, const double *Anzval);
@@ -254,7 +274,8 @@ int hipkkt_kkt_solve_multi_dev(hipkkt_kkt_t h, int64_t nrhs, const double *d_rhs
  * (dtau, dx, dz, ds, dkappa) (dots, quad_form mathutils.jl:299-337, mul_Hs!) run on the device, so
  * per solve only the scalars cross PCIe.  Vectors named d_* are
  * device pointers: x-like length n, s/z-like length m.  Covers zero, nonnegative, second-order and PSD
- * cones (PSD side <= 48, the limit of hipkkt_kkt_update_from_sz). */
+ * cones (PSD side <= 48, the limit of hipkkt_kkt_update_from_sz; <= 96 on a handle that has called
+ * hipkkt_kkt_enable_large_psd). */
 /* DefaultKKTSystem constructor (kktsystem.jl:21-52): q (n), b (m) host vectors, copied */
 int hipkkt_kkt_system_init(hipkkt_kkt_t h, const double *q, const double *b);
 /* kkt_update! (kktsystem.jl:62-78): cone scaling from (s, z), refactor, constant-RHS solve */
@@ -289,7 +310,8 @@ int hipkkt_kkt_system_update_and_solve_affine(hipkkt_kkt_t h, double *d_lhs_x, d
  * the pending update).  They need hipkkt_kkt_system_init and -- except hipkkt_kkt_system_shift_to_interior -- the cone
  * scaling of a hipkkt_kkt_system_update* call.  Inputs are never modified (the reference uses step.z / step.s as work
  * space; these do not); d_out must not alias an input.  Symmetric cones only (zero, nonnegative, second-order, PSD side
- * <= 48): on a handle that holds an exponential, power or generalized power cone, or a larger PSD cone, and on a
+ * <= 48, or <= 96 after hipkkt_kkt_enable_large_psd): on a handle that holds an exponential, power or generalized
+ * power cone, or a larger PSD cone, and on a
  * deferred-status handle, every one of them returns HIPKKT_ERR_ARG (see hipkkt_last_error) and enqueues nothing.
  * Results are reproducible bit for bit: every reduction has a fixed layout and there are no floating-point atomics. */
 /* affine_ds! over all cones (coneops_compositecone.jl:153-165; nncone :117-126, socone :219-228 via circ_op! :376-392,
@@ -323,9 +345,9 @@ int hipkkt_kkt_system_shift_to_interior(hipkkt_kkt_t h, double *d_v, int primal,
 /* The same operations for cone lists that hold an exponential or a power cone, and the two that only such lists need
  * (the unit start and the barrier of the dual-scaling line search), so that their iterate stays in HBM too.  They are
  * entry points of their own: the four above keep refusing such handles.  Covered: zero, nonnegative, second-order, PSD
- * (side <= 48), exponential and power cones in any order.  Same rules as above: they need hipkkt_kkt_system_init and --
+ * (side <= 48, or <= 96 after hipkkt_kkt_enable_large_psd), exponential and power cones in any order.  Same rules as above: they need hipkkt_kkt_system_init and --
  * except hipkkt_kkt_system_unit_initialization -- the cone scaling of a hipkkt_kkt_system_update* call; on a handle that
- * holds a generalized power cone or a PSD cone of side > 48, and on a deferred-status handle, each returns
+ * holds a generalized power cone or a PSD cone of side > 48 (> 96 once enabled), and on a deferred-status handle, each returns
  * HIPKKT_ERR_ARG and enqueues nothing.  Inputs are never modified, outputs must not alias inputs, all work goes on the
  * handle's stream, results are reproducible bit for bit (fixed reduction layout, no floating-point atomics).  On the
  * rows of the symmetric cones each gives, bit for bit, what its counterpart above gives on a handle with those cones
@@ -390,9 +412,11 @@ int hipkkt_kkt_system_barrier(hipkkt_kkt_t h, const double *d_z, const double *d
 
 /* The same five operations for cone lists that hold a generalized power cone as well (coneops_genpowcone.jl), so that
  * the iterate of such a problem stays in HBM too.  Entry points of their own: the nine above keep refusing what they
- * refuse.  Covered: zero, nonnegative, second-order, PSD (side <= 48), exponential, power and generalized power cones in
+ * refuse.  Covered: zero, nonnegative, second-order, PSD (side <= 48, or <= 96 after hipkkt_kkt_enable_large_psd),
+ * exponential, power and generalized power cones in
  * any order.  Same rules as the _ns block: they need hipkkt_kkt_system_init and -- except the unit start -- the cone
- * scaling of a hipkkt_kkt_system_update* call; on a deferred-status handle or one with a PSD cone of side > 48 each
+ * scaling of a hipkkt_kkt_system_update* call; on a deferred-status handle or one with a PSD cone of side > 48 (> 96
+ * once enabled) each
  * returns HIPKKT_ERR_ARG with nothing enqueued and nothing written.  Inputs are never modified, outputs must not alias
  * inputs, all work goes on the handle's stream.  On every row that is not a generalized power cone's each call gives,
  * bit for bit, what its _ns counterpart gives on a handle with those cones alone: the same kernels are launched first,

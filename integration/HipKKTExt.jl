@@ -167,6 +167,8 @@ mutable struct HipKKTSolver{T} <: AbstractKKTSolver{T}
             h, n, m, Pt.colptr, Pt.rowval, Pt.nzval, A.colptr, A.rowval, A.nzval,
             length(kinds), kinds, dims, pptr, pvals, cs, 1)
         check(rc, "hipkkt_kkt_create_ex2") || error("hipkkt_kkt_create_ex2: numeric failure")
+        # PSD cones of side 49 ... 96 on the device too (opt-in per handle; the glue has no use for the refusal)
+        check(ccall((:hipkkt_kkt_enable_large_psd, libhipkkt), Cint, (Ptr{Cvoid}, Cint), h[], 1), "hipkkt_kkt_enable_large_psd")
         info = Ref{CInfo}()
         check(ccall((:hipkkt_kkt_info, libhipkkt), Cint, (Ptr{Cvoid}, Ref{CInfo}), h[], info), "hipkkt_kkt_info")
         obj = new(h[], m, n, zeros(T, info[].nHs), zeros(T, info[].sparse_soc_len),
