@@ -126,6 +126,14 @@ SYMBOLS = {
     "hipkkt_kkt_system_residuals": (C.c_int, [_P, _P, _P, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hipkkt_kkt_system_combined_rhs": (C.c_int, [_P, _P, _P, _P, _P, C.c_double]),
     "hipkkt_kkt_system_add_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_double]),
+    "hipkkt_kkt_system_set_problems": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "hipkkt_kkt_system_residuals_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "hipkkt_kkt_system_solve_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int]),
+    "hipkkt_kkt_system_combined_ds_batch": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "hipkkt_kkt_system_step_length_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "hipkkt_kkt_system_shift_to_interior_batch": (C.c_int, [_P, _P, C.c_int, _P]),
+    "hipkkt_kkt_system_combined_rhs_batch": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "hipkkt_kkt_system_add_step_batch": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "hipkkt_kkt_system_set_lazy": (C.c_int, [_P, C.c_int]),
     "hipkkt_kkt_system_update_cones": (C.c_int, [_P] * 10),
     "hipkkt_kkt_system_update_scaling": (C.c_int, [_P] * 6),

@@ -27,6 +27,7 @@
 #include "knobs.hpp"
 #include "schedule.hpp"
 #include "iterate_rows.hpp"
+#include "batch_plan.hpp"
 
 namespace hipkkt {
 
@@ -1835,6 +1836,7 @@ struct hipkkt_kkt_s {
     // the prefixes the iterate-residual pass walks (iterate_rows.hpp; kernels.hpp: IterDev), its slots and long-row sums
     DBuf<int64_t> it_rend, it_long_chunk_ptr, it_chunk_q;
     DBuf<int> it_long_rows;
+    std::vector<int> it_long_rows_h;                             // ... on the host, for hipkkt_kkt_system_set_problems
     DBuf<double> it_long_partial, it_partial;
     int it_nlong = 0, it_nchunks = 0;
     bool it_prefix_ok = true;
@@ -1892,6 +1894,28 @@ struct hipkkt_kkt_s {
     bool sys_lazy = false;           // hipkkt_kkt_system_set_lazy: kkt_update! leaves (x2, z2) = K \ (-q, b) to the affine kkt_solve!
     bool sys_const_pending = false;  // ... and that solve is still due
     bool sys_update_unread = false;  // lazy mode: the last kkt_update!'s status sits in the sticky record, read with the next solve's
+    // hipkkt_kkt_system_set_problems: the partition's tables on the device (batch_plan.hpp; kernels.hpp: BatchDev) and the
+    // work space of the _batch entry points, all sized by the number of members.  bat_nb = 0: no partition.
+    int bat_nb = 0, bat_nwg32 = 0, bat_nwg256 = 0, bat_nwgz = 0;
+    DBuf<int> bat_xoff, bat_zoff, bat_xmem, bat_zmem, bat_cmem, bat_socptr, bat_psdptr, bat_lorder, bat_lptr;
+    DBuf<int> bat_r32mem, bat_r32first, bat_r32ptr, bat_r256mem, bat_r256first, bat_r256ptr, bat_z256mem, bat_z256first, bat_z256ptr;
+    DBuf<double> bat_degree;
+    DBuf<double> bat_scal, bat_rec, bat_shift, bat_dtau;     // 4 nb scalars in, 12 nb results out, 3 nb shifts, nb dtau
+    DBuf<double> bat_it_partial, bat_step_partial, bat_dot_partial;
+    double* bat_pin = nullptr;       // page-locked: [0, 4 nb) the scalars on their way up, [4 nb, 16 nb) the results on their way down
+    hipEvent_t bat_ev = nullptr;     // behind the last upload from bat_pin: waited for before bat_pin is written again
+    BatchDev batch_dev() const
+    {
+        BatchDev B;
+        B.nb = bat_nb;
+        B.x_off = bat_xoff.p; B.z_off = bat_zoff.p; B.xmem = bat_xmem.p; B.zmem = bat_zmem.p; B.cone_mem = bat_cmem.p;
+        B.soc_ptr = bat_socptr.p; B.psd_ptr = bat_psdptr.p; B.degree = bat_degree.p;
+        B.rows32 = BatchChunksDev{bat_r32mem.p, bat_r32first.p, bat_r32ptr.p, bat_nwg32};
+        B.rows256 = BatchChunksDev{bat_r256mem.p, bat_r256first.p, bat_r256ptr.p, bat_nwg256};
+        B.z256 = BatchChunksDev{bat_z256mem.p, bat_z256first.p, bat_z256ptr.p, bat_nwgz};
+        B.long_order = bat_lorder.p; B.long_ptr = bat_lptr.p;
+        return B;
+    }
     DBuf<double> hst;                // staging of the *_host entry points of level C: 3 x (n + 2 m) doubles (rhs, variables, lhs)
     bool host_vars_valid = false;    // hst holds the variables of the previous hipkkt_kkt_system_solve_host call
     // "the caller's host arrays may be reused": an event behind the uploads, waited for at the end of the call -- the
@@ -1911,6 +1935,8 @@ struct hipkkt_kkt_s {
     ~hipkkt_kkt_s()
     {
         if (ev_upload) (void)hipEventDestroy(ev_upload);
+        if (bat_ev) (void)hipEventDestroy(bat_ev);
+        if (bat_pin) (void)hipHostFree(bat_pin);
         if (stream && own_stream) (void)hipStreamDestroy(stream);
     }
 
@@ -2406,6 +2432,7 @@ int hipkkt_kkt_create_ex2(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t
                 h->it_rend.upload(R.rend);
                 h->it_nlong = (int)R.long_rows.size();
                 h->it_nchunks = (int)(R.chunk_q.size() / 2);
+                h->it_long_rows_h = R.long_rows;
                 if (h->it_nlong) {
                     h->it_long_rows.upload(R.long_rows);
                     h->it_long_chunk_ptr.upload(R.long_chunk_ptr);
@@ -3959,6 +3986,245 @@ int hipkkt_kkt_system_add_step(hipkkt_kkt_t h, double* d_x, double* d_s, double*
         if ((d_x && d_x == d_dx) || (d_s && (d_s == d_ds || d_s == d_dz)) || (d_z && (d_z == d_dz || d_z == d_ds)) || (d_s && d_s == d_z))
             throw ArgError("hipkkt_kkt_system_add_step: bad argument (a step must not alias the vector it is added to)");
         launch_iterate_add_step(d_x, d_s, d_z, d_dx, d_ds, d_dz, alpha, h->K.n, h->K.m, h->stream);
+        return HIPKKT_OK;
+    });
+}
+
+// ---- a stack of independent member problems on one handle (batch_plan.hpp; kernels.hpp: BatchDev): the partition, and the
+// seven operations between the solves with every scalar an array over the members.  Each call uploads its scalar arrays
+// in ONE copy and reads its results back in ONE copy, whatever the number of members.
+int hipkkt_kkt_system_set_problems(hipkkt_kkt_t h, int64_t nb, const int64_t* x_off, const int64_t* z_off)
+{
+    return guarded([&]() {
+        if (!h) throw ArgError("null handle");
+        if (!h->sys_ready) throw ArgError("hipkkt_kkt_system_*: call hipkkt_kkt_system_init first");
+        if (h->deferred) throw ArgError("hipkkt_kkt_system_*: level C reads its scalars back (deferred status is for level B)");
+        HIP_CHECK(hipSetDevice(h->device));
+        if (nb == 0) {                                   // (the tables stay allocated until the next partition or the handle's end)
+            h->bat_nb = 0;
+            return HIPKKT_OK;
+        }
+        if (nb < 0) throw ArgError("hipkkt_kkt_system_set_problems: the number of members is negative");
+        if (h->K.nnonsym > 0 || h->K.ngenpow > 0)
+            throw ArgError("hipkkt_kkt_system_set_problems: symmetric cones only (the handle holds an exponential, power or "
+                           "generalized power cone)");
+        if (h->large_psd || h->psd_too_big)
+            throw ArgError("hipkkt_kkt_system_set_problems: PSD cones up to side 48 only (the handle has enabled large PSD cones "
+                           "or holds one)");
+        std::vector<BatchCone> cones;
+        for (const ConeInfo& ci : h->K.cones) cones.push_back(BatchCone{ci.kind, ci.off, ci.numel, ci.dim});
+        BatchPlan P;
+        const std::string err = plan_batch(h->K.n, h->K.m, nb, x_off, z_off, cones.data(), (int)cones.size(), h->K.colptr.data(),
+                                           h->K.rowval.data(), h->it_long_rows_h.data(), (int)h->it_long_rows_h.size(), P);
+        if (!err.empty()) throw ArgError("hipkkt_kkt_system_set_problems: " + err);
+        HIP_CHECK(hipStreamSynchronize(h->stream));      // (nothing in flight reads the tables that are replaced now)
+        h->bat_nb = 0;
+        h->bat_xoff.upload(P.x_off); h->bat_zoff.upload(P.z_off); h->bat_xmem.upload(P.xmem); h->bat_zmem.upload(P.zmem);
+        h->bat_cmem.upload(P.cone_mem); h->bat_socptr.upload(P.soc_ptr); h->bat_psdptr.upload(P.psd_ptr);
+        h->bat_degree.upload(P.degree);
+        h->bat_r32mem.upload(P.rows32.wg_mem); h->bat_r32first.upload(P.rows32.wg_first); h->bat_r32ptr.upload(P.rows32.wg_ptr);
+        h->bat_r256mem.upload(P.rows256.wg_mem); h->bat_r256first.upload(P.rows256.wg_first); h->bat_r256ptr.upload(P.rows256.wg_ptr);
+        h->bat_z256mem.upload(P.z256.wg_mem); h->bat_z256first.upload(P.z256.wg_first); h->bat_z256ptr.upload(P.z256.wg_ptr);
+        h->bat_lorder.upload(P.long_order); h->bat_lptr.upload(P.long_ptr);
+        h->bat_nwg32 = (int)P.rows32.wg_mem.size();
+        h->bat_nwg256 = (int)P.rows256.wg_mem.size();
+        h->bat_nwgz = (int)P.z256.wg_mem.size();
+        const size_t k = (size_t)P.nb;
+        h->bat_scal.alloc(4 * k); h->bat_rec.alloc(12 * k); h->bat_shift.alloc(3 * k); h->bat_dtau.alloc(k);
+        h->bat_it_partial.alloc((size_t)kIterValues * ((size_t)h->bat_nwg32 + (size_t)h->it_nlong));
+        h->bat_step_partial.alloc(2 * ((size_t)h->bat_nwgz + (size_t)h->nsoc + (size_t)h->npsd));
+        h->bat_dot_partial.alloc((size_t)7 * h->bat_nwg256);
+        if (h->bat_pin) { (void)hipHostFree(h->bat_pin); h->bat_pin = nullptr; }
+        HIP_CHECK(hipHostMalloc((void**)&h->bat_pin, 16 * k * sizeof(double)));
+        if (!h->bat_ev) HIP_CHECK(hipEventCreateWithFlags(&h->bat_ev, hipEventDisableTiming));
+        h->bat_nb = P.nb;
+        return HIPKKT_OK;
+    });
+}
+
+static void batch_guard(hipkkt_kkt_t h, const char* who, bool cones, bool need_scaling)
+{
+    if (!h) throw ArgError("null handle");
+    if (!h->sys_ready) throw ArgError("hipkkt_kkt_system_*: call hipkkt_kkt_system_init first");
+    if (h->deferred) throw ArgError("hipkkt_kkt_system_*: level C reads its scalars back (deferred status is for level B)");
+    if (h->bat_nb <= 0) throw ArgError(std::string(who) + ": the handle has no partition (hipkkt_kkt_system_set_problems)");
+    if (cones && h->large_psd) throw ArgError(std::string(who) + ": PSD cones up to side 48 only (large PSD cones were enabled)");
+    if (need_scaling && !h->scaling_valid) throw ArgError(std::string(who) + ": needs the cone scaling of hipkkt_kkt_system_update");
+    HIP_CHECK(hipSetDevice(h->device));
+}
+
+// k host arrays of nb doubles -> the device, array after array, in one copy; returns the device address of the first
+static const double* batch_upload(hipkkt_kkt_t h, const char* who, std::initializer_list<const double*> arrays)
+{
+    const size_t nb = (size_t)h->bat_nb;
+    for (const double* a : arrays)
+        if (!a) throw ArgError(std::string(who) + ": a scalar array is NULL");
+    HIP_CHECK(hipEventSynchronize(h->bat_ev));        // (the previous call's upload has left bat_pin)
+    size_t at = 0;
+    for (const double* a : arrays) { std::memcpy(h->bat_pin + at, a, nb * sizeof(double)); at += nb; }
+    HIP_CHECK(hipMemcpyAsync(h->bat_scal.p, h->bat_pin, at * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_CHECK(hipEventRecord(h->bat_ev, h->stream));
+    return h->bat_scal.p;
+}
+
+// per doubles per member from bat_rec to the caller's host array, in one copy; synchronises
+static void batch_download(hipkkt_kkt_t h, double* out, int per)
+{
+    const size_t count = (size_t)per * (size_t)h->bat_nb;
+    double* stage = h->bat_pin + 4 * (size_t)h->bat_nb;
+    HIP_CHECK(hipMemcpyAsync(stage, h->bat_rec.p, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->stream));
+    if (out) std::memcpy(out, stage, count * sizeof(double));
+}
+
+int hipkkt_kkt_system_residuals_batch(hipkkt_kkt_t h, const double* d_x, const double* d_s, const double* d_z, const double* tau,
+                                      double* d_rx, double* d_rz, double* d_rx_inf, double* d_rz_inf, double* d_Px,
+                                      const double* d_d, const double* d_dinv, const double* d_e, const double* d_einv, double* out)
+{
+    return guarded([&]() {
+        batch_guard(h, "hipkkt_kkt_system_residuals_batch", false, false);
+        const int n = h->K.n, m = h->K.m;
+        if (!out || !tau || (n && (!d_x || !d_rx || !d_rx_inf || !d_Px)) || (m && (!d_s || !d_z || !d_rz || !d_rz_inf)))
+            throw ArgError("hipkkt_kkt_system_residuals_batch: bad argument");
+        const int given = (d_d ? 1 : 0) + (d_dinv ? 1 : 0) + (d_e ? 1 : 0) + (d_einv ? 1 : 0);
+        if (given != 0 && given != 4)
+            throw ArgError("hipkkt_kkt_system_residuals_batch: the equilibration vectors d, dinv, e, einv are all NULL or all given");
+        {
+            const void* outs[5] = {d_rx, d_rz, d_rx_inf, d_rz_inf, d_Px};
+            const void* ins[7] = {d_x, d_s, d_z, d_d, d_dinv, d_e, d_einv};
+            for (int i = 0; i < 5; ++i) {
+                if (!outs[i]) continue;
+                for (int j = 0; j < 7; ++j)
+                    if (outs[i] == ins[j]) throw ArgError("hipkkt_kkt_system_residuals_batch: an output aliases an input");
+                for (int j = i + 1; j < 5; ++j)
+                    if (outs[i] == outs[j]) throw ArgError("hipkkt_kkt_system_residuals_batch: two outputs alias");
+            }
+        }
+        if (!h->it_prefix_ok) throw std::runtime_error("hipkkt_kkt_system_residuals_batch: the rows of A are not a prefix of K's z rows");
+        const SpmvDev A = kkt_spmv(h);
+        IterDev I;
+        I.rend = h->it_rend.p;
+        I.nlong = h->it_nlong; I.nchunks = h->it_nchunks; I.long_rows = h->it_long_rows.p;
+        I.long_chunk_ptr = h->it_long_chunk_ptr.p; I.chunk_q = h->it_chunk_q.p; I.long_partial = h->it_long_partial.p;
+        IterVecs V;
+        V.x = d_x; V.s = d_s; V.z = d_z; V.q = h->sq.p; V.b = h->sb.p; V.tau = 0.0;
+        V.rx = d_rx; V.rz = d_rz; V.rx_inf = d_rx_inf; V.rz_inf = d_rz_inf; V.Px = d_Px;
+        V.d = d_d; V.dinv = d_dinv; V.e = d_e; V.einv = d_einv;
+        const double* d_tau = batch_upload(h, "hipkkt_kkt_system_residuals_batch", {tau});
+        launch_batch_residuals(A, I, V, h->batch_dev(), d_tau, n, m, h->bat_it_partial.p, h->bat_rec.p, h->stream);
+        batch_download(h, out, 12);
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_combined_rhs_batch(hipkkt_kkt_t h, double* d_rhs_x, double* d_rhs_z, const double* d_rx, const double* d_rz,
+                                         const double* sigma)
+{
+    return guarded([&]() {
+        batch_guard(h, "hipkkt_kkt_system_combined_rhs_batch", false, false);
+        if ((h->K.n && (!d_rhs_x || !d_rx)) || (h->K.m && (!d_rhs_z || !d_rz)))
+            throw ArgError("hipkkt_kkt_system_combined_rhs_batch: bad argument");
+        const double* d_sigma = batch_upload(h, "hipkkt_kkt_system_combined_rhs_batch", {sigma});
+        launch_batch_scale(h->batch_dev(), d_rhs_x, d_rhs_z, d_rx, d_rz, d_sigma, h->K.n, h->K.m, h->stream);
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_add_step_batch(hipkkt_kkt_t h, double* d_x, double* d_s, double* d_z, const double* d_dx, const double* d_ds,
+                                     const double* d_dz, const double* alpha)
+{
+    return guarded([&]() {
+        batch_guard(h, "hipkkt_kkt_system_add_step_batch", false, false);
+        if ((h->K.n && (!d_x || !d_dx)) || (h->K.m && (!d_s || !d_z || !d_ds || !d_dz)))
+            throw ArgError("hipkkt_kkt_system_add_step_batch: bad argument");
+        if ((d_x && d_x == d_dx) || (d_s && (d_s == d_ds || d_s == d_dz)) || (d_z && (d_z == d_dz || d_z == d_ds)) || (d_s && d_s == d_z))
+            throw ArgError("hipkkt_kkt_system_add_step_batch: bad argument (a step must not alias the vector it is added to)");
+        const double* d_alpha = batch_upload(h, "hipkkt_kkt_system_add_step_batch", {alpha});
+        launch_batch_add_step(h->batch_dev(), d_x, d_s, d_z, d_dx, d_ds, d_dz, d_alpha, h->K.n, h->K.m, h->stream);
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_combined_ds_batch(hipkkt_kkt_t h, double* d_out, const double* d_step_z, const double* d_step_s,
+                                        const double* sigma_mu, const double* m_corr)
+{
+    return guarded([&]() {
+        batch_guard(h, "hipkkt_kkt_system_combined_ds_batch", true, true);
+        if (h->K.m && (!d_out || !d_step_z || !d_step_s || d_out == d_step_z || d_out == d_step_s))
+            throw ArgError("hipkkt_kkt_system_combined_ds_batch: bad argument (d_out must not alias an input)");
+        const double* d_scal = batch_upload(h, "hipkkt_kkt_system_combined_ds_batch", {sigma_mu, m_corr});
+        launch_batch_step_ds(h->cone_dev(), h->cone_state(), h->batch_dev(), d_out, d_step_z, d_step_s, d_scal, d_scal + h->bat_nb,
+                             h->K.m, h->stream);
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_step_length_batch(hipkkt_kkt_t h, const double* d_step_z, const double* d_step_s, const double* d_z,
+                                        const double* d_s, const double* step_tau, const double* step_kappa, const double* tau,
+                                        const double* kappa, double* alpha_out)
+{
+    return guarded([&]() {
+        batch_guard(h, "hipkkt_kkt_system_step_length_batch", true, true);
+        if ((h->K.m && (!d_step_z || !d_step_s || !d_z || !d_s)) || !alpha_out)
+            throw ArgError("hipkkt_kkt_system_step_length_batch: bad argument");
+        const double* d_scal = batch_upload(h, "hipkkt_kkt_system_step_length_batch", {step_tau, step_kappa, tau, kappa});
+        launch_batch_step_length(h->cone_dev(), h->cone_state(), h->batch_dev(), d_step_z, d_step_s, d_z, d_s, d_scal,
+                                 h->bat_step_partial.p, h->bat_rec.p, h->K.m, h->stream);
+        batch_download(h, alpha_out, 1);
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_shift_to_interior_batch(hipkkt_kkt_t h, double* d_v, int primal, double* margins_out)
+{
+    return guarded([&]() {
+        batch_guard(h, "hipkkt_kkt_system_shift_to_interior_batch", true, false);
+        if ((h->K.m && !d_v) || (primal != 0 && primal != 1)) throw ArgError("hipkkt_kkt_system_shift_to_interior_batch: bad argument");
+        launch_batch_shift_to_interior(h->cone_dev(), h->batch_dev(), d_v, primal == 1, h->bat_step_partial.p, h->bat_shift.p,
+                                       h->bat_rec.p, h->K.m, h->stream);
+        batch_download(h, margins_out, 2);
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_solve_batch(hipkkt_kkt_t h, double* d_lhs_x, double* d_lhs_s, double* d_lhs_z, double* lhs_tau_kappa,
+                                  const double* d_rhs_x, const double* d_rhs_s, const double* d_rhs_z, const double* rhs_tau,
+                                  const double* rhs_kappa, const double* d_var_x, const double* d_var_s, const double* d_var_z,
+                                  const double* var_tau, const double* var_kappa, int steptype)
+{
+    return guarded([&]() {
+        batch_guard(h, "hipkkt_kkt_system_solve_batch", true, true);
+        const int n = h->K.n, m = h->K.m;
+        const bool affine = steptype == 0;
+        if ((n && (!d_lhs_x || !d_rhs_x || !d_var_x)) || (m && (!d_lhs_s || !d_lhs_z || !d_rhs_z || !d_var_s || !d_var_z)) ||
+            (m && !affine && !d_rhs_s) || !lhs_tau_kappa || (steptype != 0 && steptype != 1))
+            throw ArgError("hipkkt_kkt_system_solve_batch: bad argument");
+        if (!rhs_tau || !rhs_kappa || !var_tau || !var_kappa) throw ArgError("hipkkt_kkt_system_solve_batch: a scalar array is NULL");
+        hipStream_t st = h->stream;
+        // (x2, z2) still due (lazy mode): by itself first, as kkt_update! would have done it -- the 2-column pairing is the
+        // whole-handle call's; and the status of an enqueued-only update is read before this call's own
+        int rc = sys_flush_update_status(h);
+        if (rc == HIPKKT_OK && h->sys_const_pending) {
+            h->sys_const_pending = false;
+            rc = sys_constant_rhs(h);
+        }
+        if (rc != HIPKKT_OK) return rc;
+        const double* d_scal = batch_upload(h, "hipkkt_kkt_system_solve_batch", {rhs_tau, rhs_kappa, var_tau, var_kappa});
+        // Delta_s constant term and the right-hand side (kktsystem.jl:150-173), as hipkkt_kkt_system_solve
+        if (!affine && !launch_sys_offset(h->cone_dev(), h->cone_state(), h->sconic.p, h->sworkz.p, d_rhs_s, d_var_z, d_rhs_z, m, false, st))
+            throw ArgError("hipkkt_kkt_system_solve_batch: unsupported cone kind");
+        if (affine) launch_pack_rhs_affine(h->b.p, nullptr, nullptr, d_rhs_x, d_var_s, d_rhs_z, n, m, h->K.p, 1, st);
+        else launch_pack_rhs(h->b.p, d_rhs_x, h->sworkz.p, n, m, h->K.p, st);
+        rc = kkt_solve_core(h, false, 1, nullptr, false);
+        if (rc != HIPKKT_OK) return rc;
+        const double* x1 = h->x.p;
+        // the dot products, dtau, dkappa and (dx, dz) per member (:185-206); the x2-only terms are formed here as well
+        launch_batch_sys_step(sys_spmv(h), h->Kval.p, h->batch_dev(), h->sq.p, h->sb.p, d_var_x, x1, x1 + n, h->sx2.p, h->sz2.p, d_scal,
+                              h->spa.p, h->spb.p, h->spc.p, h->sworkx.p, h->bat_dot_partial.p, h->bat_dtau.p, h->bat_rec.p, d_lhs_x,
+                              d_lhs_z, n, m, st);
+        // ds = -(Hs dz + const)                                               (:206-212)
+        launch_mul_Hs(h->cone_dev(), h->cone_state(), d_lhs_s, d_lhs_z, m, st, affine ? d_var_s : h->sconic.p);
+        batch_download(h, lhs_tau_kappa, 2);
         return HIPKKT_OK;
     });
 }

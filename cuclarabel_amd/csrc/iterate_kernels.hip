@@ -78,7 +78,8 @@ __device__ inline void iter_row_owner(const IterVecs& V, int n, int row, double 
 
 // the workgroup's 32 owner lanes (threadIdx.x % 8 == 0) -> partial[v * kIterStride + slot] for each of the 28 values:
 // eight lanes per value add four owners each (in owner order) and meet in a fixed tree
-__device__ inline void iter_fold(const double* acc, double* sh, double* __restrict__ partial, int slot)
+// (dst: the slot's first value; stride: doubles between a slot's values)
+__device__ inline void iter_fold_at(const double* acc, double* sh, double* __restrict__ dst, size_t stride)
 {
     const int tid = threadIdx.x;
     if ((tid & 7) == 0) {
@@ -92,8 +93,12 @@ __device__ inline void iter_fold(const double* acc, double* sh, double* __restri
         double s = ((p[0] + p[8]) + p[16]) + p[24];
 #pragma unroll
         for (int o = 4; o > 0; o >>= 1) s += __shfl_down(s, o, 8);
-        if (l == 0) partial[(size_t)v * kIterStride + slot] = s;
+        if (l == 0) dst[(size_t)v * stride] = s;
     }
+}
+__device__ inline void iter_fold(const double* acc, double* sh, double* __restrict__ partial, int slot)
+{
+    iter_fold_at(acc, sh, partial + slot, kIterStride);
 }
 
 __global__ __launch_bounds__(256) void k_iterate_residuals(SpmvDev A, IterDev I, IterVecs V, int n, int m,
@@ -206,6 +211,86 @@ __global__ __launch_bounds__(256) void k_iterate_add_step(double* x, double* s, 
     }
 }
 
+// ---- the same pass over a stack of member problems (kernels.hpp: BatchDev): workgroup w takes 32 combined rows of ONE
+// member -- the row sums are formed exactly as above, the owner lane applies the member's own tau -- and leaves its 28
+// values in slot w; a long row is a slot of its own behind them; member b's workgroup folds b's slots in slot order.
+// partial[v * nslots + slot].
+__global__ __launch_bounds__(256) void k_batch_residuals(SpmvDev A, IterDev I, IterVecs V, BatchDev B, const double* __restrict__ tau,
+                                                         int n, double* __restrict__ partial, size_t nslots)
+{
+    __shared__ double sh[kIterValues * kIterOwners];
+    const int sub = threadIdx.x & 7;
+    const int b = B.rows32.wg_mem[blockIdx.x];
+    const int x0 = B.x_off[b], nx = B.x_off[b + 1] - x0, z0 = B.z_off[b], nrows = nx + (B.z_off[b + 1] - z0);
+    const int local = B.rows32.wg_first[blockIdx.x] + (int)(threadIdx.x >> 3);
+    V.tau = tau[b];
+    double acc[kIterValues];
+#pragma unroll
+    for (int v = 0; v < kIterValues; ++v) acc[v] = 0.0;
+    if (local < nrows) {
+        const int row = local < nx ? x0 + local : n + z0 + (local - nx);
+        const int64_t q0 = A.ptr[row], q1 = I.rend[row];
+        if (q1 - q0 <= kLongRow) {                                       // (a long one: k_iterate_long_chunks, k_batch_long_finish)
+            double ap = 0.0, aa = 0.0;
+            for (int64_t q = q0 + sub; q < q1; q += 8) {
+                const int c = A.col[q];
+                const double v = A.val[q];
+                if (c < n) ap = fma(v, V.x[c], ap);
+                else aa = fma(v, V.z[c - n], aa);
+            }
+#pragma unroll
+            for (int o = 4; o > 0; o >>= 1) { ap += __shfl_down(ap, o, 8); aa += __shfl_down(aa, o, 8); }
+            if (sub == 0) iter_row_owner(V, n, row, ap, aa, acc);
+        }
+    }
+    iter_fold_at(acc, sh, partial + blockIdx.x, nslots);
+}
+
+// one long row per workgroup (B.long_order): chunk sums in chunk order, the owner's work with the member's tau
+__global__ __launch_bounds__(64) void k_batch_long_finish(IterDev I, IterVecs V, BatchDev B, const double* __restrict__ tau, int n,
+                                                          double* __restrict__ partial, size_t nslots)
+{
+    if (threadIdx.x != 0) return;
+    const int t = B.long_order[blockIdx.x];
+    const int row = I.long_rows[t];
+    V.tau = tau[row < n ? B.xmem[row] : B.zmem[row - n]];
+    double acc[kIterValues];
+#pragma unroll
+    for (int v = 0; v < kIterValues; ++v) acc[v] = 0.0;
+    double ap = 0.0, aa = 0.0;
+    for (int64_t c = I.long_chunk_ptr[t]; c < I.long_chunk_ptr[t + 1]; ++c) { ap += I.long_partial[2 * c]; aa += I.long_partial[2 * c + 1]; }
+    iter_row_owner(V, n, row, ap, aa, acc);
+    double* dst = partial + (size_t)B.rows32.nwg + blockIdx.x;
+#pragma unroll
+    for (int v = 0; v < kIterValues; ++v) dst[(size_t)v * nslots] = acc[v];
+}
+
+// member b = blockIdx.x: four waves, a value each (then the next four): a lane adds every 64th of b's slots -- its
+// workgroups', then its long rows' --, the wave meets in a fixed butterfly
+__global__ __launch_bounds__(256) void k_batch_residuals_finish(BatchDev B, const double* __restrict__ partial, size_t nslots,
+                                                                double* __restrict__ rec)
+{
+    __shared__ double sh[kIterValues];
+    const int b = blockIdx.x;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int w0 = B.rows32.wg_ptr[b], nw = B.rows32.wg_ptr[b + 1] - w0;
+    const int l0 = B.rows32.nwg + B.long_ptr[b], nl = B.long_ptr[b + 1] - B.long_ptr[b];
+    for (int v = wave; v < kIterValues; v += 4) {
+        const double* p = partial + (size_t)v * nslots;
+        double s = 0.0;
+        for (int i = lane; i < nw + nl; i += 64) s += p[i < nw ? w0 + i : l0 + (i - nw)];
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) sh[v] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double* r = rec + (size_t)12 * b;
+        for (int i = 0; i < 4; ++i) r[i] = sh[i];
+        for (int j = 0; j < 8; ++j) r[4 + j] = iter_nrm_finish(sh[kIterNorm0 + 3 * j], sh[kIterNorm0 + 3 * j + 1], sh[kIterNorm0 + 3 * j + 2]);
+    }
+}
+
 inline int iter_elem_grid(int64_t len)
 {
     int64_t g = (len + 255) / 256;
@@ -232,6 +317,20 @@ void launch_iterate_residuals(const SpmvDev& A, const IterDev& I, const IterVecs
         hipLaunchKernelGGL(k_iterate_long_finish, dim3(1), dim3(256), 0, st, I, V, n, partial, g);
     }
     hipLaunchKernelGGL(k_iterate_finish, dim3(1), dim3(1024), 0, st, (const double*)partial, g + (I.nlong > 0 ? 1 : 0), rec, pub);
+}
+
+void launch_batch_residuals(const SpmvDev& A, const IterDev& I, const IterVecs& V, const BatchDev& B, const double* tau, int n,
+                            int m, double* partial, double* rec, hipStream_t st)
+{
+    (void)m;
+    const size_t nslots = batch_residual_slots(B, I);
+    if (B.rows32.nwg > 0)
+        hipLaunchKernelGGL(k_batch_residuals, dim3(B.rows32.nwg), dim3(256), 0, st, A, I, V, B, tau, n, partial, nslots);
+    if (I.nlong > 0) {
+        hipLaunchKernelGGL(k_iterate_long_chunks, dim3(I.nchunks), dim3(256), 0, st, A, I, V, n);
+        hipLaunchKernelGGL(k_batch_long_finish, dim3(I.nlong), dim3(64), 0, st, I, V, B, tau, n, partial, nslots);
+    }
+    hipLaunchKernelGGL(k_batch_residuals_finish, dim3(B.nb), dim3(256), 0, st, B, (const double*)partial, nslots, rec);
 }
 
 void launch_iterate_scale(double* ox, double* oz, const double* rx, const double* rz, double f, int n, int m, hipStream_t st)

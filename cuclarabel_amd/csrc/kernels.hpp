@@ -629,6 +629,55 @@ void launch_iterate_scale(double* ox, double* oz, const double* rx, const double
 void launch_iterate_add_step(double* x, double* s, double* z, const double* dx, const double* ds, const double* dz, double alpha,
                              int n, int m, hipStream_t st);
 
+// ---- the same operations on a stack of independent member problems (hipkkt_kkt_system_set_problems): every
+// scalar is an array over the members on the device, every reduction is segmented by member.  The tables are those of
+// batch_plan.hpp on the device.  A workgroup of a reducing kernel belongs to ONE member (wg_mem) and leaves its partial
+// values in its own slot; member b's slots are wg_ptr[b] .. wg_ptr[b + 1] - 1 (and the slots of its second-order cones,
+// PSD cones and long rows, ranges as well), folded in slot order by the member's own finishing wave / workgroup: fixed
+// layout, no floating-point atomic, and the number of launches does not depend on the number of members.
+struct BatchChunksDev { const int* wg_mem; const int* wg_first; const int* wg_ptr; int nwg; };
+struct BatchDev {
+    int nb;
+    const int *x_off, *z_off;        // nb + 1
+    const int *xmem, *zmem;          // row -> member
+    const int* cone_mem;             // cone -> member
+    const int *soc_ptr, *psd_ptr;    // nb + 1: a member's range in ConeDev::soc_list / psd_list
+    const double* degree;            // nb
+    BatchChunksDev rows32, rows256, z256;
+    const int *long_order, *long_ptr;    // the residual pass's long rows by member (positions in IterDev::long_rows)
+};
+// slots of the batched residual pass: one per 32-row workgroup and one per long row, kIterValues values each
+inline size_t batch_residual_slots(const BatchDev& B, const IterDev& I) { return (size_t)B.rows32.nwg + (size_t)I.nlong; }
+// rec[12 b .. 12 b + 11]: the record of launch_iterate_residuals over member b's rows, rx and rz formed with tau[b]
+void launch_batch_residuals(const SpmvDev& A, const IterDev& I, const IterVecs& V, const BatchDev& B, const double* tau, int n,
+                            int m, double* partial, double* rec, hipStream_t st);
+// ox = (1 - sigma[b]) rx, oz = (1 - sigma[b]) rz on member b's rows
+void launch_batch_scale(const BatchDev& B, double* ox, double* oz, const double* rx, const double* rz, const double* sigma, int n,
+                        int m, hipStream_t st);
+// x += alpha[b] dx, s += alpha[b] ds, z += alpha[b] dz on member b's rows; alpha[b] == 0: the rows are not written
+void launch_batch_add_step(const BatchDev& B, double* x, double* s, double* z, const double* dx, const double* ds, const double* dz,
+                           const double* alpha, int n, int m, hipStream_t st);
+// launch_step_ds(combined) with member b's sigma_mu[b], m_corr[b] on its cones
+void launch_batch_step_ds(const ConeDev& C, const ConeState& S, const BatchDev& B, double* out, const double* step_z,
+                          const double* step_s, const double* sigma_mu, const double* m_corr, int m, hipStream_t st);
+// slots of the batched step length / margins: elementwise workgroups, second-order cones, PSD cones (margins: twice)
+inline size_t batch_step_slots(const ConeDev& C, const BatchDev& B) { return (size_t)B.z256.nwg + (size_t)C.nsoc + (size_t)C.npsd; }
+// rec[b] = min(1, member b's tau / kappa limits, its cones' limits); scal = {step_tau, step_kappa, tau, kappa}, nb each
+void launch_batch_step_length(const ConeDev& C, const ConeState& S, const BatchDev& B, const double* dz, const double* ds,
+                              const double* z, const double* s, const double* scal, double* partial, double* rec, int m,
+                              hipStream_t st);
+// rec[2 b .. 2 b + 1] = member b's (min_margin, pos_margin) of v, then its branch of _shift_to_cone_interior! applied to its
+// rows (shift: 3 nb doubles of work space)
+void launch_batch_shift_to_interior(const ConeDev& C, const BatchDev& B, double* v, bool primal, double* partial, double* shift,
+                                    double* rec, int m, hipStream_t st);
+// the step recovery of kkt_solve! per member (kktsystem.jl:185-206): scal = {rhs_tau, rhs_kappa, var_tau, var_kappa}, nb
+// each; out[2 b .. 2 b + 1] = (dtau_b, dkappa_b); (dx, dz) = (x1, z1) + dtau_b (x2, z2).  pa, pb, pc, xm: n doubles of work
+// space each; partial: 7 slots per 256-row workgroup; dtau: nb doubles
+void launch_batch_sys_step(const SpmvDev& A, const double* Kval, const BatchDev& B, const double* q, const double* bvec,
+                           const double* x, const double* x1, const double* z1, const double* x2, const double* z2,
+                           const double* scal, double* pa, double* pb, double* pc, double* xm, double* partial, double* dtau,
+                           double* out, double* dx, double* dz, int n, int m, hipStream_t st);
+
 
 // ---- Ruiz equilibration of (P, A, q, b) (problemdata.jl:133-221, mathutils.jl:129-269), all vectors on the device
 struct EquilDev {

@@ -268,13 +268,12 @@ __global__ __launch_bounds__(256) void k_step_ds(ConeDev C, ConeState S, double*
 
 // PSD cones (coneops_psdtrianglecone.jl:189-205, circ_op! :361-382): Z = R'mat(m dz)R, Y = Rinv mat(ds) Rinv',
 // out = svec((YZ + ZY)/2) with lambda_i^2 - sigma_mu added on the diagonal.  LDS: four k x k matrices.
-__global__ __launch_bounds__(256) void k_step_ds_psd(ConeDev C, ConeState S, double* __restrict__ out,
-                                                    const double* __restrict__ dz, const double* __restrict__ ds,
-                                                    double sigma_mu, double m_corr, int combined)
+// (the cone's workgroup: c = the cone, smem = its dynamic LDS)
+__device__ inline void step_ds_psd_body(const ConeDev& C, const ConeState& S, double* __restrict__ out,
+                                        const double* __restrict__ dz, const double* __restrict__ ds, double sigma_mu,
+                                        double m_corr, int combined, int c, double* smem)
 {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
     const int tid = threadIdx.x;
-    const int c = C.psd_list[blockIdx.x];
     const int k = C.psd_dim[c], off = C.off[c], kk = k * k, t = k * (k + 1) / 2;
     if (k == 0) return;
     const double* lam = S.lam + off;
@@ -307,6 +306,13 @@ __global__ __launch_bounds__(256) void k_step_ds_psd(ConeDev C, ConeState S, dou
         const double v = 0.5 * (a1 + a2);
         out[off + idx] = r == cl ? lam[r] * lam[r] + (v - sigma_mu) : v * kS2;
     }
+}
+__global__ __launch_bounds__(256) void k_step_ds_psd(ConeDev C, ConeState S, double* __restrict__ out,
+                                                    const double* __restrict__ dz, const double* __restrict__ ds,
+                                                    double sigma_mu, double m_corr, int combined)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    step_ds_psd_body(C, S, out, dz, ds, sigma_mu, m_corr, combined, C.psd_list[blockIdx.x], smem);
 }
 
 // The big PSD class (C.psdb_list, side <= kPsdBigMaxDim): the same steps with kPsdBigThreads threads and two matrices
@@ -427,15 +433,14 @@ __global__ __launch_bounds__(256) void k_step_length(ConeDev C, const double* __
 
 // PSD cones (coneops_psdtrianglecone.jl:230-254, :439-466): both components by the cone's workgroup.
 // gamma = lambda_min(Lam^{-1/2} mat(d) Lam^{-1/2}), d = W dz or W^{-T} ds; the limit is 1/(-gamma) where gamma < 0.
-__global__ __launch_bounds__(256) void k_step_length_psd(ConeDev C, ConeState S, const double* __restrict__ dz,
-                                                        const double* __restrict__ ds, double* __restrict__ slots)
+// (the cone's workgroup: c = the cone, slot = where its limit goes, smem = its dynamic LDS, sh = 256 doubles of LDS)
+__device__ inline void step_length_psd_body(const ConeDev& C, const ConeState& S, const double* __restrict__ dz,
+                                            const double* __restrict__ ds, double* __restrict__ slot, int c, double* smem,
+                                            double* sh)
 {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    __shared__ double sh[256];
     const int tid = threadIdx.x;
-    const int c = C.psd_list[blockIdx.x];
     const int k = C.psd_dim[c], off = C.off[c], kk = k * k;
-    if (k == 0) { if (tid == 0) slots[blockIdx.x] = DBL_MAX; return; }
+    if (k == 0) { if (tid == 0) *slot = DBL_MAX; return; }
     double* G = smem;
     double* X = smem + kk;
     double* T = smem + 2 * kk;
@@ -458,7 +463,14 @@ __global__ __launch_bounds__(256) void k_step_length_psd(ConeDev C, ConeState S,
         if (g < 0.0) alpha = fmin(alpha, 1.0 / (-g));
         __syncthreads();
     }
-    if (tid == 0) slots[blockIdx.x] = alpha;
+    if (tid == 0) *slot = alpha;
+}
+__global__ __launch_bounds__(256) void k_step_length_psd(ConeDev C, ConeState S, const double* __restrict__ dz,
+                                                        const double* __restrict__ ds, double* __restrict__ slots)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    __shared__ double sh[256];
+    step_length_psd_body(C, S, dz, ds, slots + blockIdx.x, C.psd_list[blockIdx.x], smem, sh);
 }
 
 // ... of the big class: G and X in LDS, T through the work area, M in X's place, where the two-sided Jacobi then runs
@@ -517,6 +529,22 @@ __global__ __launch_bounds__(256) void k_step_length_finish(const double* __rest
 // =====================================================================================================================
 //  margins (composite :49-63) and scaled_unit_shift!
 // =====================================================================================================================
+// one wave per second-order cone (coneops_socone.jl:13-23); pmin / psum: where the cone's two values go
+__device__ inline void margins_soc_body(const ConeDev& C, const double* __restrict__ v, double* __restrict__ pmin,
+                                        double* __restrict__ psum, int ci, int lane)
+{
+    const int c = C.soc_list[ci];
+    const int off = C.off[c], n = C.numel[c];
+    double sq = 0.0;
+    for (int i = 1 + lane; i < n; i += 64) sq += v[off + i] * v[off + i];
+    sq = st_wave_sum(sq);
+    if (lane == 0) {
+        const double a = v[off] - sqrt(sq);
+        *pmin = a;
+        *psum = fmax(0.0, a);
+    }
+}
+
 __global__ __launch_bounds__(256) void k_margins(ConeDev C, const double* __restrict__ v, int m, double* __restrict__ pmin,
                                                  double* __restrict__ psum, int ge)
 {
@@ -537,27 +565,16 @@ __global__ __launch_bounds__(256) void k_margins(ConeDev C, const double* __rest
     }
     const int ci = (bx - ge) * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (ci >= C.nsoc) return;
-    const int c = C.soc_list[ci];                                      // coneops_socone.jl:13-23
-    const int off = C.off[c], n = C.numel[c];
-    double sq = 0.0;
-    for (int i = 1 + lane; i < n; i += 64) sq += v[off + i] * v[off + i];
-    sq = st_wave_sum(sq);
-    if (lane == 0) {
-        const double a = v[off] - sqrt(sq);
-        pmin[ge + ci] = a;
-        psum[ge + ci] = fmax(0.0, a);
-    }
+    margins_soc_body(C, v, pmin + ge + ci, psum + ge + ci, ci, lane);
 }
 
-// PSD cones (coneops_psdtrianglecone.jl:8-27): the eigenvalues of mat(v)
-__global__ __launch_bounds__(256) void k_margins_psd(ConeDev C, const double* __restrict__ v, double* __restrict__ pmin,
-                                                    double* __restrict__ psum)
+// PSD cones (coneops_psdtrianglecone.jl:8-27): the eigenvalues of mat(v).  The cone's workgroup: c = the cone, pmin / psum
+// = where its two values go, smem = its dynamic LDS, sh = 256 doubles of LDS
+__device__ inline void margins_psd_body(const ConeDev& C, const double* __restrict__ v, double* __restrict__ pmin,
+                                        double* __restrict__ psum, int c, double* smem, double* sh)
 {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    __shared__ double sh[256];
-    const int c = C.psd_list[blockIdx.x];
     const int k = C.psd_dim[c], off = C.off[c];
-    if (k == 0) { if (threadIdx.x == 0) { pmin[blockIdx.x] = DBL_MAX; psum[blockIdx.x] = 0.0; } return; }
+    if (k == 0) { if (threadIdx.x == 0) { *pmin = DBL_MAX; *psum = 0.0; } return; }
     psd_load_mat(smem, v + off, 1.0, k);
     __syncthreads();
     sym_jacobi_eig(smem, k, sh);
@@ -568,9 +585,16 @@ __global__ __launch_bounds__(256) void k_margins_psd(ConeDev C, const double* __
             mn = fmin(mn, e);
             if (e > 0.0) sum += e;
         }
-        pmin[blockIdx.x] = mn;
-        psum[blockIdx.x] = sum;
+        *pmin = mn;
+        *psum = sum;
     }
+}
+__global__ __launch_bounds__(256) void k_margins_psd(ConeDev C, const double* __restrict__ v, double* __restrict__ pmin,
+                                                    double* __restrict__ psum)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    __shared__ double sh[256];
+    margins_psd_body(C, v, pmin + blockIdx.x, psum + blockIdx.x, C.psd_list[blockIdx.x], smem, sh);
 }
 
 __global__ __launch_bounds__(kPsdBigThreads) void k_margins_psd_big(ConeDev C, const double* __restrict__ v,
@@ -613,25 +637,195 @@ __global__ __launch_bounds__(256) void k_margins_finish(const double* __restrict
 // scaled_unit_shift! of every cone: v += a e (nonnegative: every element, coneops_nncone.jl:42-52; second-order: element 0,
 // coneops_socone.jl:26-37; PSD: the diagonal entries, coneops_psdtrianglecone.jl:30-44), a zero cone's rows set to 0 for the
 // primal cone.  two: a second shift a2 applied AFTER the first, not their sum (variables.jl:190-191).
+__device__ inline void unit_shift_row(const ConeDev& C, double* __restrict__ v, double a1, double a2, int two, int primal, int i)
+{
+    const int c = C.elem_cone[i];
+    const int kind = C.kind[c];
+    bool hit;
+    if (kind == 0) { if (primal) v[i] = 0.0; return; }
+    else if (kind == 1) hit = true;
+    else if (kind == 2) hit = i == C.off[c];
+    else {
+        int r, cl;
+        st_svec_index(i - C.off[c], r, cl);
+        hit = r == cl;
+    }
+    if (!hit) return;
+    double x = v[i] + a1;
+    if (two) x = x + a2;
+    v[i] = x;
+}
 __global__ __launch_bounds__(256) void k_unit_shift(ConeDev C, double* __restrict__ v, double a1, double a2, int two, int primal,
                                                     int m)
 {
-    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) {
-        const int c = C.elem_cone[i];
-        const int kind = C.kind[c];
-        bool hit;
-        if (kind == 0) { if (primal) v[i] = 0.0; continue; }
-        else if (kind == 1) hit = true;
-        else if (kind == 2) hit = i == C.off[c];
-        else {
-            int r, cl;
-            st_svec_index(i - C.off[c], r, cl);
-            hit = r == cl;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) unit_shift_row(C, v, a1, a2, two, primal, i);
+}
+
+// =====================================================================================================================
+//  The same operations on a stack of member problems (kernels.hpp: BatchDev): a cone lies in one member, so every
+//  per-cone body above runs as it is with the scalars of the cone's member; the elementwise part is cut by member
+//  (B.z256: 256 z rows of one member per workgroup), and the finishing kernels fold member b's slots -- its elementwise
+//  workgroups', its second-order cones', its PSD cones' -- with wave b.  The minima are order-free; the margins' sums
+//  are taken lane-strided in slot order and met in a fixed butterfly.
+// =====================================================================================================================
+__global__ __launch_bounds__(256) void k_batch_step_ds(ConeDev C, ConeState S, BatchDev B, double* __restrict__ out,
+                                                       const double* __restrict__ dz, const double* __restrict__ ds,
+                                                       const double* __restrict__ sigma_mu, const double* __restrict__ m_corr,
+                                                       int m, int ge)
+{
+    if ((int)blockIdx.x < ge) {
+        for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += ge * 256) {
+            const int kind = C.kind[C.elem_cone[i]];
+            if (kind == 0) out[i] = 0.0;
+            else if (kind == 1) {                                       // (as step_ds_elementwise_body, the member's scalars)
+                const int b = B.zmem[i];
+                const double l = S.lam[i], w = S.w[i];
+                double o = l * l;
+                o += (ds[i] / w) * (w * (m_corr[b] * dz[i])) - sigma_mu[b];
+                out[i] = o;
+            }
         }
-        if (!hit) continue;
-        double x = v[i] + a1;
-        if (two) x = x + a2;
-        v[i] = x;
+        return;
+    }
+    const int ci = ((int)blockIdx.x - ge) * 4 + (int)(threadIdx.x >> 6);
+    if (ci >= C.nsoc) return;
+    const int b = B.cone_mem[C.soc_list[ci]];
+    step_ds_soc_body(C, S, out, dz, ds, sigma_mu[b], m_corr[b], 1, ci, threadIdx.x & 63);
+}
+
+__global__ __launch_bounds__(256) void k_batch_step_ds_psd(ConeDev C, ConeState S, BatchDev B, double* __restrict__ out,
+                                                           const double* __restrict__ dz, const double* __restrict__ ds,
+                                                           const double* __restrict__ sigma_mu, const double* __restrict__ m_corr)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int c = C.psd_list[blockIdx.x];
+    const int b = B.cone_mem[c];
+    step_ds_psd_body(C, S, out, dz, ds, sigma_mu[b], m_corr[b], 1, c, smem);
+}
+
+// slots: [0, nwg) the elementwise workgroups, then a slot per second-order cone
+__global__ __launch_bounds__(256) void k_batch_step_length(ConeDev C, BatchDev B, const double* __restrict__ dz,
+                                                           const double* __restrict__ ds, const double* __restrict__ z,
+                                                           const double* __restrict__ s, double* __restrict__ partial)
+{
+    __shared__ double sh[256];
+    const int ge = B.z256.nwg;
+    if ((int)blockIdx.x < ge) {
+        const int b = B.z256.wg_mem[blockIdx.x];
+        const int i = B.z_off[b] + B.z256.wg_first[blockIdx.x] + (int)threadIdx.x;
+        double a = DBL_MAX;
+        if (i < B.z_off[b + 1] && C.kind[C.elem_cone[i]] == 1) {        // coneops_nncone.jl:151-170
+            const double dzi = dz[i], dsi = ds[i];
+            if (dzi < 0.0) a = fmin(a, -z[i] / dzi);
+            if (dsi < 0.0) a = fmin(a, -s[i] / dsi);
+        }
+        a = block_reduce_256(a, sh, OpMin{});
+        if (threadIdx.x == 0) partial[blockIdx.x] = a;
+        return;
+    }
+    const int ci = ((int)blockIdx.x - ge) * 4 + (int)(threadIdx.x >> 6);
+    if (ci < C.nsoc) step_length_soc_body(C, dz, ds, z, s, partial + ge + ci, ci, threadIdx.x & 63);
+}
+
+__global__ __launch_bounds__(256) void k_batch_step_length_psd(ConeDev C, ConeState S, const double* __restrict__ dz,
+                                                               const double* __restrict__ ds, double* __restrict__ slots)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    __shared__ double sh[256];
+    step_length_psd_body(C, S, dz, ds, slots + blockIdx.x, C.psd_list[blockIdx.x], smem, sh);
+}
+
+// lane-strided over member b's three slot ranges, in slot order
+template <class F>
+__device__ inline void batch_member_slots(const ConeDev& C, const BatchDev& B, int b, int lane, F f)
+{
+    const int ge = B.z256.nwg;
+    for (int i = B.z256.wg_ptr[b] + lane; i < B.z256.wg_ptr[b + 1]; i += 64) f(i);
+    for (int i = B.soc_ptr[b] + lane; i < B.soc_ptr[b + 1]; i += 64) f(ge + i);
+    for (int i = B.psd_ptr[b] + lane; i < B.psd_ptr[b + 1]; i += 64) f(ge + C.nsoc + i);
+}
+
+// wave = member: variables_calc_step_length (variables.jl:14-43) without max_step_fraction, the member's tau and kappa
+__global__ __launch_bounds__(256) void k_batch_step_length_finish(ConeDev C, BatchDev B, const double* __restrict__ partial,
+                                                                  const double* __restrict__ scal, double* __restrict__ rec)
+{
+    const int b = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b >= B.nb) return;
+    double v = DBL_MAX;
+    batch_member_slots(C, B, b, lane, [&](int i) { v = fmin(v, partial[i]); });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+    if (lane == 0) {
+        const double step_tau = scal[b], step_kappa = scal[B.nb + b], tau = scal[2 * B.nb + b], kappa = scal[3 * B.nb + b];
+        const double at = step_tau < 0.0 ? -tau / step_tau : DBL_MAX;
+        const double ak = step_kappa < 0.0 ? -kappa / step_kappa : DBL_MAX;
+        rec[b] = fmin(fmin(fmin(at, ak), 1.0), v);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_batch_margins(ConeDev C, BatchDev B, const double* __restrict__ v, double* __restrict__ pmin,
+                                                       double* __restrict__ psum)
+{
+    __shared__ double sh[256];
+    const int ge = B.z256.nwg;
+    if ((int)blockIdx.x < ge) {                                         // coneops_nncone.jl:19-39; zero cone: (floatmax, 0)
+        const int b = B.z256.wg_mem[blockIdx.x];
+        const int i = B.z_off[b] + B.z256.wg_first[blockIdx.x] + (int)threadIdx.x;
+        double mn = DBL_MAX, sum = 0.0;
+        if (i < B.z_off[b + 1] && C.kind[C.elem_cone[i]] == 1) {
+            const double x = v[i];
+            mn = fmin(mn, x);
+            if (x > 0.0) sum += x;
+        }
+        mn = block_reduce_256(mn, sh, OpMin{});
+        sum = block_reduce_256(sum, sh, OpSum{});
+        if (threadIdx.x == 0) { pmin[blockIdx.x] = mn; psum[blockIdx.x] = sum; }
+        return;
+    }
+    const int ci = ((int)blockIdx.x - ge) * 4 + (int)(threadIdx.x >> 6);
+    if (ci < C.nsoc) margins_soc_body(C, v, pmin + ge + ci, psum + ge + ci, ci, threadIdx.x & 63);
+}
+
+__global__ __launch_bounds__(256) void k_batch_margins_psd(ConeDev C, const double* __restrict__ v, double* __restrict__ pmin,
+                                                           double* __restrict__ psum)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    __shared__ double sh[256];
+    margins_psd_body(C, v, pmin + blockIdx.x, psum + blockIdx.x, C.psd_list[blockIdx.x], smem, sh);
+}
+
+// wave = member: (min_margin, pos_margin) into rec, and the member's branch of _shift_to_cone_interior!
+// (variables.jl:186-204) as (a1, a2, two) into shift
+__global__ __launch_bounds__(256) void k_batch_margins_finish(ConeDev C, BatchDev B, const double* __restrict__ pmin,
+                                                              const double* __restrict__ psum, double* __restrict__ rec,
+                                                              double* __restrict__ shift)
+{
+    const int b = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (b >= B.nb) return;
+    double mn = DBL_MAX, sum = 0.0;
+    batch_member_slots(C, B, b, lane, [&](int i) { mn = fmin(mn, pmin[i]); sum += psum[i]; });
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { mn = fmin(mn, __shfl_xor(mn, o, 64)); sum += __shfl_xor(sum, o, 64); }
+    if (lane == 0) {
+        rec[2 * b] = mn;
+        rec[2 * b + 1] = sum;
+        const double degree = B.degree[b];
+        const double target = degree > 0.0 ? fmax(1.0, 0.1 * sum / degree) : 1.0;
+        double a1 = 0.0, a2 = 0.0, two = 0.0;
+        if (mn <= 0.0) { a1 = -mn; a2 = target; two = 1.0; }
+        else if (mn < target) a1 = target - mn;
+        shift[3 * b] = a1;
+        shift[3 * b + 1] = a2;
+        shift[3 * b + 2] = two;
+    }
+}
+
+__global__ __launch_bounds__(256) void k_batch_unit_shift(ConeDev C, BatchDev B, double* __restrict__ v,
+                                                          const double* __restrict__ shift, int primal, int m)
+{
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < m; i += gridDim.x * 256) {
+        const double* sp = shift + 3 * B.zmem[i];
+        unit_shift_row(C, v, sp[0], sp[1], sp[2] != 0.0, primal, i);
     }
 }
 
@@ -1377,6 +1571,54 @@ void launch_unit_shift(const ConeDev& C, double* v, double a1, double a2, bool t
 {
     if (m <= 0) return;
     hipLaunchKernelGGL(k_unit_shift, dim3(step_grid(m)), dim3(256), 0, st, C, v, a1, a2, two ? 1 : 0, primal ? 1 : 0, m);
+}
+
+void launch_batch_step_ds(const ConeDev& C, const ConeState& S, const BatchDev& B, double* out, const double* step_z,
+                          const double* step_s, const double* sigma_mu, const double* m_corr, int m, hipStream_t st)
+{
+    if (m <= 0) return;
+    if (C.npsd > 0) {
+        static PerDeviceOnce once;
+        once.run([]() { return set_max_lds(k_batch_step_ds_psd, 150 * 1024); });
+        hipLaunchKernelGGL(k_batch_step_ds_psd, dim3(C.npsd), dim3(256), step_psd_lds(C), st, C, S, B, out, step_z, step_s, sigma_mu,
+                           m_corr);
+    }
+    const int ge = step_grid(m), gs = (C.nsoc + 3) / 4;
+    hipLaunchKernelGGL(k_batch_step_ds, dim3(ge + gs), dim3(256), 0, st, C, S, B, out, step_z, step_s, sigma_mu, m_corr, m, ge);
+}
+
+void launch_batch_step_length(const ConeDev& C, const ConeState& S, const BatchDev& B, const double* dz, const double* ds,
+                              const double* z, const double* s, const double* scal, double* partial, double* rec, int m,
+                              hipStream_t st)
+{
+    (void)m;
+    const int ge = B.z256.nwg, gs = (C.nsoc + 3) / 4;
+    if (C.npsd > 0) {
+        static PerDeviceOnce once;
+        once.run([]() { return set_max_lds(k_batch_step_length_psd, 150 * 1024); });
+        hipLaunchKernelGGL(k_batch_step_length_psd, dim3(C.npsd), dim3(256), step_psd_lds(C), st, C, S, dz, ds, partial + ge + C.nsoc);
+    }
+    if (ge + gs > 0) hipLaunchKernelGGL(k_batch_step_length, dim3(ge + gs), dim3(256), 0, st, C, B, dz, ds, z, s, partial);
+    hipLaunchKernelGGL(k_batch_step_length_finish, dim3((B.nb + 3) / 4), dim3(256), 0, st, C, B, (const double*)partial, scal, rec);
+}
+
+void launch_batch_shift_to_interior(const ConeDev& C, const BatchDev& B, double* v, bool primal, double* partial, double* shift,
+                                    double* rec, int m, hipStream_t st)
+{
+    const int ge = B.z256.nwg, gs = (C.nsoc + 3) / 4;
+    double* pmin = partial;
+    double* psum = partial + batch_step_slots(C, B);
+    if (C.npsd > 0) {
+        static PerDeviceOnce once;
+        once.run([]() { return set_max_lds(k_batch_margins_psd, 150 * 1024); });
+        hipLaunchKernelGGL(k_batch_margins_psd, dim3(C.npsd), dim3(256), (size_t)C.psd_kmax * C.psd_kmax * sizeof(double), st, C,
+                           (const double*)v, pmin + ge + C.nsoc, psum + ge + C.nsoc);
+    }
+    if (ge + gs > 0) hipLaunchKernelGGL(k_batch_margins, dim3(ge + gs), dim3(256), 0, st, C, B, (const double*)v, pmin, psum);
+    hipLaunchKernelGGL(k_batch_margins_finish, dim3((B.nb + 3) / 4), dim3(256), 0, st, C, B, (const double*)pmin, (const double*)psum,
+                       rec, shift);
+    if (m > 0)
+        hipLaunchKernelGGL(k_batch_unit_shift, dim3(step_grid(m)), dim3(256), 0, st, C, B, v, (const double*)shift, primal ? 1 : 0, m);
 }
 
 // the generalized power cones' rows (mode 0: the unit start into out and out2; 1: a copy of s; 2: s + sigma_mu grad f*(z))

@@ -137,6 +137,255 @@ def solve_device_genpow(P, q, A, b, cone_specs, settings=None, inspect=None, plu
     return _solve(P, q, A, b, cone_specs, settings, inspect, plumbing == "device", True, True)
 
 
+def solve_device_batch(problems, settings=None, inspect=None):
+    """A batch of INDEPENDENT problems solved as one block-diagonal stack on one handle -> list of IPMResult, one per
+    member: its own status, iteration count, history, x, z, s and objectives.
+
+    problems: list of (P, q, A, b, cone_specs); symmetric cones with PSD side <= 48 only (anything else is refused with
+    ValueError before a handle is built).
+
+    The loop is `solve_device(plumbing="device")` on the stacked handle with every scalar -- tau, kappa, mu, sigma,
+    alpha, the residual norms, (dtau, dkappa) -- a numpy array over the members, through the library's _batch entry
+    points (hipkkt_kkt_system_set_problems and the seven calls behind it); every line of the termination logic
+    (info.jl:65-120, :196-211, :270-330) is applied per member.  A member that has reached a final status is FROZEN: its
+    alpha is 0 from then on (its rows are not written), its status, iterate and history no longer change, and its result
+    is the iterate it ended on; restoring the previous iterate on INSUFFICIENT_PROGRESS copies back that member's rows
+    only.  From the iteration after it ended, its block of K is scaled at the member's start point and its rows of the
+    right-hand sides are zero, so that a finished member costs the members still running nothing of their solves'
+    refinement (see the loop).  The loop ends when no member is UNSOLVED; max_iter counts per member (all members start together, so that is
+    the loop's own count).  What stays joint, because the factorisation is one: a failed kkt_update! or solve ends every
+    member still UNSOLVED with NUMERICAL_ERROR; the static regulariser and the refinement's stopping rule see the whole
+    stack; `ir_iterations` of every result is the stack's total.  The symmetric start takes the handle's LP / QP branch
+    (kktsystem.jl:95-143), which is decided by nnz(P) of the STACK: a batch that mixes members with and without a P starts
+    its LP members from the QP start (another interior point; the answers agree to the tolerances, the iteration counts
+    need not).
+
+    inspect (optional): called once per iteration with (dict of the tensors the loop holds, the HipSystemBackend)."""
+    import torch
+    problems = list(problems)
+    if not problems:
+        raise ValueError("solve_device_batch needs at least one problem")
+    members = []
+    for (P, q, A, b, cone_specs) in problems:
+        cone_specs = _check_cones("solve_device_batch", cone_specs, _SYMMETRIC,
+                                  "solve_device_batch covers the symmetric cones only (zero, nonnegative, second-order, PSD); "
+                                  "got {}")
+        if any(isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE for c in cone_specs):
+            raise ValueError(f"solve_device_batch covers PSD cones up to side {PSD_MAX_SIDE}")
+        Pt = sp.triu(sp.csc_matrix(P), format="csc")
+        members.append((Pt, np.asarray(q, float), sp.csc_matrix(A), np.asarray(b, float), cone_specs))
+    st = settings or IPMSettings()
+    nb = len(members)
+    P = sp.block_diag([mb[0] for mb in members], format="csc")
+    A = sp.block_diag([mb[2] for mb in members], format="csc")
+    q = np.concatenate([mb[1] for mb in members])
+    b = np.concatenate([mb[3] for mb in members])
+    cone_specs = [c for mb in members for c in mb[4]]
+    blocks = [(mb[0].shape[0], mb[2].shape[0]) for mb in members]
+    x_off = np.concatenate([[0], np.cumsum([bl[0] for bl in blocks])]).astype(int)
+    z_off = np.concatenate([[0], np.cumsum([bl[1] for bl in blocks])]).astype(int)
+    n, m = int(x_off[-1]), int(z_off[-1])
+    degree = np.array([sum(c.dim if isinstance(c, (NonnegativeConeT, PSDTriangleConeT)) else 1 if isinstance(c, SecondOrderConeT)
+                           else 0 for c in mb[4]) for mb in members], float)
+    normq = np.array([np.abs(mb[1]).max() if mb[1].size else 0.0 for mb in members])
+    normb = np.array([np.abs(mb[3]).max() if mb[3].size else 0.0 for mb in members])
+
+    backend = HipSystemBackend(P, A, cone_specs)
+    ks, system = backend.ks, backend.system
+    dev = system._devstr
+    ks.set_stream(torch.cuda.current_stream(torch.device(dev)).cuda_stream)
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    new = lambda k: torch.zeros(max(k, 1), dtype=torch.float64, device=dev)[:k]
+    qd, bd = up(q), up(b)
+    p = lambda t: t.data_ptr()
+    ir_total = 0
+
+    # ---- default start (solver.jl:383-404), the shifts per member
+    x, s, z = new(n), new(m), new(m)
+    dx, ds, dz = new(n), new(m), new(m)
+    aff_s, rhs_s = new(m), new(m)
+    rx, rx_inf, Px, rhs_x = new(n), new(n), new(n), new(n)
+    rz, rz_inf, rhs_z = new(m), new(m), new(m)
+    aff_x, aff_z = new(n), new(m)                        # the affine right-hand side with the frozen members' rows zeroed
+    system.init(q, b)
+    system.set_problems(blocks)
+    backend.update_identity()
+    system.solve_constant_rhs()
+    system.solve_initial_point_dev(p(x), p(s), p(z))
+    system.shift_to_interior_batch_dev(p(s), True)
+    system.shift_to_interior_batch_dev(p(z), False)
+    tau, kappa = np.ones(nb), np.ones(nb)
+    s0, z0 = s.clone(), z.clone()                        # the start: where a frozen member's block of K is scaled (below)
+
+    it = 0
+    nfrozen = 0
+    alpha = np.zeros(nb)
+    status = [UNSOLVED] * nb
+    iterations = [0] * nb
+    prev = [None] * nb
+    hist = [[] for _ in range(nb)]
+    prev_vars = None
+    tiny = 100 * np.finfo(float).eps
+    with np.errstate(all="ignore"):                      # (a frozen member's scalars may overflow; they are not used)
+        while True:
+            active = [k for k in range(nb) if status[k] == UNSOLVED]
+            # ---- residuals (residuals.jl:1-37); every member's twelve scalars in ONE read-back
+            R = system.residuals_batch_dev(p(x), p(s), p(z), tau, p(rx), p(rz), p(rx_inf), p(rz_inf), p(Px))
+            qx, bz, sz, xPx = R[:, 0], R[:, 1], R[:, 2], R[:, 3]
+            rtau = qx + bz + kappa + xPx / tau
+            mu = (sz + tau * kappa) / (degree + 1)
+            if inspect is not None:
+                inspect(dict(x=x, s=s, z=z, dx=dx, ds=ds, dz=dz, aff_s=aff_s, rhs_s=rhs_s, rx=rx, rz=rz, rx_inf=rx_inf,
+                             rz_inf=rz_inf, Px=Px, q=qd, b=bd), backend)
+            for k in active:
+                # ---- info_update! (info.jl:1-63), no equilibration
+                nx, nz, ns, n_rxi, n_Px, n_rzi, n_rz, n_rx = (float(v) for v in R[k, 4:12])
+                tinv = 1.0 / tau[k]
+                cost_p = qx[k] * tinv + xPx[k] * tinv * tinv / 2
+                cost_d = -bz[k] * tinv - xPx[k] * tinv * tinv / 2
+                res_pinf = n_rxi / max(1.0, nz)
+                res_dinf = max(n_Px / max(1.0, nx), n_rzi / max(1.0, nx + ns))
+                nx, nz, ns = nx * tinv, nz * tinv, ns * tinv
+                res_p = n_rz * tinv / max(1.0, normb[k] + nx + ns)
+                res_d = n_rx * tinv / max(1.0, normq[k] + nx + nz)
+                gap_abs = abs(cost_p - cost_d)
+                gap_rel = gap_abs / max(1.0, min(abs(cost_p), abs(cost_d)))
+                kt = kappa[k] * tinv
+                hist[k].append(dict(iter=it, pcost=float(cost_p), dcost=float(cost_d), gap=float(gap_abs), pres=res_p, dres=res_d,
+                                    kt=float(kt), mu=float(mu[k]), step=float(alpha[k])))
+                # ---- termination (info.jl:65-120, 270-330)
+                stk = UNSOLVED
+                if kt <= 1 and (gap_abs < st.tol_gap_abs or gap_rel < st.tol_gap_rel) and res_p < st.tol_feas and res_d < st.tol_feas:
+                    stk = SOLVED
+                elif kt > 1000.0 / st.tol_ktratio:
+                    if bz[k] < -st.tol_infeas_abs and res_pinf < -st.tol_infeas_rel * bz[k]:
+                        stk = PRIMAL_INFEASIBLE
+                    elif qx[k] < -st.tol_infeas_abs and res_dinf < -st.tol_infeas_rel * qx[k]:
+                        stk = DUAL_INFEASIBLE
+                pv = prev[k]
+                if stk == UNSOLVED and it > 1 and pv is not None and (res_d > pv["res_d"] or res_p > pv["res_p"]):
+                    if kt < tiny and (pv["gap_abs"] < st.tol_gap_abs or pv["gap_rel"] < st.tol_gap_rel):
+                        stk = INSUFFICIENT_PROGRESS
+                    if kt < 1 and ((res_d > 100 * st.tol_feas and res_d > 100 * pv["res_d"]) or
+                                   (res_p > 100 * st.tol_feas and res_p > 100 * pv["res_p"])):
+                        stk = INSUFFICIENT_PROGRESS
+                if stk == UNSOLVED and it == st.max_iter:
+                    stk = MAX_ITERATIONS
+                prev[k] = dict(res_p=res_p, res_d=res_d, gap_abs=gap_abs, gap_rel=gap_rel)
+                if stk != UNSOLVED:
+                    status[k], iterations[k] = stk, it
+                    if stk == INSUFFICIENT_PROGRESS and prev_vars is not None:      # this member's rows only
+                        px, ps, pz, ptau, pkappa = prev_vars
+                        x[x_off[k]:x_off[k + 1]] = px[x_off[k]:x_off[k + 1]]
+                        s[z_off[k]:z_off[k + 1]] = ps[z_off[k]:z_off[k + 1]]
+                        z[z_off[k]:z_off[k + 1]] = pz[z_off[k]:z_off[k + 1]]
+                        tau[k], kappa[k] = ptau[k], pkappa[k]
+            active = [k for k in range(nb) if status[k] == UNSOLVED]
+            if not active:
+                break
+            act = np.zeros(nb, bool)
+            act[active] = True
+            # ---- kkt_update!: cone scaling from (s, z), refactor, constant-RHS solve (solver.jl:258-280); joint
+            it += 1
+            # What a frozen member leaves in the stack.  The iterate a member ENDS on is one that no stand-alone loop ever
+            # factorises (the loop stops before the next kkt_update!); with s z ~ 1e-10 its block of K spoils the refinement
+            # of the whole stack's solves, whose accept / stop rule is joint: a member SOLVED after 11 iterations alone ended
+            # ALMOST_SOLVED after 15 beside one that had ended after 10.  So from the iteration after it ended
+            #   - a frozen member's block of K is scaled at the member's START point (s0, z0), which is well conditioned
+            #     (a row mask and torch.where: two elementwise launches), and
+            #   - its rows of the affine and the combined right-hand side are made exactly ZERO, so that its rows of the
+            #     solutions and of the refinement's error are exactly zero too (K is block diagonal) and its size does not enter
+            #     the joint tolerance reltol ||b||_inf -- by the library's own elementwise calls with 0 / 1 as the members'
+            #     scalars, three small launches.
+            # Its step is discarded anyway (alpha = 0); nothing here runs before a member has ended.
+            frozen = (~act).astype(float)
+            any_frozen = len(active) < nb
+            if nb - len(active) != nfrozen:
+                nfrozen = nb - len(active)
+                hm = np.zeros(m, bool)
+                for k in range(nb):
+                    if not act[k]:
+                        hm[z_off[k]:z_off[k + 1]] = True
+                frozen_rows = torch.from_numpy(hm).to(dev)
+            s_u, z_u = (torch.where(frozen_rows, s0, s), torch.where(frozen_rows, z0, z)) if any_frozen else (s, z)
+            ok = system.update_dev(p(s_u), p(z_u))
+            if ok:
+                # ---- affine step (solver.jl:282-295): right-hand side (rx, s - rz)
+                system.affine_ds_dev(p(aff_s))
+                arx, arz = rx, rz
+                if any_frozen:
+                    system.combined_rhs_batch_dev(p(aff_x), p(aff_z), p(rx), p(rz), frozen)      # frozen rows: 0, others: rx, rz
+                    # ... and aff_z = 0 + 1 s there, so that s - aff_z = 0 (dx, ds: scratch, written by the solve below)
+                    system.add_step_batch_dev(p(dx), p(ds), p(aff_z), p(rx), p(rz), p(s), frozen)
+                    arx, arz = aff_x, aff_z
+                ok, dtau, dkappa = system.solve_batch_dev((p(dx), p(ds), p(dz)), (p(arx), p(aff_s), p(arz)), rtau, tau * kappa,
+                                                          (p(x), p(s), p(z)), tau, kappa, True)
+                ir_total += backend.last_ir_iterations
+            if ok:
+                # ---- combined step (solver.jl:297-323)
+                alpha = system.step_length_batch_dev(p(dz), p(ds), p(z), p(s), dtau, dkappa, tau, kappa)
+                sigma = np.where(act, (1 - alpha) ** 3, 1.0)                 # (frozen: (1 - sigma) rx = 0)
+                mcorr = np.where(act, np.ones(nb) if it > 1 else alpha, 0.0)
+                system.combined_ds_batch_dev(p(rhs_s), p(dz), p(ds), np.where(act, sigma * mu, 0.0), mcorr)
+                if any_frozen:                                               # rhs_s = 0 on frozen rows (rhs_x: rewritten below)
+                    system.combined_rhs_batch_dev(p(rhs_x), p(rhs_s), p(rx), p(rhs_s), frozen)
+                system.combined_rhs_batch_dev(p(rhs_x), p(rhs_z), p(rx), p(rz), sigma)
+                ok, dtau, dkappa = system.solve_batch_dev((p(dx), p(ds), p(dz)), (p(rhs_x), p(rhs_s), p(rhs_z)), (1 - sigma) * rtau,
+                                                          -sigma * mu + mcorr * dtau * dkappa + tau * kappa,
+                                                          (p(x), p(s), p(z)), tau, kappa, False)
+                ir_total += backend.last_ir_iterations
+            if not ok:
+                alpha = np.zeros(nb)
+                for k in active:
+                    status[k], iterations[k] = NUMERICAL_ERROR, it
+                break
+            alpha = system.step_length_batch_dev(p(dz), p(ds), p(z), p(s), dtau, dkappa, tau, kappa) * st.max_step_fraction
+            alpha[~act] = 0.0
+            for k in active:
+                if not alpha[k] > max(0.0, st.min_terminate_step_length):
+                    status[k], iterations[k] = INSUFFICIENT_PROGRESS, it
+                    alpha[k] = 0.0
+            prev_vars = (x.clone(), s.clone(), z.clone(), tau.copy(), kappa.copy())
+            system.add_step_batch_dev(p(x), p(s), p(z), p(dx), p(ds), p(dz), alpha)
+            go = alpha != 0.0
+            tau = np.where(go, tau + alpha * dtau, tau)
+            kappa = np.where(go, kappa + alpha * dkappa, kappa)
+
+        # ---- info_post_process! (info.jl:196-211) per member: after an error / limit exit, an iterate that meets the reduced
+        #      tolerances is ALMOST_SOLVED
+        late = [k for k in range(nb) if status[k] in (NUMERICAL_ERROR, INSUFFICIENT_PROGRESS, MAX_ITERATIONS)]
+        if late:
+            R = system.residuals_batch_dev(p(x), p(s), p(z), tau, p(rx), p(rz), p(rx_inf), p(rz_inf), p(Px))
+            for k in late:
+                qx, bz, xPx, nx, nz, ns, n_rz, n_rx = (float(R[k, i]) for i in (0, 1, 3, 4, 5, 6, 10, 11))
+                tinv = 1.0 / tau[k]
+                cp = qx * tinv + xPx * tinv * tinv / 2
+                cd = -bz * tinv - xPx * tinv * tinv / 2
+                nx, nz, ns = nx * tinv, nz * tinv, ns * tinv
+                rp = n_rz * tinv / max(1.0, normb[k] + nx + ns)
+                rd = n_rx * tinv / max(1.0, normq[k] + nx + nz)
+                ga = abs(cp - cd)
+                gr = ga / max(1.0, min(abs(cp), abs(cd)))
+                if kappa[k] * tinv <= 1 and (ga < st.reduced_tol_gap_abs or gr < st.reduced_tol_gap_rel) and \
+                        rp < st.reduced_tol_feas and rd < st.reduced_tol_feas:
+                    status[k] = ALMOST_SOLVED
+    # ---- solution_post_process! per member: unscale by the member's tau (kappa for certificates); one copy to the host
+    torch.cuda.synchronize()
+    xh, zh, sh = x.cpu().numpy(), z.cpu().numpy(), s.cpu().numpy()
+    out = []
+    for k, (Pt, qk, _, bk, _) in enumerate(members):
+        infeasible = status[k] in (PRIMAL_INFEASIBLE, DUAL_INFEASIBLE)
+        sc = 1.0 / (kappa[k] if infeasible else tau[k])
+        xo, zo, so = xh[x_off[k]:x_off[k + 1]] * sc, zh[z_off[k]:z_off[k + 1]] * sc, sh[z_off[k]:z_off[k + 1]] * sc
+        Pfull = (Pt + sp.triu(Pt, 1).T).tocsr()
+        quad = 0.5 * xo @ (Pfull @ xo)
+        objp, objd = qk @ xo + quad, -bk @ zo - quad
+        if infeasible:
+            objp = objd = float("nan")
+        out.append(IPMResult(status[k], xo, zo, so, objp, objd, iterations[k], ir_total, hist[k]))
+    return out
+
+
 def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym, genpow=False):
     """The loop the entry points share.  nonsym: the reference's path for a list that does not allow the symmetric
     start (solver.jl:383-404) -- every line that differs sits under `if nonsym`.  genpow (with nonsym): the cone

@@ -333,6 +333,7 @@ class HipKKTSystem:
     def __init__(self, kktsolver):
         self.ks = kktsolver
         self._ready = False
+        self.nb = 0                  # members of the partition (set_problems); 0: none
 
     def init(self, q, b):
         q, b = f64(q), f64(b)
@@ -485,6 +486,97 @@ class HipKKTSystem:
         return check(_lib.lib().hipkkt_kkt_system_add_step(self.ks._h, C.c_void_p(d_x), C.c_void_p(d_s), C.c_void_p(d_z),
                                                             C.c_void_p(d_dx), C.c_void_p(d_ds), C.c_void_p(d_dz), float(alpha)),
                      "hipkkt_kkt_system_add_step")
+
+    # ---- a stack of independent member problems on this handle: the partition, and the operations between the solves
+    #      with every scalar a numpy array over the members (the _batch symbols).  One upload of the scalar arrays and one
+    #      read-back per call; the number of launches does not depend on the number of members.
+    def set_problems(self, blocks):
+        """The partition of the stack: blocks = the members' (n_b, m_b) in stacking order, or None / [] to clear it.
+        Raises HipKKTError where the library refuses it (a coupling entry, a cone across a boundary, a cone kind or PSD
+        side outside the batched set)."""
+        blocks = [] if blocks is None else [(int(nb_), int(mb_)) for nb_, mb_ in blocks]
+        x_off = i64(np.concatenate([[0], np.cumsum([b_[0] for b_ in blocks])])) if blocks else i64([0])
+        z_off = i64(np.concatenate([[0], np.cumsum([b_[1] for b_ in blocks])])) if blocks else i64([0])
+        check(_lib.lib().hipkkt_kkt_system_set_problems(self.ks._h, len(blocks), ptr(x_off), ptr(z_off)),
+              "hipkkt_kkt_system_set_problems")
+        self.nb = len(blocks)
+
+    def _scalars(self, *arrays):
+        """The members' scalars as contiguous float64 arrays of length nb (a Python float is not broadcast: one value per
+        member is the point of these calls)."""
+        out = []
+        for a in arrays:
+            if a is None:                                # (NULL: the library's to refuse)
+                out.append(None)
+                continue
+            a = f64(a)
+            if self.nb and a.shape != (self.nb,):        # (no partition: the library's to refuse)
+                raise ValueError(f"a scalar array must have one entry per member ({self.nb}), got shape {a.shape}")
+            out.append(a)
+        return out
+
+    def residuals_batch_dev(self, d_x, d_s, d_z, tau, d_rx, d_rz, d_rx_inf, d_rz_inf, d_Px, d_equil=None):
+        """residuals_dev per member: rx, rz with the row's own tau[b] -> numpy array (nb, 12), row b the twelve scalars over
+        member b's rows."""
+        tau, = self._scalars(tau)
+        out = np.zeros((self.nb, 12))
+        eq = (None,) * 4 if d_equil is None else tuple(d_equil)
+        check(_lib.lib().hipkkt_kkt_system_residuals_batch(
+            self.ks._h, C.c_void_p(d_x), C.c_void_p(d_s), C.c_void_p(d_z), ptr(tau), C.c_void_p(d_rx), C.c_void_p(d_rz),
+            C.c_void_p(d_rx_inf), C.c_void_p(d_rz_inf), C.c_void_p(d_Px), C.c_void_p(eq[0]), C.c_void_p(eq[1]),
+            C.c_void_p(eq[2]), C.c_void_p(eq[3]), ptr(out)), "hipkkt_kkt_system_residuals_batch")
+        return out
+
+    def solve_batch_dev(self, d_lhs, d_rhs, rhs_tau, rhs_kappa, d_var, var_tau, var_kappa, affine):
+        """solve_dev per member: the scalars are arrays over the members.  Returns (is_success, dtau, dkappa) with dtau,
+        dkappa numpy arrays of nb; is_success is the joint status of the one stacked solve."""
+        rhs_tau, rhs_kappa, var_tau, var_kappa = self._scalars(rhs_tau, rhs_kappa, var_tau, var_kappa)
+        tk = np.zeros((self.nb, 2))
+        ok = check(_lib.lib().hipkkt_kkt_system_solve_batch(
+            self.ks._h, C.c_void_p(d_lhs[0]), C.c_void_p(d_lhs[1]), C.c_void_p(d_lhs[2]), ptr(tk),
+            C.c_void_p(d_rhs[0]), C.c_void_p(d_rhs[1]), C.c_void_p(d_rhs[2]), ptr(rhs_tau), ptr(rhs_kappa),
+            C.c_void_p(d_var[0]), C.c_void_p(d_var[1]), C.c_void_p(d_var[2]), ptr(var_tau), ptr(var_kappa),
+            0 if affine else 1), "hipkkt_kkt_system_solve_batch")
+        return ok, tk[:, 0].copy(), tk[:, 1].copy()
+
+    def combined_ds_batch_dev(self, d_out, d_step_z, d_step_s, sigma_mu, m_corr):
+        """combined_ds_dev with member b's sigma_mu[b], m_corr[b] on its cones."""
+        sigma_mu, m_corr = self._scalars(sigma_mu, m_corr)
+        return check(_lib.lib().hipkkt_kkt_system_combined_ds_batch(self.ks._h, C.c_void_p(d_out), C.c_void_p(d_step_z),
+                                                                     C.c_void_p(d_step_s), ptr(sigma_mu), ptr(m_corr)),
+                     "hipkkt_kkt_system_combined_ds_batch")
+
+    def step_length_batch_dev(self, d_step_z, d_step_s, d_z, d_s, step_tau, step_kappa, tau, kappa):
+        """step_length_dev per member (without the max_step_fraction factor) -> numpy array of nb."""
+        step_tau, step_kappa, tau, kappa = self._scalars(step_tau, step_kappa, tau, kappa)
+        out = np.zeros(self.nb)
+        check(_lib.lib().hipkkt_kkt_system_step_length_batch(self.ks._h, C.c_void_p(d_step_z), C.c_void_p(d_step_s),
+                                                             C.c_void_p(d_z), C.c_void_p(d_s), ptr(step_tau), ptr(step_kappa),
+                                                             ptr(tau), ptr(kappa), ptr(out)),
+              "hipkkt_kkt_system_step_length_batch")
+        return out
+
+    def shift_to_interior_batch_dev(self, d_v, primal):
+        """_shift_to_cone_interior! per member, in place -> numpy array (nb, 2): (min_margin, pos_margin) before the shift."""
+        out = np.zeros((self.nb, 2))
+        check(_lib.lib().hipkkt_kkt_system_shift_to_interior_batch(self.ks._h, C.c_void_p(d_v), 1 if primal else 0, ptr(out)),
+              "hipkkt_kkt_system_shift_to_interior_batch")
+        return out
+
+    def combined_rhs_batch_dev(self, d_rhs_x, d_rhs_z, d_rx, d_rz, sigma):
+        """rhs_x = (1 - sigma[b]) rx, rhs_z = (1 - sigma[b]) rz on member b's rows."""
+        sigma, = self._scalars(sigma)
+        return check(_lib.lib().hipkkt_kkt_system_combined_rhs_batch(self.ks._h, C.c_void_p(d_rhs_x), C.c_void_p(d_rhs_z),
+                                                                      C.c_void_p(d_rx), C.c_void_p(d_rz), ptr(sigma)),
+                     "hipkkt_kkt_system_combined_rhs_batch")
+
+    def add_step_batch_dev(self, d_x, d_s, d_z, d_dx, d_ds, d_dz, alpha):
+        """x += alpha[b] dx, s += alpha[b] ds, z += alpha[b] dz on member b's rows; alpha[b] == 0 leaves them untouched."""
+        alpha, = self._scalars(alpha)
+        return check(_lib.lib().hipkkt_kkt_system_add_step_batch(self.ks._h, C.c_void_p(d_x), C.c_void_p(d_s), C.c_void_p(d_z),
+                                                                  C.c_void_p(d_dx), C.c_void_p(d_ds), C.c_void_p(d_dz),
+                                                                  ptr(alpha)),
+                     "hipkkt_kkt_system_add_step_batch")
 
     def prepared(self, d_lhs, d_rhs, rhs_tau, rhs_kappa, d_var, var_tau, var_kappa):
         """(update, solve_affine, solve_combined) closures over pre-converted ctypes arguments for a caller that issues the

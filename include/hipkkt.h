@@ -516,6 +516,101 @@ int hipkkt_kkt_system_combined_rhs(hipkkt_kkt_t h, double *d_rhs_x, double *d_rh
 int hipkkt_kkt_system_add_step(hipkkt_kkt_t h, double *d_x, double *d_s, double *d_z, const double *d_dx,
                                const double *d_ds, const double *d_dz, double alpha);
 
+/* ------------------------------------------- Level C on a stack of INDEPENDENT problems
+ * A batch of independent conic problems is put on ONE handle as a block-diagonal stack (P = blkdiag(P_b), A = blkdiag(A_b),
+ * the cone lists one behind the other), so that the elimination forest shares every per-level launch.  The calls below
+ * make such a stack solvable as the problems it consists of: every scalar the loop keeps between its solves -- tau,
+ * kappa, mu, sigma, alpha, the residual norms, the margins, (dtau, dkappa) -- exists once per member.  Each _batch entry
+ * point is its scalar twin with every scalar argument a HOST array of nb doubles and every scalar result a host array
+ * with member b's values contiguous; vector arguments stay whole-stack device pointers.  Per call the scalar arrays go
+ * up in one copy and the results come back in one copy, and the number of kernel launches does not depend on nb: the
+ * reductions are segmented by member on the device (a workgroup belongs to one member; member b's wave folds b's slots
+ * in slot order -- fixed layout, no floating-point atomic, two calls give the same bits).
+ * What stays JOINT on a partitioned handle, because the factorisation is one: the status of hipkkt_kkt_system_update and
+ * of the solves (a failed kkt_update!, kktsystem.jl:62-78, fails for every member); the static regulariser's epsilon,
+ * scaled by the largest diagonal entry of the whole K (kktsolver_directldl.jl:297-310); and the iterative refinement's
+ * stopping rule, whose infinity-norms run over the stack (kktsolver_directldl.jl:389-470).  hipkkt_kkt_system_update,
+ * _solve_constant_rhs, _solve_initial_point and _affine_ds have no scalar argument and serve a partitioned handle as
+ * they are: the block-diagonal K does their work per member.  No scalar entry point changes its behaviour on a
+ * partitioned handle. */
+/* The partition: member b owns rows x_off[b] .. x_off[b+1]-1 of every x-like vector and z_off[b] .. z_off[b+1]-1 of every
+ * s/z-like vector (DefaultProblemData's P, q, A, b of problemdata.jl:3-88 cut member by member; the cones of
+ * compositecone_type.jl:114-141 likewise).  x_off, z_off: HOST arrays of nb + 1 entries, copied.  Callable after
+ * hipkkt_kkt_system_init, again to replace the partition, and with nb = 0 (offsets ignored) to clear it.  HIPKKT_ERR_ARG,
+ * with a text in hipkkt_last_error that names the offending member or entry and the handle's partition left as it was,
+ * unless: the offsets start at 0, do not decrease and end at n and m; every member has at least one x row (a member
+ * without z rows is allowed); every cone lies inside one member's z range; every stored entry of P has its row and its
+ * column in the same member; every entry of A has its row's member equal to its column's.  Symmetric cones with PSD side
+ * <= 48 only: a handle that holds an exponential, power or generalized power cone or a PSD cone of side > 48, or that
+ * has called hipkkt_kkt_enable_large_psd, is refused with HIPKKT_ERR_ARG, and so is a deferred-status handle.  The
+ * tables (row -> member, cone -> member, workgroup -> (member, chunk)) and all work space are sized by nb; nb is bounded
+ * by n only.  Synchronises with the handle's stream once (tables in use are replaced); enqueues no kernel. */
+int hipkkt_kkt_system_set_problems(hipkkt_kkt_t h, int64_t nb, const int64_t *x_off, const int64_t *z_off);
+
+/* Rules for the seven _batch calls: on a handle without a partition, on a deferred-status handle and with a NULL scalar
+ * array each returns HIPKKT_ERR_ARG and enqueues nothing; the aliasing rules are the twin's. */
+/* hipkkt_kkt_system_residuals per member (residuals.jl:1-37, info.jl:33-51): rx and rz are formed with the row's own
+ * tau[b]; out (host, 12 nb) receives for member b at out[12 b ..] the twelve scalars of the twin over THAT member's rows
+ * only.  The five vectors are, bit for bit, what the twin writes on member b's rows when called with tau[b].  The
+ * equilibration vectors are all NULL or all given; the outputs alias neither an input nor each other.  Synchronises: one
+ * upload (tau), one read-back. */
+int hipkkt_kkt_system_residuals_batch(hipkkt_kkt_t h, const double *d_x, const double *d_s, const double *d_z,
+                                      const double *tau, double *d_rx, double *d_rz, double *d_rx_inf, double *d_rz_inf,
+                                      double *d_Px, const double *d_d, const double *d_dinv, const double *d_e,
+                                      const double *d_einv, double *out);
+
+/* kkt_solve! per member (kktsystem.jl:145-215), steptype 0 = :affine, 1 = :combined: ONE solve of the stacked system
+ * for (x1, z1) (:150-173, as hipkkt_kkt_system_solve), then per member, from that member's rows of q, b, x, x1, x2, z1,
+ * z2: every dot product of :185-196, P x1 and P (x / tau_b - x2), dtau_b, (dx, dz) = (x1, z1) + dtau_b (x2, z2)
+ * (:200-203) and dkappa_b (:206); ds = -(Hs dz + const) (:206-212) is per cone anyway.  rhs_tau, rhs_kappa, var_tau,
+ * var_kappa: host arrays of nb; lhs_tau_kappa (host, 2 nb) receives (dtau_b, dkappa_b) at [2 b], [2 b + 1].  The x2-only
+ * terms of tau_den are formed per member by this call itself.  On a lazy handle (hipkkt_kkt_system_set_lazy) with the
+ * constant-RHS solve pending, that solve runs by itself first, as for a :combined hipkkt_kkt_system_solve arriving
+ * first; there is no 2-column pairing for batches.  The return value is the joint status of the solve.  Inputs are not
+ * modified; the lhs vectors must not alias an input.  Synchronises: one upload, one read-back (besides the solve's own
+ * refinement read-backs, as in the twin). */
+int hipkkt_kkt_system_solve_batch(hipkkt_kkt_t h, double *d_lhs_x, double *d_lhs_s, double *d_lhs_z, double *lhs_tau_kappa,
+                                  const double *d_rhs_x, const double *d_rhs_s, const double *d_rhs_z,
+                                  const double *rhs_tau, const double *rhs_kappa,
+                                  const double *d_var_x, const double *d_var_s, const double *d_var_z,
+                                  const double *var_tau, const double *var_kappa, int steptype);
+
+/* hipkkt_kkt_system_combined_ds per member (variables.jl:124-162; coneops_symmetric_common.jl:1-35): on member b's
+ * cones out = lambda o lambda + m_corr[b] (W^{-T} step_s) o (W step_z) - sigma_mu[b] e -- bit for bit what the twin
+ * writes there with member b's scalars (the same per-cone code runs).  d_out must not alias an input.  One upload, no
+ * synchronisation. */
+int hipkkt_kkt_system_combined_ds_batch(hipkkt_kkt_t h, double *d_out, const double *d_step_z, const double *d_step_s,
+                                        const double *sigma_mu, const double *m_corr);
+
+/* hipkkt_kkt_system_step_length per member (variables.jl:14-43; coneops_compositecone.jl:205-243), WITHOUT the
+ * max_step_fraction factor as in the twin: alpha_out[b] = min(1, -tau[b]/step_tau[b] if step_tau[b] < 0, the same for
+ * kappa, the limits of member b's cones) -- an order-free minimum, so it equals the twin's result on a handle that holds
+ * member b alone.  step_tau, step_kappa, tau, kappa, alpha_out: host arrays of nb.  Inputs are not modified.
+ * Synchronises: one upload, one read-back. */
+int hipkkt_kkt_system_step_length_batch(hipkkt_kkt_t h, const double *d_step_z, const double *d_step_s, const double *d_z,
+                                        const double *d_s, const double *step_tau, const double *step_kappa,
+                                        const double *tau, const double *kappa, double *alpha_out);
+
+/* _shift_to_cone_interior! per member (variables.jl:180-208): the margins of member b's cones, then the branch they
+ * select, applied to member b's rows in place; the degree is that of the member's own cones.  margins_out (host, 2 nb,
+ * may be NULL) receives (min_margin_b, pos_margin_b) as found BEFORE the shift.  The branch is chosen on the device: no
+ * upload, one read-back.  Synchronises. */
+int hipkkt_kkt_system_shift_to_interior_batch(hipkkt_kkt_t h, double *d_v, int primal, double *margins_out);
+
+/* hipkkt_kkt_system_combined_rhs per member (variables.jl:124-162): rhs_x = (1 - sigma[b]) rx, rhs_z = (1 - sigma[b]) rz
+ * on member b's rows, bit for bit the twin's values with sigma[b]; the s part is hipkkt_kkt_system_combined_ds_batch.
+ * Outputs may alias inputs.  A pointer to a vector of length 0 may be NULL, any other NULL is HIPKKT_ERR_ARG.  One launch
+ * on the handle's stream behind one upload (sigma), no synchronisation. */
+int hipkkt_kkt_system_combined_rhs_batch(hipkkt_kkt_t h, double *d_rhs_x, double *d_rhs_z, const double *d_rx,
+                                         const double *d_rz, const double *sigma);
+
+/* variables_add_step! per member (variables.jl:107-122): x += alpha[b] dx, s += alpha[b] ds, z += alpha[b] dz on member
+ * b's rows, each element fl(v + fl(alpha[b] d)) as in the twin; alpha[b] == 0 leaves member b's rows bit for bit as they
+ * were (they are not written).  A step must not alias the vector it is added to, and d_s must not be d_z.  One upload,
+ * no synchronisation. */
+int hipkkt_kkt_system_add_step_batch(hipkkt_kkt_t h, double *d_x, double *d_s, double *d_z, const double *d_dx,
+                                     const double *d_ds, const double *d_dz, const double *alpha);
+
 /* Lazy constant-RHS solve: the same pairing reached through the reference's own TWO calls, so that solver.jl:278-295
  * stays as it is.  With lazy = 1, kkt_update! (hipkkt_kkt_system_update / _update_cones) scales, scatters and
  * refactors, returns the factorisation's status and only NOTES that (x2, z2) = K \ (-q, b) is due

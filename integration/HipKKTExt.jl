@@ -397,6 +397,79 @@ function kkt_solve!(s::HipKKTSystem{T}, lhs::DefaultVariables{T}, rhs::DefaultVa
     return true
 end
 
+# ---- a batch of independent problems stacked block-diagonally on one handle (include/hipkkt.h, "Level C on a stack of
+# INDEPENDENT problems"): the partition and the seven operations between the solves with every scalar a Vector over the
+# members.  Vectors named d_* are device pointers (Ptr{Cdouble}) of the whole stack; the scalar arrays are host Vectors of
+# length nb.  Thin wrappers for a caller that keeps its iterate in HBM; the glue above (host-resident DefaultVariables)
+# does not use them.
+const DPtr = Ptr{Cdouble}
+
+function set_problems!(s::HipKKTSystem{T}, x_off::Vector{Int64}, z_off::Vector{Int64}) where {T}
+    nb = length(x_off) - 1
+    GC.@preserve x_off z_off check(ccall((:hipkkt_kkt_system_set_problems, libhipkkt), Cint,
+        (Ptr{Cvoid}, Int64, Ptr{Int64}, Ptr{Int64}), s.kktsolver.handle, nb, x_off, z_off), "hipkkt_kkt_system_set_problems")
+    return nb
+end
+
+function residuals_batch!(s::HipKKTSystem{T}, out::Matrix{T}, d_x::DPtr, d_s::DPtr, d_z::DPtr, tau::Vector{T},
+                          d_rx::DPtr, d_rz::DPtr, d_rx_inf::DPtr, d_rz_inf::DPtr, d_Px::DPtr;
+                          equil::NTuple{4,DPtr} = (C_NULL, C_NULL, C_NULL, C_NULL)) where {T}
+    # out: 12 x nb, column b the twelve scalars of member b
+    GC.@preserve out tau check(ccall((:hipkkt_kkt_system_residuals_batch, libhipkkt), Cint,
+        (Ptr{Cvoid}, DPtr, DPtr, DPtr, Ptr{Cdouble}, DPtr, DPtr, DPtr, DPtr, DPtr, DPtr, DPtr, DPtr, DPtr, Ptr{Cdouble}),
+        s.kktsolver.handle, d_x, d_s, d_z, tau, d_rx, d_rz, d_rx_inf, d_rz_inf, d_Px, equil[1], equil[2], equil[3], equil[4], out),
+        "hipkkt_kkt_system_residuals_batch")
+    return out
+end
+
+function solve_batch!(s::HipKKTSystem{T}, tk::Matrix{T}, d_lhs::NTuple{3,DPtr}, d_rhs::NTuple{3,DPtr}, rhs_tau::Vector{T},
+                      rhs_kappa::Vector{T}, d_var::NTuple{3,DPtr}, var_tau::Vector{T}, var_kappa::Vector{T}, steptype::Symbol) where {T}
+    # tk: 2 x nb, column b = (dtau_b, dkappa_b); the triples are (x, s, z); returns the joint is_success
+    return GC.@preserve tk rhs_tau rhs_kappa var_tau var_kappa check(ccall((:hipkkt_kkt_system_solve_batch, libhipkkt), Cint,
+        (Ptr{Cvoid}, DPtr, DPtr, DPtr, Ptr{Cdouble}, DPtr, DPtr, DPtr, Ptr{Cdouble}, Ptr{Cdouble}, DPtr, DPtr, DPtr, Ptr{Cdouble},
+         Ptr{Cdouble}, Cint),
+        s.kktsolver.handle, d_lhs[1], d_lhs[2], d_lhs[3], tk, d_rhs[1], d_rhs[2], d_rhs[3], rhs_tau, rhs_kappa, d_var[1], d_var[2],
+        d_var[3], var_tau, var_kappa, steptype === :affine ? 0 : 1), "hipkkt_kkt_system_solve_batch")
+end
+
+function combined_ds_batch!(s::HipKKTSystem{T}, d_out::DPtr, d_step_z::DPtr, d_step_s::DPtr, sigma_mu::Vector{T},
+                            m_corr::Vector{T}) where {T}
+    GC.@preserve sigma_mu m_corr check(ccall((:hipkkt_kkt_system_combined_ds_batch, libhipkkt), Cint,
+        (Ptr{Cvoid}, DPtr, DPtr, DPtr, Ptr{Cdouble}, Ptr{Cdouble}), s.kktsolver.handle, d_out, d_step_z, d_step_s, sigma_mu, m_corr),
+        "hipkkt_kkt_system_combined_ds_batch")
+    return nothing
+end
+
+function step_length_batch!(s::HipKKTSystem{T}, alpha::Vector{T}, d_step_z::DPtr, d_step_s::DPtr, d_z::DPtr, d_s::DPtr,
+                            step_tau::Vector{T}, step_kappa::Vector{T}, tau::Vector{T}, kappa::Vector{T}) where {T}
+    GC.@preserve alpha step_tau step_kappa tau kappa check(ccall((:hipkkt_kkt_system_step_length_batch, libhipkkt), Cint,
+        (Ptr{Cvoid}, DPtr, DPtr, DPtr, DPtr, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        s.kktsolver.handle, d_step_z, d_step_s, d_z, d_s, step_tau, step_kappa, tau, kappa, alpha), "hipkkt_kkt_system_step_length_batch")
+    return alpha                                     # without max_step_fraction, as the scalar call
+end
+
+function shift_to_interior_batch!(s::HipKKTSystem{T}, margins::Matrix{T}, d_v::DPtr, primal::Bool) where {T}
+    # margins: 2 x nb, column b = (min_margin_b, pos_margin_b) before the shift
+    GC.@preserve margins check(ccall((:hipkkt_kkt_system_shift_to_interior_batch, libhipkkt), Cint,
+        (Ptr{Cvoid}, DPtr, Cint, Ptr{Cdouble}), s.kktsolver.handle, d_v, primal ? 1 : 0, margins), "hipkkt_kkt_system_shift_to_interior_batch")
+    return margins
+end
+
+function combined_rhs_batch!(s::HipKKTSystem{T}, d_rhs_x::DPtr, d_rhs_z::DPtr, d_rx::DPtr, d_rz::DPtr, sigma::Vector{T}) where {T}
+    GC.@preserve sigma check(ccall((:hipkkt_kkt_system_combined_rhs_batch, libhipkkt), Cint,
+        (Ptr{Cvoid}, DPtr, DPtr, DPtr, DPtr, Ptr{Cdouble}), s.kktsolver.handle, d_rhs_x, d_rhs_z, d_rx, d_rz, sigma),
+        "hipkkt_kkt_system_combined_rhs_batch")
+    return nothing
+end
+
+function add_step_batch!(s::HipKKTSystem{T}, d_x::DPtr, d_s::DPtr, d_z::DPtr, d_dx::DPtr, d_ds::DPtr, d_dz::DPtr,
+                         alpha::Vector{T}) where {T}
+    GC.@preserve alpha check(ccall((:hipkkt_kkt_system_add_step_batch, libhipkkt), Cint,
+        (Ptr{Cvoid}, DPtr, DPtr, DPtr, DPtr, DPtr, DPtr, Ptr{Cdouble}), s.kktsolver.handle, d_x, d_s, d_z, d_dx, d_ds, d_dz, alpha),
+        "hipkkt_kkt_system_add_step_batch")
+    return nothing                                   # alpha[b] == 0 leaves member b's rows as they were
+end
+
 end # module
 
 # ---- boundary B only: the one-line dispatch at src/kktsystem.jl:33 ("Always LDL for now")

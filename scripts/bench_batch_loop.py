@@ -1,0 +1,72 @@
+#!/usr/bin/env python
+"""Per-iteration time of the interior-point loop on a batch of independent cfg4 members (problems.config4), two ways:
+
+  --mode batch    ipm_device.solve_device_batch on the members: every member its own scalars and status
+  --mode stacked  ipm_device.solve_device(plumbing="device") on problems.block_diagonal of the same members: ONE conic
+                  problem -- the only loop a library without the _batch entry points can run on such a stack
+
+Both loops do the same vector work per iteration (one update, two solves, the same elementwise and cone kernels), so
+their per-iteration times are comparable; the iteration COUNTS are not the same thing (the stacked loop ends with one
+status).  One JSON line per run.  --root: the tree whose cuclarabel_amd is imported (another build of the library for an
+A/B comparison in one session: run this script with the other tree's root and --mode stacked).
+
+    python scripts/bench_batch_loop.py --mode batch --members 64 --n 10000 --runs 3
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mode", choices=["batch", "stacked", "alone"], default="batch")
+    ap.add_argument("--members", type=int, default=64)
+    ap.add_argument("--n", type=int, default=10_000)
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    args = ap.parse_args()
+    sys.path.insert(0, args.root)
+    import torch
+    from cuclarabel_amd import ipm_device, problems
+
+    pbs = [problems.config4(j, n=args.n) for j in range(args.members)]
+    # the loops call `inspect` once per iteration, right behind the residual call's read-back: the time between the first
+    # and the last call is the loop's own, without the handle's set-up (symbolic analysis) and the final copy
+    stamps = []
+    stamp = lambda tensors, backend: stamps.append(time.perf_counter())
+    if args.mode == "batch":
+        data = [(pb.P, pb.q, pb.A, pb.b, pb.cones) for pb in pbs]
+        run = lambda: ipm_device.solve_device_batch(data, inspect=stamp)
+        iters = lambda res: max(r.iterations for r in res)
+        extra = lambda res: dict(iterations_per_member=[r.iterations for r in res],
+                                 statuses=sorted(set(r.status for r in res)))
+    elif args.mode == "stacked":
+        st = problems.block_diagonal(pbs)
+        run = lambda: ipm_device.solve_device(st.P, st.q, st.A, st.b, st.cones, inspect=stamp, plumbing="device")
+        iters = lambda res: res.iterations
+        extra = lambda res: dict(statuses=[res.status])
+    else:                                                # every member by itself: the counts the batch's are compared with
+        run = lambda: [ipm_device.solve_device(pb.P, pb.q, pb.A, pb.b, pb.cones, plumbing="device") for pb in pbs]
+        iters = lambda res: sum(r.iterations for r in res)
+        extra = lambda res: dict(iterations_per_member=[r.iterations for r in res], iterations_max=max(r.iterations for r in res),
+                                 statuses=sorted(set(r.status for r in res)))
+    run()                                                # warm-up: kernels loaded, allocator primed
+    for k in range(args.runs):
+        torch.cuda.synchronize()
+        del stamps[:]
+        t0 = time.perf_counter()
+        res = run()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        out = dict(mode=args.mode, members=args.members, n=args.n, run=k, seconds=round(dt, 6), loop_iterations=iters(res),
+                   root=os.path.basename(os.path.abspath(args.root)))
+        if len(stamps) > 1:
+            out["ms_per_iteration"] = round(1e3 * (stamps[-1] - stamps[0]) / (len(stamps) - 1), 4)
+        out.update(extra(res))
+        print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
