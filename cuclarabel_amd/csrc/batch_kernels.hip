@@ -10,6 +10,8 @@
 // leaves them in its slot; member b's wave adds b's slots lane-strided in slot order and meets in a fixed butterfly.  No
 // floating-point atomic.  Compiled without FMA contraction, as the twins are.
 #include "kernels.hpp"
+#include "launch_shapes.hpp"
+#include "refine_device.hpp"
 #include <cmath>
 
 namespace hipkkt {
@@ -168,7 +170,206 @@ __global__ __launch_bounds__(256) void k_batch_sys_step(BatchDev B, double* __re
     }
 }
 
+// ---- the refinement rule per member (kernels.hpp: MemberIrDev; kktsolver_directldl.jl:389-449 on each member's rows).
+// maxima of up to two slot ranges [s0, s1), known to every thread afterwards (a maximum does not depend on the order, so
+// every workgroup of a member gets the same bits)
+__device__ inline void block_max2_all(const double* __restrict__ p0, const double* __restrict__ p1, int s0, int s1, double& o0,
+                                      double& o1, double (*sh)[4])
+{
+    double v0 = 0.0, v1 = 0.0;
+    for (int i = s0 + (int)threadIdx.x; i < s1; i += 256) {
+        v0 = fmax(v0, p0[i]);
+        if (p1) v1 = fmax(v1, p1[i]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { v0 = fmax(v0, __shfl_xor(v0, o, 64)); v1 = fmax(v1, __shfl_xor(v1, o, 64)); }
+    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = v0; sh[1][threadIdx.x >> 6] = v1; }
+    __syncthreads();
+    o0 = fmax(fmax(sh[0][0], sh[0][1]), fmax(sh[0][2], sh[0][3]));
+    o1 = fmax(fmax(sh[1][0], sh[1][1]), fmax(sh[1][2], sh[1][3]));
+}
+
+// workgroup w: the positions wg_first[w] .. + chunk - 1 of member wg_mem[w]'s list of image rows, G lanes per row; a
+// row's sum is k_residual<G, 1>'s (residual_row_dot), so e holds the same bits.  pe / pb: the slot arrays (pb null: not
+// the first residual of a solve).  Long rows are left to the chunk kernel and k_member_long_finish.
+template <int G>
+__global__ __launch_bounds__(256) void k_member_residual(SpmvDev A, const double* __restrict__ K, MemberIrDev M,
+                                                         const double* __restrict__ b, const double* __restrict__ x,
+                                                         double* __restrict__ e, double* __restrict__ pe, double* __restrict__ pb)
+{
+    __shared__ double sh[2][4];
+    const int mem = M.wg_mem[blockIdx.x];
+    const int first = M.wg_first[blockIdx.x];
+    const int end = min(first + M.chunk, M.img_ptr[mem + 1]);
+    const int sub = threadIdx.x % G;
+    double vmax = 0.0, bmax = 0.0;
+    bool bad = false;
+    // (the row comes from a table here, one dependent load more than k_residual's: the next pass's row and entry range are
+    //  fetched while this pass's row is summed)
+    int pos = first + (int)threadIdx.x / G;
+    int row = -1;
+    int64_t q0 = 0, q1 = 0;
+    if (pos < end) { row = M.img_rows[pos]; q0 = A.ptr[row]; q1 = A.ptr[row + 1]; }
+    while (pos < end) {
+        const int row_now = row;
+        const int64_t q0_now = q0, q1_now = q1;
+        pos += 256 / G;
+        if (pos < end) { row = M.img_rows[pos]; q0 = A.ptr[row]; q1 = A.ptr[row + 1]; }
+        if (q1_now - q0_now > kLongRow) continue;
+        double acc[1];
+        residual_row_dot<G, 1>(A, K, x, 0, q0_now, q1_now, sub, acc);
+        if (sub == 0) {
+            const double bv = b[row_now];
+            const double r = bv - acc[0];
+            e[row_now] = r;
+            if (!isfinite(r)) bad = true;
+            vmax = fmax(vmax, fabs(r));
+            bmax = isfinite(bv) ? fmax(bmax, fabs(bv)) : INFINITY;
+        }
+    }
+    if (bad) vmax = INFINITY;                        // (marks non-finite, as k_residual does)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { vmax = fmax(vmax, __shfl_xor(vmax, o, 64)); bmax = fmax(bmax, __shfl_xor(bmax, o, 64)); }
+    if ((threadIdx.x & 63) == 0) { sh[0][threadIdx.x >> 6] = vmax; sh[1][threadIdx.x >> 6] = bmax; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const int slot = (int)blockIdx.x + mem;
+        pe[slot] = fmax(fmax(sh[0][0], sh[0][1]), fmax(sh[0][2], sh[0][3]));
+        if (pb) pb[slot] = fmax(fmax(sh[1][0], sh[1][1]), fmax(sh[1][2], sh[1][3]));
+    }
+}
+
+// wave = member: its long rows' residuals from the chunk sums (summed in chunk order, as k_residual_long_finish does) and
+// their maxima into the member's last slot
+__global__ __launch_bounds__(256) void k_member_long_finish(SpmvDev A, MemberIrDev M, const double* __restrict__ b,
+                                                            double* __restrict__ e, double* __restrict__ pe, double* __restrict__ pb)
+{
+    const int mem = blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (mem >= M.nb) return;
+    double vmax = 0.0, bmax = 0.0;
+    bool bad = false;
+    for (int i = M.long_ptr[mem] + lane; i < M.long_ptr[mem + 1]; i += 64) {
+        const int t = M.long_order[i];
+        const int row = A.long_rows[t];
+        double acc = 0.0;
+        for (int64_t c = A.long_chunk_ptr[t]; c < A.long_chunk_ptr[t + 1]; ++c) acc += A.long_partial[c];
+        const double bv = b[row];
+        const double r = bv - acc;
+        e[row] = r;
+        if (!isfinite(r)) bad = true;
+        vmax = fmax(vmax, fabs(r));
+        bmax = isfinite(bv) ? fmax(bmax, fabs(bv)) : INFINITY;
+    }
+    if (bad) vmax = INFINITY;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { vmax = fmax(vmax, __shfl_xor(vmax, o, 64)); bmax = fmax(bmax, __shfl_xor(bmax, o, 64)); }
+    if (lane == 0) {
+        const int slot = M.wg_ptr[mem + 1] + mem;
+        pe[slot] = vmax;
+        if (pb) pb[slot] = bmax;
+    }
+}
+
+// The aggregate over the members without a second launch: every member's leading workgroup adds {1, active, bad} to ONE
+// packed 64-bit counter (whole numbers, kMemberCountBits bits each) after folding its norme into a 64-bit maximum (the bit
+// pattern of a non-negative double orders as the double does); both are agent-scope atomics on both sides.  The leader
+// whose add completes the count writes the record and clears the two words for the next kernel.
+constexpr int kMemberCountBits = 21;
+
+__global__ __launch_bounds__(256) void k_member_ir_round(MemberIrDev M, int r, const int* __restrict__ flag_in, double* __restrict__ x,
+                                                         const double* __restrict__ dx, double* __restrict__ e, double abstol,
+                                                         double reltol, double stop_ratio, int max_iter, double* __restrict__ readback)
+{
+    __shared__ double sh[2][4];
+    const int mem = M.wg_mem[blockIdx.x];
+    const int s0 = M.wg_ptr[mem] + mem, s1 = M.wg_ptr[mem + 1] + mem + 1;
+    const int S = M.nwg + M.nb;
+    double active, rounds, bad, norme, normb;
+    bool accept = false;
+    if (r == 0) {
+        double ne0;
+        block_max2_all(M.slots, M.slots + S, s0, s1, ne0, normb, sh);
+        ir_initial(ne0, normb, abstol, reltol, max_iter, active, rounds, bad, norme);
+    } else {
+        const double* prev = M.state + ((size_t)(r - 1) * M.nb + mem) * 4;
+        active = prev[0]; rounds = prev[1]; bad = prev[2]; norme = prev[3];
+        normb = M.normb[mem];
+        if (active != 0.0) {                         // (uniform over the workgroup: the barrier inside is safe)
+            double cand, unused;
+            block_max2_all(M.slots + 2 * (size_t)S, nullptr, s0, s1, cand, unused, sh);
+            accept = ir_apply_rule(cand, r, max_iter, abstol, reltol, stop_ratio, normb, active, rounds, bad, norme);
+        }
+    }
+    // a member that has left its loop is not written again: its x stays, its rows of e are zero for the next sweeps
+    const int first = M.wg_first[blockIdx.x];
+    const int end = min(first + M.chunk, M.img_ptr[mem + 1]);
+    if (accept || active == 0.0) {
+        for (int pos = first + (int)threadIdx.x; pos < end; pos += 4 * 256) {          // (four rows in flight)
+            int rows[4];
+            double v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) rows[u] = (pos + u * 256 < end) ? M.img_rows[pos + u * 256] : -1;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) v[u] = (accept && rows[u] >= 0) ? dx[rows[u]] : 0.0;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (rows[u] < 0) continue;
+                if (accept) x[rows[u]] = v[u];
+                if (active == 0.0) e[rows[u]] = 0.0;
+            }
+        }
+    }
+    if ((int)blockIdx.x != M.wg_ptr[mem] || threadIdx.x != 0) return;
+    double* st = M.state + ((size_t)r * M.nb + mem) * 4;
+    st[0] = active; st[1] = rounds; st[2] = bad; st[3] = norme;
+    if (r == 0) M.normb[mem] = normb;
+    double* info = M.info + 4 * (size_t)mem;
+    info[0] = rounds; info[1] = norme; info[2] = normb; info[3] = bad;
+    unsigned long long* agg = M.agg;                                   // [0] the packed counts, [1] the largest norme's bits
+    // (norme is never NaN: the residual kernels mark non-finite rows as +Inf)
+    unsigned long long seen = __hip_atomic_fetch_max(agg + 1, (unsigned long long)__double_as_longlong(norme), __ATOMIC_RELAXED,
+                                                     __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(seen) : : "memory");      // the maximum has been performed before the count moves
+    const unsigned long long add = 1ull + ((active != 0.0 ? 1ull : 0ull) << kMemberCountBits) +
+                                   ((bad != 0.0 ? 1ull : 0ull) << (2 * kMemberCountBits));
+    const unsigned long long before = __hip_atomic_fetch_add(agg, add, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long now = before + add, mask = (1ull << kMemberCountBits) - 1;
+    if ((now & mask) != (unsigned long long)M.nb) return;
+    const unsigned long long top = __hip_atomic_load(agg + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(agg, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(agg + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the most rounds any member took: a member's rounds are the rounds it entered active, so the count grows by one in
+    // every round that some member entered active (the previous kernel's record says whether one did)
+    const double most = r == 0 ? 0.0 : (readback[0] != 0.0 ? (double)r : readback[1]);
+    readback[0] = ((now >> kMemberCountBits) & mask) ? 1.0 : 0.0;
+    readback[1] = most;
+    readback[2] = ((now >> (2 * kMemberCountBits)) & mask) ? 1.0 : 0.0;
+    readback[3] = __longlong_as_double((long long)top);
+    readback[4] = (flag_in && flag_in[0]) ? 1.0 : 0.0;
+}
+
 }  // namespace
+
+void launch_member_residual(const SpmvDev& A, const double* Kval, const MemberIrDev& M, const double* b, const double* x, double* e,
+                            bool first, hipStream_t st)
+{
+    const size_t S = (size_t)M.nwg + (size_t)M.nb;
+    double* pe = first ? M.slots : M.slots + 2 * S;
+    double* pb = first ? M.slots + S : nullptr;
+    if (A.lanes_per_row == 8) hipLaunchKernelGGL(k_member_residual<8>, dim3(M.nwg), dim3(256), 0, st, A, Kval, M, b, x, e, pe, pb);
+    else hipLaunchKernelGGL(k_member_residual<64>, dim3(M.nwg), dim3(256), 0, st, A, Kval, M, b, x, e, pe, pb);
+    if (A.nlong > 0) {
+        launch_residual_long_chunks(A, Kval, x, st);
+        hipLaunchKernelGGL(k_member_long_finish, dim3((M.nb + 3) / 4), dim3(256), 0, st, A, M, b, e, pe, pb);
+    }
+}
+
+void launch_member_ir_round(const MemberIrDev& M, int r, const int* flag_in, double* x, const double* dx, double* e, double abstol,
+                            double reltol, double stop_ratio, int max_iter, double* readback, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_member_ir_round, dim3(M.nwg), dim3(256), 0, st, M, r, flag_in, x, dx, e, abstol, reltol, stop_ratio, max_iter,
+                       readback);
+}
 
 void launch_batch_scale(const BatchDev& B, double* ox, double* oz, const double* rx, const double* rz, const double* sigma, int n,
                         int m, hipStream_t st)

@@ -115,4 +115,64 @@ std::string plan_batch(int n, int m, int64_t nb64, const int64_t* x_off, const i
     return "";
 }
 
+std::string plan_batch_image(int n, int m, int p, const BatchPlan& B, const BatchImageCone* cones, int ncones, const int* long_rows,
+                             int nlong, int chunk, BatchImagePlan& out)
+{
+    if (n < 0 || m < 0 || p < 0 || (int64_t)n + m + p > INT_MAX) return "the image's row count does not fit 32 bits";
+    if (chunk < 1) return "the chunk must be positive";
+    const int nb = B.nb, N = n + m + p;
+    if (nb < 1 || (int)B.xmem.size() != n || (int)B.zmem.size() != m || (int)B.cone_mem.size() != ncones)
+        return "the partition does not belong to this image";
+    if ((int64_t)N + nb > INT_MAX) return "N + nb does not fit the tables' 32-bit indices";
+    BatchImagePlan& I = out;
+    I = BatchImagePlan{};
+    I.nb = nb; I.N = N; I.chunk = chunk;
+    I.rowmem.assign((size_t)N, -1);
+    for (int i = 0; i < n; ++i) I.rowmem[(size_t)i] = B.xmem[(size_t)i];
+    for (int i = 0; i < m; ++i) I.rowmem[(size_t)n + i] = B.zmem[(size_t)i];
+    for (int c = 0; c < ncones; ++c) {
+        const BatchImageCone& ci = cones[c];
+        if (ci.pwidth == 0) continue;
+        if (ci.pwidth < 0 || ci.pcol < 0 || (int64_t)ci.pcol + ci.pwidth > p) return "cone " + num(c) + " has expansion rows outside the image";
+        for (int t = 0; t < ci.pwidth; ++t) {
+            int& r = I.rowmem[(size_t)n + m + ci.pcol + t];
+            if (r >= 0) return "expansion row " + num(ci.pcol + t) + " belongs to two cones";
+            r = B.cone_mem[(size_t)c];
+        }
+    }
+    for (int i = n + m; i < N; ++i)
+        if (I.rowmem[(size_t)i] < 0) return "expansion row " + num(i - n - m) + " belongs to no cone";
+    // ---- the rows by member (a counting sort: stable, so ascending inside a member)
+    I.img_ptr.assign((size_t)nb + 1, 0);
+    for (int i = 0; i < N; ++i) ++I.img_ptr[(size_t)I.rowmem[(size_t)i] + 1];
+    for (int k = 0; k < nb; ++k) I.img_ptr[(size_t)k + 1] += I.img_ptr[(size_t)k];
+    I.img_rows.assign((size_t)N, 0);
+    {
+        std::vector<int> at(I.img_ptr.begin(), I.img_ptr.end() - 1);
+        for (int i = 0; i < N; ++i) I.img_rows[(size_t)at[(size_t)I.rowmem[(size_t)i]]++] = i;
+    }
+    // ---- workgroups
+    I.wg.wg_ptr.assign((size_t)nb + 1, 0);
+    for (int b = 0; b < nb; ++b) {
+        for (int64_t first = I.img_ptr[(size_t)b]; first < I.img_ptr[(size_t)b + 1]; first += chunk) {
+            I.wg.wg_mem.push_back(b);
+            I.wg.wg_first.push_back((int)first);
+        }
+        I.wg.wg_ptr[(size_t)b + 1] = (int)I.wg.wg_mem.size();
+    }
+    // ---- long rows by member
+    I.long_ptr.assign((size_t)nb + 1, 0);
+    I.long_order.assign((size_t)nlong, 0);
+    for (int t = 0; t < nlong; ++t) {
+        if (long_rows[t] < 0 || long_rows[t] >= N) return "long row " + num(t) + " lies outside the image";
+        ++I.long_ptr[(size_t)I.rowmem[(size_t)long_rows[t]] + 1];
+    }
+    for (int k = 0; k < nb; ++k) I.long_ptr[(size_t)k + 1] += I.long_ptr[(size_t)k];
+    {
+        std::vector<int> at(I.long_ptr.begin(), I.long_ptr.end() - 1);
+        for (int t = 0; t < nlong; ++t) I.long_order[(size_t)at[(size_t)I.rowmem[(size_t)long_rows[t]]]++] = t;
+    }
+    return "";
+}
+
 }  // namespace hipkkt

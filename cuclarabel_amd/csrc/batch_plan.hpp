@@ -50,4 +50,32 @@ BatchChunks plan_batch_chunks(int nb, const int* x_off, const int* z_off, int ch
 std::string plan_batch(int n, int m, int64_t nb, const int64_t* x_off, const int64_t* z_off, const BatchCone* cones, int ncones,
                        const int64_t* colptr, const int* rowval, const int* long_rows, int nlong, BatchPlan& out);
 
+// ---- the member refinement rule (hipkkt_kkt_system_set_member_refinement): the partition carried over to ALL N = n + m + p
+// rows of K's image, where the refinement's residual e = b - K x lives.  Member b's image rows are its x rows, its z rows
+// and the expansion rows n + m + pcol .. n + m + pcol + pwidth - 1 of its sparse second-order cones, which lie far from
+// its other rows; so the rows are listed by member (img_rows, ascending inside a member) and a workgroup walks a chunk of
+// that list:
+//   workgroups     workgroup w belongs to member wg.wg_mem[w] and takes the positions wg.wg_first[w] .. wg.wg_first[w] +
+//                  chunk - 1 of img_rows (cut at img_ptr[b + 1]; wg_first is a position in img_rows here, not a local
+//                  index); member b's workgroups are wg.wg_ptr[b] .. wg.wg_ptr[b + 1] - 1
+//   slots          member b folds the slots wg.wg_ptr[b] + b .. wg.wg_ptr[b + 1] + b: one per workgroup (workgroup w
+//                  writes slot w + wg_mem[w]) and, last, one for its long rows -- side by side, nwg + nb in all
+//   long rows      positions in the residual pass's list of long rows (all of the image this time), grouped by member
+struct BatchImageCone { int pcol, pwidth; };           // per cone, as in ConeInfo (pwidth 0: no expansion rows)
+
+struct BatchImagePlan {
+    int nb = 0, N = 0, chunk = 0;
+    std::vector<int> rowmem;               // N: row of the image -> member
+    std::vector<int> img_rows;             // N: the rows by member
+    std::vector<int> img_ptr;              // nb + 1
+    BatchChunks wg;
+    std::vector<int> long_order;           // positions in long_rows, grouped by member (ascending inside a member)
+    std::vector<int> long_ptr;             // nb + 1
+};
+
+// B: a plan of plan_batch for the same n, m.  cones: one entry per cone of B.cone_mem.  long_rows: nlong rows of the image
+// in [0, n + m + p), ascending.  chunk >= 1: rows per workgroup.  Returns "" and fills `out`, or the text of the refusal.
+std::string plan_batch_image(int n, int m, int p, const BatchPlan& B, const BatchImageCone* cones, int ncones, const int* long_rows,
+                             int nlong, int chunk, BatchImagePlan& out);
+
 }  // namespace hipkkt

@@ -1916,6 +1916,24 @@ struct hipkkt_kkt_s {
         B.long_order = bat_lorder.p; B.long_ptr = bat_lptr.p;
         return B;
     }
+    // hipkkt_kkt_system_set_member_refinement: the tables of plan_batch_image on the device, the slots and the members'
+    // state (kernels.hpp: MemberIrDev), all allocated when the rule is enabled.  mr_valid: a solve has run under it.
+    bool mr_on = false, mr_valid = false;
+    BatchPlan bat_plan;              // the partition on the host
+    std::vector<int> long_rows_h;    // the image's long rows on the host
+    int mr_nwg = 0, mr_chunk = 0;
+    DBuf<int> mr_wgmem, mr_wgfirst, mr_wgptr, mr_rows, mr_ptr, mr_lorder, mr_lptr;
+    DBuf<double> mr_slots, mr_state, mr_normb, mr_info;
+    DBuf<unsigned long long> mr_agg;
+    MemberIrDev member_dev() const
+    {
+        MemberIrDev M;
+        M.nb = bat_nb; M.N = K.N; M.chunk = mr_chunk; M.nwg = mr_nwg;
+        M.wg_mem = mr_wgmem.p; M.wg_first = mr_wgfirst.p; M.wg_ptr = mr_wgptr.p;
+        M.img_rows = mr_rows.p; M.img_ptr = mr_ptr.p; M.long_order = mr_lorder.p; M.long_ptr = mr_lptr.p;
+        M.slots = mr_slots.p; M.state = mr_state.p; M.normb = mr_normb.p; M.info = mr_info.p; M.agg = mr_agg.p;
+        return M;
+    }
     DBuf<double> hst;                // staging of the *_host entry points of level C: 3 x (n + 2 m) doubles (rhs, variables, lhs)
     bool host_vars_valid = false;    // hst holds the variables of the previous hipkkt_kkt_system_solve_host call
     // "the caller's host arrays may be reused": an event behind the uploads, waited for at the end of the call -- the
@@ -2463,6 +2481,7 @@ int hipkkt_kkt_create_ex2(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t
                     lptr.push_back((int64_t)cq.size() / 2);
                 }
                 h->nlong = (int)lrows.size();
+                h->long_rows_h = lrows;
                 h->nchunks = (int)(cq.size() / 2);
                 if (h->nlong) {
                     h->long_rows.upload(lrows);
@@ -2864,6 +2883,65 @@ static void kkt_enqueue_round(hipkkt_kkt_t h, int r, bool first, bool readback, 
     kkt_enqueue_refine_error(h, h->dx.p, kkt_ir_norms(h, nr).cand, nullptr, nr, true);  // e <- b - K (x + dx), its norm -> cand
     kkt_launch_ir(h, r, first, readback, fold, nr);
 }
+// The same loop with the rule applied per member of the partition (hipkkt_kkt_system_set_member_refinement; kernels.hpp:
+// MemberIrDev): sweeps and residual passes run once per round over the whole stack, as long as any member is active; the
+// protocol with the host -- r_spec rounds ahead, one 5-double record, the abort word and its repeat -- is the joint
+// path's, on the aggregate over the members.  The initial state has a launch of its own here (round 0), so that e is zero
+// on the rows of members that need no refinement before the first refinement sweep reads it.
+static int kkt_solve_core(hipkkt_kkt_t h, bool may_defer, int nr, int64_t* ir_out, bool force_defer);
+static void kkt_member_residual(hipkkt_kkt_t h, const MemberIrDev& M, const double* xi, bool first)
+{
+    const SpmvDev A = kkt_spmv(h);
+    int pr = h->prof.begin(3, h->stream);
+    launch_member_residual(A, h->Kval.p, M, h->b.p, xi, h->e.p, first, h->stream);
+    h->prof.end(pr, h->stream);
+}
+static void kkt_member_ir(hipkkt_kkt_t h, const MemberIrDev& M, int r)
+{
+    const hipkkt_settings& st = h->st;
+    launch_member_ir_round(M, r, h->eng->top_abort_word(), h->x.p, h->dx.p, h->e.p, st.iterative_refinement_abstol,
+                           st.iterative_refinement_reltol, st.iterative_refinement_stop_ratio,
+                           std::max(st.iterative_refinement_max_iter, 0), h->ir_readback, h->stream);
+}
+static void kkt_member_round(hipkkt_kkt_t h, const MemberIrDev& M, int r)
+{
+    kkt_trisolve(h, h->e.p, h->dx.p, true, 1);                                    // dx = K^{-1} e (zero on inactive members' rows)
+    launch_axpby_sum(h->dx.p, h->dx.p, h->x.p, (int64_t)h->K.N, h->stream);       // prospective solution x + dx
+    kkt_member_residual(h, M, h->dx.p, false);                                    // e <- b - K (x + dx), the members' norms
+    kkt_member_ir(h, M, r);
+}
+static int kkt_solve_core_members(hipkkt_kkt_t h, int64_t* ir_out)
+{
+    const MemberIrDev M = h->member_dev();
+    const int max_iter = std::max(h->st.iterative_refinement_max_iter, 0);
+    int R = std::min(max_iter, std::max(h->r_spec, 0));
+    h->mr_valid = false;
+    kkt_trisolve(h, h->b.p, h->x.p, true, 1);
+    kkt_member_residual(h, M, h->x.p, true);
+    kkt_member_ir(h, M, 0);
+    for (int r = 1; r <= R; ++r) kkt_member_round(h, M, r);
+    for (;;) {
+        HIP_CHECK(hipMemcpyAsync(h->pin->h + 16, h->ir_readback, 5 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        const double* rb = h->pin->h + 16;
+        if (rb[4] != 0.0 && h->eng->top_abort_word() != nullptr) {      // never expected; see TopOwner
+            h->eng->top_gave_up();                                      // the per-level path from now on: repeat the solve
+            return kkt_solve_core(h, false, 1, ir_out, false);
+        }
+        const int64_t most = (int64_t)rb[1];
+        h->last_ir = most;
+        if (ir_out) ir_out[0] = most;
+        h->mr_valid = true;
+        if (rb[0] == 0.0 || R >= max_iter) break;
+        ++R;                                                            // some member's loop goes on: one more round
+        kkt_member_round(h, M, R);
+    }
+    h->prof.acc.ir_iterations += h->last_ir;
+    // (a bad member does not end the others' loops: they finish first, then the solve as a whole fails)
+    if (h->pin->h[16 + 2] != 0.0) return HIPKKT_NUMERIC_FAILURE;
+    h->r_spec = (int)std::min<int64_t>(h->last_ir, max_iter);
+    return HIPKKT_OK;
+}
 // nr = 1, 2 or 4 right-hand sides (columns of h->b, N apart) share every sweep; each column goes through the
 // reference's loop on its own.  ir_out (nullable, nr entries): rounds per column (-1 in deferred mode).
 static int kkt_solve_core(hipkkt_kkt_t h, bool may_defer = false, int nr = 1, int64_t* ir_out = nullptr, bool force_defer = false)
@@ -2874,6 +2952,7 @@ static int kkt_solve_core(hipkkt_kkt_t h, bool may_defer = false, int nr = 1, in
     h->cur_dx = h->dx.p;
     h->last_ir = 0;
     if (ir_out) for (int c = 0; c < nr; ++c) ir_out[c] = deferred ? -1 : 0;
+    if (h->mr_on && h->bat_nb > 0 && nr == 1 && !deferred && st.iterative_refinement_enable) return kkt_solve_core_members(h, ir_out);
     if (!st.iterative_refinement_enable) {
         kkt_trisolve(h, h->b.p, h->x.p, false, nr);   // nothing reads the abort word back on this path
         int bad = 0;
@@ -3567,7 +3646,8 @@ static int sys_solve_step(hipkkt_kkt_t h, double* d_lhs_x, double* d_lhs_s, doub
     if (h->deferred) throw ArgError("hipkkt_kkt_system_*: level C reads its scalars back (deferred status is for level B)");
     HIP_CHECK(hipSetDevice(h->device));
     hipStream_t st = h->stream;
-    const bool pair = h->sys_const_pending && affine && h->eng->supports_nr(2);
+    // (under the member refinement rule the pairing is not taken: the rule covers single-column solves)
+    const bool pair = h->sys_const_pending && affine && h->eng->supports_nr(2) && !h->mr_on;
     if (h->sys_const_pending && !pair) {
         // (x2, z2) is due and cannot ride with this solve: by itself first, as kkt_update! would have done it
         h->sys_const_pending = false;
@@ -3605,7 +3685,7 @@ static int sys_solve_step(hipkkt_kkt_t h, double* d_lhs_x, double* d_lhs_s, doub
                         (defer && h->publish_ok) ? Publish{h->pin->h + 40, h->ir_sticky, 10, 8, (double)++h->publish_seq} : Publish{});
         return HIPKKT_OK;
     };
-    if (h->sys_lazy && h->st.iterative_refinement_enable) {
+    if (h->sys_lazy && h->st.iterative_refinement_enable && !h->mr_on) {
         // Lazy mode: ONE read-back per call -- the sticky status record (this call's solve, and the kkt_update! before it
         // if that was enqueued only) together with (dtau, dkappa).  If the record says that the reference's refinement loop
         // would have gone on, or that a bounded wait gave up, the call is repeated with the synchronous sequence.
@@ -4002,6 +4082,7 @@ int hipkkt_kkt_system_set_problems(hipkkt_kkt_t h, int64_t nb, const int64_t* x_
         HIP_CHECK(hipSetDevice(h->device));
         if (nb == 0) {                                   // (the tables stay allocated until the next partition or the handle's end)
             h->bat_nb = 0;
+            h->mr_on = h->mr_valid = false;             // (the member refinement rule goes with its partition)
             return HIPKKT_OK;
         }
         if (nb < 0) throw ArgError("hipkkt_kkt_system_set_problems: the number of members is negative");
@@ -4019,6 +4100,7 @@ int hipkkt_kkt_system_set_problems(hipkkt_kkt_t h, int64_t nb, const int64_t* x_
         if (!err.empty()) throw ArgError("hipkkt_kkt_system_set_problems: " + err);
         HIP_CHECK(hipStreamSynchronize(h->stream));      // (nothing in flight reads the tables that are replaced now)
         h->bat_nb = 0;
+        h->mr_on = h->mr_valid = false;
         h->bat_xoff.upload(P.x_off); h->bat_zoff.upload(P.z_off); h->bat_xmem.upload(P.xmem); h->bat_zmem.upload(P.zmem);
         h->bat_cmem.upload(P.cone_mem); h->bat_socptr.upload(P.soc_ptr); h->bat_psdptr.upload(P.psd_ptr);
         h->bat_degree.upload(P.degree);
@@ -4038,6 +4120,66 @@ int hipkkt_kkt_system_set_problems(hipkkt_kkt_t h, int64_t nb, const int64_t* x_
         HIP_CHECK(hipHostMalloc((void**)&h->bat_pin, 16 * k * sizeof(double)));
         if (!h->bat_ev) HIP_CHECK(hipEventCreateWithFlags(&h->bat_ev, hipEventDisableTiming));
         h->bat_nb = P.nb;
+        h->bat_plan = std::move(P);              // (kept for hipkkt_kkt_system_set_member_refinement)
+        return HIPKKT_OK;
+    });
+}
+
+// The refinement rule per member (kktsolver_directldl.jl:389-449 on each member's rows of K's image): plans the image's
+// rows by member on the host (batch_plan.hpp: plan_batch_image), uploads the tables and allocates slots and state.
+int hipkkt_kkt_system_set_member_refinement(hipkkt_kkt_t h, int enable)
+{
+    return guarded([&]() {
+        if (!h) throw ArgError("null handle");
+        if (!h->sys_ready) throw ArgError("hipkkt_kkt_system_*: call hipkkt_kkt_system_init first");
+        if (h->bat_nb <= 0)
+            throw ArgError("hipkkt_kkt_system_set_member_refinement: the handle has no partition (hipkkt_kkt_system_set_problems)");
+        HIP_CHECK(hipSetDevice(h->device));
+        HIP_CHECK(hipStreamSynchronize(h->stream));      // (nothing in flight reads the tables that are replaced now)
+        h->mr_on = h->mr_valid = false;
+        if (!enable) return HIPKKT_OK;
+        if (h->bat_nb >= (1 << 20)) throw ArgError("hipkkt_kkt_system_set_member_refinement: at most 2^20 - 1 members");
+        std::vector<BatchImageCone> cones;
+        for (const ConeInfo& ci : h->K.cones) cones.push_back(BatchImageCone{ci.pcol, ci.pwidth});
+        // rows per workgroup: whole passes of the residual kernel's rows per block, few enough workgroups that a member's
+        // slots are folded cheaply (at most kNormParts + nb in all, as the whole-handle pass has kNormParts)
+        const int rpb = 256 / h->lanes_per_row;
+        const int passes = (int)(((int64_t)h->K.N + (int64_t)rpb * kNormParts - 1) / ((int64_t)rpb * kNormParts));
+        const int chunk = rpb * std::max(passes, 1);
+        BatchImagePlan I;
+        const std::string err = plan_batch_image(h->K.n, h->K.m, h->K.p, h->bat_plan, cones.data(), (int)cones.size(),
+                                                 h->long_rows_h.data(), (int)h->long_rows_h.size(), chunk, I);
+        if (!err.empty()) throw ArgError("hipkkt_kkt_system_set_member_refinement: " + err);
+        h->mr_wgmem.upload(I.wg.wg_mem); h->mr_wgfirst.upload(I.wg.wg_first); h->mr_wgptr.upload(I.wg.wg_ptr);
+        h->mr_rows.upload(I.img_rows); h->mr_ptr.upload(I.img_ptr);
+        h->mr_lorder.upload(I.long_order); h->mr_lptr.upload(I.long_ptr);
+        h->mr_nwg = (int)I.wg.wg_mem.size();
+        h->mr_chunk = chunk;
+        const size_t nb = (size_t)h->bat_nb, S = (size_t)h->mr_nwg + nb;
+        const size_t rounds = (size_t)std::max(h->st.iterative_refinement_max_iter, 0) + 1;
+        h->mr_slots.alloc(3 * S); h->mr_state.alloc(4 * nb * rounds); h->mr_normb.alloc(nb); h->mr_info.alloc(4 * nb);
+        h->mr_agg.alloc(2);
+        // (the long rows' slots stay zero when the image has none; the counters are zero between kernels)
+        h->mr_slots.zero(h->stream); h->mr_state.zero(h->stream); h->mr_normb.zero(h->stream); h->mr_info.zero(h->stream);
+        h->mr_agg.zero(h->stream);
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        h->mr_on = true;
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_member_refinement_info(hipkkt_kkt_t h, double* out)
+{
+    return guarded([&]() {
+        if (!h || !out) throw ArgError("hipkkt_kkt_system_member_refinement_info: bad argument");
+        if (!h->mr_on || h->bat_nb <= 0) throw ArgError("hipkkt_kkt_system_member_refinement_info: member refinement is not enabled");
+        if (!h->mr_valid) throw ArgError("hipkkt_kkt_system_member_refinement_info: no solve has run under the member rule yet");
+        HIP_CHECK(hipSetDevice(h->device));
+        const size_t count = 4 * (size_t)h->bat_nb;
+        double* stage = h->bat_pin + 4 * (size_t)h->bat_nb;
+        HIP_CHECK(hipMemcpyAsync(stage, h->mr_info.p, count * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        std::memcpy(out, stage, count * sizeof(double));
         return HIPKKT_OK;
     });
 }

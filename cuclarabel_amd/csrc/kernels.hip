@@ -2,6 +2,7 @@
 #include "kernels.hpp"
 #include "knobs.hpp"
 #include "nonsym_cone.hpp"
+#include "refine_device.hpp"
 #include <algorithm>
 
 #include <cmath>
@@ -157,19 +158,7 @@ __global__ __launch_bounds__(256) void k_residual(SpmvDev A, const double* __res
         const int64_t q0 = A.ptr[row], q1 = A.ptr[row + 1];
         if (q1 - q0 > kLongRow) continue;               // handled by k_residual_long_*
         double acc[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) acc[c] = 0.0;
-        for (int64_t q = q0 + sub; q < q1; q += G) {
-            const double a = A.val ? A.val[q] : K[A.vmap[q]];
-            const int j = A.col[q];
-#pragma unroll
-            for (int c = 0; c < NC; ++c) acc[c] = fma(a, x[c * ld + j], acc[c]);
-        }
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-#pragma unroll
-            for (int o = G / 2; o > 0; o >>= 1) acc[c] += __shfl_down(acc[c], o, G);
-        }
+        residual_row_dot<G, NC>(A, K, x, ld, q0, q1, sub, acc);
         if (sub == 0) {
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
@@ -238,6 +227,10 @@ __global__ __launch_bounds__(256) void k_residual_long_finish(SpmvDev A, const d
     if (bad) vmax = INFINITY;
     vmax = block_max_256(vmax, sh);
     if (threadIdx.x == 0) partial[blockIdx.y * (gmain + 1) + gmain] = vmax;
+}
+void launch_residual_long_chunks(const SpmvDev& A, const double* K, const double* x, hipStream_t st)
+{
+    if (A.nlong > 0) hipLaunchKernelGGL(k_residual_long_chunks, dim3(A.nchunks, 1), dim3(256), 0, st, A, K, x, (int64_t)0);
 }
 __global__ void k_finish_norm(const double* __restrict__ partial, int nparts, double* __restrict__ out,
                               const int* __restrict__ flag_in = nullptr, double* __restrict__ flag_out = nullptr,
@@ -454,14 +447,7 @@ void launch_collect_status(double* dst, const double* eps, const int* conefail, 
 // and its residual norm scal[4]; this kernel applies the reference's accept / stop rule to it and, if the candidate is
 // accepted, makes it the solution (x <- dx; e already holds its residual).  Every thread evaluates the rule from the
 // same read-only words; thread 0 of workgroup 0 publishes the new state.  r == 0: only the initial state.
-__device__ inline void ir_initial(double norme0, double normb, double abstol, double reltol, int max_iter,
-                                  double& active, double& rounds, double& bad, double& norme)
-{
-    norme = norme0;
-    bad = isfinite(norme) ? 0.0 : 1.0;
-    rounds = 0.0;
-    active = (bad == 0.0 && max_iter > 0 && !(norme <= abstol + reltol * normb)) ? 1.0 : 0.0;
-}
+// (ir_initial, ir_apply_rule: refine_device.hpp)
 // grid.y = right-hand side column c: its state at state + c * state_stride, norms norme0[c], normb[c], cand[c], vectors
 // x + c * ld, dx + c * ld, read-back record at readback + 5 c.  The sticky record is folded by column 0 only when
 // there is a single column (several columns: k_ir_fold).
@@ -528,20 +514,7 @@ __global__ __launch_bounds__(256) void k_ir_round(double* __restrict__ state, in
     }
     if (r > 0) cand_v = Q.cand ? mx[2] : cand_norm[c];
     bool accept = false;
-    if (r > 0 && active != 0.0) {
-        const double cand = cand_v;
-        rounds += 1.0;
-        if (!isfinite(cand)) {                      // :429: return is_success = false
-            bad = 1.0; active = 0.0;
-        } else {
-            const double ratio = norme / cand;      // :437-446
-            if (ratio < stop_ratio) { accept = ratio > 1.0; active = 0.0; }
-            else accept = true;
-            if (accept) norme = cand;
-            // the head of the next iteration (:407-417): tolerance met, or max_iter rounds done
-            if (active != 0.0 && (r >= max_iter || norme <= abstol + reltol * nb)) active = 0.0;
-        }
-    }
+    if (r > 0 && active != 0.0) accept = ir_apply_rule(cand_v, r, max_iter, abstol, reltol, stop_ratio, nb, active, rounds, bad, norme);
     if (accept) {
         const int stride = gridDim.x * blockDim.x;
         for (int i0 = blockIdx.x * blockDim.x + threadIdx.x; i0 < n; i0 += 4 * stride) {       // (four loads in flight)

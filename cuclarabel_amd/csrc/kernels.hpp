@@ -678,6 +678,36 @@ void launch_batch_sys_step(const SpmvDev& A, const double* Kval, const BatchDev&
                            const double* scal, double* pa, double* pb, double* pc, double* xm, double* partial, double* dtau,
                            double* out, double* dx, double* dz, int n, int m, hipStream_t st);
 
+// ---- the refinement rule per member (hipkkt_kkt_system_set_member_refinement; kktsolver_directldl.jl:389-449 applied to
+// each member's rows of K's image).  The tables are those of batch_plan.hpp's BatchImagePlan on the device.
+//   slots   3 arrays of nwg + nb partial maxima: ||e0||, ||b|| (first residual of a solve) and the candidate's ||e||;
+//           workgroup w writes slot w + wg_mem[w], member b's long rows slot wg_ptr[b + 1] + b, so that member b folds
+//           the adjacent slots wg_ptr[b] + b .. wg_ptr[b + 1] + b
+//   state   slot r (4 nb doubles) after round r: member b's {active, rounds, bad, norme} at 4 b; normb: nb
+//   info    4 nb: {rounds, norme, normb, bad} of the last round kernel, for ONE copy to the host
+//   agg     two 64-bit words, zero between kernels: the members' leading workgroups count themselves in with agent-scope
+//           integer atomics, the last one writes the aggregate (batch_kernels.hip: k_member_ir_round)
+struct MemberIrDev {
+    int nb, N, chunk, nwg;
+    const int *wg_mem, *wg_first, *wg_ptr;
+    const int *img_rows, *img_ptr;
+    const int *long_order, *long_ptr;
+    double *slots, *state, *normb, *info;
+    unsigned long long* agg;
+};
+// e = b - K x, every row by residual_row_dot as in launch_residual (one column), and the members' partial maxima: into the
+// ||e0|| and ||b|| slots (first) or the candidate's.  Two launches more when the image has long rows.
+void launch_member_residual(const SpmvDev& A, const double* Kval, const MemberIrDev& M, const double* b, const double* x, double* e,
+                            bool first, hipStream_t st);
+// Round r per member: r == 0 the initial state from the first residual's slots; r >= 1 the accept / stop rule on the
+// candidate dx (x <- dx on the rows of accepting members).  Then e = 0 on the rows of members that are not active, the
+// members' state and info, and the aggregate {any active, most rounds, any bad, largest norme, abort} in readback.
+// ONE launch whatever nb.  flag_in (nullable): the sweeps' abort word.
+void launch_member_ir_round(const MemberIrDev& M, int r, const int* flag_in, double* x, const double* dx, double* e, double abstol,
+                            double reltol, double stop_ratio, int max_iter, double* readback, hipStream_t st);
+// the long rows' chunk sums of launch_residual alone (one column), for the member pass's own finish
+void launch_residual_long_chunks(const SpmvDev& A, const double* Kval, const double* x, hipStream_t st);
+
 
 // ---- Ruiz equilibration of (P, A, q, b) (problemdata.jl:133-221, mathutils.jl:129-269), all vectors on the device
 struct EquilDev {

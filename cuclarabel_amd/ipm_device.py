@@ -161,17 +161,31 @@ def solve_device_batch(problems, settings=None, inspect=None):
     need not).
 
     inspect (optional): called once per iteration with (dict of the tensors the loop holds, the HipSystemBackend)."""
+    return _solve_batch("solve_device_batch", problems, settings, inspect, False)
+
+
+def solve_device_batch_refined(problems, settings=None, inspect=None):
+    """solve_device_batch with the refinement's accept / stop rule applied per member
+    (hipkkt_kkt_system_set_member_refinement): the loop, the freeze of finished members included, is the same; inside
+    every solve each member is refined by the reference's rule on its own rows, so that a member whose rows cannot be
+    refined further no longer ends the refinement of the others.  What stays joint: the status of kkt_update! and of a
+    solve, and the static regulariser.  `kkt_ir_rounds` of every result is that member's own total over the loop's
+    solves."""
+    return _solve_batch("solve_device_batch_refined", problems, settings, inspect, True)
+
+
+def _solve_batch(who, problems, settings, inspect, member_refinement):
+    """The loop of solve_device_batch and solve_device_batch_refined."""
     import torch
     problems = list(problems)
     if not problems:
-        raise ValueError("solve_device_batch needs at least one problem")
+        raise ValueError(f"{who} needs at least one problem")
     members = []
     for (P, q, A, b, cone_specs) in problems:
-        cone_specs = _check_cones("solve_device_batch", cone_specs, _SYMMETRIC,
-                                  "solve_device_batch covers the symmetric cones only (zero, nonnegative, second-order, PSD); "
-                                  "got {}")
+        cone_specs = _check_cones(who, cone_specs, _SYMMETRIC,
+                                  who + " covers the symmetric cones only (zero, nonnegative, second-order, PSD); got {}")
         if any(isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE for c in cone_specs):
-            raise ValueError(f"solve_device_batch covers PSD cones up to side {PSD_MAX_SIDE}")
+            raise ValueError(f"{who} covers PSD cones up to side {PSD_MAX_SIDE}")
         Pt = sp.triu(sp.csc_matrix(P), format="csc")
         members.append((Pt, np.asarray(q, float), sp.csc_matrix(A), np.asarray(b, float), cone_specs))
     st = settings or IPMSettings()
@@ -209,6 +223,9 @@ def solve_device_batch(problems, settings=None, inspect=None):
     aff_x, aff_z = new(n), new(m)                        # the affine right-hand side with the frozen members' rows zeroed
     system.init(q, b)
     system.set_problems(blocks)
+    if member_refinement:
+        system.set_member_refinement(True)
+    ir_member = np.zeros(nb, dtype=np.int64)             # (member rule: every member's own rounds)
     backend.update_identity()
     system.solve_constant_rhs()
     system.solve_initial_point_dev(p(x), p(s), p(z))
@@ -321,6 +338,8 @@ def solve_device_batch(problems, settings=None, inspect=None):
                 ok, dtau, dkappa = system.solve_batch_dev((p(dx), p(ds), p(dz)), (p(arx), p(aff_s), p(arz)), rtau, tau * kappa,
                                                           (p(x), p(s), p(z)), tau, kappa, True)
                 ir_total += backend.last_ir_iterations
+                if member_refinement:
+                    ir_member += system.member_refinement_info()[:, 0].astype(np.int64)
             if ok:
                 # ---- combined step (solver.jl:297-323)
                 alpha = system.step_length_batch_dev(p(dz), p(ds), p(z), p(s), dtau, dkappa, tau, kappa)
@@ -334,6 +353,8 @@ def solve_device_batch(problems, settings=None, inspect=None):
                                                           -sigma * mu + mcorr * dtau * dkappa + tau * kappa,
                                                           (p(x), p(s), p(z)), tau, kappa, False)
                 ir_total += backend.last_ir_iterations
+                if member_refinement:
+                    ir_member += system.member_refinement_info()[:, 0].astype(np.int64)
             if not ok:
                 alpha = np.zeros(nb)
                 for k in active:
@@ -382,7 +403,8 @@ def solve_device_batch(problems, settings=None, inspect=None):
         objp, objd = qk @ xo + quad, -bk @ zo - quad
         if infeasible:
             objp = objd = float("nan")
-        out.append(IPMResult(status[k], xo, zo, so, objp, objd, iterations[k], ir_total, hist[k]))
+        out.append(IPMResult(status[k], xo, zo, so, objp, objd, iterations[k], int(ir_member[k]) if member_refinement else ir_total,
+                             hist[k]))
     return out
 
 

@@ -501,6 +501,21 @@ class HipKKTSystem:
               "hipkkt_kkt_system_set_problems")
         self.nb = len(blocks)
 
+    def set_member_refinement(self, enable):
+        """The refinement's accept / stop rule per member of the partition instead of over the stack, for every
+        single-column solve of the handle.  Replacing or clearing the partition switches it off again.  Raises
+        HipKKTError on a handle without a partition."""
+        check(_lib.lib().hipkkt_kkt_system_set_member_refinement(self.ks._h, 1 if enable else 0),
+              "hipkkt_kkt_system_set_member_refinement")
+
+    def member_refinement_info(self):
+        """numpy array (nb, 4) of the last solve under the member rule: row b = (member b's rounds, ||e_b||_inf of its
+        accepted solution, ||b_b||_inf, 1.0 if one of its norms was not finite)."""
+        out = np.zeros((max(self.nb, 1), 4))
+        check(_lib.lib().hipkkt_kkt_system_member_refinement_info(self.ks._h, ptr(out)),
+              "hipkkt_kkt_system_member_refinement_info")
+        return out[:self.nb]
+
     def _scalars(self, *arrays):
         """The members' scalars as contiguous float64 arrays of length nb (a Python float is not broadcast: one value per
         member is the point of these calls)."""

@@ -529,7 +529,9 @@ int hipkkt_kkt_system_add_step(hipkkt_kkt_t h, double *d_x, double *d_s, double 
  * What stays JOINT on a partitioned handle, because the factorisation is one: the status of hipkkt_kkt_system_update and
  * of the solves (a failed kkt_update!, kktsystem.jl:62-78, fails for every member); the static regulariser's epsilon,
  * scaled by the largest diagonal entry of the whole K (kktsolver_directldl.jl:297-310); and the iterative refinement's
- * stopping rule, whose infinity-norms run over the stack (kktsolver_directldl.jl:389-470).  hipkkt_kkt_system_update,
+ * stopping rule, whose infinity-norms run over the stack (kktsolver_directldl.jl:389-470) -- the refinement rule is joint
+ * unless hipkkt_kkt_system_set_member_refinement (below) has been enabled; the status of a solve stays joint even then.
+ * hipkkt_kkt_system_update,
  * _solve_constant_rhs, _solve_initial_point and _affine_ds have no scalar argument and serve a partitioned handle as
  * they are: the block-diagonal K does their work per member.  No scalar entry point changes its behaviour on a
  * partitioned handle. */
@@ -546,6 +548,35 @@ int hipkkt_kkt_system_add_step(hipkkt_kkt_t h, double *d_x, double *d_s, double 
  * tables (row -> member, cone -> member, workgroup -> (member, chunk)) and all work space are sized by nb; nb is bounded
  * by n only.  Synchronises with the handle's stream once (tables in use are replaced); enqueues no kernel. */
 int hipkkt_kkt_system_set_problems(hipkkt_kkt_t h, int64_t nb, const int64_t *x_off, const int64_t *z_off);
+
+/* The iterative refinement's accept / stop rule (kktsolver_directldl.jl:389-449) per member instead of over the stack.
+ * enable != 0: from now on every single-column solve of this handle -- hipkkt_kkt_solve, hipkkt_kkt_solve_dev,
+ * hipkkt_kkt_system_solve_constant_rhs, _solve_initial_point, _solve_batch and a scalar hipkkt_kkt_system_solve --
+ * applies the reference's loop to each member separately: member b's norms are ||e_b||_inf and ||b_b||_inf over ITS rows
+ * of K's image (its x rows, its z rows and the expansion rows behind n + m of its sparse second-order cones), its
+ * tolerance is abstol + reltol ||b_b||_inf, and it has its own ratio test, accept decision, round count and bad flag.
+ * Sweeps and residual passes still run once per round over the whole stack, as long as any member is active; a member
+ * that has left its loop is not written again (x keeps its accepted solution, and its rows of the residual are zero for
+ * the following sweeps, so that its rows of every later candidate equal x).  A non-finite norm marks that member alone
+ * as bad; the other members finish their loops, then the solve returns HIPKKT_NUMERIC_FAILURE: the status stays joint.
+ * The protocol with the host is the joint rule's on the aggregate over the members (active: any member; rounds, as
+ * hipkkt_kkt_last_ir_iterations and hipkkt_info report them and hipkkt_kkt_speculative_rounds enqueues them ahead: the
+ * most any member took; bad: any member).  With nb = 1 a solve is bit for bit the joint rule's.  While enabled the lazy
+ * 2-column pairing of hipkkt_kkt_system_solve is not taken -- a pending constant-RHS solve runs by itself first, as
+ * hipkkt_kkt_system_solve_batch does it --, and hipkkt_kkt_solve_multi(_dev) with two or more columns keeps its joint
+ * rule per column.  The deferred-status mode never meets this path: hipkkt_kkt_system_set_problems refuses a
+ * deferred-status handle.  enable == 0 switches back to the joint rule; so does replacing or clearing the partition.
+ * HIPKKT_ERR_ARG on a handle without a partition, and for 2^20 members or more (the aggregate counts the members in
+ * 21-bit fields of one word).  Two launches per round (residual, rule) whatever nb, no
+ * floating-point atomic; tables, slots and state are sized by nb and iterative_refinement_max_iter and allocated HERE,
+ * not in a solve.  Synchronises with the handle's stream (tables in use are replaced). */
+int hipkkt_kkt_system_set_member_refinement(hipkkt_kkt_t h, int enable);
+
+/* What the last solve under the member rule did (kktsolver_directldl.jl:389-449, per member): out (host, 4 nb) receives
+ * for member b at out[4 b ..] {its refinement rounds, ||e_b||_inf of its accepted solution, ||b_b||_inf, 1 if a norm of
+ * its was not finite else 0}.  HIPKKT_ERR_ARG if member refinement is not enabled or no solve has run under it since it
+ * was enabled.  Synchronises: one read-back of 4 nb doubles, no kernel. */
+int hipkkt_kkt_system_member_refinement_info(hipkkt_kkt_t h, double *out);
 
 /* Rules for the seven _batch calls: on a handle without a partition, on a deferred-status handle and with a NULL scalar
  * array each returns HIPKKT_ERR_ARG and enqueues nothing; the aliasing rules are the twin's. */

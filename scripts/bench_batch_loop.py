@@ -7,7 +7,9 @@
 
 Both loops do the same vector work per iteration (one update, two solves, the same elementwise and cone kernels), so
 their per-iteration times are comparable; the iteration COUNTS are not the same thing (the stacked loop ends with one
-status).  One JSON line per run.  --root: the tree whose cuclarabel_amd is imported (another build of the library for an
+status).  --member-refinement (mode batch): ipm_device.solve_device_batch_refined, the refinement's accept / stop rule per
+member; `refinement_rounds` is the handle's total of refinement rounds (sweep pairs behind the first solve) either way,
+`refinement_rounds_per_member` each member's own total under the member rule.  One JSON line per run.  --root: the tree whose cuclarabel_amd is imported (another build of the library for an
 A/B comparison in one session: run this script with the other tree's root and --mode stacked).
 
     python scripts/bench_batch_loop.py --mode batch --members 64 --n 10000 --runs 3
@@ -25,8 +27,11 @@ def main():
     ap.add_argument("--members", type=int, default=64)
     ap.add_argument("--n", type=int, default=10_000)
     ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--member-refinement", action="store_true")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     args = ap.parse_args()
+    if args.member_refinement and args.mode != "batch":
+        ap.error("--member-refinement goes with --mode batch")
     sys.path.insert(0, args.root)
     import torch
     from cuclarabel_amd import ipm_device, problems
@@ -34,14 +39,20 @@ def main():
     pbs = [problems.config4(j, n=args.n) for j in range(args.members)]
     # the loops call `inspect` once per iteration, right behind the residual call's read-back: the time between the first
     # and the last call is the loop's own, without the handle's set-up (symbolic analysis) and the final copy
-    stamps = []
-    stamp = lambda tensors, backend: stamps.append(time.perf_counter())
+    stamps, seen = [], {}
+
+    def stamp(tensors, backend):
+        stamps.append(time.perf_counter())
+        seen["ks"] = backend.ks
     if args.mode == "batch":
         data = [(pb.P, pb.q, pb.A, pb.b, pb.cones) for pb in pbs]
-        run = lambda: ipm_device.solve_device_batch(data, inspect=stamp)
+        loop = ipm_device.solve_device_batch_refined if args.member_refinement else ipm_device.solve_device_batch
+        run = lambda: loop(data, inspect=stamp)
         iters = lambda res: max(r.iterations for r in res)
         extra = lambda res: dict(iterations_per_member=[r.iterations for r in res],
-                                 statuses=sorted(set(r.status for r in res)))
+                                 statuses=sorted(set(r.status for r in res)), member_refinement=bool(args.member_refinement),
+                                 refinement_rounds=int(seen["ks"].profile()["ir_iterations"]),
+                                 **(dict(refinement_rounds_per_member=[r.kkt_ir_rounds for r in res]) if args.member_refinement else {}))
     elif args.mode == "stacked":
         st = problems.block_diagonal(pbs)
         run = lambda: ipm_device.solve_device(st.P, st.q, st.A, st.b, st.cones, inspect=stamp, plumbing="device")
