@@ -2,6 +2,7 @@
 #include "kernels.hpp"
 #include "knobs.hpp"
 #include "nonsym_cone.hpp"
+#include "psd_cone.hpp"
 #include "refine_device.hpp"
 #include <algorithm>
 
@@ -980,415 +981,125 @@ __global__ __launch_bounds__(256) void k_cone_scaling_ns(ConeDev C, ConeState S,
 }
 
 // -------------------------------------------------------------------------------------
-//  PSD cones (coneops_psdtrianglecone.jl:78-161): one workgroup per cone, everything in LDS.
+//  PSD cones (coneops_psdtrianglecone.jl:78-161): one workgroup per cone, from the blocks of psd_cone.hpp.
 //    S, Z from svec;  L1 = chol(S), L2 = chol(Z)  (failure => not interior);
 //    SVD of M = L2' L1 = U Lam V'  -- as the reference does (:118-121), NOT an eigen-decomposition of
 //    L1' Z L1 = M'M, whose eigenvalues are the squares of the singular values: forming it squares the condition
 //    number, and on late interior-point iterates (S, Z nearly complementary) the small singular values drop below
-//    eps ||M'M||.  The SVD is a one-sided (Hestenes) Jacobi on the columns of M, which computes every singular
-//    value to high RELATIVE accuracy; rotations in the round-robin order (a sweep is m - 1 steps of m/2 rotations
-//    on disjoint column pairs, eight lanes per pair, one barrier per step).
+//    eps ||M'M||.  The SVD is psd_onesided_jacobi on the columns of M.
 //    lam = singular values sorted descending (LAPACK's order, dense_algebra.jl:219);
 //    R = L1 V Lam^{-1/2}, Rinv = Lam^{-1/2} U' L2' (:127-132); A = R R' (:135-141);
-//    Hs = A (x)_s A (skron!, :502-540) written straight into its packed upper triangle by a flat map over the
-//    t(t+1)/2 entries, t = k(k+1)/2.
+//    Hs = A (x)_s A (skron!, :502-540) written straight into its packed upper triangle.
+//  The two classes (psd_cone.hpp: PsdSmall, PsdBig):
+//    small  six k x k matrices in LDS (S -> L1, Z -> L2, M, V, R, A); Hs by the same workgroup, a flat map over the
+//           t(t+1)/2 entries, t = k(k+1)/2.
+//    big    two matrices in LDS: first S and Z for the two Cholesky factorisations, then the pair (M, V) that the
+//           Jacobi rotates.  L1, L2 and the product M = L2' L1 go through the cone's slice of C.psd_work, R and A
+//           through S.psdR / S.psdA themselves; a slice is read only by the workgroup that wrote it, behind a workgroup
+//           barrier.  512 threads = 64 groups of eight lanes, enough for the 48 column pairs of side 96.  Hs is formed
+//           by a launch of its own, k_psd_hs_big.
 // -------------------------------------------------------------------------------------
-__device__ inline void svec_index(int idx, int& row, int& col)     // idx = col(col+1)/2 + row, row <= col
+// Hs = A (x)_s A of one cone by its 256-thread workgroup, A in LDS: packed upper triangle (column-major over (row, col)
+// with row <= col), a flat map over the entries
+__device__ inline void psd_hs_flat(double* __restrict__ Hs, const double* Am, int k)
 {
-    int c = (int)((sqrt(8.0 * (double)idx + 1.0) - 1.0) * 0.5);
-    while (c * (c + 1) / 2 > idx) --c;
-    while ((c + 1) * (c + 2) / 2 <= idx) ++c;
-    col = c;
-    row = idx - c * (c + 1) / 2;
-}
-
-__global__ __launch_bounds__(256) void k_cone_psd(ConeDev C, ConeState S, const double* __restrict__ s,
-                                                  const double* __restrict__ z)
-{
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    __shared__ int sh_fail;
-    __shared__ double sh_off[32], sh_sv[kPsdMaxDim];
-    __shared__ int sh_rank[kPsdMaxDim];
-    const int tid = threadIdx.x;
-    const int c = C.psd_list[blockIdx.x];
-    const int k = C.psd_dim[c], off = C.off[c];
-    const int kk = k * k, t = k * (k + 1) / 2;
-    double* Sm = smem;            // S -> L1 (lower)
-    double* Zm = smem + kk;       // Z -> L2 (lower)
-    double* M = smem + 2 * kk;    // L2' L1 -> U diag(sv) -> U
-    double* V = smem + 3 * kk;    // right singular vectors
-    double* Tm = smem + 4 * kk;   // R
-    double* Am = smem + 5 * kk;   // A = R R'
-    const double is2 = 0.70710678118654752440;
-    if (tid == 0) sh_fail = 0;
-    for (int idx = tid; idx < t; idx += 256) {
-        int r, cl;
-        svec_index(idx, r, cl);
-        const double sv = s[off + idx], zv = z[off + idx];
-        if (r == cl) { Sm[r + cl * k] = sv; Zm[r + cl * k] = zv; }
-        else {
-            Sm[r + cl * k] = Sm[cl + r * k] = sv * is2;
-            Zm[r + cl * k] = Zm[cl + r * k] = zv * is2;
-        }
-    }
-    __syncthreads();
-    // Cholesky of S and of Z, in place, right-looking (:97-104)
-    for (int pass = 0; pass < 2; ++pass) {
-        double* Mx = pass == 0 ? Sm : Zm;
-        for (int j = 0; j < k; ++j) {
-            const double d = Mx[j + j * k];
-            if (!(d > 0.0)) { if (tid == 0) sh_fail = 1; }
-            __syncthreads();
-            if (sh_fail) break;
-            const double sd = sqrt(d);
-            for (int i = j + 1 + tid; i < k; i += 256) Mx[i + j * k] /= sd;
-            if (tid == 0) Mx[j + j * k] = sd;
-            __syncthreads();
-            for (int idx = tid; idx < (k - j - 1) * (k - j - 1); idx += 256) {
-                const int a = j + 1 + idx / (k - j - 1), b = j + 1 + idx % (k - j - 1);
-                if (a >= b) Mx[a + b * k] -= Mx[a + j * k] * Mx[b + j * k];
-            }
-            __syncthreads();
-        }
-        if (sh_fail) break;
-    }
-    if (sh_fail) { if (tid == 0) *S.fail = 1; return; }
-    for (int idx = tid; idx < kk; idx += 256) {
-        const int r = idx % k, cl = idx / k;
-        if (r < cl) { Sm[idx] = 0.0; Zm[idx] = 0.0; }
-    }
-    __syncthreads();
-    // M = L2' L1 (:113-114), V = I
-    for (int idx = tid; idx < kk; idx += 256) {
-        const int r = idx % k, cl = idx / k;
-        double acc = 0.0;
-        for (int q = (r > cl ? r : cl); q < k; ++q) acc = fma(Zm[q + r * k], Sm[q + cl * k], acc);
-        M[idx] = acc;
-        V[idx] = (r == cl) ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    // one-sided Jacobi: rotate column pairs (p, q) of M (and of V) until all columns are mutually orthogonal
-    const int m = (k + 1) & ~1, npair = m / 2;          // k <= 48: at most 24 pairs, eight lanes each
-    const int grp = tid >> 3, sub = tid & 7;
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        double myoff = 0.0;
-        for (int step = 0; step < m - 1; ++step) {
-            if (grp < npair) {
-                int p, q;
-                if (grp == 0) { p = m - 1; q = step; }
-                else { p = (step + grp) % (m - 1); q = (step - grp + (m - 1)) % (m - 1); }
-                if (p > q) { const int tmp = p; p = q; q = tmp; }
-                if (q < k) {                                           // (q == k: the dummy index of an odd k)
-                    double a = 0.0, b = 0.0, cc = 0.0;
-                    for (int i = sub; i < k; i += 8) {
-                        const double mp = M[i + p * k], mq = M[i + q * k];
-                        a = fma(mp, mp, a); b = fma(mq, mq, b); cc = fma(mp, mq, cc);
-                    }
-#pragma unroll
-                    for (int o = 4; o > 0; o >>= 1) {
-                        a += __shfl_xor(a, o, 8); b += __shfl_xor(b, o, 8); cc += __shfl_xor(cc, o, 8);
-                    }
-                    const double ab = sqrt(a) * sqrt(b);       // (sqrt(a * b) overflows / flushes for entries beyond ~2^+-256)
-                    if (!(fabs(cc) <= 1e-300 || fabs(cc) <= 1e-17 * ab)) {
-                        myoff = fmax(myoff, fabs(cc) / ab);
-                        const double zeta = (b - a) / (2.0 * cc);
-                        const double tt = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                        const double cs = 1.0 / sqrt(1.0 + tt * tt), sn = cs * tt;
-                        for (int i = sub; i < k; i += 8) {
-                            const double mp = M[i + p * k], mq = M[i + q * k];
-                            M[i + p * k] = cs * mp - sn * mq;
-                            M[i + q * k] = sn * mp + cs * mq;
-                            const double vp = V[i + p * k], vq = V[i + q * k];
-                            V[i + p * k] = cs * vp - sn * vq;
-                            V[i + q * k] = sn * vp + cs * vq;
-                        }
-                    }
-                }
-            }
-            __syncthreads();               // the next step pairs the columns differently
-        }
-        if (sub == 0 && grp < 32) sh_off[grp] = grp < npair ? myoff : 0.0;
-        __syncthreads();
-        double offn = 0.0;
-        for (int i = 0; i < npair; ++i) offn = fmax(offn, sh_off[i]);   // uniform: every thread reads the same words
-        __syncthreads();
-        if (offn < 1e-15) break;
-    }
-    // singular values = column norms; U = M with unit columns; descending order like LAPACK's
-    if (tid < k) {
-        double nrm = 0.0;
-        for (int i = 0; i < k; ++i) nrm = fma(M[i + tid * k], M[i + tid * k], nrm);
-        sh_sv[tid] = sqrt(nrm);
-    }
-    __syncthreads();
-    if (tid < k) {
-        const double mine = sh_sv[tid];
-        int rank = 0;
-        for (int i = 0; i < k; ++i) rank += (sh_sv[i] > mine || (sh_sv[i] == mine && i < tid)) ? 1 : 0;
-        sh_rank[tid] = rank;
-        if (S.lam) S.lam[off + rank] = mine;                   // lam occupies the first k of the cone's t slots
-    }
-    if (S.lam) for (int i = k + tid; i < t; i += 256) S.lam[off + i] = 0.0;
-    __syncthreads();
-    // R = L1 V Lam^{-1/2} (columns in sorted order), Rinv = Lam^{-1/2} U' L2' (rows in sorted order)
-    double* Rout = S.psdR + C.psd_aoff[c];
-    double* Riout = S.psdRinv + C.psd_aoff[c];
-    for (int idx = tid; idx < kk; idx += 256) {
-        const int r = idx % k, cl = idx / k;
-        double acc = 0.0;
-        for (int q = 0; q <= r; ++q) acc = fma(Sm[r + q * k], V[q + cl * k], acc);
-        const double sc = 1.0 / sqrt(sh_sv[cl]);
-        const double v = acc * sc;
-        Tm[r + sh_rank[cl] * k] = v;
-        Rout[r + sh_rank[cl] * k] = v;
-        // Rinv(row cl of the unsorted order, column r): (1/sqrt(s_cl)) (1/s_cl) sum_q M(q, cl) L2(r, q)
-        double acc2 = 0.0;
-        for (int q = 0; q <= r; ++q) acc2 = fma(M[q + cl * k], Zm[r + q * k], acc2);
-        Riout[sh_rank[cl] + r * k] = acc2 * sc / sh_sv[cl];
-    }
-    __syncthreads();
-    double* Aout = S.psdA + C.psd_aoff[c];
-    for (int idx = tid; idx < kk; idx += 256) {
-        const int r = idx % k, cl = idx / k;
-        double acc = 0.0;
-        if (r <= cl) {                                           // upper triangle (syrk 'U'), mirrored: exactly symmetric
-            for (int q = 0; q < k; ++q) acc = fma(Tm[r + q * k], Tm[cl + q * k], acc);
-            Am[r + cl * k] = acc; Am[cl + r * k] = acc;
-            Aout[r + cl * k] = acc; Aout[cl + r * k] = acc;
-        }
-    }
-    __syncthreads();
-    // Hs = A (x)_s A, packed upper triangle (column-major over (row, col) with row <= col)
-    double* Hs = S.Hs + C.boff[c];
-    const double s2 = 1.41421356237309504880;
-    const int nh = t * (t + 1) / 2;
-    for (int e = tid; e < nh; e += 256) {
+    const int t = k * (k + 1) / 2, nh = t * (t + 1) / 2;
+    for (int e = threadIdx.x; e < nh; e += 256) {
         int row, col;
         svec_index(e, row, col);
         int i, j, kq, l;
         svec_index(row, i, j);          // row <-> (i, j), i <= j
         svec_index(col, kq, l);         // col <-> (k, l), k <= l
-        double v;
-        const bool ij = (i == j), kl = (kq == l);
-        if (!ij && !kl) v = Am[i + kq * k] * Am[j + l * k] + Am[i + l * k] * Am[j + kq * k];
-        else if (ij && !kl) v = s2 * Am[j + l * k] * Am[j + kq * k];
-        else if (!ij && kl) v = s2 * Am[i + l * k] * Am[j + kq * k];
-        else v = Am[j + l * k] * Am[j + l * k];
-        Hs[e] = v;
+        Hs[e] = psd_hs_entry(Am, k, i, j, kq, l);
     }
 }
 
-// y = (A (x)_s A) x = svec(A X A) for PSD cones
-__global__ __launch_bounds__(256) void k_mul_Hs_psd(ConeDev C, ConeState S, double* __restrict__ y,
-                                                    const double* __restrict__ x, const double* __restrict__ addend)
+template <class P>
+__device__ inline void cone_psd_body(const ConeDev& C, const ConeState& S, const double* __restrict__ s,
+                                     const double* __restrict__ z, double* smem)
 {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int tid = threadIdx.x;
-    const int c = C.psd_list[blockIdx.x];
-    const int k = C.psd_dim[c], off = C.off[c], kk = k * k, t = k * (k + 1) / 2;
-    double* X = smem;
-    double* Am = smem + kk;
-    double* Tm = smem + 2 * kk;
-    const double is2 = 0.70710678118654752440;
-    const double* A = S.psdA + C.psd_aoff[c];
-    for (int idx = tid; idx < kk; idx += 256) Am[idx] = A[idx];
-    for (int idx = tid; idx < t; idx += 256) {
-        int r, cl;
-        svec_index(idx, r, cl);
-        const double v = x[off + idx];
-        if (r == cl) X[r + cl * k] = v;
-        else X[r + cl * k] = X[cl + r * k] = v * is2;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < kk; idx += 256) {
-        const int r = idx % k, cl = idx / k;
-        double acc = 0.0;
-        for (int q = 0; q < k; ++q) acc = fma(X[r + q * k], Am[q + cl * k], acc);
-        Tm[idx] = acc;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < t; idx += 256) {
-        int r, cl;
-        svec_index(idx, r, cl);
-        double a1 = 0.0, a2 = 0.0;
-        for (int q = 0; q < k; ++q) { a1 = fma(Am[r + q * k], Tm[q + cl * k], a1); a2 = fma(Am[cl + q * k], Tm[q + r * k], a2); }
-        const double v = (r == cl) ? a1 : (a1 + a2) * is2;
-        y[off + idx] = addend ? -(v + addend[off + idx]) : v;
-    }
-}
-
-// -------------------------------------------------------------------------------------
-//  PSD cones of side kPsdMaxDim < k <= kPsdBigMaxDim (C.psdb_list; hipkkt_kkt_enable_large_psd).  The same steps and the
-//  same arithmetic as k_cone_psd, one workgroup per cone, but only two k x k matrices stay in LDS: first S and Z for the
-//  two Cholesky factorisations, then the pair (M, V) that the one-sided Jacobi rotates.  L1, L2 and the product
-//  M = L2' L1 go through the cone's slice of C.psd_work, R and A through S.psdR / S.psdA themselves; a slice is read
-//  only by the workgroup that wrote it, behind a workgroup barrier.  512 threads = 64 groups of eight lanes, enough for
-//  the 48 column pairs of side 96.  Hs is formed by a launch of its own, k_psd_hs_big.
-// -------------------------------------------------------------------------------------
-constexpr int kPsdBigGroups = kPsdBigThreads / 8;
-static_assert((kPsdBigMaxDim + 1) / 2 <= kPsdBigGroups, "one group of eight lanes per column pair");
-
-__global__ __launch_bounds__(kPsdBigThreads) void k_cone_psd_big(ConeDev C, ConeState S, const double* __restrict__ s,
-                                                                 const double* __restrict__ z)
-{
-    extern __shared__ __attribute__((aligned(16))) double smem[];
     __shared__ int sh_fail;
-    __shared__ double sh_off[kPsdBigGroups], sh_sv[kPsdBigMaxDim];
-    __shared__ int sh_rank[kPsdBigMaxDim];
-    constexpr int NT = kPsdBigThreads;
+    __shared__ double sh_off[P::NT / 8], sh_sv[P::kMaxDim];
+    __shared__ int sh_rank[P::kMaxDim];
+    constexpr int NT = P::NT;
     const int tid = threadIdx.x;
-    const int c = C.psdb_list[blockIdx.x];
+    const int c = P::cone(C);
     const int k = C.psd_dim[c], off = C.off[c];
-    const int kk = k * k, t = k * (k + 1) / 2;
-    double* Sm = smem;            // S -> L1 (lower), then M = L2' L1 -> U diag(sv)
-    double* Zm = smem + kk;       // Z -> L2 (lower), then V
-    double* W = C.psd_work + (size_t)blockIdx.x * 3 * C.psdb_kmax * C.psdb_kmax;
-    double* L1 = W;
-    double* L2 = W + kk;
-    double* Mg = W + 2 * kk;
-    const double is2 = 0.70710678118654752440;
+    const int kk = k * k;
+    double* Sm = smem;            // S -> L1 (lower); big: then M
+    double* Zm = smem + kk;       // Z -> L2 (lower); big: then V
+    double *L1 = Sm, *L2 = Zm;    // where the factors are read from after the Jacobi
+    double* M = smem + 2 * kk;    // L2' L1 -> U diag(sv)
+    double* V = smem + 3 * kk;    // right singular vectors
+    if constexpr (P::kBig) {
+        L1 = P::work(C);
+        L2 = L1 + kk;
+        M = L2 + kk;
+    }
     if (tid == 0) sh_fail = 0;
-    for (int idx = tid; idx < t; idx += NT) {
-        int r, cl;
-        svec_index(idx, r, cl);
-        const double sv = s[off + idx], zv = z[off + idx];
-        if (r == cl) { Sm[r + cl * k] = sv; Zm[r + cl * k] = zv; }
-        else {
-            Sm[r + cl * k] = Sm[cl + r * k] = sv * is2;
-            Zm[r + cl * k] = Zm[cl + r * k] = zv * is2;
-        }
-    }
+    psd_load_pair<NT>(Sm, Zm, s + off, z + off, k);
     __syncthreads();
-    // Cholesky of S and of Z, in place, right-looking (:97-104)
-    for (int pass = 0; pass < 2; ++pass) {
-        double* Mx = pass == 0 ? Sm : Zm;
-        for (int j = 0; j < k; ++j) {
-            const double d = Mx[j + j * k];
-            if (!(d > 0.0)) { if (tid == 0) sh_fail = 1; }
-            __syncthreads();
-            if (sh_fail) break;
-            const double sd = sqrt(d);
-            for (int i = j + 1 + tid; i < k; i += NT) Mx[i + j * k] /= sd;
-            if (tid == 0) Mx[j + j * k] = sd;
-            __syncthreads();
-            for (int idx = tid; idx < (k - j - 1) * (k - j - 1); idx += NT) {
-                const int a = j + 1 + idx / (k - j - 1), b = j + 1 + idx % (k - j - 1);
-                if (a >= b) Mx[a + b * k] -= Mx[a + j * k] * Mx[b + j * k];
-            }
-            __syncthreads();
-        }
-        if (sh_fail) break;
-    }
+    psd_cholesky<NT>(Sm, k, &sh_fail, [](double) {});
+    if (!sh_fail) psd_cholesky<NT>(Zm, k, &sh_fail, [](double) {});
     if (sh_fail) { if (tid == 0) *S.fail = 1; return; }
     for (int idx = tid; idx < kk; idx += NT) {
         const int r = idx % k, cl = idx / k;
         if (r < cl) { Sm[idx] = 0.0; Zm[idx] = 0.0; }
     }
     __syncthreads();
-    // L1, L2 to the work area; M = L2' L1 (:113-114) beside them, since both its operands are still being read
+    // M = L2' L1 (:113-114), V = I.  big: M beside L1 and L2 in the work area, since both its operands are still being
+    // read, then into S's place, with V in Z's
     for (int idx = tid; idx < kk; idx += NT) {
         const int r = idx % k, cl = idx / k;
         double acc = 0.0;
         for (int q = (r > cl ? r : cl); q < k; ++q) acc = fma(Zm[q + r * k], Sm[q + cl * k], acc);
-        Mg[idx] = acc;
-        L1[idx] = Sm[idx];
-        L2[idx] = Zm[idx];
+        M[idx] = acc;
+        if constexpr (P::kBig) { L1[idx] = Sm[idx]; L2[idx] = Zm[idx]; }
+        else V[idx] = (r == cl) ? 1.0 : 0.0;
     }
     __syncthreads();
-    double* M = Sm;
-    double* V = Zm;
-    for (int idx = tid; idx < kk; idx += NT) {
-        M[idx] = Mg[idx];
-        V[idx] = (idx % k == idx / k) ? 1.0 : 0.0;
-    }
-    __syncthreads();
-    // one-sided Jacobi: rotate column pairs (p, q) of M (and of V) until all columns are mutually orthogonal
-    const int m = (k + 1) & ~1, npair = m / 2;          // k <= 96: at most 48 pairs, eight lanes each
-    const int grp = tid >> 3, sub = tid & 7;
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        double myoff = 0.0;
-        for (int step = 0; step < m - 1; ++step) {
-            if (grp < npair) {
-                int p, q;
-                if (grp == 0) { p = m - 1; q = step; }
-                else { p = (step + grp) % (m - 1); q = (step - grp + (m - 1)) % (m - 1); }
-                if (p > q) { const int tmp = p; p = q; q = tmp; }
-                if (q < k) {                                           // (q == k: the dummy index of an odd k)
-                    double a = 0.0, b = 0.0, cc = 0.0;
-                    for (int i = sub; i < k; i += 8) {
-                        const double mp = M[i + p * k], mq = M[i + q * k];
-                        a = fma(mp, mp, a); b = fma(mq, mq, b); cc = fma(mp, mq, cc);
-                    }
-#pragma unroll
-                    for (int o = 4; o > 0; o >>= 1) {
-                        a += __shfl_xor(a, o, 8); b += __shfl_xor(b, o, 8); cc += __shfl_xor(cc, o, 8);
-                    }
-                    const double ab = sqrt(a) * sqrt(b);       // (sqrt(a * b) overflows / flushes for entries beyond ~2^+-256)
-                    if (!(fabs(cc) <= 1e-300 || fabs(cc) <= 1e-17 * ab)) {
-                        myoff = fmax(myoff, fabs(cc) / ab);
-                        const double zeta = (b - a) / (2.0 * cc);
-                        const double tt = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-                        const double cs = 1.0 / sqrt(1.0 + tt * tt), sn = cs * tt;
-                        for (int i = sub; i < k; i += 8) {
-                            const double mp = M[i + p * k], mq = M[i + q * k];
-                            M[i + p * k] = cs * mp - sn * mq;
-                            M[i + q * k] = sn * mp + cs * mq;
-                            const double vp = V[i + p * k], vq = V[i + q * k];
-                            V[i + p * k] = cs * vp - sn * vq;
-                            V[i + q * k] = sn * vp + cs * vq;
-                        }
-                    }
-                }
-            }
-            __syncthreads();               // the next step pairs the columns differently
+    if constexpr (P::kBig) {
+        const double* Mg = M;
+        M = Sm;
+        V = Zm;
+        for (int idx = tid; idx < kk; idx += NT) {
+            M[idx] = Mg[idx];
+            V[idx] = (idx % k == idx / k) ? 1.0 : 0.0;
         }
-        if (sub == 0) sh_off[grp] = grp < npair ? myoff : 0.0;
         __syncthreads();
-        double offn = 0.0;
-        for (int i = 0; i < npair; ++i) offn = fmax(offn, sh_off[i]);   // uniform: every thread reads the same words
-        __syncthreads();
-        if (offn < 1e-15) break;
     }
-    // singular values = column norms; U = M with unit columns; descending order like LAPACK's
-    if (tid < k) {
-        double nrm = 0.0;
-        for (int i = 0; i < k; ++i) nrm = fma(M[i + tid * k], M[i + tid * k], nrm);
-        sh_sv[tid] = sqrt(nrm);
-    }
-    __syncthreads();
-    if (tid < k) {
-        const double mine = sh_sv[tid];
-        int rank = 0;
-        for (int i = 0; i < k; ++i) rank += (sh_sv[i] > mine || (sh_sv[i] == mine && i < tid)) ? 1 : 0;
-        sh_rank[tid] = rank;
-        if (S.lam) S.lam[off + rank] = mine;                   // lam occupies the first k of the cone's t slots
-    }
-    if (S.lam) for (int i = k + tid; i < t; i += NT) S.lam[off + i] = 0.0;
-    __syncthreads();
-    // R = L1 V Lam^{-1/2} (columns in sorted order), Rinv = Lam^{-1/2} U' L2' (rows in sorted order)
+    psd_onesided_jacobi<NT>(M, V, k, sh_off);
+    psd_singular_values<NT>(M, k, sh_sv, sh_rank, S.lam ? S.lam + off : nullptr);
     double* Rout = S.psdR + C.psd_aoff[c];
-    double* Riout = S.psdRinv + C.psd_aoff[c];
-    for (int idx = tid; idx < kk; idx += NT) {
-        const int r = idx % k, cl = idx / k;
-        double acc = 0.0;
-        for (int q = 0; q <= r; ++q) acc = fma(L1[r + q * k], V[q + cl * k], acc);
-        const double sc = 1.0 / sqrt(sh_sv[cl]);
-        Rout[r + sh_rank[cl] * k] = acc * sc;
-        // Rinv(row cl of the unsorted order, column r): (1/sqrt(s_cl)) (1/s_cl) sum_q M(q, cl) L2(r, q)
-        double acc2 = 0.0;
-        for (int q = 0; q <= r; ++q) acc2 = fma(M[q + cl * k], L2[r + q * k], acc2);
-        Riout[sh_rank[cl] + r * k] = acc2 * sc / sh_sv[cl];
-    }
-    __syncthreads();
     double* Aout = S.psdA + C.psd_aoff[c];
-    for (int idx = tid; idx < kk; idx += NT) {
-        const int r = idx % k, cl = idx / k;
-        double acc = 0.0;
-        if (r <= cl) {                                           // upper triangle (syrk 'U'), mirrored: exactly symmetric
-            for (int q = 0; q < k; ++q) acc = fma(Rout[r + q * k], Rout[cl + q * k], acc);
-            Aout[r + cl * k] = acc; Aout[cl + r * k] = acc;
-        }
+    if constexpr (P::kBig) {
+        psd_R_Rinv<NT>(L1, L2, M, V, k, sh_sv, sh_rank, S.psdRinv + C.psd_aoff[c], [&](int i, double v) { Rout[i] = v; });
+        __syncthreads();
+        psd_A_from_R_sym<NT>(Rout, k, [&](int r, int cl, double v) { Aout[r + cl * k] = v; Aout[cl + r * k] = v; });
+    } else {
+        double* Tm = smem + 4 * kk;   // R
+        double* Am = smem + 5 * kk;   // A = R R'
+        psd_R_Rinv<NT>(L1, L2, M, V, k, sh_sv, sh_rank, S.psdRinv + C.psd_aoff[c], [&](int i, double v) { Tm[i] = v; Rout[i] = v; });
+        __syncthreads();
+        psd_A_from_R_sym<NT>(Tm, k, [&](int r, int cl, double v) {
+            Am[r + cl * k] = v; Am[cl + r * k] = v;
+            Aout[r + cl * k] = v; Aout[cl + r * k] = v;
+        });
+        __syncthreads();
+        psd_hs_flat(S.Hs + C.boff[c], Am, k);
     }
+}
+__global__ __launch_bounds__(PsdSmall::NT) void k_cone_psd(ConeDev C, ConeState S, const double* __restrict__ s,
+                                                           const double* __restrict__ z)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    cone_psd_body<PsdSmall>(C, S, s, z, smem);
+}
+__global__ __launch_bounds__(PsdBig::NT) void k_cone_psd_big(ConeDev C, ConeState S, const double* __restrict__ s,
+                                                             const double* __restrict__ z)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    cone_psd_body<PsdBig>(C, S, s, z, smem);
 }
 
 // (A cone whose S or Z is not positive definite leaves k_cone_psd_big before R and A are written; this launch, which
@@ -1396,7 +1107,7 @@ __global__ __launch_bounds__(kPsdBigThreads) void k_cone_psd_big(ConeDev C, Cone
 // untouched instead.  Either way the update reports the failure and the block's contents are unspecified: hipkkt.h.)
 // Hs = A (x)_s A of the big class, packed upper triangle: at side 96 the block has 10.8 M entries, so the columns of a
 // cone are dealt round-robin to gridDim.x workgroups (blockIdx.y = the cone), each with A in LDS.  (k, l) of a column is
-// found once; a thread's rows advance by 256, and (i, j) with them.  Each entry is the expression of k_cone_psd's tail.
+// found once; a thread's rows advance by 256, and (i, j) with them.
 constexpr int kPsdBigHsChunks = 128;
 __global__ __launch_bounds__(256) void k_psd_hs_big(ConeDev C, ConeState S)
 {
@@ -1409,83 +1120,121 @@ __global__ __launch_bounds__(256) void k_psd_hs_big(ConeDev C, ConeState S)
     for (int idx = tid; idx < k * k; idx += 256) Am[idx] = A[idx];
     __syncthreads();
     double* Hs = S.Hs + C.boff[c];
-    const double s2 = 1.41421356237309504880;
     int i0, j0;
     svec_index(tid, i0, j0);                                   // (t > 256: row tid exists)
     for (int col = blockIdx.x; col < t; col += gridDim.x) {
         int kq, l;
         svec_index(col, kq, l);         // col <-> (k, l), k <= l
-        const bool kl = (kq == l);
         double* Hc = Hs + (int64_t)col * (col + 1) / 2;
         int i = i0, j = j0;             // row <-> (i, j), i <= j
         for (int row = tid; row <= col; row += 256) {
-            double v;
-            const bool ij = (i == j);
-            if (!ij && !kl) v = Am[i + kq * k] * Am[j + l * k] + Am[i + l * k] * Am[j + kq * k];
-            else if (ij && !kl) v = s2 * Am[j + l * k] * Am[j + kq * k];
-            else if (!ij && kl) v = s2 * Am[i + l * k] * Am[j + kq * k];
-            else v = Am[j + l * k] * Am[j + l * k];
-            Hc[row] = v;
+            Hc[row] = psd_hs_entry(Am, k, i, j, kq, l);
             i += 256;
             while (i > j) { i -= j + 1; ++j; }
         }
     }
 }
 
-// y = (A (x)_s A) x = svec(A X A) for the big class: X and A in LDS, T = X A through the work area and then in X's place.
-// (The round trip through HBM exists only to reuse X's space: T cannot be written over X while other threads still read
-// X's rows, and a third matrix does not fit LDS at side 96.  A thread copies back the entries it wrote itself.)
-__global__ __launch_bounds__(kPsdBigThreads) void k_mul_Hs_psd_big(ConeDev C, ConeState S, double* __restrict__ y,
-                                                                   const double* __restrict__ x,
-                                                                   const double* __restrict__ addend)
+// y = (A (x)_s A) x = svec(A X A) for PSD cones, or y = -(that + addend).  LDS: X, A and (small class) T = X A; the big
+// class sends T through its work area into X's place, a third matrix does not fit LDS at side 96.
+template <class P>
+__device__ inline void mul_Hs_psd_body(const ConeDev& C, const ConeState& S, double* __restrict__ y,
+                                       const double* __restrict__ x, const double* __restrict__ addend, double* smem)
 {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    constexpr int NT = kPsdBigThreads;
-    const int tid = threadIdx.x;
-    const int c = C.psdb_list[blockIdx.x];
-    const int k = C.psd_dim[c], off = C.off[c], kk = k * k, t = k * (k + 1) / 2;
+    constexpr int NT = P::NT;
+    const int c = P::cone(C);
+    const int k = C.psd_dim[c], off = C.off[c], kk = k * k;
     double* X = smem;
     double* Am = smem + kk;
-    double* Tg = C.psd_work + (size_t)blockIdx.x * 3 * C.psdb_kmax * C.psdb_kmax;
-    const double is2 = 0.70710678118654752440;
+    double *T = smem + 2 * kk, *Tl = T;
+    if constexpr (P::kBig) { T = P::work(C); Tl = X; }
     const double* A = S.psdA + C.psd_aoff[c];
-    for (int idx = tid; idx < kk; idx += NT) Am[idx] = A[idx];
-    for (int idx = tid; idx < t; idx += NT) {
-        int r, cl;
-        svec_index(idx, r, cl);
-        const double v = x[off + idx];
-        if (r == cl) X[r + cl * k] = v;
-        else X[r + cl * k] = X[cl + r * k] = v * is2;
-    }
+    for (int idx = threadIdx.x; idx < kk; idx += NT) Am[idx] = A[idx];
+    psd_load_mat<NT>(X, x + off, 1.0, k);
     __syncthreads();
-    for (int idx = tid; idx < kk; idx += NT) {
-        const int r = idx % k, cl = idx / k;
-        double acc = 0.0;
-        for (int q = 0; q < k; ++q) acc = fma(X[r + q * k], Am[q + cl * k], acc);
-        Tg[idx] = acc;
-    }
-    __syncthreads();
-    double* Tm = X;
-    for (int idx = tid; idx < kk; idx += NT) Tm[idx] = Tg[idx];
-    __syncthreads();
-    for (int idx = tid; idx < t; idx += NT) {
-        int r, cl;
-        svec_index(idx, r, cl);
-        double a1 = 0.0, a2 = 0.0;
-        for (int q = 0; q < k; ++q) { a1 = fma(Am[r + q * k], Tm[q + cl * k], a1); a2 = fma(Am[cl + q * k], Tm[q + r * k], a2); }
-        const double v = (r == cl) ? a1 : (a1 + a2) * is2;
+    psd_sandwich_svec<NT, false, P::kBig>(X, Am, T, Tl, k, [&](int idx, double v) {
         y[off + idx] = addend ? -(v + addend[off + idx]) : v;
-    }
+    });
+}
+__global__ __launch_bounds__(PsdSmall::NT) void k_mul_Hs_psd(ConeDev C, ConeState S, double* __restrict__ y,
+                                                             const double* __restrict__ x, const double* __restrict__ addend)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    mul_Hs_psd_body<PsdSmall>(C, S, y, x, addend, smem);
+}
+__global__ __launch_bounds__(PsdBig::NT) void k_mul_Hs_psd_big(ConeDev C, ConeState S, double* __restrict__ y,
+                                                               const double* __restrict__ x, const double* __restrict__ addend)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    mul_Hs_psd_body<PsdBig>(C, S, y, x, addend, smem);
 }
 
-static void psd_big_set_lds()
+// out = W'(lambda \ ds) for a PSD cone (_Delta_s_from_Delta_z_offset_symmetric!, coneops_symmetric_common.jl:39-52):
+// X = mat(ds); X(i, j) <- 2 X(i, j) / (lam_i + lam_j) (lambda_inv_circ_op!, coneops_psdtrianglecone.jl:335-353);
+// out = svec(R X R') (mul_W! with :T, :409-437), into konst, and out - rhs_z into workz.  LDS as mul_Hs_psd_body, R for A.
+template <class P>
+__device__ inline void sys_offset_psd_body(const ConeDev& C, const ConeState& S, double* __restrict__ konst,
+                                           double* __restrict__ workz, const double* __restrict__ ds,
+                                           const double* __restrict__ rhs_z, double* smem)
 {
-    static PerDeviceOnce once;
-    once.run([]() {
+    constexpr int NT = P::NT;
+    const int tid = threadIdx.x;
+    const int c = P::cone(C);
+    const int k = C.psd_dim[c], off = C.off[c], kk = k * k, t = k * (k + 1) / 2;
+    double* X = smem;
+    double* Rm = smem + kk;
+    double *T = smem + 2 * kk, *Tl = T;
+    if constexpr (P::kBig) { T = P::work(C); Tl = X; }
+    const double* R = S.psdR + C.psd_aoff[c];
+    const double* lam = S.lam + off;
+    for (int idx = tid; idx < kk; idx += NT) Rm[idx] = R[idx];
+    for (int idx = tid; idx < t; idx += NT) {
+        int r, cl;
+        svec_index(idx, r, cl);
+        const double v = ds[off + idx] * (r == cl ? 1.0 : kIs2) * 2.0 / (lam[r] + lam[cl]);
+        X[r + cl * k] = v;
+        X[cl + r * k] = v;
+    }
+    __syncthreads();
+    psd_sandwich_svec<NT, true, P::kBig>(X, Rm, T, Tl, k, [&](int idx, double o) {
+        konst[off + idx] = o;
+        workz[off + idx] = o - rhs_z[off + idx];
+    });
+}
+__global__ __launch_bounds__(PsdSmall::NT) void k_sys_offset_psd(ConeDev C, ConeState S, double* __restrict__ konst,
+                                                                 double* __restrict__ workz, const double* __restrict__ ds,
+                                                                 const double* __restrict__ rhs_z)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    sys_offset_psd_body<PsdSmall>(C, S, konst, workz, ds, rhs_z, smem);
+}
+__global__ __launch_bounds__(PsdBig::NT) void k_sys_offset_psd_big(ConeDev C, ConeState S, double* __restrict__ konst,
+                                                                   double* __restrict__ workz, const double* __restrict__ ds,
+                                                                   const double* __restrict__ rhs_z)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    sys_offset_psd_body<PsdBig>(C, S, konst, workz, ds, rhs_z, smem);
+}
+
+// the dynamic LDS of this file's PSD kernels beyond the 64 KiB default, once per device: the small class's six matrices
+// (scaling) and three (sys_offset) of side kPsdMaxDim; the big class's one or two of side kPsdBigMaxDim
+static void psd_set_lds(bool big)
+{
+    static PerDeviceOnce once_small, once_big;
+    if (!big) {
+        once_small.run([]() {
+            hipError_t e = set_max_lds(k_cone_psd, 150 * 1024);
+            if (e == hipSuccess) e = set_max_lds(k_sys_offset_psd, 150 * 1024);
+            return e;
+        });
+        return;
+    }
+    once_big.run([]() {
         const int one = kPsdBigMaxDim * kPsdBigMaxDim * (int)sizeof(double);
         hipError_t e = set_max_lds(k_cone_psd_big, 2 * one);
         if (e == hipSuccess) e = set_max_lds(k_psd_hs_big, one);
         if (e == hipSuccess) e = set_max_lds(k_mul_Hs_psd_big, 2 * one);
+        if (e == hipSuccess) e = set_max_lds(k_sys_offset_psd_big, 2 * one);
         return e;
     });
 }
@@ -1494,7 +1243,7 @@ void launch_cone_scaling(const ConeDev& C, const ConeState& S, const double* s, 
                          hipStream_t st)
 {
     if (C.npsdb > 0) {
-        psd_big_set_lds();
+        psd_set_lds(true);
         const size_t one = (size_t)C.psdb_kmax * C.psdb_kmax * sizeof(double);
         hipLaunchKernelGGL(k_cone_psd_big, dim3(C.npsdb), dim3(kPsdBigThreads), 2 * one, st, C, S, s, z);
         hipLaunchKernelGGL(k_psd_hs_big, dim3(kPsdBigHsChunks, C.npsdb), dim3(256), one, st, C, S);
@@ -1506,8 +1255,7 @@ void launch_cone_scaling(const ConeDev& C, const ConeState& S, const double* s, 
         hipLaunchKernelGGL(k_cone_scaling_ns, dim3(ge + gs + gx + gp + gg), dim3(256), 0, st, C, S, s, z, m, ge, gs, gx, gp);
     else if (ge + gs > 0) hipLaunchKernelGGL(k_cone_scaling, dim3(ge + gs), dim3(256), 0, st, C, S, s, z, m, ge);
     if (C.npsd > 0) {
-        static PerDeviceOnce once;
-        once.run([]() { return set_max_lds(k_cone_psd, 150 * 1024); });
+        psd_set_lds(false);
         const size_t lds = (size_t)6 * C.psd_kmax * C.psd_kmax * sizeof(double);
         hipLaunchKernelGGL(k_cone_psd, dim3(C.npsd), dim3(256), lds, st, C, S, s, z);
     }
@@ -1592,9 +1340,11 @@ __global__ __launch_bounds__(256) void k_mul_Hs_gp(ConeDev C, ConeState S, doubl
     }
     mul_Hs_genpow_body<256>(C, S, y, x, addend, C.gp_big[b0 - gq], threadIdx.x, sh);
 }
-// A = R R' per PSD cone, from a caller-supplied R (hipkkt_kkt_system_update_cones); one workgroup per cone
-__device__ inline void psd_A_from_R_body(const ConeDev& C, const ConeState& S, int c)
+// A = R R' per PSD cone, from a caller-supplied R (hipkkt_kkt_system_update_cones); one workgroup per cone of `list`
+// (C.psd_list or C.psdb_list: nothing lies in LDS, so the side does not matter)
+__global__ __launch_bounds__(256) void k_psd_A_from_R(ConeDev C, ConeState S, const int* __restrict__ list)
 {
+    const int c = list[blockIdx.x];
     const int k = C.psd_dim[c];
     const double* R = S.psdR + C.psd_aoff[c];
     double* A = S.psdA + C.psd_aoff[c];
@@ -1605,20 +1355,18 @@ __device__ inline void psd_A_from_R_body(const ConeDev& C, const ConeState& S, i
         A[idx] = acc;
     }
 }
-__global__ __launch_bounds__(256) void k_psd_A_from_R(ConeDev C, ConeState S) { psd_A_from_R_body(C, S, C.psd_list[blockIdx.x]); }
-// ... and for the big class (nothing in LDS, so the side does not matter: only the list differs)
-__global__ __launch_bounds__(256) void k_psd_A_from_R_big(ConeDev C, ConeState S) { psd_A_from_R_body(C, S, C.psdb_list[blockIdx.x]); }
 void launch_psd_A_from_R(const ConeDev& C, const ConeState& S, hipStream_t st)
 {
-    if (C.npsd > 0) hipLaunchKernelGGL(k_psd_A_from_R, dim3(C.npsd), dim3(256), 0, st, C, S);
-    if (C.npsdb > 0) hipLaunchKernelGGL(k_psd_A_from_R_big, dim3(C.npsdb), dim3(256), 0, st, C, S);
+    if (C.npsd > 0) hipLaunchKernelGGL(k_psd_A_from_R, dim3(C.npsd), dim3(256), 0, st, C, S, C.psd_list);
+    if (C.npsdb > 0) hipLaunchKernelGGL(k_psd_A_from_R, dim3(C.npsdb), dim3(256), 0, st, C, S, C.psdb_list);
 }
 
 // ---- get_Hs! and the sparse second-order-cone vectors from a GIVEN scaling (w, eta; psdA = R R'): what a caller that
 // holds the reference's cone objects need not send over PCIe -- Hsblocks, u, v, eta^2 are functions of (w, eta, R)
 // (coneops_nncone.jl:91-101, coneops_socone.jl:125-192, coneops_psdtrianglecone.jl:135-161).  The arithmetic is the
-// tail of k_cone_elementwise / k_cone_soc / k_cone_psd, term for term and in the same order, so that a scaling computed
-// on the device and fed back gives bit-identical K values for the elementwise and second-order cones.
+// tail of k_cone_elementwise / k_cone_soc, term for term and in the same order, so that a scaling computed on the
+// device and fed back gives bit-identical K values for the elementwise and second-order cones; the PSD blocks come
+// from psd_hs_flat / k_psd_hs_big, the scaling kernels' own Hs writers.
 __global__ void k_hs_from_w_elementwise(ConeDev C, ConeState S, int m)
 {
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < m; i += gridDim.x * blockDim.x) {
@@ -1672,43 +1420,25 @@ __global__ __launch_bounds__(64) void k_soc_from_w(ConeDev C, ConeState S)
 __global__ __launch_bounds__(256) void k_psd_hs_from_A(ConeDev C, ConeState S)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int tid = threadIdx.x;
     const int c = C.psd_list[blockIdx.x];
-    const int k = C.psd_dim[c], t = k * (k + 1) / 2;
-    double* Am = smem;
+    const int k = C.psd_dim[c];
     const double* A = S.psdA + C.psd_aoff[c];
-    for (int idx = tid; idx < k * k; idx += 256) Am[idx] = A[idx];
+    for (int idx = threadIdx.x; idx < k * k; idx += 256) smem[idx] = A[idx];
     __syncthreads();
-    double* Hs = S.Hs + C.boff[c];
-    const double s2 = 1.41421356237309504880;
-    const int nh = t * (t + 1) / 2;
-    for (int e = tid; e < nh; e += 256) {
-        int row, col;
-        svec_index(e, row, col);
-        int i, j, kq, l;
-        svec_index(row, i, j);
-        svec_index(col, kq, l);
-        double v;
-        const bool ij = (i == j), kl = (kq == l);
-        if (!ij && !kl) v = Am[i + kq * k] * Am[j + l * k] + Am[i + l * k] * Am[j + kq * k];
-        else if (ij && !kl) v = s2 * Am[j + l * k] * Am[j + kq * k];
-        else if (!ij && kl) v = s2 * Am[i + l * k] * Am[j + kq * k];
-        else v = Am[j + l * k] * Am[j + l * k];
-        Hs[e] = v;
-    }
+    psd_hs_flat(S.Hs + C.boff[c], smem, k);
 }
 void launch_cone_from_scaling(const ConeDev& C, const ConeState& S, int m, hipStream_t st)
 {
     if (m > 0) hipLaunchKernelGGL(k_hs_from_w_elementwise, dim3(grid_for(m, 256)), dim3(256), 0, st, C, S, m);
     if (C.nsoc > 0) hipLaunchKernelGGL(k_soc_from_w, dim3(C.nsoc), dim3(64), 0, st, C, S);
     if (C.npsd > 0) {
-        hipLaunchKernelGGL(k_psd_A_from_R, dim3(C.npsd), dim3(256), 0, st, C, S);
+        hipLaunchKernelGGL(k_psd_A_from_R, dim3(C.npsd), dim3(256), 0, st, C, S, C.psd_list);
         const size_t lds = (size_t)C.psd_kmax * C.psd_kmax * sizeof(double);
         hipLaunchKernelGGL(k_psd_hs_from_A, dim3(C.npsd), dim3(256), lds, st, C, S);
     }
     if (C.npsdb > 0) {
-        psd_big_set_lds();
-        hipLaunchKernelGGL(k_psd_A_from_R_big, dim3(C.npsdb), dim3(256), 0, st, C, S);
+        psd_set_lds(true);
+        hipLaunchKernelGGL(k_psd_A_from_R, dim3(C.npsdb), dim3(256), 0, st, C, S, C.psdb_list);
         const size_t lds = (size_t)C.psdb_kmax * C.psdb_kmax * sizeof(double);
         hipLaunchKernelGGL(k_psd_hs_big, dim3(kPsdBigHsChunks, C.npsdb), dim3(256), lds, st, C, S);
     }
@@ -1727,7 +1457,7 @@ void launch_mul_Hs(const ConeDev& C, const ConeState& S, double* y, const double
         hipLaunchKernelGGL(k_mul_Hs_psd, dim3(C.npsd), dim3(256), lds, st, C, S, y, x, addend);
     }
     if (C.npsdb > 0) {
-        psd_big_set_lds();
+        psd_set_lds(true);
         const size_t lds = (size_t)2 * C.psdb_kmax * C.psdb_kmax * sizeof(double);
         hipLaunchKernelGGL(k_mul_Hs_psd_big, dim3(C.npsdb), dim3(kPsdBigThreads), lds, st, C, S, y, x, addend);
     }
@@ -1800,97 +1530,7 @@ __device__ inline void sys_offset_soc_body(const ConeDev& C, const ConeState& S,
     }
 }
 
-// out = W'(lambda \ ds) for a PSD cone (_Delta_s_from_Delta_z_offset_symmetric!, coneops_symmetric_common.jl:39-52):
-// X = mat(ds); X(i, j) <- 2 X(i, j) / (lam_i + lam_j) (lambda_inv_circ_op!, coneops_psdtrianglecone.jl:335-353);
-// out = svec(R X R') (mul_W! with :T, :409-437).  One workgroup per cone.
-__global__ __launch_bounds__(256) void k_sys_offset_psd(ConeDev C, ConeState S, double* __restrict__ konst,
-                                                       double* __restrict__ workz, const double* __restrict__ ds,
-                                                       const double* __restrict__ rhs_z)
-{
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    const int tid = threadIdx.x;
-    const int c = C.psd_list[blockIdx.x];
-    const int k = C.psd_dim[c], off = C.off[c], kk = k * k, t = k * (k + 1) / 2;
-    double* X = smem;
-    double* Rm = smem + kk;
-    double* Tm = smem + 2 * kk;
-    const double is2 = 0.70710678118654752440;
-    const double* R = S.psdR + C.psd_aoff[c];
-    const double* lam = S.lam + off;
-    for (int idx = tid; idx < kk; idx += 256) Rm[idx] = R[idx];
-    for (int idx = tid; idx < t; idx += 256) {
-        int r, cl;
-        svec_index(idx, r, cl);
-        const double v = ds[off + idx] * (r == cl ? 1.0 : is2) * 2.0 / (lam[r] + lam[cl]);
-        X[r + cl * k] = v;
-        X[cl + r * k] = v;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < kk; idx += 256) {          // Tm = X R'
-        const int r = idx % k, cl = idx / k;
-        double acc = 0.0;
-        for (int q = 0; q < k; ++q) acc = fma(X[r + q * k], Rm[cl + q * k], acc);
-        Tm[idx] = acc;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < t; idx += 256) {           // Y = R Tm, svec
-        int r, cl;
-        svec_index(idx, r, cl);
-        double a1 = 0.0, a2 = 0.0;
-        for (int q = 0; q < k; ++q) { a1 = fma(Rm[r + q * k], Tm[q + cl * k], a1); a2 = fma(Rm[cl + q * k], Tm[q + r * k], a2); }
-        const double o = (r == cl) ? a1 : (a1 + a2) * is2;
-        konst[off + idx] = o;
-        workz[off + idx] = o - rhs_z[off + idx];
-    }
-}
-
-// ... for the big class: X and R in LDS, Tm = X R' through the work area and then in X's place (as k_mul_Hs_psd_big)
-__global__ __launch_bounds__(kPsdBigThreads) void k_sys_offset_psd_big(ConeDev C, ConeState S, double* __restrict__ konst,
-                                                                       double* __restrict__ workz,
-                                                                       const double* __restrict__ ds,
-                                                                       const double* __restrict__ rhs_z)
-{
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    constexpr int NT = kPsdBigThreads;
-    const int tid = threadIdx.x;
-    const int c = C.psdb_list[blockIdx.x];
-    const int k = C.psd_dim[c], off = C.off[c], kk = k * k, t = k * (k + 1) / 2;
-    double* X = smem;
-    double* Rm = smem + kk;
-    double* Tg = C.psd_work + (size_t)blockIdx.x * 3 * C.psdb_kmax * C.psdb_kmax;
-    const double is2 = 0.70710678118654752440;
-    const double* R = S.psdR + C.psd_aoff[c];
-    const double* lam = S.lam + off;
-    for (int idx = tid; idx < kk; idx += NT) Rm[idx] = R[idx];
-    for (int idx = tid; idx < t; idx += NT) {
-        int r, cl;
-        svec_index(idx, r, cl);
-        const double v = ds[off + idx] * (r == cl ? 1.0 : is2) * 2.0 / (lam[r] + lam[cl]);
-        X[r + cl * k] = v;
-        X[cl + r * k] = v;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < kk; idx += NT) {           // Tm = X R'
-        const int r = idx % k, cl = idx / k;
-        double acc = 0.0;
-        for (int q = 0; q < k; ++q) acc = fma(X[r + q * k], Rm[cl + q * k], acc);
-        Tg[idx] = acc;
-    }
-    __syncthreads();
-    double* Tm = X;
-    for (int idx = tid; idx < kk; idx += NT) Tm[idx] = Tg[idx];
-    __syncthreads();
-    for (int idx = tid; idx < t; idx += NT) {            // Y = R Tm, svec
-        int r, cl;
-        svec_index(idx, r, cl);
-        double a1 = 0.0, a2 = 0.0;
-        for (int q = 0; q < k; ++q) { a1 = fma(Rm[r + q * k], Tm[q + cl * k], a1); a2 = fma(Rm[cl + q * k], Tm[q + r * k], a2); }
-        const double o = (r == cl) ? a1 : (a1 + a2) * is2;
-        konst[off + idx] = o;
-        workz[off + idx] = o - rhs_z[off + idx];
-    }
-}
-
+// (PSD cones: k_sys_offset_psd / k_sys_offset_psd_big, beside the other PSD kernels above)
 __global__ __launch_bounds__(256) void k_sys_offset(ConeDev C, ConeState S, double* __restrict__ konst, double* __restrict__ workz,
                                                     const double* __restrict__ ds, const double* __restrict__ z,
                                                     const double* __restrict__ rhs_z, int m, int affine, int ge)
@@ -1904,14 +1544,12 @@ bool launch_sys_offset(const ConeDev& C, const ConeState& S, double* konst, doub
 {
     if (m <= 0) return true;
     if (!affine && C.npsd > 0) {
-        static PerDeviceOnce once;
-        once.run([]() { return set_max_lds(k_sys_offset_psd, 150 * 1024); });
+        psd_set_lds(false);
         const size_t lds = (size_t)3 * C.psd_kmax * C.psd_kmax * sizeof(double);
         hipLaunchKernelGGL(k_sys_offset_psd, dim3(C.npsd), dim3(256), lds, st, C, S, konst, workz, ds, rhs_z);
     }
     if (!affine && C.npsdb > 0) {
-        static PerDeviceOnce once;
-        once.run([]() { return set_max_lds(k_sys_offset_psd_big, 2 * kPsdBigMaxDim * kPsdBigMaxDim * (int)sizeof(double)); });
+        psd_set_lds(true);
         const size_t lds = (size_t)2 * C.psdb_kmax * C.psdb_kmax * sizeof(double);
         hipLaunchKernelGGL(k_sys_offset_psd_big, dim3(C.npsdb), dim3(kPsdBigThreads), lds, st, C, S, konst, workz, ds, rhs_z);
     }

@@ -3,9 +3,10 @@
 //   step_length                         coneops_compositecone.jl:205-243
 //   margins, scaled_unit_shift!         coneops_compositecone.jl:49-76
 // for the symmetric cones (zero, nonnegative, second-order, PSD side <= kPsdMaxDim; on an opted-in handle the big PSD
-// class up to kPsdBigMaxDim, whose kernels stand beside the small class's below).  Launch shapes as k_sys_offset /
-// k_sys_offset_psd: an elementwise grid-stride part with one wave per second-order cone riding behind it, one 256-thread
-// workgroup per PSD cone with its matrices in LDS.  Compiled without FMA contraction: the exact-zero branches of the
+// class up to kPsdBigMaxDim: one body per operation, instantiated for either class, see psd_cone.hpp).  Launch shapes as
+// k_sys_offset / k_sys_offset_psd: an elementwise grid-stride part with one wave per second-order cone riding behind it,
+// one workgroup per PSD cone (256 threads and its matrices in LDS; the big class 512 threads, at most two matrices in
+// LDS and the others in its work area).  Compiled without FMA contraction: the exact-zero branches of the
 // second-order step length are tested on products and differences formed as the reference forms them.
 //
 // The exponential and the power cone (three rows each) ride behind them for handles that hold one: one lane per cone
@@ -17,15 +18,13 @@
 // a fixed order) and there is no floating-point atomic: the same call on the same data gives the same bits.
 #include "kernels.hpp"
 #include "nonsym_cone.hpp"
+#include "psd_cone.hpp"
 #include <cfloat>
 #include <cmath>
 
 namespace hipkkt {
 
 namespace {
-
-constexpr double kIs2 = 0.70710678118654752440;
-constexpr double kS2 = 1.41421356237309504880;
 
 __device__ inline double st_wave_sum(double v)
 {
@@ -34,34 +33,6 @@ __device__ inline double st_wave_sum(double v)
     return v;
 }
 
-__device__ inline void st_svec_index(int idx, int& row, int& col)     // idx = col(col+1)/2 + row, row <= col
-{
-    int c = (int)((sqrt(8.0 * (double)idx + 1.0) - 1.0) * 0.5);
-    while (c * (c + 1) / 2 > idx) --c;
-    while ((c + 1) * (c + 2) / 2 <= idx) ++c;
-    col = c;
-    row = idx - c * (c + 1) / 2;
-}
-
-struct OpMin { __device__ double operator()(double a, double b) const { return fmin(a, b); } };
-struct OpMax { __device__ double operator()(double a, double b) const { return fmax(a, b); } };
-struct OpSum { __device__ double operator()(double a, double b) const { return a + b; } };
-
-// fixed tree over the NT threads of a workgroup; every thread gets the result
-template <int NT, class Op>
-__device__ inline double block_reduce_n(double v, double* sh, Op op)
-{
-    const int tid = threadIdx.x;
-    sh[tid] = v;
-    __syncthreads();
-    for (int o = NT / 2; o > 0; o >>= 1) {
-        if (tid < o) sh[tid] = op(sh[tid], sh[tid + o]);
-        __syncthreads();
-    }
-    const double r = sh[0];
-    __syncthreads();
-    return r;
-}
 template <class Op>
 __device__ inline double block_reduce_256(double v, double* sh, Op op) { return block_reduce_n<256>(v, sh, op); }
 
@@ -70,130 +41,6 @@ __device__ inline void st_publish(const Publish& P)
     for (int i = 0; i < P.n; ++i) P.dst[i] = P.rec[i];
     P.dst[P.n] = P.seq;
     for (int i = 0; i < P.nzero; ++i) P.rec[i] = 0.0;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-//  Eigenvalues of a symmetric k x k matrix in LDS (both triangles stored, column-major): cyclic two-sided Jacobi with the
-//  round-robin pairing of k_cone_psd -- m/2 disjoint pairs (p, q) per step, eight lanes per pair.  A step is
-//      1. every pair reads (a_pp, a_qq, a_pq) and forms its rotation (c, s)         [barrier]
-//      2. A <- A J: the pair rotates its two columns                                [barrier]
-//      3. A <- J'A: the pair rotates its two rows; the 2 x 2 block gets its exact values (a_pq = 0)   [barrier]
-//  The pairs of a step touch disjoint columns in 2 and disjoint rows in 3.  Unlike the one-sided sweep (an SVD) this
-//  keeps the signs, and its error in every eigenvalue is ABSOLUTE, a modest multiple of k u ||A|| -- what the step
-//  length needs of the smallest one (the reference calls LAPACK's syevr).  Rotations stop when a whole sweep saw no
-//  off-diagonal entry above 2^-60 ||A||_F.  On return the eigenvalues are the diagonal.  All NT threads call; NT / 8
-//  groups of eight lanes must cover the pairs: 256 threads up to side 64, kPsdBigThreads up to kPsdBigMaxDim.
-// ---------------------------------------------------------------------------------------------------------------------
-template <int NT = 256>
-__device__ inline void sym_jacobi_eig(double* A, int k, double* sh)
-{
-    const int tid = threadIdx.x;
-    double f = 0.0;
-    for (int idx = tid; idx < k * k; idx += NT) f += A[idx] * A[idx];
-    f = sqrt(block_reduce_n<NT>(f, sh, OpSum{}));
-    if (!(f > 0.0) || !(f <= DBL_MAX)) return;          // the zero matrix (or a non-finite one: unspecified input)
-    const double thr_conv = ldexp(f, -60), thr_skip = ldexp(f, -80);
-    const int mm = (k + 1) & ~1, npair = mm / 2;         // at most NT / 8 pairs
-    const int grp = tid >> 3, sub = tid & 7;
-    for (int sweep = 0; sweep < 40; ++sweep) {
-        double myoff = 0.0;
-        for (int step = 0; step < mm - 1; ++step) {
-            bool act = false;
-            int p = 0, q = 0;
-            double c = 1.0, s = 0.0, app2 = 0.0, aqq2 = 0.0;
-            if (grp < npair) {
-                if (grp == 0) { p = mm - 1; q = step; }
-                else { p = (step + grp) % (mm - 1); q = (step - grp + (mm - 1)) % (mm - 1); }
-                if (p > q) { const int tmp = p; p = q; q = tmp; }
-                if (q < k) {                                           // (q == k: the dummy index of an odd k)
-                    const double apq = A[p + q * k], app = A[p + p * k], aqq = A[q + q * k];
-                    myoff = fmax(myoff, fabs(apq));
-                    if (fabs(apq) > thr_skip) {
-                        act = true;
-                        const double theta = (aqq - app) / (2.0 * apq);
-                        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(1.0 + theta * theta));
-                        c = 1.0 / sqrt(1.0 + t * t);
-                        s = c * t;
-                        app2 = app - t * apq;
-                        aqq2 = aqq + t * apq;
-                    }
-                }
-            }
-            __syncthreads();
-            if (act) {
-                for (int i = sub; i < k; i += 8) {
-                    const double ap = A[i + p * k], aq = A[i + q * k];
-                    A[i + p * k] = c * ap - s * aq;
-                    A[i + q * k] = s * ap + c * aq;
-                }
-            }
-            __syncthreads();
-            if (act) {
-                for (int j = sub; j < k; j += 8) {
-                    if (j == p) { A[p + p * k] = app2; A[q + p * k] = 0.0; }
-                    else if (j == q) { A[p + q * k] = 0.0; A[q + q * k] = aqq2; }
-                    else {
-                        const double ap = A[p + j * k], aq = A[q + j * k];
-                        A[p + j * k] = c * ap - s * aq;
-                        A[q + j * k] = s * ap + c * aq;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-        const double offn = block_reduce_n<NT>(myoff, sh, OpMax{});
-        if (offn <= thr_conv) break;
-    }
-}
-
-// X = mat(scale * x) of an svec vector (coneops_psdtrianglecone.jl:469-483), both triangles
-template <int NT = 256>
-__device__ inline void psd_load_mat(double* X, const double* __restrict__ x, double scale, int k)
-{
-    const int t = k * (k + 1) / 2;
-    for (int idx = threadIdx.x; idx < t; idx += NT) {
-        int r, cl;
-        st_svec_index(idx, r, cl);
-        const double v = scale * x[idx] * (r == cl ? 1.0 : kIs2);
-        X[r + cl * k] = v;
-        X[cl + r * k] = v;
-    }
-}
-
-// M = G' X G for symmetric X, exactly symmetric (each pair (r, c) from both orders, averaged).  mul_W!(:N) is G = R
-// (R' X R, :409-437 with :N), mul_Winv!(:T) is G = Rinv' (Rinv X Rinv').  T: work matrix.  Ends with a barrier.
-// (The big class passes T, and where it can M, in its work area in HBM: the workgroup's own stores, read behind a barrier.)
-template <int NT = 256>
-__device__ inline void psd_congruence(double* M, double* T, const double* G, const double* X, int k)
-{
-    const int tid = threadIdx.x, kk = k * k, t = k * (k + 1) / 2;
-    for (int idx = tid; idx < kk; idx += NT) {           // T = X G
-        const int r = idx % k, cl = idx / k;
-        double acc = 0.0;
-        for (int q = 0; q < k; ++q) acc = fma(X[r + q * k], G[q + cl * k], acc);
-        T[idx] = acc;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < t; idx += NT) {            // M = G' T
-        int r, cl;
-        st_svec_index(idx, r, cl);
-        double a1 = 0.0, a2 = 0.0;
-        for (int q = 0; q < k; ++q) { a1 = fma(G[q + r * k], T[q + cl * k], a1); a2 = fma(G[q + cl * k], T[q + r * k], a2); }
-        const double v = r == cl ? a1 : 0.5 * (a1 + a2);
-        M[r + cl * k] = v;
-        M[cl + r * k] = v;
-    }
-    __syncthreads();
-}
-
-// G = R (transpose = 0) or Rinv' (transpose = 1) into LDS
-template <int NT = 256>
-__device__ inline void psd_load_G(double* G, const double* __restrict__ src, int k, int transpose)
-{
-    for (int idx = threadIdx.x; idx < k * k; idx += NT) {
-        const int r = idx % k, cl = idx / k;
-        G[idx] = transpose ? src[cl + r * k] : src[idx];
-    }
 }
 
 // =====================================================================================================================
@@ -267,20 +114,23 @@ __global__ __launch_bounds__(256) void k_step_ds(ConeDev C, ConeState S, double*
 }
 
 // PSD cones (coneops_psdtrianglecone.jl:189-205, circ_op! :361-382): Z = R'mat(m dz)R, Y = Rinv mat(ds) Rinv',
-// out = svec((YZ + ZY)/2) with lambda_i^2 - sigma_mu added on the diagonal.  LDS: four k x k matrices.
-// (the cone's workgroup: c = the cone, smem = its dynamic LDS)
+// out = svec((YZ + ZY)/2) with lambda_i^2 - sigma_mu added on the diagonal.  One workgroup per cone, of either class
+// (psd_cone.hpp: PsdSmall, PsdBig).  LDS: the operands G and X of a product, and for the small class T and Z behind
+// them; the big class has T and Z in its work area.  c: the cone, P::cone(C); smem: the workgroup's dynamic LDS.
+template <class P>
 __device__ inline void step_ds_psd_body(const ConeDev& C, const ConeState& S, double* __restrict__ out,
                                         const double* __restrict__ dz, const double* __restrict__ ds, double sigma_mu,
                                         double m_corr, int combined, int c, double* smem)
 {
+    constexpr int NT = P::NT;
     const int tid = threadIdx.x;
     const int k = C.psd_dim[c], off = C.off[c], kk = k * k, t = k * (k + 1) / 2;
-    if (k == 0) return;
+    if constexpr (!P::kBig) if (k == 0) return;
     const double* lam = S.lam + off;
     if (!combined) {
-        for (int idx = tid; idx < t; idx += 256) {
+        for (int idx = tid; idx < t; idx += NT) {
             int r, cl;
-            st_svec_index(idx, r, cl);
+            svec_index(idx, r, cl);
             out[off + idx] = r == cl ? lam[r] * lam[r] : 0.0;
         }
         return;
@@ -289,58 +139,7 @@ __device__ inline void step_ds_psd_body(const ConeDev& C, const ConeState& S, do
     double* X = smem + kk;          // mat(ds), then Y
     double* T = smem + 2 * kk;
     double* Z = smem + 3 * kk;
-    psd_load_G(G, S.psdR + C.psd_aoff[c], k, 0);
-    psd_load_mat(X, dz + off, m_corr, k);
-    __syncthreads();
-    psd_congruence(Z, T, G, X, k);
-    psd_load_G(G, S.psdRinv + C.psd_aoff[c], k, 1);
-    psd_load_mat(X, ds + off, 1.0, k);
-    __syncthreads();
-    psd_congruence(X, T, G, X, k);                       // (the product X G is complete before X is overwritten)
-    const double* Y = X;
-    for (int idx = tid; idx < t; idx += 256) {
-        int r, cl;
-        st_svec_index(idx, r, cl);
-        double a1 = 0.0, a2 = 0.0;
-        for (int q = 0; q < k; ++q) { a1 = fma(Y[r + q * k], Z[q + cl * k], a1); a2 = fma(Z[r + q * k], Y[q + cl * k], a2); }
-        const double v = 0.5 * (a1 + a2);
-        out[off + idx] = r == cl ? lam[r] * lam[r] + (v - sigma_mu) : v * kS2;
-    }
-}
-__global__ __launch_bounds__(256) void k_step_ds_psd(ConeDev C, ConeState S, double* __restrict__ out,
-                                                    const double* __restrict__ dz, const double* __restrict__ ds,
-                                                    double sigma_mu, double m_corr, int combined)
-{
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    step_ds_psd_body(C, S, out, dz, ds, sigma_mu, m_corr, combined, C.psd_list[blockIdx.x], smem);
-}
-
-// The big PSD class (C.psdb_list, side <= kPsdBigMaxDim): the same steps with kPsdBigThreads threads and two matrices
-// in LDS -- the operands G and X of a product; T and Z go through the cone's slice of C.psd_work.
-__global__ __launch_bounds__(kPsdBigThreads) void k_step_ds_psd_big(ConeDev C, ConeState S, double* __restrict__ out,
-                                                                    const double* __restrict__ dz,
-                                                                    const double* __restrict__ ds, double sigma_mu,
-                                                                    double m_corr, int combined)
-{
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    constexpr int NT = kPsdBigThreads;
-    const int tid = threadIdx.x;
-    const int c = C.psdb_list[blockIdx.x];
-    const int k = C.psd_dim[c], off = C.off[c], kk = k * k, t = k * (k + 1) / 2;
-    const double* lam = S.lam + off;
-    if (!combined) {
-        for (int idx = tid; idx < t; idx += NT) {
-            int r, cl;
-            st_svec_index(idx, r, cl);
-            out[off + idx] = r == cl ? lam[r] * lam[r] : 0.0;
-        }
-        return;
-    }
-    double* W = C.psd_work + (size_t)blockIdx.x * 3 * C.psdb_kmax * C.psdb_kmax;
-    double* G = smem;
-    double* X = smem + kk;          // mat(ds), then Y
-    double* T = W;
-    double* Z = W + kk;
+    if constexpr (P::kBig) { T = P::work(C); Z = T + kk; }
     psd_load_G<NT>(G, S.psdR + C.psd_aoff[c], k, 0);
     psd_load_mat<NT>(X, dz + off, m_corr, k);
     __syncthreads();
@@ -352,12 +151,26 @@ __global__ __launch_bounds__(kPsdBigThreads) void k_step_ds_psd_big(ConeDev C, C
     const double* Y = X;
     for (int idx = tid; idx < t; idx += NT) {
         int r, cl;
-        st_svec_index(idx, r, cl);
+        svec_index(idx, r, cl);
         double a1 = 0.0, a2 = 0.0;
         for (int q = 0; q < k; ++q) { a1 = fma(Y[r + q * k], Z[q + cl * k], a1); a2 = fma(Z[r + q * k], Y[q + cl * k], a2); }
         const double v = 0.5 * (a1 + a2);
         out[off + idx] = r == cl ? lam[r] * lam[r] + (v - sigma_mu) : v * kS2;
     }
+}
+__global__ __launch_bounds__(PsdSmall::NT) void k_step_ds_psd(ConeDev C, ConeState S, double* __restrict__ out,
+                                                              const double* __restrict__ dz, const double* __restrict__ ds,
+                                                              double sigma_mu, double m_corr, int combined)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    step_ds_psd_body<PsdSmall>(C, S, out, dz, ds, sigma_mu, m_corr, combined, PsdSmall::cone(C), smem);
+}
+__global__ __launch_bounds__(PsdBig::NT) void k_step_ds_psd_big(ConeDev C, ConeState S, double* __restrict__ out,
+                                                                const double* __restrict__ dz, const double* __restrict__ ds,
+                                                                double sigma_mu, double m_corr, int combined)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    step_ds_psd_body<PsdBig>(C, S, out, dz, ds, sigma_mu, m_corr, combined, PsdBig::cone(C), smem);
 }
 
 // =====================================================================================================================
@@ -431,63 +244,25 @@ __global__ __launch_bounds__(256) void k_step_length(ConeDev C, const double* __
     if (ci < C.nsoc) step_length_soc_body(C, dz, ds, z, s, partial + ge + ci, ci, threadIdx.x & 63);
 }
 
-// PSD cones (coneops_psdtrianglecone.jl:230-254, :439-466): both components by the cone's workgroup.
-// gamma = lambda_min(Lam^{-1/2} mat(d) Lam^{-1/2}), d = W dz or W^{-T} ds; the limit is 1/(-gamma) where gamma < 0.
-// (the cone's workgroup: c = the cone, slot = where its limit goes, smem = its dynamic LDS, sh = 256 doubles of LDS)
+// PSD cones (coneops_psdtrianglecone.jl:230-254, :439-466): both components by the cone's workgroup, its limit into
+// slots[blockIdx.x].  gamma = lambda_min(Lam^{-1/2} mat(d) Lam^{-1/2}), d = W dz or W^{-T} ds; the limit is 1/(-gamma)
+// where gamma < 0.  LDS: G and X, and for the small class T and M behind them; the big class has T in its work area and
+// M in X's place, where the two-sided Jacobi then runs.
+template <class P>
 __device__ inline void step_length_psd_body(const ConeDev& C, const ConeState& S, const double* __restrict__ dz,
-                                            const double* __restrict__ ds, double* __restrict__ slot, int c, double* smem,
-                                            double* sh)
+                                            const double* __restrict__ ds, double* __restrict__ slots, double* smem)
 {
+    __shared__ double sh[P::NT];
+    constexpr int NT = P::NT;
     const int tid = threadIdx.x;
+    const int c = P::cone(C);
     const int k = C.psd_dim[c], off = C.off[c], kk = k * k;
-    if (k == 0) { if (tid == 0) *slot = DBL_MAX; return; }
+    if constexpr (!P::kBig) if (k == 0) { if (tid == 0) slots[blockIdx.x] = DBL_MAX; return; }
     double* G = smem;
     double* X = smem + kk;
     double* T = smem + 2 * kk;
     double* M = smem + 3 * kk;
-    const double* lam = S.lam + off;
-    double alpha = DBL_MAX;
-    for (int comp = 0; comp < 2; ++comp) {
-        psd_load_G(G, (comp == 0 ? S.psdR : S.psdRinv) + C.psd_aoff[c], k, comp);
-        psd_load_mat(X, (comp == 0 ? dz : ds) + off, 1.0, k);
-        __syncthreads();
-        psd_congruence(M, T, G, X, k);
-        for (int idx = tid; idx < kk; idx += 256) {      // lrscale! with Lam^{-1/2} (symmetric entries get the same factors)
-            const int r = idx % k, cl = idx / k;
-            M[idx] = M[idx] * ((1.0 / sqrt(lam[r])) * (1.0 / sqrt(lam[cl])));
-        }
-        __syncthreads();
-        sym_jacobi_eig(M, k, sh);
-        double g = DBL_MAX;
-        for (int i = 0; i < k; ++i) g = fmin(g, M[i + i * k]);          // uniform: every thread reads the same words
-        if (g < 0.0) alpha = fmin(alpha, 1.0 / (-g));
-        __syncthreads();
-    }
-    if (tid == 0) *slot = alpha;
-}
-__global__ __launch_bounds__(256) void k_step_length_psd(ConeDev C, ConeState S, const double* __restrict__ dz,
-                                                        const double* __restrict__ ds, double* __restrict__ slots)
-{
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    __shared__ double sh[256];
-    step_length_psd_body(C, S, dz, ds, slots + blockIdx.x, C.psd_list[blockIdx.x], smem, sh);
-}
-
-// ... of the big class: G and X in LDS, T through the work area, M in X's place, where the two-sided Jacobi then runs
-__global__ __launch_bounds__(kPsdBigThreads) void k_step_length_psd_big(ConeDev C, ConeState S, const double* __restrict__ dz,
-                                                                        const double* __restrict__ ds,
-                                                                        double* __restrict__ slots)
-{
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    __shared__ double sh[kPsdBigThreads];
-    constexpr int NT = kPsdBigThreads;
-    const int tid = threadIdx.x;
-    const int c = C.psdb_list[blockIdx.x];
-    const int k = C.psd_dim[c], off = C.off[c], kk = k * k;
-    double* G = smem;
-    double* X = smem + kk;
-    double* T = C.psd_work + (size_t)blockIdx.x * 3 * C.psdb_kmax * C.psdb_kmax;
-    double* M = X;
+    if constexpr (P::kBig) { T = P::work(C); M = X; }
     const double* lam = S.lam + off;
     double alpha = DBL_MAX;
     for (int comp = 0; comp < 2; ++comp) {
@@ -507,6 +282,18 @@ __global__ __launch_bounds__(kPsdBigThreads) void k_step_length_psd_big(ConeDev 
         __syncthreads();
     }
     if (tid == 0) slots[blockIdx.x] = alpha;
+}
+__global__ __launch_bounds__(PsdSmall::NT) void k_step_length_psd(ConeDev C, ConeState S, const double* __restrict__ dz,
+                                                                  const double* __restrict__ ds, double* __restrict__ slots)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    step_length_psd_body<PsdSmall>(C, S, dz, ds, slots, smem);
+}
+__global__ __launch_bounds__(PsdBig::NT) void k_step_length_psd_big(ConeDev C, ConeState S, const double* __restrict__ dz,
+                                                                    const double* __restrict__ ds, double* __restrict__ slots)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    step_length_psd_body<PsdBig>(C, S, dz, ds, slots, smem);
 }
 
 // variables_calc_step_length (variables.jl:14-43) without max_step_fraction: min(1, tau limit, kappa limit, cones)
@@ -568,45 +355,19 @@ __global__ __launch_bounds__(256) void k_margins(ConeDev C, const double* __rest
     margins_soc_body(C, v, pmin + ge + ci, psum + ge + ci, ci, lane);
 }
 
-// PSD cones (coneops_psdtrianglecone.jl:8-27): the eigenvalues of mat(v).  The cone's workgroup: c = the cone, pmin / psum
-// = where its two values go, smem = its dynamic LDS, sh = 256 doubles of LDS
+// PSD cones (coneops_psdtrianglecone.jl:8-27): the eigenvalues of mat(v), one matrix in LDS for either class.  The
+// cone's workgroup leaves its two values in pmin[blockIdx.x], psum[blockIdx.x].
+template <class P>
 __device__ inline void margins_psd_body(const ConeDev& C, const double* __restrict__ v, double* __restrict__ pmin,
-                                        double* __restrict__ psum, int c, double* smem, double* sh)
+                                        double* __restrict__ psum, double* smem)
 {
+    __shared__ double sh[P::NT];
+    const int c = P::cone(C);
     const int k = C.psd_dim[c], off = C.off[c];
-    if (k == 0) { if (threadIdx.x == 0) { *pmin = DBL_MAX; *psum = 0.0; } return; }
-    psd_load_mat(smem, v + off, 1.0, k);
+    if constexpr (!P::kBig) if (k == 0) { if (threadIdx.x == 0) { pmin[blockIdx.x] = DBL_MAX; psum[blockIdx.x] = 0.0; } return; }
+    psd_load_mat<P::NT>(smem, v + off, 1.0, k);
     __syncthreads();
-    sym_jacobi_eig(smem, k, sh);
-    if (threadIdx.x == 0) {
-        double mn = DBL_MAX, sum = 0.0;
-        for (int i = 0; i < k; ++i) {
-            const double e = smem[i + i * k];
-            mn = fmin(mn, e);
-            if (e > 0.0) sum += e;
-        }
-        *pmin = mn;
-        *psum = sum;
-    }
-}
-__global__ __launch_bounds__(256) void k_margins_psd(ConeDev C, const double* __restrict__ v, double* __restrict__ pmin,
-                                                    double* __restrict__ psum)
-{
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    __shared__ double sh[256];
-    margins_psd_body(C, v, pmin + blockIdx.x, psum + blockIdx.x, C.psd_list[blockIdx.x], smem, sh);
-}
-
-__global__ __launch_bounds__(kPsdBigThreads) void k_margins_psd_big(ConeDev C, const double* __restrict__ v,
-                                                                    double* __restrict__ pmin, double* __restrict__ psum)
-{
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    __shared__ double sh[kPsdBigThreads];
-    const int c = C.psdb_list[blockIdx.x];
-    const int k = C.psd_dim[c], off = C.off[c];
-    psd_load_mat<kPsdBigThreads>(smem, v + off, 1.0, k);
-    __syncthreads();
-    sym_jacobi_eig<kPsdBigThreads>(smem, k, sh);
+    sym_jacobi_eig<P::NT>(smem, k, sh);
     if (threadIdx.x == 0) {
         double mn = DBL_MAX, sum = 0.0;
         for (int i = 0; i < k; ++i) {
@@ -617,6 +378,18 @@ __global__ __launch_bounds__(kPsdBigThreads) void k_margins_psd_big(ConeDev C, c
         pmin[blockIdx.x] = mn;
         psum[blockIdx.x] = sum;
     }
+}
+__global__ __launch_bounds__(PsdSmall::NT) void k_margins_psd(ConeDev C, const double* __restrict__ v, double* __restrict__ pmin,
+                                                              double* __restrict__ psum)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    margins_psd_body<PsdSmall>(C, v, pmin, psum, smem);
+}
+__global__ __launch_bounds__(PsdBig::NT) void k_margins_psd_big(ConeDev C, const double* __restrict__ v,
+                                                                double* __restrict__ pmin, double* __restrict__ psum)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    margins_psd_body<PsdBig>(C, v, pmin, psum, smem);
 }
 
 __global__ __launch_bounds__(256) void k_margins_finish(const double* __restrict__ pmin, const double* __restrict__ psum,
@@ -647,7 +420,7 @@ __device__ inline void unit_shift_row(const ConeDev& C, double* __restrict__ v, 
     else if (kind == 2) hit = i == C.off[c];
     else {
         int r, cl;
-        st_svec_index(i - C.off[c], r, cl);
+        svec_index(i - C.off[c], r, cl);
         hit = r == cl;
     }
     if (!hit) return;
@@ -700,7 +473,7 @@ __global__ __launch_bounds__(256) void k_batch_step_ds_psd(ConeDev C, ConeState 
     extern __shared__ __attribute__((aligned(16))) double smem[];
     const int c = C.psd_list[blockIdx.x];
     const int b = B.cone_mem[c];
-    step_ds_psd_body(C, S, out, dz, ds, sigma_mu[b], m_corr[b], 1, c, smem);
+    step_ds_psd_body<PsdSmall>(C, S, out, dz, ds, sigma_mu[b], m_corr[b], 1, c, smem);
 }
 
 // slots: [0, nwg) the elementwise workgroups, then a slot per second-order cone
@@ -725,14 +498,6 @@ __global__ __launch_bounds__(256) void k_batch_step_length(ConeDev C, BatchDev B
     }
     const int ci = ((int)blockIdx.x - ge) * 4 + (int)(threadIdx.x >> 6);
     if (ci < C.nsoc) step_length_soc_body(C, dz, ds, z, s, partial + ge + ci, ci, threadIdx.x & 63);
-}
-
-__global__ __launch_bounds__(256) void k_batch_step_length_psd(ConeDev C, ConeState S, const double* __restrict__ dz,
-                                                               const double* __restrict__ ds, double* __restrict__ slots)
-{
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    __shared__ double sh[256];
-    step_length_psd_body(C, S, dz, ds, slots + blockIdx.x, C.psd_list[blockIdx.x], smem, sh);
 }
 
 // lane-strided over member b's three slot ranges, in slot order
@@ -784,14 +549,6 @@ __global__ __launch_bounds__(256) void k_batch_margins(ConeDev C, BatchDev B, co
     }
     const int ci = ((int)blockIdx.x - ge) * 4 + (int)(threadIdx.x >> 6);
     if (ci < C.nsoc) margins_soc_body(C, v, pmin + ge + ci, psum + ge + ci, ci, threadIdx.x & 63);
-}
-
-__global__ __launch_bounds__(256) void k_batch_margins_psd(ConeDev C, const double* __restrict__ v, double* __restrict__ pmin,
-                                                           double* __restrict__ psum)
-{
-    extern __shared__ __attribute__((aligned(16))) double smem[];
-    __shared__ double sh[256];
-    margins_psd_body(C, v, pmin + blockIdx.x, psum + blockIdx.x, C.psd_list[blockIdx.x], smem, sh);
 }
 
 // wave = member: (min_margin, pos_margin) into rec, and the member's branch of _shift_to_cone_interior!
@@ -1094,99 +851,50 @@ __global__ __launch_bounds__(256) void k_barrier(ConeDev C, const double* __rest
     }
 }
 
-// PSD cones (coneops_psdtrianglecone.jl:256-295): -logdet of mat(z + alpha dz) and of mat(s + alpha ds) by a right-looking
-// Cholesky factorisation in LDS (k x k doubles), +inf where one fails
-__global__ __launch_bounds__(256) void k_barrier_psd(ConeDev C, const double* __restrict__ z, const double* __restrict__ s,
-                                                     const double* __restrict__ dz, const double* __restrict__ ds, double alpha,
-                                                     double* __restrict__ slots)
+// PSD cones (coneops_psdtrianglecone.jl:256-295): -logdet of mat(z + alpha dz) and of mat(s + alpha ds) by psd_cholesky
+// in LDS (k x k doubles, either class), +inf where one fails
+template <class P>
+__device__ inline void barrier_psd_body(const ConeDev& C, const double* __restrict__ z, const double* __restrict__ s,
+                                        const double* __restrict__ dz, const double* __restrict__ ds, double alpha,
+                                        double* __restrict__ slots, double* X)
 {
-    extern __shared__ __attribute__((aligned(16))) double smem[];
     __shared__ int sh_fail;
     const int tid = threadIdx.x;
-    const int c = C.psd_list[blockIdx.x];
+    const int c = P::cone(C);
     const int k = C.psd_dim[c], off = C.off[c], t = k * (k + 1) / 2;
-    if (k == 0) { if (tid == 0) slots[blockIdx.x] = 0.0; return; }
-    double* X = smem;
+    if constexpr (!P::kBig) if (k == 0) { if (tid == 0) slots[blockIdx.x] = 0.0; return; }
     if (tid == 0) sh_fail = 0;
     double bar = 0.0;                                                  // (thread 0's)
     for (int comp = 0; comp < 2; ++comp) {
         const double* x = (comp == 0 ? z : s) + off;
         const double* dx = (comp == 0 ? dz : ds) + off;
-        for (int idx = tid; idx < t; idx += 256) {
+        for (int idx = tid; idx < t; idx += P::NT) {
             int r, cl;
-            st_svec_index(idx, r, cl);
+            svec_index(idx, r, cl);
             const double v = (x[idx] + alpha * dx[idx]) * (r == cl ? 1.0 : kIs2);
             X[r + cl * k] = v;
             X[cl + r * k] = v;
         }
         __syncthreads();
-        for (int j = 0; j < k; ++j) {
-            const double d = X[j + j * k];
-            if (!(d > 0.0)) { if (tid == 0) sh_fail = 1; }
-            __syncthreads();
-            if (sh_fail) break;
-            const double sd = sqrt(d);
-            for (int i = j + 1 + tid; i < k; i += 256) X[i + j * k] /= sd;
-            if (tid == 0) { X[j + j * k] = sd; bar -= 2.0 * log(sd); }
-            __syncthreads();
-            const int w = k - j - 1;
-            for (int idx = tid; idx < w * w; idx += 256) {
-                const int a = j + 1 + idx / w, b = j + 1 + idx % w;
-                if (a >= b) X[a + b * k] -= X[a + j * k] * X[b + j * k];
-            }
-            __syncthreads();
-        }
+        psd_cholesky<P::NT>(X, k, &sh_fail, [&](double sd) { bar -= 2.0 * log(sd); });
         if (sh_fail) break;
     }
     if (tid == 0) slots[blockIdx.x] = sh_fail ? HUGE_VAL : bar;
 }
-
-// ... of the big class: the one matrix still fits LDS; kPsdBigThreads threads
-__global__ __launch_bounds__(kPsdBigThreads) void k_barrier_psd_big(ConeDev C, const double* __restrict__ z,
-                                                                    const double* __restrict__ s,
-                                                                    const double* __restrict__ dz,
-                                                                    const double* __restrict__ ds, double alpha,
-                                                                    double* __restrict__ slots)
+__global__ __launch_bounds__(PsdSmall::NT) void k_barrier_psd(ConeDev C, const double* __restrict__ z, const double* __restrict__ s,
+                                                              const double* __restrict__ dz, const double* __restrict__ ds,
+                                                              double alpha, double* __restrict__ slots)
 {
     extern __shared__ __attribute__((aligned(16))) double smem[];
-    __shared__ int sh_fail;
-    constexpr int NT = kPsdBigThreads;
-    const int tid = threadIdx.x;
-    const int c = C.psdb_list[blockIdx.x];
-    const int k = C.psd_dim[c], off = C.off[c], t = k * (k + 1) / 2;
-    double* X = smem;
-    if (tid == 0) sh_fail = 0;
-    double bar = 0.0;                                                  // (thread 0's)
-    for (int comp = 0; comp < 2; ++comp) {
-        const double* x = (comp == 0 ? z : s) + off;
-        const double* dx = (comp == 0 ? dz : ds) + off;
-        for (int idx = tid; idx < t; idx += NT) {
-            int r, cl;
-            st_svec_index(idx, r, cl);
-            const double v = (x[idx] + alpha * dx[idx]) * (r == cl ? 1.0 : kIs2);
-            X[r + cl * k] = v;
-            X[cl + r * k] = v;
-        }
-        __syncthreads();
-        for (int j = 0; j < k; ++j) {
-            const double d = X[j + j * k];
-            if (!(d > 0.0)) { if (tid == 0) sh_fail = 1; }
-            __syncthreads();
-            if (sh_fail) break;
-            const double sd = sqrt(d);
-            for (int i = j + 1 + tid; i < k; i += NT) X[i + j * k] /= sd;
-            if (tid == 0) { X[j + j * k] = sd; bar -= 2.0 * log(sd); }
-            __syncthreads();
-            const int w = k - j - 1;
-            for (int idx = tid; idx < w * w; idx += NT) {
-                const int a = j + 1 + idx / w, b = j + 1 + idx % w;
-                if (a >= b) X[a + b * k] -= X[a + j * k] * X[b + j * k];
-            }
-            __syncthreads();
-        }
-        if (sh_fail) break;
-    }
-    if (tid == 0) slots[blockIdx.x] = sh_fail ? HUGE_VAL : bar;
+    barrier_psd_body<PsdSmall>(C, z, s, dz, ds, alpha, slots, smem);
+}
+__global__ __launch_bounds__(PsdBig::NT) void k_barrier_psd_big(ConeDev C, const double* __restrict__ z,
+                                                                const double* __restrict__ s, const double* __restrict__ dz,
+                                                                const double* __restrict__ ds, double alpha,
+                                                                double* __restrict__ slots)
+{
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    barrier_psd_body<PsdBig>(C, z, s, dz, ds, alpha, slots, smem);
 }
 
 __global__ __launch_bounds__(256) void k_barrier_ns(ConeDev C, const double* __restrict__ z, const double* __restrict__ s,
@@ -1238,7 +946,7 @@ __global__ __launch_bounds__(256) void k_unit_initialization(ConeDev C, double* 
         else if (kind == 2) v = j == 0 ? 1.0 : 0.0;
         else if (kind == 3) {
             int r, cl;
-            st_svec_index(j, r, cl);
+            svec_index(j, r, cl);
             v = r == cl ? 1.0 : 0.0;
         } else if (kind == 4) v = j == 0 ? -1.051383945322714 : j == 1 ? 0.556409619469370 : 1.258967884768947;
         else if (kind == 5) {
@@ -1490,12 +1198,23 @@ inline int step_grid(int m)
 }
 
 inline size_t step_psd_lds(const ConeDev& C) { return (size_t)4 * C.psd_kmax * C.psd_kmax * sizeof(double); }
-// the big PSD class: n matrices of its largest side; the attribute is set once for all four kernels
+// the big PSD class: n matrices of its largest side
 inline size_t step_psdb_lds(const ConeDev& C, int n) { return (size_t)n * C.psdb_kmax * C.psdb_kmax * sizeof(double); }
-inline void step_psdb_set_lds()
+// the dynamic LDS of this file's PSD kernels beyond the 64 KiB default, once per device and class
+inline void step_psd_set_lds(bool big)
 {
-    static PerDeviceOnce once;
-    once.run([]() {
+    static PerDeviceOnce once_small, once_big;
+    if (!big) {
+        once_small.run([]() {
+            hipError_t e = set_max_lds(k_step_ds_psd, 150 * 1024);
+            if (e == hipSuccess) e = set_max_lds(k_batch_step_ds_psd, 150 * 1024);
+            if (e == hipSuccess) e = set_max_lds(k_step_length_psd, 150 * 1024);
+            if (e == hipSuccess) e = set_max_lds(k_margins_psd, 150 * 1024);
+            return e;
+        });
+        return;
+    }
+    once_big.run([]() {
         const int one = kPsdBigMaxDim * kPsdBigMaxDim * (int)sizeof(double);
         hipError_t e = set_max_lds(k_step_ds_psd_big, 2 * one);
         if (e == hipSuccess) e = set_max_lds(k_step_length_psd_big, 2 * one);
@@ -1512,13 +1231,12 @@ void launch_step_ds(const ConeDev& C, const ConeState& S, double* out, const dou
 {
     if (m <= 0) return;
     if (C.npsd > 0) {
-        static PerDeviceOnce once;
-        once.run([]() { return set_max_lds(k_step_ds_psd, 150 * 1024); });
+        step_psd_set_lds(false);
         hipLaunchKernelGGL(k_step_ds_psd, dim3(C.npsd), dim3(256), combined ? step_psd_lds(C) : 0, st, C, S, out, step_z, step_s,
                            sigma_mu, m_corr, combined ? 1 : 0);
     }
     if (C.npsdb > 0) {
-        step_psdb_set_lds();
+        step_psd_set_lds(true);
         hipLaunchKernelGGL(k_step_ds_psd_big, dim3(C.npsdb), dim3(kPsdBigThreads), combined ? step_psdb_lds(C, 2) : 0, st, C, S,
                            out, step_z, step_s, sigma_mu, m_corr, combined ? 1 : 0);
     }
@@ -1533,12 +1251,11 @@ void launch_step_length(const ConeDev& C, const ConeState& S, const double* dz, 
 {
     const int ge = step_grid(m), gs = (C.nsoc + 3) / 4;
     if (C.npsd > 0) {
-        static PerDeviceOnce once;
-        once.run([]() { return set_max_lds(k_step_length_psd, 150 * 1024); });
+        step_psd_set_lds(false);
         hipLaunchKernelGGL(k_step_length_psd, dim3(C.npsd), dim3(256), step_psd_lds(C), st, C, S, dz, ds, partial + ge + C.nsoc);
     }
     if (C.npsdb > 0) {
-        step_psdb_set_lds();
+        step_psd_set_lds(true);
         hipLaunchKernelGGL(k_step_length_psd_big, dim3(C.npsdb), dim3(kPsdBigThreads), step_psdb_lds(C, 2), st, C, S, dz, ds,
                            partial + ge + C.nsoc + C.npsd);
     }
@@ -1553,13 +1270,12 @@ void launch_margins(const ConeDev& C, const double* v, double* partial, double* 
     double* pmin = partial;
     double* psum = partial + np;
     if (C.npsd > 0) {
-        static PerDeviceOnce once;
-        once.run([]() { return set_max_lds(k_margins_psd, 150 * 1024); });
+        step_psd_set_lds(false);
         hipLaunchKernelGGL(k_margins_psd, dim3(C.npsd), dim3(256), (size_t)C.psd_kmax * C.psd_kmax * sizeof(double), st, C, v,
                            pmin + ge + C.nsoc, psum + ge + C.nsoc);
     }
     if (C.npsdb > 0) {
-        step_psdb_set_lds();
+        step_psd_set_lds(true);
         hipLaunchKernelGGL(k_margins_psd_big, dim3(C.npsdb), dim3(kPsdBigThreads), step_psdb_lds(C, 1), st, C, v,
                            pmin + ge + C.nsoc + C.npsd, psum + ge + C.nsoc + C.npsd);
     }
@@ -1578,8 +1294,7 @@ void launch_batch_step_ds(const ConeDev& C, const ConeState& S, const BatchDev& 
 {
     if (m <= 0) return;
     if (C.npsd > 0) {
-        static PerDeviceOnce once;
-        once.run([]() { return set_max_lds(k_batch_step_ds_psd, 150 * 1024); });
+        step_psd_set_lds(false);
         hipLaunchKernelGGL(k_batch_step_ds_psd, dim3(C.npsd), dim3(256), step_psd_lds(C), st, C, S, B, out, step_z, step_s, sigma_mu,
                            m_corr);
     }
@@ -1594,9 +1309,8 @@ void launch_batch_step_length(const ConeDev& C, const ConeState& S, const BatchD
     (void)m;
     const int ge = B.z256.nwg, gs = (C.nsoc + 3) / 4;
     if (C.npsd > 0) {
-        static PerDeviceOnce once;
-        once.run([]() { return set_max_lds(k_batch_step_length_psd, 150 * 1024); });
-        hipLaunchKernelGGL(k_batch_step_length_psd, dim3(C.npsd), dim3(256), step_psd_lds(C), st, C, S, dz, ds, partial + ge + C.nsoc);
+        step_psd_set_lds(false);
+        hipLaunchKernelGGL(k_step_length_psd, dim3(C.npsd), dim3(256), step_psd_lds(C), st, C, S, dz, ds, partial + ge + C.nsoc);
     }
     if (ge + gs > 0) hipLaunchKernelGGL(k_batch_step_length, dim3(ge + gs), dim3(256), 0, st, C, B, dz, ds, z, s, partial);
     hipLaunchKernelGGL(k_batch_step_length_finish, dim3((B.nb + 3) / 4), dim3(256), 0, st, C, B, (const double*)partial, scal, rec);
@@ -1609,9 +1323,8 @@ void launch_batch_shift_to_interior(const ConeDev& C, const BatchDev& B, double*
     double* pmin = partial;
     double* psum = partial + batch_step_slots(C, B);
     if (C.npsd > 0) {
-        static PerDeviceOnce once;
-        once.run([]() { return set_max_lds(k_batch_margins_psd, 150 * 1024); });
-        hipLaunchKernelGGL(k_batch_margins_psd, dim3(C.npsd), dim3(256), (size_t)C.psd_kmax * C.psd_kmax * sizeof(double), st, C,
+        step_psd_set_lds(false);
+        hipLaunchKernelGGL(k_margins_psd, dim3(C.npsd), dim3(256), (size_t)C.psd_kmax * C.psd_kmax * sizeof(double), st, C,
                            (const double*)v, pmin + ge + C.nsoc, psum + ge + C.nsoc);
     }
     if (ge + gs > 0) hipLaunchKernelGGL(k_batch_margins, dim3(ge + gs), dim3(256), 0, st, C, B, (const double*)v, pmin, psum);
@@ -1683,7 +1396,7 @@ void launch_barrier(const ConeDev& C, const double* z, const double* s, const do
         hipLaunchKernelGGL(k_gp_barrier, dim3((C.ngp_small + 3) / 4 + C.ngp_big), dim3(256), 0, st, C, z, s, dz, ds, alpha,
                            pbar + ge + C.nsoc + C.npsd + gn);
     if (C.npsdb > 0) {
-        step_psdb_set_lds();
+        step_psd_set_lds(true);
         hipLaunchKernelGGL(k_barrier_psd_big, dim3(C.npsdb), dim3(kPsdBigThreads), step_psdb_lds(C, 1), st, C, z, s, dz, ds, alpha,
                            pbar + ge + C.nsoc + C.npsd + gn + ngp);
     }

@@ -1,6 +1,6 @@
 """PSD cones of side 49 ... 96 on an opted-in handle (hipkkt_kkt_enable_large_psd): the big-class scaling kernel, the
 many-workgroup Hs launch and the big-class mul_Hs (k_cone_psd_big, k_psd_hs_big, k_mul_Hs_psd_big), at level B, and K formed
-from the device's own scaling at level C (k_psd_A_from_R_big and the same Hs launch).
+from the device's own scaling at level C (k_psd_A_from_R over psdb_list and the same Hs launch).
 
 Sides: 49 (the smallest new side, odd: it has the dummy pair), 64 (exactly 32 column pairs, the most a 256-thread
 workgroup could rotate), 65 and 66 (the first sides past that, odd and even), 96 (the cap), 97 (refused).  Sides up to
