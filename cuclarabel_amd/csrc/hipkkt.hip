@@ -314,6 +314,11 @@ private:
         a.ld_b = a.ld_out = a.ld_xp = a.ld_uvec = 0;
         a.top_limit = 5000000;       // (the multi-column path has no persistent kernel)
         a.tk_pos = nullptr; a.tk_sl = nullptr; a.tbase = nullptr; a.xf = nullptr; a.chain_cnt = nullptr; a.recs = nullptr; a.tall_ws = nullptr;
+        if (knobs().verbose) {       // the instances this call takes (launch_shapes.hpp: multi_shape)
+            const MultiShape ms = multi_shape(KP, knobs().multi_vec, knobs().multi_ct);
+            std::fprintf(stderr, "[hipkkt] many-column sweep: KP %d entry %s add %d wave_v %d leaf_v %d block_bs %d block_ct %d pull_rows %d\n",
+                         KP, b_rm ? "rm" : "cm", add_rm ? 1 : 0, ms.wave_v, ms.leaf_v, ms.block_bs, ms.block_ct, n_pull_rows);
+        }
         launch_pull_leaves_multi(a, n_pull_rows, KP, stream);        // (the pulled leaves' terms, summed per receiving row)
         for (const Launch& L : sch.launches) launch_fwd_multi(a, L.begin, L.count, L.small, L.ncmax, KP, stream);
         for (size_t q = sch.launches.size(); q-- > 0;) {
@@ -1683,6 +1688,7 @@ private:
                 }
                 mptr[(size_t)nloc] = slot;
                 n_pull_rows = (int)prs.size();
+                const size_t n_pull_terms = hcol.size();      // (before the padding entry of an empty list)
                 if (hcol.empty()) { hcol.push_back(0); hl.push_back(0); }
                 if (prs.empty()) prs.push_back(0);
                 std::vector<int> hrow(hcol.size());
@@ -1691,7 +1697,7 @@ private:
                 d_pr_ptr.upload(prp); d_pr_slot.upload(prs);
                 if (knobs().verbose)
                     std::fprintf(stderr, "[hipkkt] many-column sweeps: %lld of %lld contribution rows pulled from one-column leaves into %d sums\n",
-                                 (long long)(hcol.size()), (long long)ptr[(size_t)nloc], n_pull_rows);
+                                 (long long)n_pull_terms, (long long)ptr[(size_t)nloc], n_pull_rows);
             }
         }
         d_perm.upload(S.perm);

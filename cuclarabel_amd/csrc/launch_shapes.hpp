@@ -88,6 +88,24 @@ inline int chain_seg_wgs(int nblock, int nwave, int ntiny)
     return nblock + (nwave + kChainBS / 64 - 1) / (kChainBS / 64) + (ntiny + kChainBS / 8 - 1) / (kChainBS / 8);
 }
 
+// many-column sweeps (solve_kernels.hip, "several right-hand sides"): the kernel instances one call takes, from the padded
+// column count KP (a multiple of 16) and the knobs HIPKKT_MULTI_VEC / HIPKKT_MULTI_CT.  One-wave fronts: wave_v columns
+// per lane (2 where a wave's 128 columns divide KP).  Pulled leaves, forward and backward: leaf_v columns per lane (4 where
+// 64 | KP unless the knob caps it, else 2 where 32 | KP, else 1).  Block-class fronts: block_bs threads and block_ct column
+// tiles of 16 per workgroup (two tiles from 256 columns on where 32 | KP, unless the knob says 1; 512 threads below 128
+// columns: few column blocks, so more waves per front).
+struct MultiShape { int wave_v; int leaf_v; int block_bs; int block_ct; };
+inline MultiShape multi_shape(int KP, int multi_vec, int multi_ct)
+{
+    MultiShape m;
+    m.wave_v = KP % 128 == 0 ? 2 : 1;
+    m.leaf_v = (KP % 64 == 0 && multi_vec >= 4) ? 4 : (KP % 32 == 0 ? 2 : 1);
+    const bool wide = multi_ct != 1 && KP % 32 == 0 && KP >= 256;
+    m.block_ct = wide ? 2 : 1;
+    m.block_bs = (wide || KP >= 128) ? 256 : 512;
+    return m;
+}
+
 // packed sweep records (kernels.hpp: SolveHdr): bytes of a record's header
 constexpr int kSolveHdrBytes = 64;
 struct RecSeg {                  // the records of one kernel launch's fronts, by size class: 0 block-class, 1 one-wave, 2 tiny

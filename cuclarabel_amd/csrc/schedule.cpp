@@ -101,6 +101,11 @@ static void form_launches(const Symbolic& S, const DeviceLimits& dev, int64_t pa
             L.count = (int)v.size();
             L.small = cls == 1;
             L.level = level_no;
+            // (a level is a front's height above its leaves -- symbolic.cpp, step 9 -- so level 0 holds every childless front
+            //  and nothing else: the many-column backward sweep starts the pulled leaves' kernel for level-0 launches only,
+            //  launch_bwd_multi, and the engine flags childless fronts only)
+            for (int s : v)
+                if ((level_no == 0) != (S.child_ptr[s + 1] == S.child_ptr[s])) throw std::logic_error("level 0 must hold the childless fronts and only them");
             L.ntiny = cls == 1 ? ntiny_level : 0;
             int fmax = 0, slice = 0;
             for (int s : v) {

@@ -2070,10 +2070,11 @@ __global__ __launch_bounds__(256) void k_pull_leaves_m(SolveArgs A, int nrows, i
 void launch_pull_leaves_multi(const SolveArgs& a, int nrows, int KP, hipStream_t st)
 {
     if (nrows <= 0) return;
-    const int vmax = knobs().multi_vec;
-    if (KP % 64 == 0 && vmax >= 4) hipLaunchKernelGGL(k_pull_leaves_m<4>, dim3((nrows + 15) / 16, KP / 64), dim3(256), 0, st, a, nrows, KP);
-    else if (KP % 32 == 0) hipLaunchKernelGGL(k_pull_leaves_m<2>, dim3((nrows + 15) / 16, KP / 32), dim3(256), 0, st, a, nrows, KP);
-    else hipLaunchKernelGGL(k_pull_leaves_m<1>, dim3((nrows + 15) / 16, KP / 16), dim3(256), 0, st, a, nrows, KP);
+    const int v = multi_shape(KP, knobs().multi_vec, knobs().multi_ct).leaf_v;
+    const dim3 grid((nrows + 15) / 16, KP / (16 * v));
+    if (v == 4) hipLaunchKernelGGL(k_pull_leaves_m<4>, grid, dim3(256), 0, st, a, nrows, KP);
+    else if (v == 2) hipLaunchKernelGGL(k_pull_leaves_m<2>, grid, dim3(256), 0, st, a, nrows, KP);
+    else hipLaunchKernelGGL(k_pull_leaves_m<1>, grid, dim3(256), 0, st, a, nrows, KP);
 }
 
 // Backward step of the PULLED leaves of a launch (one column, a handful of rows: TreeDev::hp_*): x_c = y_c / d_c - sum_r
@@ -2495,51 +2496,42 @@ void launch_permute_out(double* X, int64_t ldx, const double* Xp, int KP, const 
 void launch_fwd_multi(const SolveArgs& a, int begin, int count, bool small, int ncmax, int KP, hipStream_t st)
 {
     if (count <= 0) return;
+    const MultiShape ms = multi_shape(KP, knobs().multi_vec, knobs().multi_ct);
     if (small) {
-        if (KP % 128 == 0) hipLaunchKernelGGL(k_fwd_wave_m<2>, dim3((count + 3) / 4, KP / 128), dim3(256), 0, st, a, begin, count, KP);
+        if (ms.wave_v == 2) hipLaunchKernelGGL(k_fwd_wave_m<2>, dim3((count + 3) / 4, KP / 128), dim3(256), 0, st, a, begin, count, KP);
         else hipLaunchKernelGGL(k_fwd_wave_m<1>, dim3((count + 3) / 4, (KP + 63) / 64), dim3(256), 0, st, a, begin, count, KP);
         return;
     }
-    // many column blocks: smaller workgroups, more fronts in flight (measured: 256 columns 21.4 vs 23.4 ms)
-    const bool wide = knobs().multi_ct != 1;
-    if (wide && KP % 32 == 0 && KP >= 256) {         // (measured: 128 columns 6.2 vs 6.4 ms, 512 columns 19.8 vs 19.1)
-        const size_t lds = (size_t)((ncmax + 3) & ~3) * 32 * sizeof(double);
-        const dim3 grid(8, ((count + 7) / 8) * (KP / 32));
-        hipLaunchKernelGGL((k_fwd_block_m<256, 2>), grid, dim3(256), lds, st, a, begin, count, KP);
-        return;
-    }
-    const size_t lds = (size_t)((ncmax + 3) & ~3) * 16 * sizeof(double);
-    const dim3 grid(8, ((count + 7) / 8) * (KP / kMultiCB));
-    if (KP >= 128) hipLaunchKernelGGL((k_fwd_block_m<256, 1>), grid, dim3(256), lds, st, a, begin, count, KP);
+    // many column blocks: smaller workgroups, more fronts in flight (measured: 256 columns 21.4 vs 23.4 ms); two column
+    // tiles per workgroup (measured: 128 columns 6.2 vs 6.4 ms, 512 columns 19.8 vs 19.1)
+    const size_t lds = (size_t)((ncmax + 3) & ~3) * 16 * ms.block_ct * sizeof(double);
+    const dim3 grid(8, ((count + 7) / 8) * (KP / (kMultiCB * ms.block_ct)));
+    if (ms.block_ct == 2) hipLaunchKernelGGL((k_fwd_block_m<256, 2>), grid, dim3(256), lds, st, a, begin, count, KP);
+    else if (ms.block_bs == 256) hipLaunchKernelGGL((k_fwd_block_m<256, 1>), grid, dim3(256), lds, st, a, begin, count, KP);
     else hipLaunchKernelGGL((k_fwd_block_m<512, 1>), grid, dim3(512), lds, st, a, begin, count, KP);
 }
 void launch_bwd_multi(const SolveArgs& a, int begin, int count, bool small, int ncmax, int KP, hipStream_t st, bool leaves)
 {
     if (count <= 0) return;
+    const MultiShape ms = multi_shape(KP, knobs().multi_vec, knobs().multi_ct);
     if (small) {
-        if (KP % 128 == 0) hipLaunchKernelGGL(k_bwd_wave_m<2>, dim3((count + 3) / 4, KP / 128), dim3(256), 0, st, a, begin, count, KP);
+        if (ms.wave_v == 2) hipLaunchKernelGGL(k_bwd_wave_m<2>, dim3((count + 3) / 4, KP / 128), dim3(256), 0, st, a, begin, count, KP);
         else hipLaunchKernelGGL(k_bwd_wave_m<1>, dim3((count + 3) / 4, (KP + 63) / 64), dim3(256), 0, st, a, begin, count, KP);
         // the launch's pulled leaves (tree level 0 only: they have no children)
         if (leaves) {
-            const int vmax = knobs().multi_vec;
-            if (KP % 64 == 0 && vmax >= 4) hipLaunchKernelGGL(k_bwd_leaf_m<4>, dim3((count + 15) / 16, KP / 64), dim3(256), 0, st, a, begin, count, KP);
-            else if (KP % 32 == 0) hipLaunchKernelGGL(k_bwd_leaf_m<2>, dim3((count + 15) / 16, KP / 32), dim3(256), 0, st, a, begin, count, KP);
-            else hipLaunchKernelGGL(k_bwd_leaf_m<1>, dim3((count + 15) / 16, KP / 16), dim3(256), 0, st, a, begin, count, KP);
+            const dim3 grid((count + 15) / 16, KP / (16 * ms.leaf_v));
+            if (ms.leaf_v == 4) hipLaunchKernelGGL(k_bwd_leaf_m<4>, grid, dim3(256), 0, st, a, begin, count, KP);
+            else if (ms.leaf_v == 2) hipLaunchKernelGGL(k_bwd_leaf_m<2>, grid, dim3(256), 0, st, a, begin, count, KP);
+            else hipLaunchKernelGGL(k_bwd_leaf_m<1>, grid, dim3(256), 0, st, a, begin, count, KP);
         }
         return;
     }
-    // at most max(8, nt) partial tiles of 16 x 16
+    // at most max(8, nt) partial tiles of 16 x 16 per column tile
     const int nt = (ncmax + 15) >> 4;
-    const bool wide = knobs().multi_ct != 1;
-    if (wide && KP % 32 == 0 && KP >= 256) {         // (measured: 128 columns 6.2 vs 6.4 ms, 512 columns 19.8 vs 19.1)
-        const size_t lds = (size_t)std::max(8, nt) * 256 * 2 * sizeof(double);
-        const dim3 grid(8, ((count + 7) / 8) * (KP / 32));
-        hipLaunchKernelGGL((k_bwd_block_m<256, 2>), grid, dim3(256), lds, st, a, begin, count, KP);
-        return;
-    }
-    const size_t lds = (size_t)std::max(8, nt) * 256 * sizeof(double);
-    const dim3 grid(8, ((count + 7) / 8) * (KP / kMultiCB));
-    if (KP >= 128) hipLaunchKernelGGL((k_bwd_block_m<256, 1>), grid, dim3(256), lds, st, a, begin, count, KP);
+    const size_t lds = (size_t)std::max(8, nt) * 256 * ms.block_ct * sizeof(double);
+    const dim3 grid(8, ((count + 7) / 8) * (KP / (kMultiCB * ms.block_ct)));
+    if (ms.block_ct == 2) hipLaunchKernelGGL((k_bwd_block_m<256, 2>), grid, dim3(256), lds, st, a, begin, count, KP);
+    else if (ms.block_bs == 256) hipLaunchKernelGGL((k_bwd_block_m<256, 1>), grid, dim3(256), lds, st, a, begin, count, KP);
     else hipLaunchKernelGGL((k_bwd_block_m<512, 1>), grid, dim3(512), lds, st, a, begin, count, KP);
 }
 

@@ -164,6 +164,31 @@ def symmetric_matvec_ld(K, x):
     return y
 
 
+_LD_CSR = {}
+
+
+def symmetric_matmat_ld(K, X):
+    """K_full @ X in long double from the upper triangle K, for a block of columns: every product and sum in long double,
+    as symmetric_matvec_ld does column by column (scipy's CSR product in extended precision; the order of a row's sums
+    differs from symmetric_matvec_ld's, both are exact to ~1e-19 relative).  The extended copy of K is kept per matrix."""
+    key = id(K)
+    if key not in _LD_CSR or _LD_CSR[key][0] is not K:
+        _LD_CSR[key] = (K, full(K).tocsr().astype(np.longdouble))
+    Y = _LD_CSR[key][1] @ np.asarray(X, dtype=np.longdouble)
+    assert Y.dtype == np.longdouble
+    return Y
+
+
+def errors_columns(case, X, Xt, B):
+    """errors() for the columns of X against known Xt and right-hand sides B: (forward errors, backward errors)."""
+    xt = np.abs(Xt).max(axis=0)
+    fwd = np.abs(X - Xt).max(axis=0) / np.where(xt > 0, xt, 1.0)
+    Bl = np.asarray(B, np.longdouble)
+    R = np.abs(Bl - symmetric_matmat_ld(case.Kt, X)).max(axis=0)
+    den = np.longdouble(norm_inf_sym(case.Kt)) * np.abs(X).max(axis=0).astype(np.longdouble) + np.abs(Bl).max(axis=0)
+    return fwd, (R / np.where(den > 0, den, 1)).astype(np.float64)
+
+
 def norm_inf_sym(K):
     K = sp.coo_matrix(K)
     a = np.abs(K.data)
@@ -425,6 +450,55 @@ def sweep_cases():
     T = {n: c for n, c in sweep_table().items()}
     A = all_cases()
     T.update({n: A[n] for n in SWEEP_EXTRA})
+    return T
+
+
+# --------------------------------------------------------------------------- cases for the many-column sweeps
+# (tests/test_gpu_multi_sweeps.py; csrc/solve_kernels.hip, "several right-hand sides")
+MULTI_FROM_SWEEP = ("tiny_n9", "tiny_n33", "wave9_n5", "wave39_n5", "wave_16_28_n5", "wave_1_38_n5", "mixed_few", "mixed_129",
+                    "tall_mixed")
+MULTI_FROM_SHAPES = ("panel_nc15", "panel_nc17", "panel_nc33", "panel_nc95", "panel_nc96", "schur_nb1", "schur_nb65", "bs_f129",
+                     "trap_96_151", "chain_nc97")
+
+# one-wave fronts around kWC = 16 (k_fwd_wave_m / k_bwd_wave_m keep a front's first 16 own unknowns in registers and re-read
+# the others from the work vector): 15, 16, 17 and 33 columns, as roots and with rows below (f <= 64, f nc + nb^2 <= 1536)
+WC_FRONTS = ((15, 29), (16, 28), (17, 24), (33, 10))
+
+
+def bwd_multi_slices(nc, f, nwaves):
+    """(nt, ns) of k_bwd_block_m for a front: nt = ceil(nc / 16) column tiles, ns = min(nwaves / nt, ceil(f / 32)) row
+    slices, at least one (csrc/solve_kernels.hip: bwd_multi_slices); nwaves = 8 below 128 columns, 4 from there on."""
+    nt = (nc + 15) // 16
+    return nt, max(1, min(nwaves // nt, (f + 31) // 32))
+
+
+# block-class fronts for that rule, f on both sides of 32 ns: name -> [(nc, nb), ...], one designed tree each, side by side
+# (nt = 1 with all eight slices needs f > 224 and a stick of 600 rows above it: left out, ns = NW / nt binds at nt = 2)
+SLICE_FRONTS = {
+    "slice_nt1": [(16, 48), (16, 49), (16, 112), (16, 113)],       # ns = 2 | 3 and 4 | 5 by f (8 waves), 2 | 3 and 4 | 4 (4 waves)
+    "slice_nt2": [(32, 32), (32, 33), (32, 96), (32, 97)],         # ns = 2 | 3 by f, 4 | 4 (8 waves); 2 | 2 (4 waves)
+    "slice_nt3": [(48, 16), (48, 17)],                             # ns = 2 | 2 of 8 waves (two idle); 1 of 4 (one idle)
+    "slice_nt5": [(80, 16), (80, 17)],                             # ns = 1: five tiles on 8 waves (three idle), on 4 in two rounds
+    "slice_nt6": [(96, 32), (96, 33)],                             # ns = 1: six tiles
+}
+
+
+def multi_forests():
+    """name -> (spec, level-0 fronts as sorted (nc, nb) pairs, classes): the new forests of the many-column tests."""
+    T = {}
+    T["wc_roots"] = (forest(*[designed(nc, 0) for nc, _ in WC_FRONTS]), sorted((nc, 0) for nc, _ in WC_FRONTS), "wave")
+    T["wc_designed"] = (forest(*[designed(nc, nb) for nc, nb in WC_FRONTS]), sorted(WC_FRONTS), "wave")
+    for name, fronts in SLICE_FRONTS.items():
+        T[name] = (forest(*[designed(nc, nb) for nc, nb in fronts]), sorted(fronts), "block")
+    return T
+
+
+def multi_specs():
+    """name -> spec of every front_shapes case of the many-column tests."""
+    S, A = sweep_table(), all_cases()
+    T = {n: S[n][0] for n in MULTI_FROM_SWEEP}
+    T.update({n: A[n][0] for n in MULTI_FROM_SHAPES})
+    T.update({n: v[0] for n, v in multi_forests().items()})
     return T
 
 

@@ -58,7 +58,7 @@ def tree(rp, sp_, ng, k, leaves, others=()):
     return cols, rows
 
 
-def make_case(cols, rows, seed):
+def make_case(cols, rows, seed, signs=None):
     """front_shapes.make_case for explicit (cols, rows) lists."""
     from cuclarabel_amd import _lib
     rng = np.random.default_rng(seed)
@@ -82,6 +82,8 @@ def make_case(cols, rows, seed):
     np.add.at(rowsum, I[off], np.abs(v[off]))
     np.add.at(rowsum, J[off], np.abs(v[off]))
     dsigns = np.where(rng.random(N) < 0.5, -1, 1).astype(np.int64)
+    if signs is not None:
+        dsigns = np.asarray(signs, np.int64)          # (after the draw, as in front_shapes: the other values do not move)
     d = ~off
     v[d] = dsigns[I[d]] * (1.0 + rowsum[I[d]] + rng.uniform(0.0, 0.5, d.sum()))
     K = sp.csc_matrix((v, (I, J)), shape=(N, N))
@@ -145,6 +147,79 @@ def cases():
 
 def case(name, seed=1):
     cols, rows, *_ = cases()[name]
+    return make_case(cols, rows, seed)
+
+
+# --------------------------------------------------------------------------- the many-column sweeps' pulled leaves
+# (csrc/hipkkt.hip, upload(): a leaf is pulled by the SOLVES when it has no children, one column, a parent, 1 <= nb <= 47
+# rows and sits in a one-wave launch -- whatever its parent's class.)  Two things follow from the schedule and shape the
+# cases:
+#   * a one-column front of nb rows is one-wave only up to nb = 38 (f + nb^2 <= 1536), so nb = 39 .. 47 is a block-class
+#     front, never in a one-wave launch and never pulled: the rule's bound of 47 cannot bind;
+#   * a level with a block-class front keeps up to 128 one-wave fronts in that front's launch (merge_small): one such front
+#     in level 0 and NO leaf of the tree is pulled.
+W16_28 = dict(rp=4, sp_=28, ng=120, k=12)        # P' = (16, 28): one-wave; twelve poison columns so that tall leaves stay out
+B16_29 = dict(rp=4, sp_=29, ng=120, k=12)        # P' = (16, 29): block-class
+B40_65 = dict(rp=32, sp_=65, ng=120, k=8)        # P' = (40, 65): block-class, f = 105
+
+
+def _rows_of(nb, shape, first=0):
+    """nb positions of the parent's front: `first` (a column of P), the others spread over its columns and update rows."""
+    f = shape["rp"] + shape["sp_"]
+    if nb == 1:
+        return [first]
+    cand = list(range(first + 1, f))
+    pos = [first] + [cand[int(i)] for i in np.round(np.linspace(0, len(cand) - 1, nb - 1))]
+    assert len(set(pos)) == nb and pos == sorted(pos)
+    return pos
+
+
+def solve_cases():
+    """name -> (cols, rows, expect): expect = (a, b, c) of the engine's "<a> of <b> contribution rows pulled from one-column
+    leaves into <c> sums" line, from the construction: a = the pulled leaves' rows, b = the rows below every front that has
+    a parent, c = the distinct parent rows the pulled leaves reach; plus `pulled`, the first columns of the pulled leaves."""
+    T = {}
+
+    def add(name, shape, leaves, others=(), pulled=None):
+        cols, rows = tree(leaves=leaves, others=others, **shape)
+        pulled = list(range(len(leaves))) if pulled is None else pulled
+        a = sum(len(leaves[i]) for i in pulled)
+        # (the root of ng > 96 columns is cut into a chain of equal panels, symbolic.cpp 7b: each link's rows are the
+        #  columns of the links above it)
+        parts = -(-shape["ng"] // 96)
+        w = -(-shape["ng"] // parts)
+        chain = sum(max(shape["ng"] - w * (i + 1), 0) for i in range(parts))
+        b = sum(len(p) for p in leaves) + sum(len(p) for _, p in others) + shape["sp_"] + chain
+        c = len({q for i in pulled for q in leaves[i]})
+        T[name] = (cols, rows, dict(a=a, b=b, c=c, pulled=[cols[i][0] for i in pulled], shape=shape))
+
+    # leaf heights around the chunks of eight of k_bwd_leaf_m (1, 8, 9) and the tallest one-wave single column (38; 31 under
+    # the 32-row front of (16, 28)), rows in the parent's columns AND its update rows (i >= nc), under a one-wave parent
+    # and two block-class ones
+    for name, shape, tall in (("heights_16_28", W16_28, 31), ("heights_16_29", B16_29, 32), ("heights_40_65", B40_65, 38)):
+        add(name, shape, [_rows_of(nb, shape, first=i % shape["rp"]) for i, nb in enumerate((tall, 1, 8, 9))])
+    # 1, 3, 4, 5 and 9 leaves on one parent row (pr_ptr is walked in chunks of four), each count on a column row p and on
+    # an update row 40 + p of P' = (40, 65)
+    many = []
+    for p, n in enumerate((1, 3, 4, 5, 9)):
+        many += [[p, 40 + p]] * n
+    add("counts_40_65", B40_65, many)
+    add("counts_16_28", W16_28, [[p, 20 + p] for p, n in enumerate((1, 3, 4)) for _ in range(n)] + [[3]] * 5)
+    # one parent row with pulled terms only (0, 2), one with pulled terms and a stored contribution of a regular child (1:
+    # the sum takes the first slot of the row's run), rows with stored contributions only (3, 50 / 25)
+    add("slots_40_65", B40_65, [[0, 1], [1, 2]], others=[(2, [1, 3, 50])])
+    add("slots_16_28", W16_28, [[0, 1], [1, 2]], others=[(2, [1, 3, 25])])
+    # nb = 39, 47 and 48: block-class leaves, and with them in level 0 the short leaves ride in their launch -- nothing pulled
+    add("ride_40_65", B40_65, [_rows_of(nb, B40_65) for nb in (1, 8, 39, 47, 48)], pulled=[])
+    # no leaf at all: gather lists of 5, 4, 3, 1 and 0 STORED contributions (k_fwd_wave_m sums them four at a time) on rows
+    # of a one-wave parent of 17 columns -- a row among its first 16 own unknowns (8), its 17th (16: past kWC) and update rows
+    add("gather_17_24", dict(rp=9, sp_=24, ng=40, k=8), [],
+        others=[(2, [0, 8, 20, 30]), (2, [0, 8, 20]), (2, [0, 8, 20]), (2, [0, 8]), (2, [0])])
+    return T
+
+
+def solve_case(name, seed=1):
+    cols, rows, _ = solve_cases()[name]
     return make_case(cols, rows, seed)
 
 

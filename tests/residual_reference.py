@@ -428,3 +428,21 @@ def refinement_case(name, k=5, scales=SCALES, abstol=None):
 # absolute tolerances: every comparison of every column of the cases is clear of them by 4 x or more (norm sequences in
 # tests/test_gpu_refinement.py; each test re-asserts the margins from its own prediction)
 REFINE_ABSTOL = {"edges64": 3e-9, "edges8": 5e-9, "accept320k": 1e-9}
+
+# The many-column sweeps' `add` store (tests/test_gpu_multi_sweeps.py): three trees of tests/front_shapes.py and
+# tests/pulled_leaf_shapes.py as P of a problem without constraints (every sign +1), under the same settings.  name ->
+# (scale of the matrix, abstol).  The tolerance sits in the gap between the second residual of the 10^0 columns (two
+# rounds) and the first residual of the 10^-6 columns (none); that gap is (eps / d) / 1e-6 wide for diagonal entries ~ d,
+# less the spread of the random columns: 24 (wc_roots), 59 (counts_40_65) and, with panel_nc33's values as they are, 9 -- not
+# enough for a 4 x margin on both sides, so that case's matrix is halved (19).  Predicted sequences (10^0 | 10^-3 | 10^-6):
+#   wc_roots      6e-5 -> 2e-9 -> 9e-14 (2 rounds) | 1e-7 -> 4e-12 (1) | 9e-11 (0)
+#   counts_40_65  2e-4 -> 1e-8 -> 1e-12 (2 rounds) | 2e-7 -> 2e-11 (1) | 2e-10 (0)
+#   panel_nc33    1e-4 -> 3e-9 -> 3e-13 (2 rounds) | 1e-7 -> 1e-11 (1) | 2e-10 (0)
+# tests/test_multi_sweeps_host.py re-checks the conditions (first residual >= 1e4 abstol, every decision clear by 4 x).
+MULTI_REFINE = {"wc_roots": (1.0, 4.6e-10), "counts_40_65": (1.0, 1.3e-9), "panel_nc33": (0.5, 6.8e-10)}
+MULTI_REFINE_COLUMNS = ((9, SCALES_ACTIVE, 59), (33, SCALES, 83))      # (k, column scales, seed)
+
+
+def multi_refine_settings(abstol):
+    return dict(static_regularization_constant=REG_EPS, static_regularization_proportional=0.0,
+                iterative_refinement_reltol=0.0, iterative_refinement_abstol=abstol, iterative_refinement_max_iter=20)

@@ -12,7 +12,14 @@
 // analysed in its natural order, as the tests' forests are, and the sweep-plan lines of HIPKKT_VERBOSE=2 are printed
 // for it as the engine prints them -- under the HIPKKT_* knobs of this process (tests/test_schedule_host.py; built
 // without sanitizers there).
+//
+// host_driver --multi-shape KP...: one line per padded column count with the kernel instances the many-column sweeps take
+// (launch_shapes.hpp: multi_shape) under HIPKKT_MULTI_VEC / HIPKKT_MULTI_CT of this process (tests/test_multi_sweeps_host.py).
+// host_driver --launches FILE...: per pattern (as for --plans) one line per launch and one per supernode, for the tests
+// that reason about which fronts the many-column sweeps pull (tests/test_multi_sweeps_host.py).
 #include "kkt_assembly.hpp"
+#include "knobs.hpp"
+#include "launch_shapes.hpp"
 #include "schedule.hpp"
 #include "symbolic.hpp"
 
@@ -76,6 +83,9 @@ static void check_schedule(const Symbolic& S, const Schedule& sch, const DeviceL
     // every front's children sit in an earlier launch
     for (int sn = 0; sn < S.nsuper; ++sn)
         require(S.sn_parent[sn] < 0 || launch_of[(size_t)sn] < launch_of[(size_t)S.sn_parent[sn]], "children in earlier launches");
+    // a childless front sits in a level-0 launch (the many-column backward sweep runs the pulled leaves' kernel there only)
+    for (int sn = 0; sn < S.nsuper; ++sn)
+        require(S.child_ptr[sn + 1] != S.child_ptr[sn] || Ls[(size_t)launch_of[(size_t)sn]].level == 0, "childless fronts in level-0 launches");
     // tiles, row slices and W lists: each launch's range follows the previous one's and holds its own fronts'
     require((int)sch.tile_base.size() == S.nsuper, "tile_base size");
     size_t tile = 0, slice = 0, tinv = 0;
@@ -185,9 +195,55 @@ static void print_plans(const char* path)
     }
 }
 
+// --launches: the launch schedule of one pattern in its natural order -- "L q level small count" per launch and
+// "S sn c0 nc nb parent nchildren launch rel..." per supernode (rel: its rows' positions in the parent's front)
+static void print_launches(const char* path)
+{
+    FILE* f = std::fopen(path, "rb");
+    if (!f) throw std::runtime_error(std::string("cannot open ") + path);
+    const auto h = rd<int64_t>(f, 2);
+    const auto colptr = rd<int64_t>(f, (size_t)h[0] + 1), rowval = rd<int64_t>(f, (size_t)h[1]);
+    std::fclose(f);
+    SymbolicOptions opt;
+    opt.ordering = ORDER_NATURAL;
+    apply_knobs(opt);
+    Symbolic S;
+    analyse((int)h[0], colptr.data(), rowval.data(), 0, opt, S);
+    const DeviceLimits dev = fixed_limits();
+    const Schedule sch = build_schedule(S, dev, opt.panel_cap, std::max(1, opt.panel_max_slices));
+    check_schedule(S, sch, dev);
+    std::printf("@@case %s launches %zu\n", path, sch.launches.size());
+    std::vector<int> launch_of((size_t)S.nsuper, -1);
+    for (size_t q = 0; q < sch.launches.size(); ++q) {
+        const Launch& L = sch.launches[q];
+        std::printf("L %zu %d %d %d\n", q, L.level, L.small ? 1 : 0, L.count);
+        for (int t = L.begin; t < L.begin + L.count; ++t) launch_of[(size_t)sch.sched[(size_t)t]] = (int)q;
+    }
+    for (int sn = 0; sn < S.nsuper; ++sn) {
+        // (c0 in the caller's numbering: the postorder may move siblings)
+        std::printf("S %d %d %d %d %d %d %d", sn, S.perm[(size_t)S.sn_start[sn]], S.sn_start[sn + 1] - S.sn_start[sn], (int)(S.rowptr[sn + 1] - S.rowptr[sn]),
+                    S.sn_parent[sn], (int)(S.child_ptr[sn + 1] - S.child_ptr[sn]), launch_of[(size_t)sn]);
+        for (int64_t q = S.rowptr[sn]; q < S.rowptr[sn + 1]; ++q) std::printf(" %d", S.rel[q]);
+        std::printf("\n");
+    }
+}
+
 int main(int argc, char** argv)
 {
     try {
+        if (argc > 1 && !std::strcmp(argv[1], "--launches")) {
+            for (int a = 2; a < argc; ++a) print_launches(argv[a]);
+            return 0;
+        }
+        if (argc > 1 && !std::strcmp(argv[1], "--multi-shape")) {
+            // the many-column sweeps' instances (launch_shapes.hpp: multi_shape) under the knobs of this process
+            for (int a = 2; a < argc; ++a) {
+                const int KP = std::atoi(argv[a]);
+                const MultiShape ms = multi_shape(KP, knobs().multi_vec, knobs().multi_ct);
+                std::printf("KP %d wave_v %d leaf_v %d block_bs %d block_ct %d\n", KP, ms.wave_v, ms.leaf_v, ms.block_bs, ms.block_ct);
+            }
+            return 0;
+        }
         if (argc > 1 && !std::strcmp(argv[1], "--plans")) {
             for (int a = 2; a < argc; ++a) print_plans(argv[a]);
             return 0;
