@@ -126,6 +126,13 @@ SYMBOLS = {
     "hipkkt_kkt_system_residuals": (C.c_int, [_P, _P, _P, _P, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "hipkkt_kkt_system_combined_rhs": (C.c_int, [_P, _P, _P, _P, _P, C.c_double]),
     "hipkkt_kkt_system_add_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_double]),
+    "hipkkt_kkt_system_set_equilibration": (C.c_int, [_P, _P, _P, C.c_double]),
+    "hipkkt_kkt_system_equilibration_dev": (C.c_int, [_P, _P, _P, _P, _P]),
+    "hipkkt_kkt_system_update_data_P": (C.c_int, [_P, _P, _P, C.c_int64]),
+    "hipkkt_kkt_system_update_data_A": (C.c_int, [_P, _P, _P, C.c_int64]),
+    "hipkkt_kkt_system_update_data_q": (C.c_int, [_P, _P, _P, C.c_int64]),
+    "hipkkt_kkt_system_update_data_b": (C.c_int, [_P, _P, _P, C.c_int64]),
+    "hipkkt_kkt_system_data_norms": (C.c_int, [_P, _P]),
     "hipkkt_kkt_system_set_problems": (C.c_int, [_P, C.c_int64, _P, _P]),
     "hipkkt_kkt_system_set_member_refinement": (C.c_int, [_P, C.c_int]),
     "hipkkt_kkt_system_member_refinement_info": (C.c_int, [_P, _P]),

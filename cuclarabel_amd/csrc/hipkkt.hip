@@ -26,6 +26,7 @@
 #include "symbolic.hpp"
 #include "knobs.hpp"
 #include "schedule.hpp"
+#include "data_update.hpp"
 #include "iterate_rows.hpp"
 #include "batch_plan.hpp"
 
@@ -1940,6 +1941,16 @@ struct hipkkt_kkt_s {
         M.slots = mr_slots.p; M.state = mr_state.p; M.normb = mr_normb.p; M.info = mr_info.p; M.agg = mr_agg.p;
         return M;
     }
+    // data updating (hipkkt_kkt_system_set_equilibration and the four hipkkt_kkt_system_update_data_* calls): the frozen
+    // scalings d, 1/d (n), e, 1/e (m) and c, every stored P / A entry's row and column (data_update.hpp) and the staging of
+    // an indexed update's positions -- all built once (data_ensure), sized for the longest update there can be
+    DBuf<double> eq_d, eq_dinv, eq_e, eq_einv, du_norms;
+    double eq_c = 1.0;
+    bool eq_ready = false;
+    DBuf<int> du_Prow, du_Pcol, du_Arow, du_Acol;
+    DBuf<int64_t> du_idx;
+    bool data_factor_stale = false;  // P or A changed since the last factorisation
+    bool data_const_stale = false;   // P, A, q or b changed since (x2, z2) and the cached constant terms were formed
     DBuf<double> hst;                // staging of the *_host entry points of level C: 3 x (n + 2 m) doubles (rhs, variables, lhs)
     bool host_vars_valid = false;    // hst holds the variables of the previous hipkkt_kkt_system_solve_host call
     // "the caller's host arrays may be reused": an event behind the uploads, waited for at the end of the call -- the
@@ -2637,6 +2648,7 @@ int hipkkt_kkt_info(hipkkt_kkt_t h, hipkkt_info* info)
 static int kkt_update_device(hipkkt_kkt_t h, bool deferred = false)
 {
     KKTAssembly& K = h->K;
+    h->data_factor_stale = false;                    // (every value of Kval, updated P and A included, is factorised below)
     int pu = h->prof.begin(0, h->stream);
     // -Hs (:225-228) and the sparse cones' columns (:235-241) in one launch, written through to the residual's copy of K
     // when that copy is current (otherwise it is gathered whole before the next residual: kkt_spmv)
@@ -3457,14 +3469,32 @@ static int sys_solve_into(hipkkt_kkt_t h, const double* rx, const double* rz, do
 }
 
 static void sys_cache_constant_terms(hipkkt_kkt_t h);
+// data updates (hipkkt_kkt_system_update_data_*) leave the factorisation (P, A) and (x2, z2) with its cached terms (all
+// four) stale until the next kkt_update! / constant-RHS solve; a call that would read either is refused before it
+// enqueues anything
+static void data_refuse_stale_factor(hipkkt_kkt_t h, const char* what)
+{
+    if (h->data_factor_stale)
+        throw ArgError(std::string("hipkkt_kkt_system_*: ") + what + " would read a factorisation that is stale since "
+                       "hipkkt_kkt_system_update_data_P / _A: call hipkkt_kkt_system_update first");
+}
+static void data_refuse_stale_solve(hipkkt_kkt_t h)
+{
+    data_refuse_stale_factor(h, "the solve");
+    if (h->data_const_stale && !h->sys_const_pending)
+        throw ArgError("hipkkt_kkt_system_*: the solve would read (x2, z2) that is stale since a hipkkt_kkt_system_update_data_* "
+                       "call: call hipkkt_kkt_system_update (or _solve_constant_rhs) first");
+}
 static int sys_flush_update_status(hipkkt_kkt_t h);
 static int sys_flush_startup(hipkkt_kkt_t h);
 static int sys_constant_rhs(hipkkt_kkt_t h)
 {
     // _kkt_solve_constant_rhs! (kktsystem.jl:80-92): (x2, z2) = K \ (-q, b)
+    data_refuse_stale_factor(h, "the constant-RHS solve");
     int rc = sys_solve_into(h, h->snegq.p, h->sb.p, h->sx2.p, h->sz2.p);
     if (rc != HIPKKT_OK) return rc;
     sys_cache_constant_terms(h);
+    h->data_const_stale = false;
     return HIPKKT_OK;
 }
 
@@ -3472,6 +3502,7 @@ int hipkkt_kkt_system_solve_constant_rhs(hipkkt_kkt_t h)
 {
     return guarded([&]() {
         if (!h || !h->sys_ready) throw ArgError("hipkkt_kkt_system_*: call hipkkt_kkt_system_init first");
+        data_refuse_stale_factor(h, "the constant-RHS solve");
         HIP_CHECK(hipSetDevice(h->device));
         h->sys_const_pending = false;
         const int rc = sys_flush_update_status(h);      // (an enqueued-only kkt_update! before it: its status is due here)
@@ -3537,6 +3568,7 @@ int hipkkt_kkt_system_solve_initial_point(hipkkt_kkt_t h, double* d_x, double* d
     return guarded([&]() {
         if (!h || !h->sys_ready) throw ArgError("hipkkt_kkt_system_*: call hipkkt_kkt_system_init first");
         if ((h->K.n && !d_x) || (h->K.m && (!d_s || !d_z))) throw ArgError("hipkkt_kkt_system_solve_initial_point: bad argument");
+        data_refuse_stale_factor(h, "the initial-point solve");
         HIP_CHECK(hipSetDevice(h->device));
         const int n = h->K.n, m = h->K.m;
         int rc = sys_flush_startup(h);
@@ -3650,6 +3682,7 @@ static int sys_solve_step(hipkkt_kkt_t h, double* d_lhs_x, double* d_lhs_s, doub
         throw ArgError("hipkkt_kkt_system_solve: bad argument");
     if (!h->scaling_valid) throw ArgError("hipkkt_kkt_system_solve: needs the cone scaling of hipkkt_kkt_system_update");
     if (h->deferred) throw ArgError("hipkkt_kkt_system_*: level C reads its scalars back (deferred status is for level B)");
+    data_refuse_stale_solve(h);
     HIP_CHECK(hipSetDevice(h->device));
     hipStream_t st = h->stream;
     // (under the member refinement rule the pairing is not taken: the rule covers single-column solves)
@@ -3676,6 +3709,7 @@ static int sys_solve_step(hipkkt_kkt_t h, double* d_lhs_x, double* d_lhs_s, doub
             launch_pack_rhs_affine(h->b.p, h->snegq.p, h->sb.p, d_rhs_x, d_var_s, d_rhs_z, n, m, h->K.p, 2, st);
             int rc = kkt_solve_core(h, false, 2, nullptr, defer);
             if (rc != HIPKKT_OK) return rc;
+            h->data_const_stale = false;
             // ((x2, z2) = column 0 outlives this solve: sys_finish_step copies it on its way)
         } else {
             // (x1, z1) = K \ (rhs.x, const - rhs.z)                              (:170-173)
@@ -4050,6 +4084,182 @@ int hipkkt_kkt_system_residuals(hipkkt_kkt_t h, const double* d_x, const double*
     });
 }
 
+// ---- data updating (update_data!, data_updating.jl:26-247): the equilibration frozen on the handle, and new P, A, q, b
+// values scaled by it on the device.  The host-only parts (index check, entry tables) are data_update.cpp's.
+static void data_ensure(hipkkt_kkt_t h)
+{
+    // the tables and the staging, once; scalings of ones until hipkkt_kkt_system_set_equilibration says otherwise
+    if (h->eq_ready) return;
+    const KKTAssembly& K = h->K;
+    const EntryTables T = build_entry_tables(K.n, K.m, K.N, K.colptr.data(), K.rowval.data(), K.mapP.data(), (int64_t)K.mapP.size(),
+                                             K.mapA.data(), (int64_t)K.mapA.size());
+    if (!T.ok) throw std::runtime_error("data updating: an entry of P or A lies outside its block of K");
+    h->du_Prow.upload(T.Prow); h->du_Pcol.upload(T.Pcol);
+    h->du_Arow.upload(T.Arow); h->du_Acol.upload(T.Acol);
+    const std::vector<double> ones((size_t)std::max(K.n, K.m), 1.0);
+    auto fill = [&](DBuf<double>& v, int len) {
+        v.alloc((size_t)len);
+        if (len) HIP_CHECK(hipMemcpy(v.p, ones.data(), (size_t)len * sizeof(double), hipMemcpyHostToDevice));
+    };
+    fill(h->eq_d, K.n); fill(h->eq_dinv, K.n); fill(h->eq_e, K.m); fill(h->eq_einv, K.m);
+    h->eq_c = 1.0;
+    h->du_idx.alloc(std::max(std::max(K.mapP.size(), K.mapA.size()), (size_t)std::max(K.n, K.m)));
+    h->du_norms.alloc(2);
+    h->eq_ready = true;
+}
+
+int hipkkt_kkt_system_set_equilibration(hipkkt_kkt_t h, const double* d, const double* e, double c)
+{
+    return guarded([&]() {
+        if (!h) throw ArgError("null handle");
+        const int n = h->K.n, m = h->K.m;
+        const bool clear = !d && !e;
+        if (!clear && ((n > 0 && !d) || (m > 0 && !e)))
+            throw ArgError("hipkkt_kkt_system_set_equilibration: d and e are both given or both NULL");
+        if (clear) c = 1.0;
+        if (!(c > 0.0) || !std::isfinite(c)) throw ArgError("hipkkt_kkt_system_set_equilibration: c must be positive and finite");
+        HIP_CHECK(hipSetDevice(h->device));
+        data_ensure(h);
+        hipStream_t st = h->stream;
+        if (clear) {
+            const std::vector<double> ones((size_t)std::max(n, m), 1.0);
+            for (DBuf<double>* v : {&h->eq_d, &h->eq_dinv, &h->eq_e, &h->eq_einv})
+                if (v->n) HIP_CHECK(hipMemcpyAsync(v->p, ones.data(), v->n * sizeof(double), hipMemcpyHostToDevice, st));
+        } else {
+            if (n) HIP_CHECK(hipMemcpyAsync(h->eq_d.p, d, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+            if (m) HIP_CHECK(hipMemcpyAsync(h->eq_e.p, e, (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
+            launch_reciprocals(h->eq_dinv.p, h->eq_d.p, n, h->eq_einv.p, h->eq_e.p, m, st);
+        }
+        HIP_CHECK(hipStreamSynchronize(st));             // the caller's (and this call's) host arrays may go away
+        h->eq_c = c;
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_equilibration_dev(hipkkt_kkt_t h, const double** d_d, const double** d_dinv, const double** d_e,
+                                        const double** d_einv)
+{
+    return guarded([&]() {
+        if (!h || !d_d || !d_dinv || !d_e || !d_einv) throw ArgError("hipkkt_kkt_system_equilibration_dev: bad argument");
+        HIP_CHECK(hipSetDevice(h->device));
+        data_ensure(h);
+        *d_d = h->eq_d.p; *d_dinv = h->eq_dinv.p; *d_e = h->eq_e.p; *d_einv = h->eq_einv.p;
+        return HIPKKT_OK;
+    });
+}
+
+// the checks the four calls share -> the device copy of the positions (nullptr: the vector form), staged behind nothing
+// but its own upload; returns false for the no-op k = 0.  Nothing of the handle is touched before every check has passed.
+static bool data_update_begin(hipkkt_kkt_t h, const char* who, const double* d_values, const int64_t* index, int64_t k,
+                              int64_t len, bool need_init, const int64_t** d_index)
+{
+    if (!h) throw ArgError("null handle");
+    if (h->deferred) throw ArgError("hipkkt_kkt_system_*: level C reads its scalars back (deferred status is for level B)");
+    if (need_init && !h->sys_ready) throw ArgError("hipkkt_kkt_system_*: call hipkkt_kkt_system_init first");
+    if (k < 0) throw ArgError(std::string(who) + ": k is negative");
+    if (k == 0) return false;                            // (data_updating.jl:61, 189, 223)
+    if (!d_values) throw ArgError(std::string(who) + ": d_values is NULL");
+    if (!index && k != len)
+        throw ArgError(std::string(who) + ": the vector form takes " + std::to_string(len) + " values, got k = " + std::to_string(k));
+    if (index) {
+        const IndexCheck ic = check_update_index(index, k, len);
+        if (ic.fault == IndexFault::OutOfRange)
+            throw ArgError(std::string(who) + ": index[" + std::to_string(ic.pos) + "] = " + std::to_string(ic.value) +
+                           " is out of range [0, " + std::to_string(len) + ")");
+        if (ic.fault == IndexFault::Repeated)
+            throw ArgError(std::string(who) + ": index[" + std::to_string(ic.pos) + "] = " + std::to_string(ic.value) +
+                           " repeats an earlier position (a parallel scatter cannot apply repeats in order)");
+    }
+    HIP_CHECK(hipSetDevice(h->device));
+    data_ensure(h);
+    *d_index = nullptr;
+    if (index) {
+        HIP_CHECK(hipMemcpyAsync(h->du_idx.p, index, (size_t)k * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+        h->host_upload_mark(h->stream);
+        *d_index = h->du_idx.p;
+    }
+    return true;
+}
+
+static int data_update_matrix(hipkkt_kkt_t h, const char* who, bool isP, const double* d_values, const int64_t* index, int64_t k)
+{
+    return guarded([&]() {
+        const int64_t len = h ? (int64_t)(isP ? h->K.mapP.size() : h->K.mapA.size()) : 0;
+        const int64_t* d_index = nullptr;
+        if (!data_update_begin(h, who, d_values, index, k, len, false, &d_index)) return HIPKKT_OK;
+        DataMatDev M;
+        M.val = isP ? h->Pval.p : h->Aval.p;
+        M.K = h->Kval.p;
+        M.fval = h->fval_dirty ? nullptr : h->fval.p;    // (through to a current image, never into a dirty one)
+        M.kpos = h->kpos.p;
+        M.map = isP ? h->mapP.p : h->mapA.p;
+        M.row = isP ? h->du_Prow.p : h->du_Arow.p;
+        M.col = isP ? h->du_Pcol.p : h->du_Acol.p;
+        M.L = isP ? h->eq_d.p : h->eq_e.p;
+        M.R = h->eq_d.p;
+        M.c = isP ? h->eq_c : 1.0;                       // (a product by 1.0 is exact: A's fl(v * fl(e d)))
+        launch_data_update_matrix(M, d_values, d_index, k, h->stream);
+        HIP_CHECK(hipGetLastError());
+        h->data_factor_stale = true;
+        h->data_const_stale = true;
+        if (index) h->host_upload_wait();
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_update_data_P(hipkkt_kkt_t h, const double* d_values, const int64_t* index, int64_t k)
+{
+    return data_update_matrix(h, "hipkkt_kkt_system_update_data_P", true, d_values, index, k);
+}
+
+int hipkkt_kkt_system_update_data_A(hipkkt_kkt_t h, const double* d_values, const int64_t* index, int64_t k)
+{
+    return data_update_matrix(h, "hipkkt_kkt_system_update_data_A", false, d_values, index, k);
+}
+
+static int data_update_vector(hipkkt_kkt_t h, const char* who, bool isq, const double* d_values, const int64_t* index, int64_t k)
+{
+    return guarded([&]() {
+        const int64_t len = h ? (isq ? h->K.n : h->K.m) : 0;
+        const int64_t* d_index = nullptr;
+        if (!data_update_begin(h, who, d_values, index, k, len, true, &d_index)) return HIPKKT_OK;
+        if (isq) launch_data_update_vector(h->sq.p, h->snegq.p, h->eq_d.p, h->eq_c, d_values, d_index, k, h->stream);
+        else launch_data_update_vector(h->sb.p, nullptr, h->eq_e.p, 1.0, d_values, d_index, k, h->stream);
+        HIP_CHECK(hipGetLastError());
+        h->data_const_stale = true;
+        if (index) h->host_upload_wait();
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_update_data_q(hipkkt_kkt_t h, const double* d_values, const int64_t* index, int64_t k)
+{
+    return data_update_vector(h, "hipkkt_kkt_system_update_data_q", true, d_values, index, k);
+}
+
+int hipkkt_kkt_system_update_data_b(hipkkt_kkt_t h, const double* d_values, const int64_t* index, int64_t k)
+{
+    return data_update_vector(h, "hipkkt_kkt_system_update_data_b", false, d_values, index, k);
+}
+
+int hipkkt_kkt_system_data_norms(hipkkt_kkt_t h, double out[2])
+{
+    return guarded([&]() {
+        iterate_guard(h);
+        if (!out) throw ArgError("hipkkt_kkt_system_data_norms: bad argument");
+        data_ensure(h);
+        hipStream_t st = h->stream;
+        HIP_CHECK(hipMemsetAsync(h->du_norms.p, 0, 2 * sizeof(double), st));
+        launch_data_norms(h->sq.p, h->eq_dinv.p, h->K.n, h->sb.p, h->eq_einv.p, h->K.m, h->du_norms.p, st);
+        HIP_CHECK(hipGetLastError());
+        HIP_CHECK(hipMemcpyAsync(h->pin->h + 52, h->du_norms.p, 2 * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        out[0] = h->pin->h[52] / h->eq_c;                // data_get_normq!: the unscaled norm, cinv applied (problemdata.jl:91-100)
+        out[1] = h->pin->h[53];
+        return HIPKKT_OK;
+    });
+}
+
 int hipkkt_kkt_system_combined_rhs(hipkkt_kkt_t h, double* d_rhs_x, double* d_rhs_z, const double* d_rx, const double* d_rz,
                                    double sigma)
 {
@@ -4348,6 +4558,7 @@ int hipkkt_kkt_system_solve_batch(hipkkt_kkt_t h, double* d_lhs_x, double* d_lhs
             (m && !affine && !d_rhs_s) || !lhs_tau_kappa || (steptype != 0 && steptype != 1))
             throw ArgError("hipkkt_kkt_system_solve_batch: bad argument");
         if (!rhs_tau || !rhs_kappa || !var_tau || !var_kappa) throw ArgError("hipkkt_kkt_system_solve_batch: a scalar array is NULL");
+        data_refuse_stale_solve(h);
         hipStream_t st = h->stream;
         // (x2, z2) still due (lazy mode): by itself first, as kkt_update! would have done it -- the 2-column pairing is the
         // whole-handle call's; and the status of an enqueued-only update is read before this call's own

@@ -87,6 +87,102 @@ void launch_scale(double* K, const int* idx, double scale, int64_t n, hipStream_
     hipLaunchKernelGGL(k_scale, dim3(grid_for(n, 256)), dim3(256), 0, st, K, idx, scale, n);
 }
 
+// ---- data updates (update_P! / update_A! / update_q! / update_b!, data_updating.jl:56-147, _update_matrix :181-194,
+// _update_vector :216-231).  One launch per call: item t of k takes the user's UNSCALED value v[t] for position
+// j = idx ? idx[t] : t, scales it by the handle's frozen equilibration and writes it everywhere the handle keeps it.
+// Matrix entries: fl(fl(v * fl(L[row] * R[col])) * c) -- k_lrscale's order -- into the matrix's own copy, into Kval and,
+// where the residual's copy is current (fval != nullptr), through to its one or two slots like a cone update.
+__global__ void k_data_update_matrix(DataMatDev M, const double* __restrict__ v, const int64_t* __restrict__ idx, int64_t k)
+{
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < k; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t j = idx ? idx[t] : t;
+        const double s = v[t] * (M.L[M.row[j]] * M.R[M.col[j]]) * M.c;
+        M.val[j] = s;
+        put_k(M.K, M.fval, M.kpos, M.map[j], s);
+    }
+}
+void launch_data_update_matrix(const DataMatDev& M, const double* v, const int64_t* idx, int64_t k, hipStream_t st)
+{
+    if (k <= 0) return;
+    hipLaunchKernelGGL(k_data_update_matrix, dim3(grid_for(k, 256, kDataUpdateGridCap)), dim3(256), 0, st, M, v, idx, k);
+}
+// vector entries: y[j] = fl(fl(v * scale[j]) * c), and yneg[j] = -y[j] where the handle keeps the negated copy (q)
+__global__ void k_data_update_vector(double* __restrict__ y, double* __restrict__ yneg, const double* __restrict__ scale, double c,
+                                     const double* __restrict__ v, const int64_t* __restrict__ idx, int64_t k)
+{
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < k; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t j = idx ? idx[t] : t;
+        const double s = v[t] * scale[j] * c;
+        y[j] = s;
+        if (yneg) yneg[j] = -s;
+    }
+}
+void launch_data_update_vector(double* y, double* yneg, const double* scale, double c, const double* v, const int64_t* idx,
+                               int64_t k, hipStream_t st)
+{
+    if (k <= 0) return;
+    hipLaunchKernelGGL(k_data_update_vector, dim3(grid_for(k, 256, kDataUpdateGridCap)), dim3(256), 0, st, y, yneg, scale, c, v, idx, k);
+}
+// scalings on the handle: dinv = 1 / d, einv = 1 / e (IEEE quotients) in one launch over n + m items
+__global__ void k_reciprocals(double* __restrict__ dinv, const double* __restrict__ d, int64_t n, double* __restrict__ einv,
+                              const double* __restrict__ e, int64_t m)
+{
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n + m; i += (int64_t)gridDim.x * blockDim.x) {
+        if (i < n) dinv[i] = 1.0 / d[i];
+        else einv[i - n] = 1.0 / e[i - n];
+    }
+}
+void launch_reciprocals(double* dinv, const double* d, int64_t n, double* einv, const double* e, int64_t m, hipStream_t st)
+{
+    if (n + m <= 0) return;
+    hipLaunchKernelGGL(k_reciprocals, dim3(grid_for(n + m, 256, kDataUpdateGridCap)), dim3(256), 0, st, dinv, d, n, einv, e, m);
+}
+// data_get_normq! / data_get_normb! (problemdata.jl:91-109): out[0] = max |q_i dinv_i|, out[1] = max |b_i einv_i| in one
+// launch.  The maxima are taken on the BIT PATTERNS of the non-negative products (the order of non-negative doubles is
+// the order of their patterns, and a NaN's pattern lies above infinity's: a non-finite entry gives a non-finite result),
+// workgroup by workgroup and then with an integer atomicMax into out, which the caller zeroed: exact, and the same
+// whatever the order.
+__global__ void k_data_norms(const double* __restrict__ q, const double* __restrict__ dinv, int64_t n, const double* __restrict__ b,
+                             const double* __restrict__ einv, int64_t m, unsigned long long* __restrict__ out)
+{
+    __shared__ unsigned long long sh[2][4];
+    unsigned long long vq = 0ull, vb = 0ull;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n + m; i += (int64_t)gridDim.x * blockDim.x) {
+        if (i < n) {
+            const unsigned long long p = (unsigned long long)__double_as_longlong(fabs(q[i] * dinv[i]));
+            vq = p > vq ? p : vq;
+        } else {
+            const unsigned long long p = (unsigned long long)__double_as_longlong(fabs(b[i - n] * einv[i - n]));
+            vb = p > vb ? p : vb;
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long oq = (unsigned long long)__double_as_longlong(__shfl_down(__longlong_as_double((long long)vq), o, 64));
+        const unsigned long long ob = (unsigned long long)__double_as_longlong(__shfl_down(__longlong_as_double((long long)vb), o, 64));
+        vq = oq > vq ? oq : vq;
+        vb = ob > vb ? ob : vb;
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) { sh[0][wave] = vq; sh[1][wave] = vb; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) {
+            vq = sh[0][w] > vq ? sh[0][w] : vq;
+            vb = sh[1][w] > vb ? sh[1][w] : vb;
+        }
+        if (vq) atomicMax(out, vq);
+        if (vb) atomicMax(out + 1, vb);
+    }
+}
+void launch_data_norms(const double* q, const double* dinv, int64_t n, const double* b, const double* einv, int64_t m,
+                       double* out2, hipStream_t st)
+{
+    if (n + m <= 0) return;
+    hipLaunchKernelGGL(k_data_norms, dim3(grid_for(n + m, 256, kDataNormsGridCap)), dim3(256), 0, st, q, dinv, n, b, einv, m,
+                       (unsigned long long*)out2);
+}
+
 // ---- reductions: block max -> partial[], then one small block finishes
 __device__ inline double block_max_256(double v, double* sh)
 {

@@ -313,6 +313,25 @@ inline int chain_seg_wgs(const ChainSeg& s) { return chain_seg_wgs(s.nblock, s.n
 
 // ---- KKT value updates (kktsolver_directldl.jl:130-188, 211-245, 374-386)
 void launch_scatter(double* Kval, const int* idx, const double* vals, int64_t n, double scale, hipStream_t st);
+// ---- data updates with the handle's frozen equilibration (data_updating.jl:56-247): one matrix of the handle as the
+// update kernel sees it.  val: the handle's scaled copy of the matrix's values; map: its entries' places in K; row / col:
+// every entry's row and column in the matrix's own numbering (data_update.hpp); L, R, c: the scalings (P: d, d, c;
+// A: e, d, 1).  fval = nullptr: the residual's copy is dirty and is left alone (it will be gathered whole).
+struct DataMatDev {
+    double* val; double* K; double* fval;
+    const int* kpos; const int* map; const int* row; const int* col;
+    const double* L; const double* R;
+    double c;
+};
+// v: k unscaled values; idx: their positions (device, int64) or nullptr for positions 0 .. k - 1
+void launch_data_update_matrix(const DataMatDev& M, const double* v, const int64_t* idx, int64_t k, hipStream_t st);
+// y[j] = fl(fl(v * scale[j]) * c), yneg[j] = -y[j] (yneg nullable)
+void launch_data_update_vector(double* y, double* yneg, const double* scale, double c, const double* v, const int64_t* idx,
+                               int64_t k, hipStream_t st);
+void launch_reciprocals(double* dinv, const double* d, int64_t n, double* einv, const double* e, int64_t m, hipStream_t st);
+// out2[0] = max |q dinv|, out2[1] = max |b einv|; out2 (two doubles) must hold zeros when the kernel starts
+void launch_data_norms(const double* q, const double* dinv, int64_t n, const double* b, const double* einv, int64_t m,
+                       double* out2, hipStream_t st);
 void launch_scale(double* Kval, const int* idx, double scale, int64_t n, hipStream_t st);
 // eps = c0 + c1 * max_i |Kval[diag[i]]|  (kktsolver_directldl.jl:297-310) -> *eps_out
 void launch_regularizer(const double* Kval, const int* diag, int N, double c0, double c1,

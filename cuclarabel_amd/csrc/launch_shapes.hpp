@@ -15,6 +15,11 @@ constexpr size_t kLdsCap = 160 * 1024 - 512;
 constexpr int kLongRow = 4096;
 constexpr int kLongChunk = 2048;
 
+// the data updates of level C (kernels.hip, "data updates"): most workgroups of 256 lanes an update kernel is launched
+// with (grid-stride beyond kDataUpdateGridCap * 256 items), and of the one-launch maximum behind hipkkt_kkt_system_data_norms
+constexpr int kDataUpdateGridCap = 4096;
+constexpr int kDataNormsGridCap = 256;
+
 // one-wave fronts (a wave per front in the factorisation and the sweeps)
 constexpr int kSmallFrontMax = 64;         // f <= 64 ...
 constexpr int kSmallSliceMax = 1536;       // ... and f*nc + nb*nb <= this many doubles of LDS per wave

@@ -409,24 +409,74 @@ def _solve_batch(who, problems, settings, inspect, member_refinement):
 
 
 def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym, genpow=False):
-    """The loop the entry points share.  nonsym: the reference's path for a list that does not allow the symmetric
-    start (solver.jl:383-404) -- every line that differs sits under `if nonsym`.  genpow (with nonsym): the cone
-    operations are the _gp calls, which cover generalized power cones as well."""
+    """What the entry points share: the set-up, then the loop from the default start."""
+    return _loop(_setup(P, q, A, b, cone_specs, settings, native, nonsym, genpow), inspect)
+
+
+class _Setup:
+    """Everything a solve needs that does not depend on the iterate: the handle (ordering, symbolic analysis, schedule,
+    allocations), the loop's device tensors, the host copies the objectives are computed from.  Built once by _setup;
+    _loop runs on it any number of times (solver_device.DeviceSolver)."""
+
+
+def _setup(P, q, A, b, cone_specs, settings, native, nonsym, genpow=False, kkt_data=None):
+    """kkt_data: (P, q, A, b) the handle is built from where that is not the data of the objectives (equilibrated data:
+    solver_device.DeviceSolver); None: the same."""
     import torch
-    st = settings or IPMSettings()
+    c = _Setup()
+    c.st = settings or IPMSettings()
+    c.native, c.nonsym, c.genpow, c.cone_specs = native, nonsym, genpow, cone_specs
     P = sp.csc_matrix(P)
     Pt = sp.triu(P, format="csc")
-    Pfull_h = (Pt + sp.triu(Pt, 1).T).tocsr()
-    q, b = np.asarray(q, float), np.asarray(b, float)
-    n, m = Pfull_h.shape[0], sp.csc_matrix(A).shape[0]      # (Pfull_h: the objective of the final solution, on the host)
-    degree = sum(c.dim if isinstance(c, (NonnegativeConeT, PSDTriangleConeT)) else 1 if isinstance(c, SecondOrderConeT)
-                 else 3 if isinstance(c, (ExponentialConeT, PowerConeT))
-                 else len(c.alpha) + 1 if isinstance(c, GenPowerConeT) else 0 for c in cone_specs)
-    normq = np.abs(q).max() if n else 0.0
-    normb = np.abs(b).max() if m else 0.0
+    c.Pfull_h = (Pt + sp.triu(Pt, 1).T).tocsr()              # (the objective of the final solution, on the host)
+    c.q, c.b = np.asarray(q, float), np.asarray(b, float)
+    n, m = c.Pfull_h.shape[0], sp.csc_matrix(A).shape[0]
+    c.n, c.m = n, m
+    c.degree = sum(k.dim if isinstance(k, (NonnegativeConeT, PSDTriangleConeT)) else 1 if isinstance(k, SecondOrderConeT)
+                   else 3 if isinstance(k, (ExponentialConeT, PowerConeT))
+                   else len(k.alpha) + 1 if isinstance(k, GenPowerConeT) else 0 for k in cone_specs)
+    c.normq = np.abs(c.q).max() if n else 0.0
+    c.normb = np.abs(c.b).max() if m else 0.0
+    kP, kq, kA, kb = (P, c.q, A, c.b) if kkt_data is None else kkt_data
+    large_psd = any(isinstance(k, PSDTriangleConeT) and k.dim > PSD_MAX_SIDE for k in cone_specs)
+    c.backend = HipSystemBackend(kP, kA, cone_specs, large_psd=large_psd)
+    ks, system = c.backend.ks, c.backend.system
+    c.dev = dev = system._devstr
+    ks.set_stream(torch.cuda.current_stream(torch.device(dev)).cuda_stream)     # torch's kernels and the library's: one queue
+    if not native:
+        A_h = sp.csr_matrix(kA)
+        kPt = sp.triu(sp.csc_matrix(kP), format="csc")
+        c.csr = (_Csr((kPt + sp.triu(kPt, 1).T).tocsr(), dev), _Csr(A_h, dev), _Csr(A_h.T, dev))
+    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    new = lambda k: torch.zeros(max(k, 1), dtype=torch.float64, device=dev)[:k]
+    c.qd, c.bd = up(kq), up(kb)
+    c.x, c.s, c.z = new(n), new(m), new(m)
+    c.dx, c.ds, c.dz = new(n), new(m), new(m)
+    c.aff_s, c.rhs_s = new(m), new(m)
+    if native:
+        c.rx, c.rx_inf, c.Px, c.rhs_x = new(n), new(n), new(n), new(n)
+        c.rz, c.rz_inf, c.rhs_z = new(m), new(m), new(m)
+    system.init(kq, kb)
+    return c
 
-    large_psd = any(isinstance(c, PSDTriangleConeT) and c.dim > PSD_MAX_SIDE for c in cone_specs)
-    backend = HipSystemBackend(P, A, cone_specs, large_psd=large_psd)
+
+def _loop(c, inspect=None, equil=None):
+    """The loop the entry points share, from the default start (as the reference's solve!, solver.jl:189-380), on a
+    _Setup.  nonsym: the reference's path for a list that does not allow the symmetric start (solver.jl:383-404) -- every
+    line that differs sits under `if nonsym`.  genpow (with nonsym): the cone operations are the _gp calls, which cover
+    generalized power cones as well.
+    equil (solver_device.DeviceSolver; needs the library's own plumbing): the handle was built from equilibrated data --
+    .ptrs: the device pointers (d, dinv, e, einv) that residuals_dev takes, .cinv: 1 / c, .d, .e, .einv: device tensors
+    for variables_unscale!.  None: the loop as it always was."""
+    import torch
+    st, native, nonsym, genpow, cone_specs = c.st, c.native, c.nonsym, c.genpow, c.cone_specs
+    assert equil is None or native
+    Pfull_h, q, b, n, m, degree = c.Pfull_h, c.q, c.b, c.n, c.m, c.degree
+    # (equilibrated: the norms of the UNSCALED q and b from the handle's scaled ones, once per solve -- info.jl:14-16)
+    normq, normb = (c.normq, c.normb) if equil is None else c.backend.system.data_norms()
+    d_equil = None if equil is None else equil.ptrs
+    cinv = 1.0 if equil is None else equil.cinv
+    backend = c.backend
     ks, system = backend.ks, backend.system
     if genpow:                                           # the five cone operations of a non-symmetric list
         unit_initialization, affine_ds_ns, combined_ds_ns, step_length_ns_dev, barrier_dev = (
@@ -436,28 +486,23 @@ def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym, genpow=Fal
         unit_initialization, affine_ds_ns, combined_ds_ns, step_length_ns_dev, barrier_dev = (
             system.unit_initialization_dev, system.affine_ds_ns_dev, system.combined_ds_ns_dev, system.step_length_ns_dev,
             system.barrier_dev)
-    dev = system._devstr
-    ks.set_stream(torch.cuda.current_stream(torch.device(dev)).cuda_stream)     # torch's kernels and the library's: one queue
     if not native:
-        A_h = sp.csr_matrix(A)
-        Pfull, Ad, At = _Csr(Pfull_h, dev), _Csr(A_h, dev), _Csr(A_h.T, dev)
-    up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
-    new = lambda k: torch.zeros(max(k, 1), dtype=torch.float64, device=dev)[:k]
-    qd, bd = up(q), up(b)
+        Pfull, Ad, At = c.csr
+    qd, bd = c.qd, c.bd
     p = lambda t: t.data_ptr()
     ir_total = 0
 
     # ---- default start: solver.jl:383-404
-    x, s, z = new(n), new(m), new(m)
-    dx, ds, dz = new(n), new(m), new(m)
-    aff_s, rhs_s = new(m), new(m)
+    x, s, z = c.x, c.s, c.z
+    dx, ds, dz = c.dx, c.ds, c.dz
+    aff_s, rhs_s = c.aff_s, c.rhs_s
     if native:
-        rx, rx_inf, Px, rhs_x = new(n), new(n), new(n), new(n)
-        rz, rz_inf, rhs_z = new(m), new(m), new(m)
-    system.init(q, b)
+        rx, rx_inf, Px, rhs_x = c.rx, c.rx_inf, c.Px, c.rhs_x
+        rz, rz_inf, rhs_z = c.rz, c.rz_inf, c.rhs_z
     strategy = PRIMAL_DUAL                               # the reference's `scaling` (solver.jl:221); read under nonsym only
     bt_step, bt_min = st.linesearch_backtrack_step, st.min_terminate_step_length
     if nonsym:
+        x.zero_()
         unit_initialization(p(s), p(z))                  # variables_unit_initialization!: x = 0, no solve
     else:
         backend.update_identity()
@@ -496,7 +541,7 @@ def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym, genpow=Fal
         # ---- residuals (residuals.jl:1-37); the scalars in ONE read-back
         if native:
             qx, bz, sz, xPx, nx, nz, ns, n_rxi, n_Px, n_rzi, n_rz, n_rx = system.residuals_dev(
-                p(x), p(s), p(z), tau, p(rx), p(rz), p(rx_inf), p(rz_inf), p(Px)).tolist()
+                p(x), p(s), p(z), tau, p(rx), p(rz), p(rx_inf), p(rz_inf), p(Px), d_equil).tolist()
         else:
             Px = Pfull.mv(x)
             rx_inf = -At.mv(z)
@@ -510,15 +555,19 @@ def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym, genpow=Fal
         if inspect is not None:
             inspect(dict(x=x, s=s, z=z, dx=dx, ds=ds, dz=dz, aff_s=aff_s, rhs_s=rhs_s, rx=rx, rz=rz, rx_inf=rx_inf,
                          rz_inf=rz_inf, Px=Px, q=qd, b=bd), backend)
-        # ---- info_update! (info.jl:1-63), no equilibration
+        # ---- info_update! (info.jl:1-63); equilibrated: the norms came scaled by d, e and their inverses out of the
+        #      residual pass, and the cost scaling c is backed out here (cinv, info.jl:19-51)
         tinv = 1.0 / tau
         cost_p = qx * tinv + xPx * tinv * tinv / 2
         cost_d = -bz * tinv - xPx * tinv * tinv / 2
+        if equil is not None:
+            cost_p, cost_d, nz = cost_p * cinv, cost_d * cinv, nz * cinv              # info.jl:27-28, :34
+            n_rxi = n_rxi * cinv                                                      # :38
         res_pinf = n_rxi / max(1.0, nz)
         res_dinf = max(n_Px / max(1.0, nx), n_rzi / max(1.0, nx + ns))
         nx, nz, ns = nx * tinv, nz * tinv, ns * tinv
         res_p = n_rz * tinv / max(1.0, normb + nx + ns)
-        res_d = n_rx * tinv / max(1.0, normq + nx + nz)
+        res_d = (n_rx * tinv if equil is None else n_rx * tinv * cinv) / max(1.0, normq + nx + nz)      # :51
         gap_abs = abs(cost_p - cost_d)
         gap_rel = gap_abs / max(1.0, min(abs(cost_p), abs(cost_d)))
         kt = kappa * tinv
@@ -615,7 +664,7 @@ def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym, genpow=Fal
     if status in (NUMERICAL_ERROR, INSUFFICIENT_PROGRESS, MAX_ITERATIONS):
         tinv = 1.0 / tau
         if native:
-            o = system.residuals_dev(p(x), p(s), p(z), tau, p(rx), p(rz), p(rx_inf), p(rz_inf), p(Px))
+            o = system.residuals_dev(p(x), p(s), p(z), tau, p(rx), p(rz), p(rx_inf), p(rz_inf), p(Px), d_equil)
             qx, bz, xPx, nx, nz, ns, n_rz, n_rx = (float(o[i]) for i in (0, 1, 3, 4, 5, 6, 10, 11))
         else:
             Px = Pfull.mv(x)
@@ -623,6 +672,8 @@ def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym, genpow=Fal
                 [qd @ x, bd @ z, x @ Px, nrm(x), nrm(z), nrm(s), nrm(Ad.mv(x) + s - bd * tau), nrm(-At.mv(z) - Px - qd * tau)]).tolist()
         cp = qx * tinv + xPx * tinv * tinv / 2
         cd = -bz * tinv - xPx * tinv * tinv / 2
+        if equil is not None:
+            cp, cd, nz, n_rx = cp * cinv, cd * cinv, nz * cinv, n_rx * cinv
         nx, nz, ns = nx * tinv, nz * tinv, ns * tinv
         rp = n_rz * tinv / max(1.0, normb + nx + ns)
         rd = n_rx * tinv / max(1.0, normq + nx + nz)
@@ -635,7 +686,12 @@ def _solve(P, q, A, b, cone_specs, settings, inspect, native, nonsym, genpow=Fal
     infeasible = status in (PRIMAL_INFEASIBLE, DUAL_INFEASIBLE)
     sc = 1.0 / (kappa if infeasible else tau)
     torch.cuda.synchronize()
-    xo, zo, so = (x * sc).cpu().numpy(), (z * sc).cpu().numpy(), (s * sc).cpu().numpy()
+    if equil is None:
+        xo, zo, so = (x * sc).cpu().numpy(), (z * sc).cpu().numpy(), (s * sc).cpu().numpy()
+    else:
+        # variables_unscale! (variables.jl:247-275): x *= d / scale, z *= e / (scale c), s *= einv / scale
+        xo, zo, so = ((x * (equil.d * sc)).cpu().numpy(), (z * (equil.e * (sc * cinv))).cpu().numpy(),
+                      (s * (equil.einv * sc)).cpu().numpy())
     objp = q @ xo + 0.5 * xo @ (Pfull_h @ xo)
     objd = -b @ zo - 0.5 * xo @ (Pfull_h @ xo)
     if infeasible:

@@ -487,6 +487,60 @@ class HipKKTSystem:
                                                             C.c_void_p(d_dx), C.c_void_p(d_ds), C.c_void_p(d_dz), float(alpha)),
                      "hipkkt_kkt_system_add_step")
 
+    # ---- data updating (update_P! / update_A! / update_q! / update_b!, data_updating.jl:26-247) with the equilibration
+    #      frozen on the handle: new UNSCALED values on the device, scaled and written where the handle keeps them
+    def set_equilibration(self, eq):
+        """The frozen scalings of `equilibrate.Equilibration` (d, e, c) onto the handle, or None to clear them to ones."""
+        if eq is None:
+            check(_lib.lib().hipkkt_kkt_system_set_equilibration(self.ks._h, None, None, 1.0),
+                  "hipkkt_kkt_system_set_equilibration")
+            return
+        d, e = f64(eq.d), f64(eq.e)
+        if d.size != self.ks.n or e.size != self.ks.m:
+            raise ValueError("d must have length n and e length m")
+        check(_lib.lib().hipkkt_kkt_system_set_equilibration(self.ks._h, ptr(d), ptr(e), float(eq.c)),
+              "hipkkt_kkt_system_set_equilibration")
+
+    def equilibration_dev(self):
+        """(d, dinv, e, einv) device pointers of the handle's scalings, as `residuals_dev(d_equil=...)` takes them."""
+        out = [C.c_void_p() for _ in range(4)]
+        check(_lib.lib().hipkkt_kkt_system_equilibration_dev(self.ks._h, *[C.byref(o) for o in out]),
+              "hipkkt_kkt_system_equilibration_dev")
+        return tuple(o.value for o in out)
+
+    def _update_data(self, name, d_values_ptr, index, k):
+        idx = None if index is None else i64(index)
+        if idx is not None and idx.ndim != 1:
+            raise ValueError("index must be one-dimensional")
+        if k is None:
+            if idx is None:
+                raise ValueError("the vector form needs k (the number of values behind the pointer)")
+            k = idx.size
+        elif idx is not None and idx.size != int(k):
+            raise ValueError("index must have k entries")
+        fn = getattr(_lib.lib(), "hipkkt_kkt_system_update_data_" + name)
+        check(fn(self.ks._h, C.c_void_p(d_values_ptr), ptr(idx), int(k)), "hipkkt_kkt_system_update_data_" + name)
+
+    def update_data_P_dev(self, d_values_ptr, index=None, k=None):
+        """k unscaled values of triu(P) behind a device pointer; index: their zero-based positions in its nzval (host), or
+        None for all of them in order (k = nnz).  Refusals raise HipKKTError and leave the handle as it was."""
+        self._update_data("P", d_values_ptr, index, k)
+
+    def update_data_A_dev(self, d_values_ptr, index=None, k=None):
+        self._update_data("A", d_values_ptr, index, k)
+
+    def update_data_q_dev(self, d_values_ptr, index=None, k=None):
+        self._update_data("q", d_values_ptr, index, k)
+
+    def update_data_b_dev(self, d_values_ptr, index=None, k=None):
+        self._update_data("b", d_values_ptr, index, k)
+
+    def data_norms(self):
+        """(max |q dinv| / c, max |b einv|): the norms of the unscaled q and b (data_get_normq!, data_get_normb!)."""
+        out = np.zeros(2)
+        check(_lib.lib().hipkkt_kkt_system_data_norms(self.ks._h, ptr(out)), "hipkkt_kkt_system_data_norms")
+        return float(out[0]), float(out[1])
+
     # ---- a stack of independent member problems on this handle: the partition, and the operations between the solves
     #      with every scalar a numpy array over the members (the _batch symbols).  One upload of the scalar arrays and one
     #      read-back per call; the number of launches does not depend on the number of members.

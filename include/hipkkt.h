@@ -516,6 +516,67 @@ int hipkkt_kkt_system_combined_rhs(hipkkt_kkt_t h, double *d_rhs_x, double *d_rh
 int hipkkt_kkt_system_add_step(hipkkt_kkt_t h, double *d_x, double *d_s, double *d_z, const double *d_dx,
                                const double *d_ds, const double *d_dz, double alpha);
 
+/* ------------------------------------------- Level C: data updating (parametric re-solves)
+ * update_data! / update_P! / update_A! / update_q! / update_b! (/root/reference/src/data_updating.jl:26-247): new problem
+ * data on a handle that keeps its ordering, schedule, sweep plans and allocations.  The reference scales new data by the
+ * equilibration it computed once (data_updating.jl:63-65, 93-95, 116-118, 140-141); so does the handle, which holds
+ * that equilibration on the device. */
+
+/* The frozen equilibration of data_equilibrate! (problemdata.jl:133-221) on the handle: d (n) and e (m) are HOST vectors,
+ * copied to the device once together with dinv = 1 / d and einv = 1 / e (IEEE quotients), c is the cost scaling.
+ * d = e = NULL clears the scalings to all ones with c = 1 -- the state of a handle that never called this.  c <= 0, a
+ * non-finite c, or exactly one of the two pointers NULL where its length is > 0: HIPKKT_ERR_ARG.  The first call (or the
+ * first data update, whichever comes first) also builds, once, the row and column of every stored entry of P and A from
+ * K's pattern and the assembly's maps, and the staging of an indexed update's positions.  P, A, q and b on the handle are
+ * NOT touched: the caller created the handle from data that is already scaled.  Synchronises (the host arrays may be
+ * reused when it returns). */
+int hipkkt_kkt_system_set_equilibration(hipkkt_kkt_t h, const double *d, const double *e, double c);
+
+/* The handle's device copies of d, dinv (n) and e, einv (m) -- data.equilibration of the reference, which update_P! and
+ * its siblings read (data_updating.jl:63-64, 93-94, 116, 140) -- for hipkkt_kkt_system_residuals (info_update! with
+ * equilibration, info.jl:19-51); valid until the next hipkkt_kkt_system_set_equilibration or destroy.  All ones on a
+ * handle whose scalings were never set or were cleared.  Enqueues nothing. */
+int hipkkt_kkt_system_equilibration_dev(hipkkt_kkt_t h, const double **d_d, const double **d_dinv,
+                                        const double **d_e, const double **d_einv);
+
+/* update_P! / update_A! / update_q! / update_b! (data_updating.jl:56-147).  d_values: k UNSCALED user values on the
+ * DEVICE; index: a HOST array of k zero-based positions -- into the stored upper-triangular nzval of P, the nzval of A,
+ * or the vector q / b -- or NULL for the vector form (_update_matrix :181-194, _update_vector :216-231), where k must
+ * equal nnz(triu P), nnz(A), n or m.  k = 0 is a no-op that returns HIPKKT_OK (:61, :189, :223).  An index out of range
+ * or a REPEATED index is HIPKKT_ERR_ARG with the offending place in index[] named by hipkkt_last_error, the handle
+ * untouched (the reference's tuple form, :196-213 and :234-247, applies repeats in order; a parallel scatter cannot).
+ * The checks are host-only code (csrc/data_update.cpp).
+ *   P: fl(fl(v * fl(d[row] * d[col])) * c)      A: fl(v * fl(e[row] * d[col]))
+ *   q: fl(fl(v * d[i]) * c)                     b: fl(v * e[i])
+ * without contraction -- what lrscale! followed by the product by c computes (:191-193), and the SAME order in the
+ * (index, value) form, so that an indexed update of every entry equals the vector update bit for bit.  The reference's
+ * tuple form multiplies in another order, (lscale * rscale * cscale) * value (:208-210), and can differ from its own
+ * vector form, and from this, in the last bit.
+ * P and A: the scaled value goes to the handle's copy of the matrix, to K, and -- when the residual's image of K is
+ * current -- through to its one or two slots there, as a cone update's values do; a dirty image is left alone (it is
+ * gathered whole before its next use) and the call never makes a current image dirty: a two-entry update costs two
+ * entries.  q writes q and -q, b writes b.
+ * Afterwards the factorisation is stale (P, A) and so are (x2, z2) and the cached constant terms of kkt_solve! (all four):
+ * the next hipkkt_kkt_system_update / _update_cones / _update_scaling refactors, the next constant-RHS solve (eager, or
+ * the lazy mode's paired one) renews (x2, z2).  Until then hipkkt_kkt_system_solve, _solve_batch and _solve_host
+ * (stale (x2, z2)), and _solve_constant_rhs and _solve_initial_point (stale factorisation) return HIPKKT_ERR_ARG and
+ * enqueue nothing.  hipkkt_kkt_update_P / _A of level B keep their behaviour and set no such mark.
+ * One launch per call on the handle's stream, behind the upload of index where there is one; no synchronisation beyond
+ * what that upload needs, and the number of launches does not depend on k.  The q and b calls need
+ * hipkkt_kkt_system_init; all four are refused on a deferred-status handle (HIPKKT_ERR_ARG) and work unchanged on a
+ * handle partitioned by hipkkt_kkt_system_set_problems (they carry no per-member scalar). */
+int hipkkt_kkt_system_update_data_P(hipkkt_kkt_t h, const double *d_values, const int64_t *index, int64_t k);
+int hipkkt_kkt_system_update_data_A(hipkkt_kkt_t h, const double *d_values, const int64_t *index, int64_t k);
+int hipkkt_kkt_system_update_data_q(hipkkt_kkt_t h, const double *d_values, const int64_t *index, int64_t k);
+int hipkkt_kkt_system_update_data_b(hipkkt_kkt_t h, const double *d_values, const int64_t *index, int64_t k);
+
+/* data_get_normq! / data_get_normb! (problemdata.jl:91-109): out[0] = max |q_i dinv_i| / c and out[1] = max |b_i einv_i|
+ * from the handle's scaled q and b -- the norms of the user's unscaled vectors that info_update! compares the residuals
+ * with.  One launch and one read-back (synchronises).  A maximum does not depend on the order it is taken in, so the
+ * result is exact; a non-finite entry gives a non-finite result, empty vectors give 0.  Needs hipkkt_kkt_system_init;
+ * refused on a deferred-status handle. */
+int hipkkt_kkt_system_data_norms(hipkkt_kkt_t h, double out[2]);
+
 /* ------------------------------------------- Level C on a stack of INDEPENDENT problems
  * A batch of independent conic problems is put on ONE handle as a block-diagonal stack (P = blkdiag(P_b), A = blkdiag(A_b),
  * the cone lists one behind the other), so that the elimination forest shares every per-level launch.  The calls below
