@@ -1555,6 +1555,9 @@ private:
                 int64_t n_dense = 0;
                 for (int c : fl.dense_child) n_dense += c >= 0;
                 std::fprintf(stderr, "[hipkkt] dense children: %lld\n", (long long)n_dense);
+                std::fprintf(stderr, "[hipkkt] update blocks: %d chains of panels (%d links) share two buffers each; %lld bytes kept, %lld without sharing\n",
+                             S.shared_chains, S.shared_links, (long long)(S.update_store * 8), (long long)(S.update_store_unshared * 8));
+                if (knobs().verbose >= 2) std::fputs(describe_pieces(S, sch, fl).c_str(), stderr);      // the "[pieces]" lines of this handle's lists
                 std::fprintf(stderr, "[hipkkt] pulled leaves' terms: %zu chunks of 64, deepest stack %d\n", fl.pterms.size() / 64, fl.max_depth);
             }
             std::vector<int64_t> raw(std::max<size_t>(items.size(), 1) * 4);

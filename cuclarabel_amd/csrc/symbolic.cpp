@@ -501,6 +501,8 @@ void analyse(int N, const int64_t* colptr, const int64_t* rowval, int base,
     }
     S.front_store = S.front_off[S.nsuper];
     S.update_store = S.upd_off[S.nsuper];
+    S.update_store_unshared = S.update_store;           // (step 10 may let chains share blocks: what it would be without)
+    S.shared_chains = S.shared_links = 0;
     // K entries: triu entry (i,j) of the original -> lower entry (max,min) of the permuted matrix
     S.kptr.assign(S.nsuper + 1, 0);
     S.diag_src.assign(N, -1);
@@ -583,6 +585,8 @@ void analyse(int N, const int64_t* colptr, const int64_t* rowval, int base,
             int len = 0;
             for (int m = h; m >= 0; m = next[(size_t)m]) ++len;
             if (len < 3) continue;
+            ++S.shared_chains;
+            S.shared_links += len;
             int i = 0;
             for (int m = h; m >= 0; m = next[(size_t)m], ++i) { head[(size_t)m] = h; link[(size_t)m] = i; }
         }

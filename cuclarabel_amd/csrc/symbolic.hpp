@@ -98,6 +98,8 @@ struct Symbolic {
     int max_front = 0;
     int64_t front_store = 0;             // total doubles in the front store
     int64_t update_store = 0;            // total doubles in the update store
+    int64_t update_store_unshared = 0;   // ... and what it would be with a block per supernode (diagnostics)
+    int shared_chains = 0, shared_links = 0;   // chains of panels that share two update blocks, and their links
     std::vector<int64_t> upd_off;        // nsuper+1 offsets into the update store
 };
 

@@ -33,8 +33,11 @@ def _allow(width, first):
 
 
 def tree(rp, sp_, ng, k, leaves, others=()):
-    """-> (cols, rows) per front, leaves first; raises where the amalgamation arithmetic would merge a designed front."""
+    """-> (cols, rows) per front, leaves first; raises where the amalgamation arithmetic would merge a designed front.
+    sp_ = 0 (and ng = 0): P is a root itself, there is no G."""
     assert ng >= sp_ and all(p[0] < rp and list(p) == sorted(set(p)) and p[-1] < rp + sp_ for p in leaves)
+    assert all(nc < k and p[0] < rp and list(p) == sorted(set(p)) and p[-1] < rp + sp_ for nc, p in others), \
+        "the poison sibling is the widest child; a child's first row is a column of P"
     # S into P (the first, widest child)
     z = k * (rp + sp_ - 1)
     assert z / _trap(rp + k, sp_) <= _allow(rp + k, True), "the poison sibling would stay out"
@@ -43,18 +46,28 @@ def tree(rp, sp_, ng, k, leaves, others=()):
         tot = _trap(rp + k + nc, sp_)
         frac = (tot - true_p - _trap(nc, len(pos))) / tot
         assert frac > _allow(rp + k + nc, False), ("a child would merge into its parent", nc, len(pos), frac)
-    tot = _trap(rp + k + ng, 0)
-    assert (tot - true_p - _trap(ng, 0)) / tot > _allow(rp + k + ng, True), "the parent would merge into the root"
+    if sp_:
+        tot = _trap(rp + k + ng, 0)
+        assert (tot - true_p - _trap(ng, 0)) / tot > _allow(rp + k + ng, True), "the parent would merge into the root"
+    else:
+        assert ng == 0
+    # sibling bundles (symbolic.cpp, step 5) would put the children into supernodes of their own: by their number (more than
+    # HIPKKT_BUNDLE_KIDS 200 under a front of <= 64 rows, HIPKKT_BUNDLE_KIDS_PANEL 400 per 96-column panel under a taller
+    # one) or by their update blocks, together more than 16 times the parent's front (HIPKKT_BUNDLE_COST)
+    kids, f = len(leaves) + len(others), rp + k + sp_
+    assert kids <= 200 if f <= 64 else kids * min(1.0, 96 / (rp + k)) <= 400, "the children would be bundled by their number"
+    assert sum(len(p) ** 2 for p in leaves) + sum(len(p) ** 2 for _, p in others) <= 16 * f * f, \
+        "the children would be bundled by the size of their update blocks"
     cols, rows, c = [], [], 0
-    sizes = [1] * len(leaves) + [nc for nc, _ in others] + [k, rp, ng]
+    sizes = [1] * len(leaves) + [nc for nc, _ in others] + [k, rp] + ([ng] if sp_ else [])
     for n in sizes:
         cols.append(list(range(c, c + n)))
         c += n
-    pc, gc = cols[-2], cols[-1]
+    pc, gc = (cols[-2], cols[-1]) if sp_ else (cols[-1], [])
     front = pc + gc[:sp_]
     for pos in list(leaves) + [p for _, p in others]:
         rows.append([front[i] for i in pos])
-    rows += [[pc[0]], gc[:sp_], []]
+    rows += [[pc[0]], gc[:sp_]] + ([[]] if sp_ else [])
     return cols, rows
 
 

@@ -14,6 +14,10 @@
 //   I s tcol relstart cnt   a panel item of front s
 //   U t qcol relstart cnt   a sub-item of tile t
 //   P chunk lane leaf_off target a b steps     a pulled term (steps: lane 0's count of doubling steps for the chunk)
+//   WC s base wcut[17]      the panel items' 16 wave slices as item indices; front s's I lines count from `base`
+//   TC t base tcut[5]       a tile's four wave shares as sub-item indices; tile t's U lines count from `base`
+//   SL q s sl nsl wcut[17]  row slice sl of nsl of the sliced front s: the 16 wave slices of its own item list ...
+//   J q tcol relstart cnt rfirst rlast         ... and that list's items, in order from wcut[0]
 #include "schedule.hpp"
 #include "symbolic.hpp"
 
@@ -73,6 +77,11 @@ static void dump(const char* path, int ordering)
             for (int w = 0; w <= 16; ++w) std::printf(" %d", fl.pwcut[(size_t)s * 17 + w]);
             std::printf("\n");
         }
+        if (sch.tile_base[s] >= 0) {
+            std::printf("WC %d %lld", s, (long long)fl.pptr[(size_t)S.sn_start[s]]);
+            for (int w = 0; w <= 16; ++w) std::printf(" %lld", (long long)fl.wcut[(size_t)s * 17 + w]);
+            std::printf("\n");
+        }
         for (int64_t it = fl.pptr[(size_t)S.sn_start[s]]; it < fl.pptr[(size_t)S.sn_start[s + 1]]; ++it)
             std::printf("I %d %d %d %d\n", s, fl.items[(size_t)it].tcol, fl.items[(size_t)it].relstart, fl.items[(size_t)it].cnt);
     }
@@ -83,8 +92,21 @@ static void dump(const char* path, int ordering)
         for (int w = 0; w <= 4; ++w) std::printf(" %d", fl.tcol[(size_t)(t * 5 + w)]);
         for (int w = 0; w <= 4; ++w) std::printf(" %d", fl.ptcut[(size_t)(t * 5 + w)]);
         std::printf("\n");
+        std::printf("TC %lld %lld", (long long)t, (long long)fl.tptr[(size_t)(t * 64)]);
+        for (int w = 0; w <= 4; ++w) std::printf(" %lld", (long long)fl.tcut[(size_t)(t * 5 + w)]);
+        std::printf("\n");
         for (int64_t it = fl.tptr[(size_t)(t * 64)]; it < fl.tptr[(size_t)(t * 64 + 64)]; ++it)
             std::printf("U %lld %d %d %d\n", (long long)t, (int)fl.sit[(size_t)it].qcol, fl.sit[(size_t)it].relstart, (int)fl.sit[(size_t)it].cnt);
+    }
+    for (size_t q = 0; q < sch.slice_list.size(); ++q) {
+        const int64_t* w = fl.wcut.data() + ((size_t)S.nsuper + q) * 17;
+        std::printf("SL %zu %d %d %d", q, sch.slice_list[q][0], sch.slice_list[q][1], sch.slice_list[q][2]);
+        for (int k = 0; k <= 16; ++k) std::printf(" %lld", (long long)w[k]);
+        std::printf("\n");
+        for (int64_t it = w[0]; it < w[16]; ++it) {
+            const ExtItem& e = fl.items[(size_t)it];
+            std::printf("J %zu %d %d %d %d %d\n", q, e.tcol, e.relstart, e.cnt, e.rfirst, e.rlast);
+        }
     }
     for (size_t k = 0; k < fl.pterms.size(); ++k) {
         const PullTerm& t = fl.pterms[k];

@@ -47,7 +47,7 @@ def _dump(exe, ordering, paths, env=None):
     out = []
     for chunk in r.stdout.split("@@case ")[1:]:
         head, body = chunk.split("\n", 1)
-        D = dict(S={}, REL={}, relbase={}, CH={}, W={}, T={}, I=[], U=[], P=[], nchunks=int(head.split()[-1]))
+        D = dict(S={}, REL={}, relbase={}, CH={}, W={}, T={}, I=[], U=[], P=[], WC=[], TC=[], SL=[], J=[], nchunks=int(head.split()[-1]))
         for line in body.splitlines():
             k, *v = line.split()
             v = list(map(int, v))
