@@ -348,7 +348,84 @@ __global__ __launch_bounds__(256) void k_member_ir_round(MemberIrDev M, int r, c
     readback[4] = (flag_in && flag_in[0]) ? 1.0 : 0.0;
 }
 
+// ---- the static regulariser and the failure words per member (kernels.hpp: MemberStatusDev;
+// kktsolver_directldl.jl:259-310 on each member's rows of K's image).
+// max |K_ii| over every member's image rows, and over all rows, on the bit patterns of the non-negative values (their
+// order is the doubles' order) with an integer atomicMax into words the caller zeroed: exact whatever the order.  A NaN
+// diagonal counts as 0, as k_diag_absmax's fmax drops it.  A member's rows are runs of the image (its x rows, its z rows,
+// its cones' expansion rows), so nearly every wave holds ONE member and folds its 64 values before its single atomic;
+// a wave that straddles members sends its lanes' values one by one.
+__global__ __launch_bounds__(256) void k_member_diag_max(MemberStatusDev M, const double* __restrict__ K, const int* __restrict__ diag)
+{
+    __shared__ unsigned long long sh[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long all = 0ull;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < M.N; base += (int64_t)gridDim.x * 256) {      // (uniform over the workgroup)
+        const int64_t i = base + (int64_t)threadIdx.x;
+        const bool valid = i < M.N;
+        const int mem = valid ? M.rowmem[i] : -1;
+        const double v = valid ? fmax(0.0, fabs(K[diag[i]])) : 0.0;
+        unsigned long long p = (unsigned long long)__double_as_longlong(v);
+        all = p > all ? p : all;
+        if (base + wave * 64 >= M.N) continue;                                       // (the wave has no row: uniform over the wave)
+        const int lead = __builtin_amdgcn_readfirstlane(mem);                        // (lane 0's row is valid: the rows are a prefix)
+        if (__all(!valid || mem == lead)) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned long long q = (unsigned long long)__double_as_longlong(__shfl_xor(__longlong_as_double((long long)p), o, 64));
+                p = q > p ? q : p;
+            }
+            if (lane == 0 && p) atomicMax(M.maxbits + lead, p);
+        } else if (valid && p) {
+            atomicMax(M.maxbits + mem, p);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long q = (unsigned long long)__double_as_longlong(__shfl_xor(__longlong_as_double((long long)all), o, 64));
+        all = q > all ? q : all;
+    }
+    if (lane == 0) sh[wave] = all;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; ++w) all = sh[w] > all ? sh[w] : all;
+        if (all) atomicMax(M.maxbits + M.nb, all);
+    }
+}
+
+// eps_b = c0 + c1 max_b (k_finish_regularizer's expression) per member, per column of the factor through the column's
+// member, and the largest of them -- c0 + c1 (the stack's maximum), as the expression does not decrease in the maximum
+__global__ __launch_bounds__(256) void k_member_eps(MemberStatusDev M, double c0, double c1, double* __restrict__ eps_top)
+{
+    const int len = M.N > M.nb ? M.N : M.nb;
+    for (int k = blockIdx.x * 256 + (int)threadIdx.x; k < len; k += gridDim.x * 256) {
+        if (k < M.N) M.eps_col[k] = c0 + c1 * __longlong_as_double((long long)M.maxbits[M.colmem[k]]);
+        if (k < M.nb) M.eps_mem[k] = c0 + c1 * __longlong_as_double((long long)M.maxbits[k]);
+        if (k == 0) eps_top[0] = c0 + c1 * __longlong_as_double((long long)M.maxbits[M.nb]);
+    }
+}
+
+// behind the factorisation: column k of the factor marks its member if its pivot's reciprocal is not finite (the
+// predicate of FactorArgs::flags[1], on the value the factor kernels stored)
+__global__ __launch_bounds__(256) void k_member_pivot_scan(MemberStatusDev M, const double* __restrict__ Dinv)
+{
+    for (int k = blockIdx.x * 256 + (int)threadIdx.x; k < M.N; k += gridDim.x * 256)
+        if (!isfinite(Dinv[k])) M.piv_bad[M.colmem[k]] = 1;
+}
+
 }  // namespace
+
+void launch_member_regularizer(const MemberStatusDev& M, const double* Kval, const int* diag, double c0, double c1, double* eps_top,
+                               hipStream_t st)
+{
+    hipLaunchKernelGGL(k_member_diag_max, dim3(batch_elem_grid(M.N)), dim3(256), 0, st, M, Kval, diag);
+    hipLaunchKernelGGL(k_member_eps, dim3(batch_elem_grid(M.N > M.nb ? M.N : M.nb)), dim3(256), 0, st, M, c0, c1, eps_top);
+}
+
+void launch_member_pivot_scan(const MemberStatusDev& M, const double* Dinv, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_member_pivot_scan, dim3(batch_elem_grid(M.N)), dim3(256), 0, st, M, Dinv);
+}
 
 void launch_member_residual(const SpmvDev& A, const double* Kval, const MemberIrDev& M, const double* b, const double* x, double* e,
                             bool first, hipStream_t st)

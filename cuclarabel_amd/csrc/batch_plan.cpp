@@ -175,4 +175,23 @@ std::string plan_batch_image(int n, int m, int p, const BatchPlan& B, const Batc
     return "";
 }
 
+std::string plan_column_members(int N, int nb, const int* perm, size_t nperm, const int* rowmem, size_t nrowmem, std::vector<int>& colmem)
+{
+    if (N < 0 || nb < 1) return "the column table needs N >= 0 and at least one member";
+    if (nperm != (size_t)N) return "the permutation has " + num((int64_t)nperm) + " entries, the image has " + num(N) + " rows";
+    if (nrowmem != (size_t)N) return "the row table has " + num((int64_t)nrowmem) + " entries, the image has " + num(N) + " rows";
+    for (int i = 0; i < N; ++i)
+        if (rowmem[i] < 0 || rowmem[i] >= nb) return "row " + num(i) + " of the image belongs to no member below " + num(nb);
+    std::vector<char> seen((size_t)N, 0);
+    colmem.assign((size_t)N, 0);
+    for (int k = 0; k < N; ++k) {
+        const int r = perm[k];
+        if (r < 0 || r >= N) return "column " + num(k) + " of the factor maps to row " + num(r) + " outside the image";
+        if (seen[(size_t)r]) return "row " + num(r) + " of the image appears twice in the permutation";
+        seen[(size_t)r] = 1;
+        colmem[(size_t)k] = rowmem[r];
+    }
+    return "";
+}
+
 }  // namespace hipkkt

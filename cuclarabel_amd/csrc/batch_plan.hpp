@@ -78,4 +78,9 @@ struct BatchImagePlan {
 std::string plan_batch_image(int n, int m, int p, const BatchPlan& B, const BatchImageCone* cones, int ncones, const int* long_rows,
                              int nlong, int chunk, BatchImagePlan& out);
 
+// ---- per-member regulariser and pivot status (hipkkt_kkt_system_set_member_status): column k of the factor's numbering
+// holds row perm[k] of the image, so colmem[k] = rowmem[perm[k]].  perm must be a permutation of 0 .. N - 1 (nperm = N
+// entries) and rowmem must have N entries in [0, nb).  Returns "" and fills colmem, or the text of the refusal.
+std::string plan_column_members(int N, int nb, const int* perm, size_t nperm, const int* rowmem, size_t nrowmem, std::vector<int>& colmem);
+
 }  // namespace hipkkt

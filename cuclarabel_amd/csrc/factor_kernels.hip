@@ -130,7 +130,9 @@ __global__ __launch_bounds__(256) void k_front_wave(FactorArgs A, int begin, int
         for (int e = lane; e < ne; e += 64) P[T.kdst[e0 + e]] = A.Kval[T.ksrc[e0 + e]];
     }
     WAVE_FENCE();
-    if (A.eps) {
+    if (A.eps_col) {                                   // (the column's member's regulariser; uniform over the launch)
+        if (lane < nc) P[lane + lane * f] += A.eps_col[c0 + lane] * (double)T.psign[c0 + lane];
+    } else if (A.eps) {
         const double eps = *A.eps;
         if (lane < nc) P[lane + lane * f] += eps * (double)T.psign[c0 + lane];
     }
@@ -252,7 +254,9 @@ __global__ __launch_bounds__(256) void k_front_tiny(FactorArgs A, int begin, int
         for (int e = sub; e < ne; e += 8) P[T.kdst[e0 + e]] = A.Kval[T.ksrc[e0 + e]];
     }
     WAVE_FENCE();
-    if (A.eps) {
+    if (A.eps_col) {
+        if (sub < nc) P[sub + sub * f] += A.eps_col[c0 + sub] * (double)T.psign[c0 + sub];
+    } else if (A.eps) {
         const double eps = *A.eps;
         if (sub < nc) P[sub + sub * f] += eps * (double)T.psign[c0 + sub];
     }
@@ -568,7 +572,9 @@ __global__ __launch_bounds__(BS) void k_panel(FactorArgs A, int begin)
         }
     }
     __syncthreads();
-    if (A.eps) {
+    if (A.eps_col) {
+        for (int k = tid; k < nc; k += BS) P[k + pcol(k, f)] += A.eps_col[c0 + k] * sgn[k];
+    } else if (A.eps) {
         const double eps = *A.eps;
         for (int k = tid; k < nc; k += BS) P[k + pcol(k, f)] += eps * sgn[k];
     }

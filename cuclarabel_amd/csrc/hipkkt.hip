@@ -197,7 +197,8 @@ public:
         // measured on MI355X/ROCm 7.2: replay is ~25 % slower than eager launches for these ~100-node
         // chains (the work is GPU-latency-bound, not host-bound), so graphs are opt-in
         const bool no_graph = !knobs().graph;
-        if (want_stamps || no_graph || n_factor_calls++ == 0) {
+        // (a per-column regulariser is not part of a captured graph's key: such a factorisation is enqueued)
+        if (want_stamps || no_graph || eps_col || n_factor_calls++ == 0) {
             enqueue_factor(d_Kval, d_eps, stream, nullptr, want_stamps);
             return;
         }
@@ -508,6 +509,7 @@ private:
         a.T = tree();
         a.Kval = d_Kval;
         a.eps = d_eps;
+        a.eps_col = d_eps ? eps_col : nullptr;
         a.fronts = fronts.p;
         a.upd = upd.p;
         a.Dinv = Dinv.p;
@@ -1195,6 +1197,9 @@ public:
     bool ov_active() const { return overlap_wanted() && !ov_disabled && sch.ov_first < sch.launches.size(); }
 
     int* flags_ptr() { return flags.p; }
+    const double* dinv_ptr() const { return Dinv.p; }
+    // hipkkt_kkt_system_set_member_status: N regularisers in the factor's column order that replace *d_eps (FactorArgs::eps_col)
+    const double* eps_col = nullptr;
 
 private:
     DBuf<int> d_sn_start, d_rows, d_rel, d_ncolpar, d_child_ptr, d_child_idx, d_ksrc, d_kdst, d_sched, d_perm;
@@ -1944,6 +1949,24 @@ struct hipkkt_kkt_s {
         M.slots = mr_slots.p; M.state = mr_state.p; M.normb = mr_normb.p; M.info = mr_info.p; M.agg = mr_agg.p;
         return M;
     }
+    // hipkkt_kkt_system_set_member_status: row -> member and column -> member on the device, the maxima's words, the column
+    // table of regularisers and the record {eps_b (nb doubles), cone words, pivot words (nb ints each)} that
+    // hipkkt_kkt_system_member_status reads back in one copy -- all allocated when the mode is enabled.  ms_valid: an update
+    // has run under it.
+    bool ms_on = false, ms_valid = false;
+    DBuf<int> ms_rowmem, ms_colmem;
+    DBuf<unsigned long long> ms_maxbits;
+    DBuf<double> ms_epscol, ms_rec;
+    bool member_status_on() const { return ms_on && bat_nb > 0; }
+    MemberStatusDev member_status_dev() const
+    {
+        MemberStatusDev M;
+        M.nb = bat_nb; M.N = K.N;
+        M.rowmem = ms_rowmem.p; M.colmem = ms_colmem.p; M.maxbits = ms_maxbits.p;
+        M.eps_mem = ms_rec.p; M.eps_col = ms_epscol.p;
+        M.cone_fail = (int*)(ms_rec.p + bat_nb); M.piv_bad = M.cone_fail + bat_nb;
+        return M;
+    }
     // data updating (hipkkt_kkt_system_set_equilibration and the four hipkkt_kkt_system_update_data_* calls): the frozen
     // scalings d, 1/d (n), e, 1/e (m) and c, every stored P / A entry's row and column (data_update.hpp) and the staging of
     // an indexed update's positions -- all built once (data_ensure), sized for the longest update there can be
@@ -2002,6 +2025,7 @@ struct hipkkt_kkt_s {
         S.ns_grad = ns_grad.p; S.ns_H = ns_H.p;
         S.gp_grad = gp_grad.p; S.gp_d = gp_d.p; S.gp_p = gp_p.p; S.gp_qr = gp_qr.p;
         S.Kval = Kval.p; S.fval = fval_dirty ? nullptr : fval.p; S.kpos = kpos.p;
+        if (member_status_on()) { S.fail_mem = (int*)(ms_rec.p + bat_nb); S.cone_mem = bat_cmem.p; }
         return S;
     }
 };
@@ -2646,11 +2670,24 @@ int hipkkt_kkt_info(hipkkt_kkt_t h, hipkkt_info* info)
     });
 }
 
+// the cone-failure word in front of a value update and, under hipkkt_kkt_system_set_member_status, the members' words
+// and the maxima in the same launch
+static void kkt_zero_update_words(hipkkt_kkt_t h)
+{
+    if (!h->member_status_on()) { launch_zero_ints(h->fail.p, 1, h->stream); return; }
+    ZeroList zl;
+    zl.add(h->fail.p, 1);
+    zl.add((int*)(h->ms_rec.p + h->bat_nb), 2 * h->bat_nb);
+    zl.add((int*)h->ms_maxbits.p, 2 * (h->bat_nb + 1));
+    launch_zero_ints_multi(zl, h->stream);
+}
+
 // scatter of -Hs and the sparse-cone columns, static regulariser, numeric factorisation
 // (kktsolver_directldl.jl:211-294).  Hs/u/v/eta2 already on the device.
 static int kkt_update_device(hipkkt_kkt_t h, bool deferred = false)
 {
     KKTAssembly& K = h->K;
+    const bool members = h->member_status_on();
     h->data_factor_stale = false;                    // (every value of Kval, updated P and A included, is factorised below)
     int pu = h->prof.begin(0, h->stream);
     // -Hs (:225-228) and the sparse cones' columns (:235-241) in one launch, written through to the residual's copy of K
@@ -2659,14 +2696,26 @@ static int kkt_update_device(hipkkt_kkt_t h, bool deferred = false)
                          h->soc_eta2.p, h->soc_of_entry.p, K.sparse_len, K.nsparse, h->fval_dirty ? nullptr : h->fval.p,
                          h->kpos.p, h->stream);
     const double* eps_ptr = nullptr;
+    h->eng->eps_col = nullptr;
     if (h->st.static_regularization_enable) {                                      // :259-279
-        launch_regularizer(h->Kval.p, h->mapDiag.p, K.N, h->st.static_regularization_constant,
-                           h->st.static_regularization_proportional, h->partial.p, h->scal.p, h->stream);
+        if (members) {
+            // eps_b from member b's own rows of the image, handed to the factor kernels column by column; scal[0]: the largest
+            launch_member_regularizer(h->member_status_dev(), h->Kval.p, h->mapDiag.p, h->st.static_regularization_constant,
+                                      h->st.static_regularization_proportional, h->scal.p, h->stream);
+            h->eng->eps_col = h->ms_epscol.p;
+        } else {
+            launch_regularizer(h->Kval.p, h->mapDiag.p, K.N, h->st.static_regularization_constant,
+                               h->st.static_regularization_proportional, h->partial.p, h->scal.p, h->stream);
+        }
         eps_ptr = h->scal.p;
     }
     h->prof.end(pu, h->stream);
     int pf = h->prof.begin(1, h->stream);
     h->eng->factor(h->Kval.p, eps_ptr);          // K itself stays un-regularised (:283-291)
+    if (members) {
+        launch_member_pivot_scan(h->member_status_dev(), h->eng->dinv_ptr(), h->stream);
+        h->ms_valid = true;
+    }
     h->prof.end(pf, h->stream);
     // read back: flags, eps, cone failure
     // (one small kernel gathers the four words, one copy into pinned memory brings them over: three separate
@@ -2679,6 +2728,7 @@ static int kkt_update_device(hipkkt_kkt_t h, bool deferred = false)
     if (h->pin->h[12] != 0.0) {                      // never expected; see LDLEngine::ov_gave_up: repeat level by level
         h->eng->ov_gave_up();
         h->eng->factor(h->Kval.p, eps_ptr);
+        if (members) launch_member_pivot_scan(h->member_status_dev(), h->eng->dinv_ptr(), h->stream);
         launch_collect_status(h->scal.p + 8, h->scal.p, h->fail.p, h->eng->flags_ptr(), h->stream);
         HIP_CHECK(hipMemcpyAsync(h->pin->h + 8, h->scal.p + 8, 5 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIP_CHECK(hipStreamSynchronize(h->stream));
@@ -2707,7 +2757,7 @@ int hipkkt_kkt_update_cones(hipkkt_kkt_t h, const double* Hs, const double* soc_
             HIP_CHECK(hipMemcpyAsync(h->soc_v.p, soc_v, (size_t)K.sparse_len * sizeof(double), hipMemcpyHostToDevice, h->stream));
             HIP_CHECK(hipMemcpyAsync(h->soc_eta2.p, soc_eta2, (size_t)K.nsparse * sizeof(double), hipMemcpyHostToDevice, h->stream));
         }
-        launch_zero_ints(h->fail.p, 1, h->stream);
+        kkt_zero_update_words(h);
         h->scaling_valid = false;
         return kkt_update_device(h);
     });
@@ -2722,7 +2772,7 @@ static int kkt_update_from_sz_dev_impl(hipkkt_kkt_t h, const double* d_s, const 
         if (h->psdb_kmax > kPsdBigMaxDim)
             throw ArgError("update_from_sz: PSD cones with side > 96 are scaled by the caller; use hipkkt_kkt_update_cones");
         HIP_CHECK(hipSetDevice(h->device));
-        launch_zero_ints(h->fail.p, 1, h->stream);
+        kkt_zero_update_words(h);
         int pu = h->prof.begin(0, h->stream);
         h->gp_mu = h->ns_mu;
         launch_cone_scaling(h->cone_dev(), h->cone_state(), d_s, d_z, h->K.m, h->stream);
@@ -3559,7 +3609,9 @@ int hipkkt_kkt_system_update(hipkkt_kkt_t h, const double* d_s, const double* d_
     // trip for kkt_update! + kkt_solve!(:affine) instead of three.  A failed factorisation therefore surfaces at the
     // affine kkt_solve! -- `is_kkt_solve_success = kkt_update!(...)` and `is_kkt_solve_success && kkt_solve!(...)`
     // (solver.jl:279-295) reach the same branch either way.
-    const bool enqueue_only = h && h->sys_lazy && h->sys_ready;
+    // (not under hipkkt_kkt_system_set_member_status: a failed update is answered member by member before the solve, so it
+    //  is read back at once, as member refinement keeps the lazy pairing's solves apart)
+    const bool enqueue_only = h && h->sys_lazy && h->sys_ready && !h->member_status_on();
     int rc = kkt_update_from_sz_dev_impl(h, d_s, d_z, enqueue_only);
     if (rc != HIPKKT_OK) return rc;                    // "bail if the factorization has failed" (:71)
     if (enqueue_only) h->sys_update_unread = true;
@@ -4302,6 +4354,7 @@ int hipkkt_kkt_system_set_problems(hipkkt_kkt_t h, int64_t nb, const int64_t* x_
         if (nb == 0) {                                   // (the tables stay allocated until the next partition or the handle's end)
             h->bat_nb = 0;
             h->mr_on = h->mr_valid = false;             // (the member refinement rule goes with its partition)
+            h->ms_on = h->ms_valid = false;             // (... and so does the member status)
             return HIPKKT_OK;
         }
         if (nb < 0) throw ArgError("hipkkt_kkt_system_set_problems: the number of members is negative");
@@ -4320,6 +4373,7 @@ int hipkkt_kkt_system_set_problems(hipkkt_kkt_t h, int64_t nb, const int64_t* x_
         HIP_CHECK(hipStreamSynchronize(h->stream));      // (nothing in flight reads the tables that are replaced now)
         h->bat_nb = 0;
         h->mr_on = h->mr_valid = false;
+        h->ms_on = h->ms_valid = false;
         h->bat_xoff.upload(P.x_off); h->bat_zoff.upload(P.z_off); h->bat_xmem.upload(P.xmem); h->bat_zmem.upload(P.zmem);
         h->bat_cmem.upload(P.cone_mem); h->bat_socptr.upload(P.soc_ptr); h->bat_psdptr.upload(P.psd_ptr);
         h->bat_degree.upload(P.degree);
@@ -4344,6 +4398,22 @@ int hipkkt_kkt_system_set_problems(hipkkt_kkt_t h, int64_t nb, const int64_t* x_
     });
 }
 
+// the partition carried over to K's image (batch_plan.hpp: plan_batch_image), for either member mode; returns the chunk
+static int member_image_plan(hipkkt_kkt_t h, const char* who, BatchImagePlan& I)
+{
+    std::vector<BatchImageCone> cones;
+    for (const ConeInfo& ci : h->K.cones) cones.push_back(BatchImageCone{ci.pcol, ci.pwidth});
+    // rows per workgroup: whole passes of the residual kernel's rows per block, few enough workgroups that a member's
+    // slots are folded cheaply (at most kNormParts + nb in all, as the whole-handle pass has kNormParts)
+    const int rpb = 256 / h->lanes_per_row;
+    const int passes = (int)(((int64_t)h->K.N + (int64_t)rpb * kNormParts - 1) / ((int64_t)rpb * kNormParts));
+    const int chunk = rpb * std::max(passes, 1);
+    const std::string err = plan_batch_image(h->K.n, h->K.m, h->K.p, h->bat_plan, cones.data(), (int)cones.size(),
+                                             h->long_rows_h.data(), (int)h->long_rows_h.size(), chunk, I);
+    if (!err.empty()) throw ArgError(std::string(who) + ": " + err);
+    return chunk;
+}
+
 // The refinement rule per member (kktsolver_directldl.jl:389-449 on each member's rows of K's image): plans the image's
 // rows by member on the host (batch_plan.hpp: plan_batch_image), uploads the tables and allocates slots and state.
 int hipkkt_kkt_system_set_member_refinement(hipkkt_kkt_t h, int enable)
@@ -4358,17 +4428,8 @@ int hipkkt_kkt_system_set_member_refinement(hipkkt_kkt_t h, int enable)
         h->mr_on = h->mr_valid = false;
         if (!enable) return HIPKKT_OK;
         if (h->bat_nb >= (1 << 20)) throw ArgError("hipkkt_kkt_system_set_member_refinement: at most 2^20 - 1 members");
-        std::vector<BatchImageCone> cones;
-        for (const ConeInfo& ci : h->K.cones) cones.push_back(BatchImageCone{ci.pcol, ci.pwidth});
-        // rows per workgroup: whole passes of the residual kernel's rows per block, few enough workgroups that a member's
-        // slots are folded cheaply (at most kNormParts + nb in all, as the whole-handle pass has kNormParts)
-        const int rpb = 256 / h->lanes_per_row;
-        const int passes = (int)(((int64_t)h->K.N + (int64_t)rpb * kNormParts - 1) / ((int64_t)rpb * kNormParts));
-        const int chunk = rpb * std::max(passes, 1);
         BatchImagePlan I;
-        const std::string err = plan_batch_image(h->K.n, h->K.m, h->K.p, h->bat_plan, cones.data(), (int)cones.size(),
-                                                 h->long_rows_h.data(), (int)h->long_rows_h.size(), chunk, I);
-        if (!err.empty()) throw ArgError("hipkkt_kkt_system_set_member_refinement: " + err);
+        const int chunk = member_image_plan(h, "hipkkt_kkt_system_set_member_refinement", I);
         h->mr_wgmem.upload(I.wg.wg_mem); h->mr_wgfirst.upload(I.wg.wg_first); h->mr_wgptr.upload(I.wg.wg_ptr);
         h->mr_rows.upload(I.img_rows); h->mr_ptr.upload(I.img_ptr);
         h->mr_lorder.upload(I.long_order); h->mr_lptr.upload(I.long_ptr);
@@ -4383,6 +4444,59 @@ int hipkkt_kkt_system_set_member_refinement(hipkkt_kkt_t h, int enable)
         h->mr_agg.zero(h->stream);
         HIP_CHECK(hipStreamSynchronize(h->stream));
         h->mr_on = true;
+        return HIPKKT_OK;
+    });
+}
+
+// The static regulariser and the failure words per member (kktsolver_directldl.jl:259-310, directldl_qdldl.jl:72-81 on
+// each member's rows and columns): row -> member from the image plan, column -> member through the factor's permutation
+// (batch_plan.hpp: plan_column_members), and the work space of the three kernels.
+int hipkkt_kkt_system_set_member_status(hipkkt_kkt_t h, int enable)
+{
+    return guarded([&]() {
+        if (!h) throw ArgError("null handle");
+        if (!h->sys_ready) throw ArgError("hipkkt_kkt_system_*: call hipkkt_kkt_system_init first");
+        if (h->bat_nb <= 0)
+            throw ArgError("hipkkt_kkt_system_set_member_status: the handle has no partition (hipkkt_kkt_system_set_problems)");
+        HIP_CHECK(hipSetDevice(h->device));
+        HIP_CHECK(hipStreamSynchronize(h->stream));      // (nothing in flight reads the tables that are replaced now)
+        h->ms_on = h->ms_valid = false;
+        h->eng->eps_col = nullptr;
+        if (!enable) return HIPKKT_OK;
+        BatchImagePlan I;
+        (void)member_image_plan(h, "hipkkt_kkt_system_set_member_status", I);
+        std::vector<int> colmem;
+        const std::vector<int>& perm = h->eng->S.perm;
+        const std::string err = plan_column_members(h->K.N, h->bat_nb, perm.data(), perm.size(), I.rowmem.data(), I.rowmem.size(), colmem);
+        if (!err.empty()) throw ArgError("hipkkt_kkt_system_set_member_status: " + err);
+        h->ms_rowmem.upload(I.rowmem); h->ms_colmem.upload(colmem);
+        const size_t nb = (size_t)h->bat_nb;
+        h->ms_maxbits.alloc(nb + 1); h->ms_epscol.alloc((size_t)h->K.N); h->ms_rec.alloc(2 * nb);
+        // (eps_b stays 0 when the static regulariser is disabled: nothing writes it then)
+        h->ms_maxbits.zero(h->stream); h->ms_epscol.zero(h->stream); h->ms_rec.zero(h->stream);
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        h->ms_on = true;
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_member_status(hipkkt_kkt_t h, double* out)
+{
+    return guarded([&]() {
+        if (!h || !out) throw ArgError("hipkkt_kkt_system_member_status: bad argument");
+        if (!h->member_status_on()) throw ArgError("hipkkt_kkt_system_member_status: member status is not enabled");
+        if (!h->ms_valid) throw ArgError("hipkkt_kkt_system_member_status: no update has run since member status was enabled");
+        HIP_CHECK(hipSetDevice(h->device));
+        const size_t nb = (size_t)h->bat_nb;
+        double* stage = h->bat_pin + 4 * nb;             // {eps_b, the cone words, the pivot words}: 2 nb doubles
+        HIP_CHECK(hipMemcpyAsync(stage, h->ms_rec.p, 2 * nb * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->stream));
+        const int* words = (const int*)(stage + nb);
+        for (size_t b = 0; b < nb; ++b) {
+            out[3 * b] = words[b] ? 1.0 : 0.0;
+            out[3 * b + 1] = words[nb + b] ? 1.0 : 0.0;
+            out[3 * b + 2] = h->st.static_regularization_enable ? stage[b] : 0.0;
+        }
         return HIPKKT_OK;
     });
 }
@@ -4578,7 +4692,10 @@ int hipkkt_kkt_system_solve_batch(hipkkt_kkt_t h, double* d_lhs_x, double* d_lhs
         if (affine) launch_pack_rhs_affine(h->b.p, nullptr, nullptr, d_rhs_x, d_var_s, d_rhs_z, n, m, h->K.p, 1, st);
         else launch_pack_rhs(h->b.p, d_rhs_x, h->sworkz.p, n, m, h->K.p, st);
         rc = kkt_solve_core(h, false, 1, nullptr, false);
-        if (rc != HIPKKT_OK) return rc;
+        // Under member status AND member refinement a failed solve names its members (hipkkt_kkt_system_member_refinement_info)
+        // and the others' rows are finished: the step is recovered for every member, the return value stays the joint one
+        const bool attributed = rc == HIPKKT_NUMERIC_FAILURE && h->member_status_on() && h->mr_on && h->mr_valid;
+        if (rc != HIPKKT_OK && !attributed) return rc;
         const double* x1 = h->x.p;
         // the dot products, dtau, dkappa and (dx, dz) per member (:185-206); the x2-only terms are formed here as well
         launch_batch_sys_step(sys_spmv(h), h->Kval.p, h->batch_dev(), h->sq.p, h->sb.p, d_var_x, x1, x1 + n, h->sx2.p, h->sz2.p, d_scal,
@@ -4587,7 +4704,7 @@ int hipkkt_kkt_system_solve_batch(hipkkt_kkt_t h, double* d_lhs_x, double* d_lhs
         // ds = -(Hs dz + const)                                               (:206-212)
         launch_mul_Hs(h->cone_dev(), h->cone_state(), d_lhs_s, d_lhs_z, m, st, affine ? d_var_s : h->sconic.p);
         batch_download(h, lhs_tau_kappa, 2);
-        return HIPKKT_OK;
+        return rc;
     });
 }
 
@@ -4683,12 +4800,12 @@ int hipkkt_kkt_system_update_scaling(hipkkt_kkt_t h, const double* w, const doub
         }
         // the caller's arrays are free again once these copies have run; the kernels behind them need not have
         h->host_upload_mark(st);
-        launch_zero_ints(h->fail.p, 1, st);
+        kkt_zero_update_words(h);
         int pu = h->prof.begin(0, st);
         launch_cone_from_scaling(h->cone_dev(), h->cone_state(), h->K.m, st);      // Hs, u, v, eta^2 (and R R') on the device
         h->prof.end(pu, st);
         h->scaling_valid = true;
-        enqueue_only = h->sys_lazy && h->sys_ready;
+        enqueue_only = h->sys_lazy && h->sys_ready && !h->member_status_on();       // (as in hipkkt_kkt_system_update)
         const int r = kkt_update_device(h, enqueue_only);
         h->host_upload_wait();
         return r;

@@ -743,6 +743,13 @@ __device__ inline void cone_elementwise_body(const ConeDev& C, const ConeState& 
     }
 }
 
+// cone c's point is not interior: the handle's word and, under hipkkt_kkt_system_set_member_status, its member's
+__device__ inline void cone_mark_fail(const ConeState& S, int c)
+{
+    *S.fail = 1;
+    if (S.fail_mem) S.fail_mem[S.cone_mem[c]] = 1;
+}
+
 __device__ inline double wave_sum(double v)
 {
 #pragma unroll
@@ -767,7 +774,7 @@ __device__ inline void cone_soc_body(const ConeDev& C, const ConeState& S, const
     const double s0 = sc[0], z0 = zc[0];
     double sres = (s0 - ss) * (s0 + ss), zres = (z0 - zz) * (z0 + zz);
     const double sscale = sres > 0.0 ? sqrt(sres) : 0.0, zscale = zres > 0.0 ? sqrt(zres) : 0.0;
-    if (sscale == 0.0 || zscale == 0.0) { if (lane == 0) *S.fail = 1; return; }
+    if (sscale == 0.0 || zscale == 0.0) { if (lane == 0) cone_mark_fail(S, c); return; }
     const double eta = sqrt(sscale / zscale);
     // w = s/sscale + J z/zscale, normalised
     double w1sq = 0.0;
@@ -781,7 +788,7 @@ __device__ inline void cone_soc_body(const ConeDev& C, const ConeState& S, const
     const double w1n = sqrt(w1sq);
     const double wres = (w0 - w1n) * (w0 + w1n);
     const double wscale = wres > 0.0 ? sqrt(wres) : 0.0;
-    if (wscale == 0.0) { if (lane == 0) *S.fail = 1; return; }
+    if (wscale == 0.0) { if (lane == 0) cone_mark_fail(S, c); return; }
     double w1sqn = 0.0;
     for (int i = 1 + lane; i < n; i += 64) {
         const double wi = w[i] / wscale;
@@ -924,7 +931,7 @@ __device__ inline void cone_nonsym_body(const ConeDev& C, const ConeState& S, co
         ns_update_Hs(sv, zv, g, H, zt, C.ns_strategy, C.ns_mu, Hs);
         for (int i = 0; i < 9; ++i) ok = ok && isfinite(Hs[i]);
     }
-    if (!ok) { *S.fail = 1; return; }
+    if (!ok) { cone_mark_fail(S, c); return; }
     double* out = S.Hs + C.boff[c];
     out[0] = Hs[0];                                   // pack_triu: columns of the upper triangle
     out[1] = Hs[1]; out[2] = Hs[4];
@@ -981,7 +988,7 @@ __device__ inline void cone_genpow_body(const ConeDev& C, const ConeState& S, co
     }
     gp_reduce3<NT, true>(phi, nw, bad, sh);
     const double zeta = phi - nw;
-    if (bad != 0.0 || !(zeta > 0.0) || !isfinite(zeta)) { if (tid == 0) *S.fail = 1; return; }
+    if (bad != 0.0 || !(zeta > 0.0) || !isfinite(zeta)) { if (tid == 0) cone_mark_fail(S, c); return; }
     const double p0 = sqrt(phi * (phi + nw) / 2.0);
     const double p1 = -2.0 * phi / p0;
     const double q0 = sqrt(zeta * phi / 2.0);
@@ -1137,7 +1144,7 @@ __device__ inline void cone_psd_body(const ConeDev& C, const ConeState& S, const
     __syncthreads();
     psd_cholesky<NT>(Sm, k, &sh_fail, [](double) {});
     if (!sh_fail) psd_cholesky<NT>(Zm, k, &sh_fail, [](double) {});
-    if (sh_fail) { if (tid == 0) *S.fail = 1; return; }
+    if (sh_fail) { if (tid == 0) cone_mark_fail(S, c); return; }
     for (int idx = tid; idx < kk; idx += NT) {
         const int r = idx % k, cl = idx / k;
         if (r < cl) { Sm[idx] = 0.0; Zm[idx] = 0.0; }

@@ -157,6 +157,7 @@ struct FactorArgs {
     TreeDev T;
     const double* Kval;          // caller's K.nzval (original order, un-regularised)
     const double* eps;           // device scalar: static regulariser to add as eps*sign, or null
+    const double* eps_col;       // N, permuted order: the regulariser of each column's member instead of *eps, or null
     double* fronts;
     double* upd;
     double* Dinv;                // N, permuted order
@@ -495,7 +496,10 @@ struct ConeState {
     double* psdR;                // per PSD cone: R = L1 V Lam^{-1/2} and Rinv = Lam^{-1/2} U' L2' (k x k col-major, same
     double* psdRinv;             //   offsets as psdA); the singular values Lam go to lam[off .. off + k), descending
     int* fail;                   // set to 1 when a point is not interior
-    double* ns_grad = nullptr;   // per exponential / power cone: grad f*(z), 3 doubles
+    // hipkkt_kkt_system_set_member_status: fail_mem[cone_mem[c]] is set beside *fail (nb words; cone_mem: BatchDev's)
+    int* fail_mem = nullptr;
+    const int* cone_mem = nullptr;
+    double* ns_grad = nullptr;  // per exponential / power cone: grad f*(z), 3 doubles
     double* ns_H = nullptr;      // ... and H*(z), 3 x 3
     // generalized power cones, per row at gp_off: grad f*(z), d = (d1, d2 ...), p, and q followed by r -- all unscaled
     double* gp_grad = nullptr;
@@ -726,6 +730,26 @@ void launch_member_ir_round(const MemberIrDev& M, int r, const int* flag_in, dou
                             double reltol, double stop_ratio, int max_iter, double* readback, hipStream_t st);
 // the long rows' chunk sums of launch_residual alone (one column), for the member pass's own finish
 void launch_residual_long_chunks(const SpmvDev& A, const double* Kval, const double* x, hipStream_t st);
+
+// ---- the static regulariser and the failure words per member (hipkkt_kkt_system_set_member_status)
+//   rowmem[i]   member of row i of K's image (batch_plan.hpp: BatchImagePlan::rowmem)
+//   colmem[k]   member of column k of the factor's numbering (plan_column_members)
+//   maxbits     nb + 1 words, zeroed by the caller before every update: the bit patterns of max |K_ii| per member, [nb] the stack's
+//   eps_mem     nb: c0 + c1 max_b;  eps_col: N, eps_mem through colmem (FactorArgs::eps_col)
+//   cone_fail   nb words, set by the cone scaling (ConeState::fail_mem);  piv_bad: nb words, set by the pivot scan
+struct MemberStatusDev {
+    int nb, N;
+    const int *rowmem, *colmem;
+    unsigned long long* maxbits;
+    double *eps_mem, *eps_col;
+    int *cone_fail, *piv_bad;
+};
+// two launches whatever nb: the segmented maximum of |K_ii| (diag: position of K_ii in Kval per image row), then eps_mem,
+// eps_col and eps_top[0] = the largest eps_b
+void launch_member_regularizer(const MemberStatusDev& M, const double* Kval, const int* diag, double c0, double c1, double* eps_top,
+                               hipStream_t st);
+// one launch behind the factorisation: piv_bad[colmem[k]] = 1 where Dinv[k] is not finite
+void launch_member_pivot_scan(const MemberStatusDev& M, const double* Dinv, hipStream_t st);
 
 
 // ---- Ruiz equilibration of (P, A, q, b) (problemdata.jl:133-221, mathutils.jl:129-269), all vectors on the device

@@ -158,7 +158,7 @@ def solve_device_batch(problems, settings=None, inspect=None):
     stack; `ir_iterations` of every result is the stack's total.  The symmetric start takes the handle's LP / QP branch
     (kktsystem.jl:95-143), which is decided by nnz(P) of the STACK: a batch that mixes members with and without a P starts
     its LP members from the QP start (another interior point; the answers agree to the tolerances, the iteration counts
-    need not).
+    need not).  solve_device_batch_isolated is this loop with the regulariser and a failure's status per member.
 
     inspect (optional): called once per iteration with (dict of the tensors the loop holds, the HipSystemBackend)."""
     return _solve_batch("solve_device_batch", problems, settings, inspect, False)
@@ -174,8 +174,30 @@ def solve_device_batch_refined(problems, settings=None, inspect=None):
     return _solve_batch("solve_device_batch_refined", problems, settings, inspect, True)
 
 
-def _solve_batch(who, problems, settings, inspect, member_refinement):
-    """The loop of solve_device_batch and solve_device_batch_refined."""
+def solve_device_batch_isolated(problems, settings=None, inspect=None, member_refinement=True):
+    """solve_device_batch in which a member that fails ends ALONE (hipkkt_kkt_system_set_member_status): every member is
+    regularised by eps_b = c0 + c1 max |K_ii| over its own rows of K, as it would be alone, and
+
+      - a failed kkt_update! reads the members' words: every active member whose cone scaling failed or whose block
+        produced a non-finite pivot ends with NUMERICAL_ERROR at that iteration and is frozen like a finished member (its
+        block scaled at its start point, its right-hand-side rows zero, alpha 0); the update is repeated in the same
+        iteration -- each repeat removes at least one member, so at most nb repeats.  If the words name no active member
+        the members still running end together, as in solve_device_batch;
+      - member_refinement=True (hipkkt_kkt_system_set_member_refinement as well): a failed solve reads the members' bad
+        flags; the flagged members end with NUMERICAL_ERROR and are frozen, the others carry on with the step the solve
+        produced for them (the member rule finishes their rows before the solve reports its failure);
+      - member_refinement=False: a failed solve stays JOINT and ends every member still running -- the joint rule's one
+        non-finite norm cannot be attributed to a member.
+
+    A member with a non-finite entry in P, q, A or b is refused with ValueError naming it before a handle is built: its
+    block could never be factorised.  Still joint: the LP / QP branch of the symmetric start, decided by nnz(P) of the
+    stack.  Without a failure the loop is solve_device_batch's (member_refinement=False) or solve_device_batch_refined's
+    (True) under the members' own regularisers."""
+    return _solve_batch("solve_device_batch_isolated", problems, settings, inspect, bool(member_refinement), True)
+
+
+def _solve_batch(who, problems, settings, inspect, member_refinement, isolate=False):
+    """The loop of solve_device_batch, solve_device_batch_refined and solve_device_batch_isolated."""
     import torch
     problems = list(problems)
     if not problems:
@@ -188,6 +210,10 @@ def _solve_batch(who, problems, settings, inspect, member_refinement):
             raise ValueError(f"{who} covers PSD cones up to side {PSD_MAX_SIDE}")
         Pt = sp.triu(sp.csc_matrix(P), format="csc")
         members.append((Pt, np.asarray(q, float), sp.csc_matrix(A), np.asarray(b, float), cone_specs))
+        if isolate:
+            for name, values in (("P", Pt.data), ("q", members[-1][1]), ("A", members[-1][2].data), ("b", members[-1][3])):
+                if not np.all(np.isfinite(values)):
+                    raise ValueError(f"{who}: member {len(members) - 1} has a non-finite entry in {name}")
     st = settings or IPMSettings()
     nb = len(members)
     P = sp.block_diag([mb[0] for mb in members], format="csc")
@@ -225,6 +251,8 @@ def _solve_batch(who, problems, settings, inspect, member_refinement):
     system.set_problems(blocks)
     if member_refinement:
         system.set_member_refinement(True)
+    if isolate:
+        system.set_member_status(True)
     ir_member = np.zeros(nb, dtype=np.int64)             # (member rule: every member's own rounds)
     backend.update_identity()
     system.solve_constant_rhs()
@@ -243,6 +271,15 @@ def _solve_batch(who, problems, settings, inspect, member_refinement):
     hist = [[] for _ in range(nb)]
     prev_vars = None
     tiny = 100 * np.finfo(float).eps
+
+    def end_members(named, act, active):
+        """isolate: the active members that `named` marks end with NUMERICAL_ERROR and leave act / active"""
+        for k in active:
+            if named[k]:
+                status[k], iterations[k] = NUMERICAL_ERROR, it
+                act[k] = False
+        return [k for k in active if act[k]]
+
     with np.errstate(all="ignore"):                      # (a frozen member's scalars may overflow; they are not used)
         while True:
             active = [k for k in range(nb) if status[k] == UNSOLVED]
@@ -315,17 +352,28 @@ def _solve_batch(who, problems, settings, inspect, member_refinement):
             #     the joint tolerance reltol ||b||_inf -- by the library's own elementwise calls with 0 / 1 as the members'
             #     scalars, three small launches.
             # Its step is discarded anyway (alpha = 0); nothing here runs before a member has ended.
-            frozen = (~act).astype(float)
-            any_frozen = len(active) < nb
-            if nb - len(active) != nfrozen:
-                nfrozen = nb - len(active)
-                hm = np.zeros(m, bool)
-                for k in range(nb):
-                    if not act[k]:
-                        hm[z_off[k]:z_off[k + 1]] = True
-                frozen_rows = torch.from_numpy(hm).to(dev)
-            s_u, z_u = (torch.where(frozen_rows, s0, s), torch.where(frozen_rows, z0, z)) if any_frozen else (s, z)
-            ok = system.update_dev(p(s_u), p(z_u))
+            while True:
+                frozen = (~act).astype(float)
+                any_frozen = len(active) < nb
+                if nb - len(active) != nfrozen:
+                    nfrozen = nb - len(active)
+                    hm = np.zeros(m, bool)
+                    for k in range(nb):
+                        if not act[k]:
+                            hm[z_off[k]:z_off[k + 1]] = True
+                    frozen_rows = torch.from_numpy(hm).to(dev)
+                s_u, z_u = (torch.where(frozen_rows, s0, s), torch.where(frozen_rows, z0, z)) if any_frozen else (s, z)
+                ok = system.update_dev(p(s_u), p(z_u))
+                if ok or not isolate:
+                    break
+                # isolate: the members the failed update names end alone, and the update is repeated without them
+                words = system.member_status()
+                named = (words[:, 0] != 0) | (words[:, 1] != 0)
+                if not any(named[k] for k in active):
+                    break                                                    # (no member to blame: joint, below)
+                active = end_members(named, act, active)
+                if not active:
+                    break
             if ok:
                 # ---- affine step (solver.jl:282-295): right-hand side (rx, s - rz)
                 system.affine_ds_dev(p(aff_s))
@@ -339,7 +387,12 @@ def _solve_batch(who, problems, settings, inspect, member_refinement):
                                                           (p(x), p(s), p(z)), tau, kappa, True)
                 ir_total += backend.last_ir_iterations
                 if member_refinement:
-                    ir_member += system.member_refinement_info()[:, 0].astype(np.int64)
+                    rinfo = system.member_refinement_info()
+                    ir_member += rinfo[:, 0].astype(np.int64)
+                    if not ok and isolate and rinfo[:, 3].any():
+                        # the flagged members end alone; the others' rows of the step are finished
+                        active = end_members(rinfo[:, 3] != 0, act, active)
+                        ok = True
             if ok:
                 # ---- combined step (solver.jl:297-323)
                 alpha = system.step_length_batch_dev(p(dz), p(ds), p(z), p(s), dtau, dkappa, tau, kappa)
@@ -354,7 +407,11 @@ def _solve_batch(who, problems, settings, inspect, member_refinement):
                                                           (p(x), p(s), p(z)), tau, kappa, False)
                 ir_total += backend.last_ir_iterations
                 if member_refinement:
-                    ir_member += system.member_refinement_info()[:, 0].astype(np.int64)
+                    rinfo = system.member_refinement_info()
+                    ir_member += rinfo[:, 0].astype(np.int64)
+                    if not ok and isolate and rinfo[:, 3].any():
+                        active = end_members(rinfo[:, 3] != 0, act, active)
+                        ok = True
             if not ok:
                 alpha = np.zeros(nb)
                 for k in active:

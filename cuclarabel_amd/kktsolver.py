@@ -570,6 +570,20 @@ class HipKKTSystem:
               "hipkkt_kkt_system_member_refinement_info")
         return out[:self.nb]
 
+    def set_member_status(self, enable):
+        """The static regulariser per member (eps_b from member b's own rows of K's image) and a failed update's cone and
+        pivot words per member, for every refactorisation of the handle.  Replacing or clearing the partition switches it
+        off again.  Raises HipKKTError on a handle without a partition."""
+        check(_lib.lib().hipkkt_kkt_system_set_member_status(self.ks._h, 1 if enable else 0),
+              "hipkkt_kkt_system_set_member_status")
+
+    def member_status(self):
+        """numpy array (nb, 3) of the last refactorisation under member status: row b = (1.0 if the scaling of one of
+        member b's cones failed, 1.0 if a pivot in its columns was not finite, eps_b)."""
+        out = np.zeros((max(self.nb, 1), 3))
+        check(_lib.lib().hipkkt_kkt_system_member_status(self.ks._h, ptr(out)), "hipkkt_kkt_system_member_status")
+        return out[:self.nb]
+
     def _scalars(self, *arrays):
         """The members' scalars as contiguous float64 arrays of length nb (a Python float is not broadcast: one value per
         member is the point of these calls)."""

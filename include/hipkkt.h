@@ -587,11 +587,15 @@ int hipkkt_kkt_system_data_norms(hipkkt_kkt_t h, double out[2]);
  * up in one copy and the results come back in one copy, and the number of kernel launches does not depend on nb: the
  * reductions are segmented by member on the device (a workgroup belongs to one member; member b's wave folds b's slots
  * in slot order -- fixed layout, no floating-point atomic, two calls give the same bits).
- * What stays JOINT on a partitioned handle, because the factorisation is one: the status of hipkkt_kkt_system_update and
- * of the solves (a failed kkt_update!, kktsystem.jl:62-78, fails for every member); the static regulariser's epsilon,
- * scaled by the largest diagonal entry of the whole K (kktsolver_directldl.jl:297-310); and the iterative refinement's
- * stopping rule, whose infinity-norms run over the stack (kktsolver_directldl.jl:389-470) -- the refinement rule is joint
- * unless hipkkt_kkt_system_set_member_refinement (below) has been enabled; the status of a solve stays joint even then.
+ * What stays JOINT on a partitioned handle unless the handle opts out: the static regulariser's epsilon, scaled by the
+ * largest diagonal entry of the whole K (kktsolver_directldl.jl:297-310), and the attribution of a failed
+ * hipkkt_kkt_system_update (a failed kkt_update!, kktsystem.jl:62-78, names no member) -- both per member once
+ * hipkkt_kkt_system_set_member_status (below) has been enabled; and the iterative refinement's stopping rule, whose
+ * infinity-norms run over the stack (kktsolver_directldl.jl:389-470) -- per member once
+ * hipkkt_kkt_system_set_member_refinement (below) has been enabled.  JOINT whatever is enabled: the RETURN VALUE of
+ * hipkkt_kkt_system_update and of the solves, the status of the call (HIPKKT_NUMERIC_FAILURE if any member failed: which
+ * member is read from hipkkt_kkt_system_member_status and hipkkt_kkt_system_member_refinement_info); the LP / QP branch of
+ * the symmetric start, decided by nnz(P) of the stack; and the count of dynamic regularisations.
  * hipkkt_kkt_system_update,
  * _solve_constant_rhs, _solve_initial_point and _affine_ds have no scalar argument and serve a partitioned handle as
  * they are: the block-diagonal K does their work per member.  No scalar entry point changes its behaviour on a
@@ -638,6 +642,37 @@ int hipkkt_kkt_system_set_member_refinement(hipkkt_kkt_t h, int enable);
  * its was not finite else 0}.  HIPKKT_ERR_ARG if member refinement is not enabled or no solve has run under it since it
  * was enabled.  Synchronises: one read-back of 4 nb doubles, no kernel. */
 int hipkkt_kkt_system_member_refinement_info(hipkkt_kkt_t h, double *out);
+
+/* The static regulariser and the failure words of a refactorisation per member instead of over the stack
+ * (kktsolver_directldl.jl:259-310, kktsystem.jl:62-78, directldl_qdldl.jl:72-81 on each member's rows and columns).
+ * enable != 0: from now on every refactorisation of this handle -- hipkkt_kkt_system_update, _update_cones,
+ * _update_scaling, _update_host, _update_and_solve_affine and the level-B updates -- takes
+ * eps_b = static_regularization_constant + static_regularization_proportional * max |K_ii| with i over member b's rows
+ * of K's image (its x rows, its z rows and the expansion rows behind n + m of its sparse second-order cones), and member
+ * b's pivots receive eps_b * sign; K itself stays un-regularised.  With static_regularization_enable = 0 nothing is
+ * added and eps_b = 0.  hipkkt_kkt_last_regularizer reports the largest eps_b.  Beside the handle's words, the scaling
+ * of a cone that fails marks its member, and one pass behind the factorisation marks the member of every column whose
+ * pivot's reciprocal is not finite (K is block diagonal: a member's columns form their own subtrees, a non-finite value
+ * never leaves its block).  The return value of the update stays the joint one, HIPKKT_NUMERIC_FAILURE if any member
+ * failed.  Three launches more per update whatever nb (the segmented maximum, eps per member and per column, the pivot
+ * pass; the members' words are zeroed by the launch that zeroes the handle's), the maxima by integer atomicMax on bit
+ * patterns: no floating-point atomic, exact.  While enabled the lazy mode's enqueue-only update is not taken: an update
+ * is read back at once, so that a failure can be answered member by member before the next solve.  While this mode AND
+ * member refinement are enabled, a hipkkt_kkt_system_solve_batch whose solve fails because members were marked bad still
+ * recovers the step of every member (the member rule has finished the others' rows) before it returns
+ * HIPKKT_NUMERIC_FAILURE; otherwise a failed solve returns at once, as before.  With nb = 1 an
+ * update and every solve behind it are bit for bit those of the same handle with the mode off.  enable == 0 switches
+ * back; so does replacing or clearing the partition.  HIPKKT_ERR_ARG on a handle without a partition.  Tables (row ->
+ * member, column of the factor -> member) and work space are sized by nb and N and allocated HERE, not in an update.
+ * Synchronises with the handle's stream (tables in use are replaced); enqueues no kernel. */
+int hipkkt_kkt_system_set_member_status(hipkkt_kkt_t h, int enable);
+
+/* What the last refactorisation under hipkkt_kkt_system_set_member_status found (kktsolver_directldl.jl:259-310,
+ * directldl_qdldl.jl:72-81, per member): out (host, 3 nb) receives for member b at out[3 b ..] {1 if the scaling of one
+ * of its cones failed else 0, 1 if a pivot in its columns was not finite else 0, eps_b}.  The OR over the members of
+ * either word is the handle's joint word.  HIPKKT_ERR_ARG if the mode is not enabled or no update has run since it was
+ * enabled.  Synchronises: one read-back of 2 nb doubles, no kernel. */
+int hipkkt_kkt_system_member_status(hipkkt_kkt_t h, double *out);
 
 /* Rules for the seven _batch calls: on a handle without a partition, on a deferred-status handle and with a NULL scalar
  * array each returns HIPKKT_ERR_ARG and enqueues nothing; the aliasing rules are the twin's. */

@@ -9,7 +9,12 @@ Both loops do the same vector work per iteration (one update, two solves, the sa
 their per-iteration times are comparable; the iteration COUNTS are not the same thing (the stacked loop ends with one
 status).  --member-refinement (mode batch): ipm_device.solve_device_batch_refined, the refinement's accept / stop rule per
 member; `refinement_rounds` is the handle's total of refinement rounds (sweep pairs behind the first solve) either way,
-`refinement_rounds_per_member` each member's own total under the member rule.  One JSON line per run.  --root: the tree whose cuclarabel_amd is imported (another build of the library for an
+`refinement_rounds_per_member` each member's own total under the member rule.  --isolate (mode batch):
+ipm_device.solve_device_batch_isolated, every member under its own static regulariser and failure status (with
+--member-refinement: its member rule as well).  --profile (mode batch): the handle's event profile is switched on at the
+loop's first iteration; `update_ms_per_update` and `factor_ms_per_update` are the device times of a kkt_update!'s value
+update (cone scaling, scatter, regulariser) and factorisation (with --isolate: the pivot pass behind it included) -- the
+timed loop is slower with the events in it, so take problems/s from a run without.  One JSON line per run.  --root: the tree whose cuclarabel_amd is imported (another build of the library for an
 A/B comparison in one session: run this script with the other tree's root and --mode stacked).
 
     python scripts/bench_batch_loop.py --mode batch --members 64 --n 10000 --runs 3
@@ -28,10 +33,14 @@ def main():
     ap.add_argument("--n", type=int, default=10_000)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--member-refinement", action="store_true")
+    ap.add_argument("--isolate", action="store_true")
+    ap.add_argument("--profile", action="store_true")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     args = ap.parse_args()
     if args.member_refinement and args.mode != "batch":
         ap.error("--member-refinement goes with --mode batch")
+    if (args.isolate or args.profile) and args.mode != "batch":
+        ap.error("--isolate and --profile go with --mode batch")
     sys.path.insert(0, args.root)
     import torch
     from cuclarabel_amd import ipm_device, problems
@@ -43,14 +52,23 @@ def main():
 
     def stamp(tensors, backend):
         stamps.append(time.perf_counter())
+        if args.profile and len(stamps) == 1:
+            backend.ks.profile_enable(True)
         seen["ks"] = backend.ks
     if args.mode == "batch":
         data = [(pb.P, pb.q, pb.A, pb.b, pb.cones) for pb in pbs]
         loop = ipm_device.solve_device_batch_refined if args.member_refinement else ipm_device.solve_device_batch
+        if args.isolate:
+            loop = lambda d, inspect: ipm_device.solve_device_batch_isolated(d, inspect=inspect, member_refinement=args.member_refinement)
         run = lambda: loop(data, inspect=stamp)
         iters = lambda res: max(r.iterations for r in res)
+        def device_times():
+            pr = seen["ks"].profile()
+            return dict(update_ms_per_update=round(pr["update_ms"] / max(pr["n_factor"], 1), 5),
+                        factor_ms_per_update=round(pr["factor_ms"] / max(pr["n_factor"], 1), 5)) if args.profile else {}
         extra = lambda res: dict(iterations_per_member=[r.iterations for r in res],
                                  statuses=sorted(set(r.status for r in res)), member_refinement=bool(args.member_refinement),
+                                 isolate=bool(args.isolate), **device_times(),
                                  refinement_rounds=int(seen["ks"].profile()["ir_iterations"]),
                                  **(dict(refinement_rounds_per_member=[r.kkt_ir_rounds for r in res]) if args.member_refinement else {}))
     elif args.mode == "stacked":
@@ -73,6 +91,8 @@ def main():
         dt = time.perf_counter() - t0
         out = dict(mode=args.mode, members=args.members, n=args.n, run=k, seconds=round(dt, 6), loop_iterations=iters(res),
                    root=os.path.basename(os.path.abspath(args.root)))
+        if args.mode == "batch":
+            out["problems_per_s"] = round(args.members / dt, 2)
         if len(stamps) > 1:
             out["ms_per_iteration"] = round(1e3 * (stamps[-1] - stamps[0]) / (len(stamps) - 1), 4)
         out.update(extra(res))
