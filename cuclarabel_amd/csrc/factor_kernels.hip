@@ -1220,17 +1220,31 @@ void launch_panel_sliced(const FactorArgs& a, int begin, int count, size_t lds, 
     if (a.ov) hipLaunchKernelGGL((k_panel<1024, true, true>), dim3(count), dim3(1024), lds, st, a, begin);
     else hipLaunchKernelGGL((k_panel<1024, true, false>), dim3(count), dim3(1024), lds, st, a, begin);
 }
-void launch_schur(const FactorArgs& a, const int2* tiles, int tile_begin, int ntiles, hipStream_t st, int ov_grid, int tile_nc)
+SchurBuild schur_build(bool ov, int ntiles, int tile_nc)
 {
-    if (ntiles <= 0) return;
+    if (ntiles <= 0) return SchurBuild::none;
     // (the pipelined chunk loop outside the overlap mode: launches of thousands of tiles whose products are four chunks deep
     //  or more -- the trailing blocks of very large fronts, cfg5's wide levels; on cfg2's wide middle levels, one to three
     //  chunks per tile, its registers cost more than the latency it hides, see k_schur)
     const int pipe_tiles = knobs().schur_pipe_tiles;
     const int pipe_nc = knobs().schur_pipe_nc;
-    if (a.ov) hipLaunchKernelGGL((k_schur<true, true>), dim3(std::max(1, std::min(ntiles, ov_grid))), dim3(256), 0, st, a, tiles, tile_begin, ntiles);
-    else if (ntiles > pipe_tiles && tile_nc >= pipe_nc) hipLaunchKernelGGL((k_schur<false, true>), dim3(ntiles), dim3(256), 0, st, a, tiles, tile_begin, ntiles);
-    else hipLaunchKernelGGL((k_schur<false, false>), dim3(ntiles), dim3(256), 0, st, a, tiles, tile_begin, ntiles);
+    if (ov) return SchurBuild::overlap;
+    return (ntiles > pipe_tiles && tile_nc >= pipe_nc) ? SchurBuild::pipelined : SchurBuild::plain;
+}
+void launch_schur(const FactorArgs& a, const int2* tiles, int tile_begin, int ntiles, hipStream_t st, int ov_grid, int tile_nc)
+{
+    switch (schur_build(a.ov != 0, ntiles, tile_nc)) {
+    case SchurBuild::none: return;
+    case SchurBuild::overlap:
+        hipLaunchKernelGGL((k_schur<true, true>), dim3(std::max(1, std::min(ntiles, ov_grid))), dim3(256), 0, st, a, tiles, tile_begin, ntiles);
+        return;
+    case SchurBuild::pipelined:
+        hipLaunchKernelGGL((k_schur<false, true>), dim3(ntiles), dim3(256), 0, st, a, tiles, tile_begin, ntiles);
+        return;
+    case SchurBuild::plain:
+        hipLaunchKernelGGL((k_schur<false, false>), dim3(ntiles), dim3(256), 0, st, a, tiles, tile_begin, ntiles);
+        return;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------------

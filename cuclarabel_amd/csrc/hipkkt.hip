@@ -177,9 +177,11 @@ public:
                         fmin = std::min(fmin, f); ncmin = std::min(ncmin, nc);
                         flops += (double)nc * (f - nc) * (f - nc) + (double)nc * nc * (f - nc) + (double)nc * nc * nc / 3;
                     }
-                    std::fprintf(stderr, "[hipkkt] launch %zu level %d: %d fronts (%s), f %d..%d, nc %d..%d, %d sliced into %d, %d tiles (%d columns deep on average), %.3f GF\n",
+                    // (the tile kernel's build: launch_schur's own decision, for an admitted overlapped factorisation)
+                    const bool ov = overlap_wanted() && q >= sch.ov_first;
+                    std::fprintf(stderr, "[hipkkt] launch %zu level %d: %d fronts (%s), f %d..%d, nc %d..%d, %d sliced into %d, %d tiles (%d columns deep on average), %.3f GF, tile kernel: %s\n",
                                  q, L.level, L.count, L.small ? "one wave" : "block", fmin, L.fmax, ncmin, L.ncmax, L.nsliced, L.slice_count,
-                                 L.ntiles, L.tile_nc, flops * 1e-9);
+                                 L.ntiles, L.tile_nc, flops * 1e-9, schur_build_name(schur_build(ov, L.ntiles, L.tile_nc)));
                 }
             if (overlap_wanted())
                 for (size_t q = sch.ov_first; q < sch.launches.size(); ++q)
@@ -1598,11 +1600,17 @@ private:
                 // wide levels (>= 150 fronts) permuted, factorisation 1.754 / 1.760 -> 1.743 / 1.751 ms; permuting the narrow
                 // levels as well costs time (>= 32: 1.766 / 1.770 -- a handful of fronts' tiles then crowd one XCD).
                 const int tile_xcd = knobs().tile_xcd;
+                int dealt_launches = 0;
+                int64_t dealt_tiles = 0;
+                std::string dealt_list;
                 if (tile_xcd > 0) {
                     std::vector<int64_t> nc2(tcut);
                     std::vector<int> pc2(ptcut);
                     for (const Launch& L : sch.launches) {
                         if (L.small || L.count < tile_xcd || L.ntiles <= 0) continue;
+                        ++dealt_launches;
+                        dealt_tiles += L.ntiles;
+                        dealt_list += " " + std::to_string(&L - sch.launches.data());
                         // the launch's fronts and their (contiguous) logical tile ranges
                         std::vector<std::pair<int64_t, int64_t>> rng;       // [first, last) per front, launch order
                         for (int t = L.begin; t < L.begin + L.count; ++t) {
@@ -1632,6 +1640,9 @@ private:
                     tcut.swap(nc2);
                     ptcut.swap(pc2);
                 }
+                if (knobs().verbose)
+                    std::fprintf(stderr, "[hipkkt] tile order: %d launches dealt to XCD residue classes (%lld tiles):%s\n", dealt_launches,
+                                 (long long)dealt_tiles, dealt_launches ? dealt_list.c_str() : " none");
             }
             d_tiles.upload(tiles_up);
             std::vector<int64_t> raw2(sit.size() * 2);

@@ -59,8 +59,8 @@ namespace hipkkt {
     KNOB(int, ov_merge, "HIPKKT_OV_MERGE", 100)             /* panel workgroups per merged panel kernel (0: a kernel per level) */      \
     KNOB(int, ov_merge_wide, "HIPKKT_OV_MERGE_WIDE", 24)    /* widest launch a merged run below the root's may hold */                 \
     KNOB(int, ov_merge_groups, "HIPKKT_OV_MERGE_GROUPS", 8) /* merged panel kernels per factorisation */                               \
-    KNOB(int, schur_pipe_tiles, "HIPKKT_SCHUR_PIPE_TILES", 1600) /* outside the mode: launches of more tiles ... */                    \
-    KNOB(int, schur_pipe_nc, "HIPKKT_SCHUR_PIPE_NC", 64)    /* ... or at least this deep on average pipeline their chunk loop */        \
+    KNOB(int, schur_pipe_tiles, "HIPKKT_SCHUR_PIPE_TILES", 1600) /* outside the mode: launches of more tiles than this ... */          \
+    KNOB(int, schur_pipe_nc, "HIPKKT_SCHUR_PIPE_NC", 64)    /* ... that are ALSO at least this deep on average pipeline their chunk loop */ \
     /* ---- sweeps */                                                                                                                  \
     FLAG_SET(no_top, "HIPKKT_NO_TOP")                       /* no persistent top-of-tree kernel */                                     \
     KNOB(int, top_tall, "HIPKKT_TOP_TALL", -1)              /* 0: the persistent kernel's 512-thread build */                          \

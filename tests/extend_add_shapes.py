@@ -258,11 +258,32 @@ def case(name, seed=1):
     if (name, seed) not in _CASES:
         if name == "tiny_parent":
             cols, rows = tiny_parent()
+        elif name == "xcd_parents":
+            cols, rows = xcd_parents()
         else:
             d = cases()[name]
             cols, rows = d["cols"], d["rows"]
         _CASES[(name, seed)] = pls.make_case(cols, rows, seed)
     return _CASES[(name, seed)]
+
+
+# --------------------------------------------------------------------------- parents side by side (tests/test_gpu_factor_builds.py)
+# Ten designed parents in ONE launch for the XCD tile order (csrc/hipkkt.hip: HIPKKT_TILE_XCD permutes a launch's tiles together
+# with their pass-through ranges, tile_cut and ptile_cut): nine whose stored children bring tile pieces -- update blocks of 120
+# and of 128 rows, three tiles each, with very different lists -- and one of 60 rows, one tile, without any.  A group of eight
+# fronts and a last group of two; the roots above are two links each, so the forest is tall enough for the overlap mode.
+XCD_PARENTS = ("len_63", "len_64", "len_65", "len_128", "len_129", "len_tail", "tile_n15", "tile_n17_b", "many_33", "panel_n15")
+
+
+def xcd_parents():
+    """(cols, rows) of the trees of XCD_PARENTS side by side in one matrix, each tree's indices behind the one before."""
+    T = cases()
+    cols, rows, base = [], [], 0
+    for n in XCD_PARENTS:
+        cols += [[i + base for i in c] for c in T[n]["cols"]]
+        rows += [[i + base for i in r] for r in T[n]["rows"]]
+        base = cols[-1][-1] + 1
+    return cols, rows
 
 
 def second(name):

@@ -502,6 +502,154 @@ def multi_specs():
     return T
 
 
+# --------------------------------------------------------------------------- cases for the builds of k_panel and k_schur
+# (tests/test_gpu_factor_builds.py).  k_schur works on 64 x 64 tiles, one 32 x 32 quadrant per wave, in chunks of KC = 16
+# columns and MFMA steps of 4; which BUILD of it (and of k_panel) a front meets is the schedule's decision:
+#   plain      k_panel<BS, false, false>, k_schur<false, false>   outside the overlap mode
+#   pipelined  k_schur<false, true>                               ... in launches of many deep tiles (HIPKKT_SCHUR_PIPE_*)
+#   overlap    k_panel<BS, false, true>, k_schur<true, true>      the schedule's tail of >= 3 block-class launches
+QUADRANT_NB = (31, 32, 33, 95, 96, 97)           # at nc = 40: a quadrant of the (last) tile row empty, full, one row over
+CHUNK_NC = (15, 16, 17, 33, 48, 49)              # chunk edges ...
+CHUNK_NB = (65, 129)                             # ... with off-diagonal tiles whose last tile row has ONE row (nr = 1, nq = 64)
+SHALLOW_NC = (3, 4, 5)                           # a partial MFMA step, one step, one step and a partial one
+# the shape-table cases that get a tall variant as well
+BUILD_FROM_SHAPES = tuple(f"panel_nc{nc}" for nc in (15, 16, 17, 31, 32, 33, 95, 96)) + \
+    tuple(f"schur_nb{nb}" for nb in (1, 63, 64, 65, 127, 128, 129, 192, 193)) + \
+    tuple(f"bs_f{f}" for f in (128, 129, 192, 193)) + ("trap_96_151", "block_1_39", "block_16_29")
+
+
+def build_table():
+    """name -> (spec, level-0 tuple, class) of the new shapes, in the form of shape_table()."""
+    T = {}
+    for nb in QUADRANT_NB:
+        T[f"quad_nb{nb}"] = _child(40, nb) + ("block",)
+    for nc, nb in [(nc, nb) for nc in CHUNK_NC for nb in CHUNK_NB] + [(96, 129)]:
+        T[f"chunk_{nc}_{nb}"] = _child(nc, nb) + ("block",)
+    # f * nc + nb^2 = 42 * 3 + 1521 > 1536: block-class fronts of 3, 4 and 5 columns
+    for nc in SHALLOW_NC:
+        T[f"shallow_{nc}_39"] = _narrow(nc, 39) + ("block",)
+    return T
+
+
+# csrc/symbolic.hpp: panel_cap, panel_max_cols, panel_slice_below, panel_max_slices
+_TRAP_CAP, _PANEL_COLS, _SLICE_BELOW, _PANEL_SLICES = 19200, 96, 64, 128
+
+
+def chain_links(W, nb=0):
+    """Widths of the links symbolic.cpp 7b cuts a supernode of W columns and nb rows into: the widest panel (<= 96 columns)
+    whose trapezoid fits the cap -- or, where that one is narrower than 64 columns and a ROW-SLICED panel (its rows in up to
+    128 slices) saves a link, the widest sliced one --, the remaining columns balanced over the remaining links.  (Fronts
+    of a few hundred rows: the sweep kernels' own cap does not bind.)"""
+    out = []
+    while W > 0:
+        f = W + nb
+        wd = w1 = min(W, _PANEL_COLS)
+        while wd > 1 and wd * (wd + 1) // 2 + -(-(f - wd) // _PANEL_SLICES) * wd > _TRAP_CAP:
+            wd -= 1
+        while w1 > 1 and _trap(w1, f - w1) > _TRAP_CAP:
+            w1 -= 1
+        if w1 >= _SLICE_BELOW or -(-W // w1) <= -(-W // wd):
+            wd = w1
+        if wd < W:
+            parts = -(-W // wd)
+            wd = -(-W // parts)
+        out.append(wd)
+        W -= wd
+    return out
+
+
+def _link_fronts(W, nb=0):
+    out = []
+    for w in chain_links(W, nb):
+        out.append((W + nb, w))
+        W -= w
+    return out
+
+
+TALL_NG = 200                                    # columns of a tall variant's root: three links of its own (67, 67, 66)
+
+
+def tall(spec):
+    """The tall variant of a designed() / beside_sibling() tree: the same fronts under a root G = (ng, 0) of at least
+    TALL_NG columns, which 7b cuts into a chain of three links or more (as the roots of tests/extend_add_shapes.py:
+    ng, _g_links) -- at least three block-class launches follow the designed front's own, the condition of the overlap
+    mode (csrc/schedule.cpp: admit_overlap)."""
+    *below, (g, nb, p) = spec
+    assert nb == 0 and p == -1 and len(below) >= 2, "one tree with a stick"
+    return below + [(max(g, TALL_NG), 0, -1)]
+
+
+def tall_fronts(spec):
+    """(f, nc) of every front ABOVE level 0 of tall(spec), lowest first, from the amalgamation arithmetic: the stick P --
+    with the sibling S = (20, 1) absorbed, in a beside_sibling tree -- merges into the wide root or stays out of it, and
+    what is wider than a panel is cut into links."""
+    (rp, sp, _), (g, _, _) = spec[-2], tall(spec)[-1]
+    sibling = spec[1][:2] == (20, 1)
+    true_p = _trap(20, 1) + _trap(1, sp) if sibling else _trap(rp, sp)
+    rp += 20 if sibling else 0
+    tot = _trap(rp + g, 0)
+    if (tot - true_p - _trap(g, 0)) / tot > _allowance(rp + g):
+        return _link_fronts(rp, sp) + _link_fronts(g)
+    return _link_fronts(rp + g)
+
+
+def build_cases():
+    """name -> (spec, tall spec, group) of every case of the factor-build tests: the new shapes and the shape-table
+    cases of BUILD_FROM_SHAPES."""
+    T, old = {}, shape_table()
+    for n, v in build_table().items():
+        T[n] = (v[0], tall(v[0]), "edges")
+    for n in BUILD_FROM_SHAPES:
+        T[n] = (old[n][0], tall(old[n][0]), "schur" if n.startswith("schur") else "panel")
+    return T
+
+
+# XCD tile order (csrc/hipkkt.hip: HIPKKT_TILE_XCD deals the tiles of a launch's fronts, eight fronts at a time, to the
+# residue classes of the workgroup index): ONE level with eleven fronts of 1, 1, 3, 3, 6 and 10 tiles -- a group of eight
+# with unequal tile counts and a last group of three -- and two block-class roots without tiles between them
+XCD_NB = (1, 193, 64, 129, 65, 128, 193, 1, 129, 65, 64)
+
+
+def xcd_forest(tall_=False):
+    trees = [designed(40, nb) for nb in XCD_NB]
+    if tall_:
+        trees = [tall(t) for t in trees]
+    trees.insert(8, [(40, 0, -1)])
+    trees.insert(3, [(40, 0, -1)])
+    return forest(*trees)
+
+
+def build_specs():
+    """name -> spec of everything the factor-build tests run that is built from specs: every case of build_cases() as it
+    is and as "<name>+tall", and the XCD forest both ways.  (The second XCD forest, parents with stored children, is
+    tests/extend_add_shapes.py's: xcd_parents.)"""
+    T = {}
+    for n, (spec, tall_spec, _) in build_cases().items():
+        T[n], T[n + "+tall"] = spec, tall_spec
+    T["xcd_forest"], T["xcd_forest+tall"] = xcd_forest(), xcd_forest(True)
+    return T
+
+
+def product_fault(case):
+    """K~ + E of a fault in the PRODUCT of the designed front (the first spec entry, a leaf of the tree): the term
+    l_ik d_k l_jk of the front's last column k is left out of ONE entry of its update block, the last row and column.  From
+    an exact LDL^T of the front (a leaf's factor depends on its own columns alone): a factorisation without that term is
+    the exact one of K~ with the term added to entry (i, i)."""
+    cols, rows = np.asarray(case.cols[0]), np.asarray(case.rows[0])
+    A = full(case.Kt).tocsr()[np.concatenate([cols, rows])][:, cols].toarray()
+    n = len(cols)
+    L, d = A.copy(), np.zeros(n)
+    for k in range(n):
+        d[k] = L[k, k]
+        L[k:, k] /= d[k]
+        L[k + 1:, k + 1:] -= np.outer(L[k + 1:, k], L[k + 1:n, k]) * d[k]
+    term = L[-1, n - 1] * d[n - 1] * L[-1, n - 1]
+    assert term != 0.0
+    K = sp.lil_matrix(case.Kt)
+    K[rows[-1], rows[-1]] = K[rows[-1], rows[-1]] + term
+    return sp.csc_matrix(K)
+
+
 def klass(f, nc):
     """Kernel class of a front of f rows and nc columns, as the schedule decides it (kernels.hpp: one-wave when
     f <= 64 and f * nc + nb^2 <= 1536; tiny fronts are one-wave fronts with a solve kernel of their own)."""

@@ -127,11 +127,115 @@ def test_the_forests_hold_the_counts_and_classes_they_are_for():
     assert not fs.UNREACHABLE.keys() & set(SWEEP)
 
 
+# ------------------------------------------------------------------------------------------------ the factor-build cases
+BUILD = fs.build_table()             # the new shapes
+BUILD_CASES = fs.build_cases()       # ... and the shape-table cases that get a tall variant: name -> (spec, tall spec, group)
+BUILD_SPECS = fs.build_specs()       # every spec of tests/test_gpu_factor_builds.py
+NEW_NAMES = list(BUILD) + [n + "+tall" for n in BUILD_CASES] + ["xcd_forest", "xcd_forest+tall", "xcd_parents"]
+
+_BUILD_DUMP = r"""
+import sys
+sys.path.insert(0, {root!r})
+from cuclarabel_amd import _lib
+from tests import test_gpu_factor_builds as fb
+for name in {names!r}:
+    print("@@case", name, file=sys.stderr, flush=True)
+    _lib.symbolic_analyse(fb.case_of(name).K, ordering=_lib.ORDER_NATURAL)
+"""
+
+
+@pytest.fixture(scope="module")
+def build_dumps():
+    """[levels] lines of every factor-build case: name -> per level (fronts, fmax, ncmax, f<=8 count, f<=64 count)."""
+    env = dict({k: v for k, v in os.environ.items() if not k.startswith("HIPKKT_")}, HIPKKT_DUMP_LEVELS="1")
+    r = subprocess.run([sys.executable, "-c", _BUILD_DUMP.format(root=ROOT, names=NEW_NAMES)], env=env, cwd=ROOT,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = {}
+    for chunk in r.stderr.split("@@case ")[1:]:
+        name, rest = chunk.split("\n", 1)
+        out[name.strip()] = [(int(m[2]), int(m[5]), int(m[6]), int(m[3]), int(m[4])) for m in _LEVEL.finditer(rest)]
+    assert set(out) == set(NEW_NAMES)
+    return out
+
+
+def test_the_build_table_holds_the_edges_it_is_for():
+    shapes = {n: v[0][0][:2] for n, v in BUILD.items()}
+    assert {s[1] for n, s in shapes.items() if n.startswith("quad")} == {31, 32, 33, 95, 96, 97}          # 32-row quadrants
+    assert all(s[0] == 40 for n, s in shapes.items() if n.startswith("quad"))
+    chunk = sorted(s for n, s in shapes.items() if n.startswith("chunk"))
+    assert chunk == sorted([(nc, nb) for nc in (15, 16, 17, 33, 48, 49) for nb in (65, 129)] + [(96, 129)])
+    # ... every one of them has an off-diagonal tile whose tile row is short: nr = 1 of 64, nq = 64
+    assert all(nb > 64 and nb % 64 == 1 for _, nb in chunk)
+    assert sorted(s for n, s in shapes.items() if n.startswith("shallow")) == [(3, 39), (4, 39), (5, 39)]
+    assert all(fs.klass(nc + nb, nc) == "block" for nc, nb in shapes.values())
+    assert not any(n.split("_")[0] in ("quad", "chunk", "shallow") for n in fs.UNREACHABLE)
+    assert set(fs.BUILD_FROM_SHAPES) <= set(CASES) and all(CASES[n][2] == "block" for n in fs.BUILD_FROM_SHAPES)
+
+
+@pytest.mark.parametrize("name", list(BUILD))
+def test_symbolic_gives_the_new_designed_fronts(build_dumps, name):
+    spec, level0, want = BUILD[name]
+    lv = build_dumps[name]
+    assert lv[0] == level0 == (1, spec[0][0] + spec[0][1], spec[0][0], 0, int(spec[0][0] + spec[0][1] <= 64)), (lv[0], level0)
+    assert all(l[0] == 1 for l in lv), lv
+    assert fs.klass(level0[1], level0[2]) == want == "block"
+
+
+@pytest.mark.parametrize("name", list(BUILD_CASES))
+def test_tall_variants_have_the_levels_the_construction_predicts(build_dumps, name):
+    """The designed front as in the plain case, above it the fronts tall_fronts() reasons out -- one per level, every one
+    block-class (a one-wave launch would end the overlap mode's tail), at least three of them."""
+    spec = BUILD_CASES[name][0]
+    lv = build_dumps[name + "+tall"]
+    assert lv[0][:3] == (1, spec[0][0] + spec[0][1], spec[0][0]), lv[0]
+    want = fs.tall_fronts(spec)
+    assert [l[:3] for l in lv[1:]] == [(1, f, nc) for f, nc in want], (lv, want)
+    assert len(want) >= 3 and all(fs.klass(f, nc) == "block" for f, nc in want), want
+
+
+def test_the_xcd_forests_hold_the_launches_they_are_for(build_dumps):
+    from tests import extend_add_shapes as ea
+    tiles = sorted((nb + 63) // 64 * ((nb + 63) // 64 + 1) // 2 for nb in fs.XCD_NB)
+    assert tiles == [1, 1, 1, 1, 3, 3, 3, 6, 6, 10, 10]              # eleven fronts: a group of eight, a group of three
+    for name in ("xcd_forest", "xcd_forest+tall"):
+        lv = build_dumps[name]
+        # all in one level, the two (40, 0) roots with them (f <= 64: those two and the two (40, 1) fronts)
+        assert lv[0] == (13, 233, 40, 0, 4), lv[0]
+        assert all(fs.klass(l[1], l[2]) == "block" for l in lv), lv
+    spec = fs.xcd_forest()
+    roots = [i for i, s in enumerate(spec) if s[:2] == (40, 0)]
+    assert len(roots) == 2 and 0 < roots[0] < roots[1] < len(spec) - 3      # between the designed fronts
+    assert len(build_dumps["xcd_forest+tall"]) >= 4
+    # parents with stored children: ten of them in level 1, their children in level 0, two links of each root above
+    lv = build_dumps["xcd_parents"]
+    assert len(lv) == 4 and lv[1][0] == len(ea.XCD_PARENTS) == 10 and lv[2][0] == lv[3][0] == 10, lv
+    assert all(fs.klass(l[1], l[2]) == "block" for l in lv), lv
+    T = ea.cases()
+    with_pieces = [n for n in ea.XCD_PARENTS if T[n]["level1"][2] > 0]
+    assert len(with_pieces) >= 9 and len({T[n]["shape"]["sp_"] for n in ea.XCD_PARENTS}) >= 3
+
+
 def _case(name, seed=1):
+    if name in NEW_NAMES:
+        from tests import test_gpu_factor_builds as fb
+        return fb.case_of(name)
     return fs.make_case((CASES.get(name) or SWEEP[name])[0], seed)
 
 
-@pytest.mark.parametrize("name", [n for n in CASES if not n.startswith("solve_bs")] + ["solve_bs_1024"] + list(SWEEP))
+@pytest.mark.parametrize("name", NEW_NAMES)
+def test_a_fault_in_the_product_is_far_over_the_bound(name):
+    """The seeded fault aimed at the product: the last column's term l_ik d_k l_jk left out of the last entry of the designed
+    front's update block misses the forward bound by 100 x or more."""
+    c = _case(name)
+    tol = fs.forward_bound(c, fs.errors(c, fs.reference_solve(c))[0])
+    fe, be = fs.errors(c, fs.reference_solve(c, K=fs.product_fault(c)))
+    print(f"\n[product fault] {name:22s} forward {fe:.2e} (bound {tol:.2e}, x{fe / tol:.0f}) backward {be:.2e}")
+    assert fe >= 100 * tol, (fe, tol)
+    assert be >= 100 * fs.BWD_BOUND, be
+
+
+@pytest.mark.parametrize("name", [n for n in CASES if not n.startswith("solve_bs")] + ["solve_bs_1024"] + list(SWEEP) + NEW_NAMES)
 def test_references_are_exact_calibrated_and_discriminating(name):
     c = _case(name)
     # b = K~ x_true was rounded once from long double

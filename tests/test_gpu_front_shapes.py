@@ -5,7 +5,15 @@ block-size rule switches; x_true is known and b = K~ x_true is exact.  Every sol
     forward error  |x - x_true|_inf / |x_true|_inf <= max(100 cond u, 10 x scipy's error on the same case)
     backward error |b - K~ x|_inf / (|K~|_inf |x|_inf + |b|_inf) <= 64 u   (long double)
 Each group runs in ONE child process under a timeout (the HIPKKT_* knobs are read once per process, the schedule
-summary of HIPKKT_VERBOSE goes to stderr), one child at a time."""
+summary of HIPKKT_VERBOSE goes to stderr), one child at a time.
+
+Which BUILD of k_panel / k_schur a case meets here follows from its tree, by the overlap mode's three-launch rule
+(csrc/schedule.cpp: admit_overlap): a designed tree is the front, a stick and the root, the stick merges into the root, and
+the overlap builds (k_panel<BS, false, true>, k_schur<true, true>) run only where that root is wide enough to be cut into
+chain links, so that three or more block-class launches end the schedule -- the cases with tall sticks (large nb, narrow
+nc).  Every other case runs the plain builds (k_panel<BS, false, false>, k_schur<false, false>); test_shape_sweep asserts
+which, per case.  The pipelined tile kernel k_schur<false, true> never runs here.  Every build at every edge, named by the
+handle's own report -- plain, pipelined and overlap, the XCD tile order on and off -- is tests/test_gpu_factor_builds.py's."""
 import json
 import os
 import re
@@ -136,6 +144,7 @@ def _run(jobs, env=None, timeout=240):
     return out
 
 
+_OVERLAP = re.compile(r"factorisation overlap: last (\d+) launches")
 _LEVEL = re.compile(r"\[levels\]\s+(\d+):\s+(\d+) fronts \(\s*(\d+) f<=8,\s+(\d+) f<=64\) fmax\s+(\d+) ncmax\s+(\d+)")
 
 
@@ -165,9 +174,19 @@ def test_shape_sweep():
     rows = _run([{"name": n} for n in names])
     _report("shape", rows)
     sched = {d["name"]: s for d, s, _ in rows}
-    for d, s, _ in rows:
+    for d, s, err in rows:
         _check(d)
         assert s["sliced_fronts"] == 0, (d["name"], s)
+        # which builds ran, by the three-launch rule (see the module docstring): the overlap mode takes the trailing
+        # block-class levels where there are three or more -- the chain links of a wide stick's root -- and nothing otherwise
+        tail = 0
+        for cnt, f, nc in reversed(s["levels"]):
+            if fs.klass(f, nc) != "block":
+                break
+            tail += 1
+        ov = int(_OVERLAP.search(err)[1])
+        print(f"[shape] {d['name']:16s} levels {len(s['levels'])}, block-class at the top {tail}: overlap mode on the last {ov} launches")
+        assert ov == (tail if tail >= 3 else 0), (d["name"], ov, s["levels"])
     # the designed front's class, read from the schedule: roots alone are the whole count
     for n in ("f1_root", "f2_root", "f8_root", "f9_root", "wave_39_0"):
         assert sched[n]["block_fronts"] == 0, (n, sched[n])
