@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256) void k_front_wave(FactorArgs A, int begin, int
             const int c = T.child_idx[ce0 + lane];
             const int64_t crp = T.rowptr[c];
             const int64_t uo = T.upd_off[c];
-            h_crp = (int)crp;                                   // (row structure is int32-indexed: hipkkt.hip checks)
+            h_crp = (int)crp;                                   // (row structure is int32-indexed: engine_tables.cpp checks)
             h_nbc = (int)(T.rowptr[c + 1] - crp);
             h_ulo = (int)(uo & 0xffffffff);
             h_uhi = (int)(uo >> 32);
@@ -566,7 +566,7 @@ __global__ __launch_bounds__(BS) void k_panel(FactorArgs A, int begin)
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) v[q] = src[q] >= 0 ? A.Kval[src[q]] : 0.0;
-            // (a row slice has a K list of its own with positions in its LDS image: hipkkt.hip, upload)
+            // (a row slice has a K list of its own with positions in its LDS image: engine_tables.cpp, build_k_lists)
 #pragma unroll
             for (int q = 0; q < 4; ++q) if (dst[q] >= 0) P[dst[q]] = v[q];
         }

@@ -26,6 +26,7 @@
 #include "symbolic.hpp"
 #include "knobs.hpp"
 #include "schedule.hpp"
+#include "engine_tables.hpp"
 #include "data_update.hpp"
 #include "iterate_rows.hpp"
 #include "batch_plan.hpp"
@@ -1000,7 +1001,6 @@ private:
     int chain_epoch = 0;
     bool chain_disabled = false;
     DBuf<int> d_chain_nchild;    // per supernode: its children in chained launches (the ones that count themselves in)
-    std::vector<int64_t> h_toff; // (upload: solve-matrix offsets, kept for build_records)
     DBuf<int64_t> d_recs;        // packed sweep records (kernels.hpp: SolveHdr); empty: the legacy layout
     DBuf<double> tall_ws;        // work space of the tall-front sweep kernels (allocated when the schedule holds such fronts)
 
@@ -1224,18 +1224,16 @@ private:
     DBuf<int64_t> d_cut_ptr;     // per supernode (as a child): offset into d_cuts
     DBuf<int> d_cuts;            // first child-row index reaching each 64-row tile boundary of the parent's U
     DBuf<int64_t> d_item_ptr;
-    DBuf<int64_t> d_items;       // ExtItem = 4 x int64
+    DBuf<ExtItem> d_items;
     DBuf<int64_t> d_dense_off;   // per supernode: offset of its dense child's update block (-1: none)
     DBuf<int64_t> d_wave_cut;
-    DBuf<int64_t> d_sitems;      // SubItem = 2 x int64
+    DBuf<SubItem> d_sitems;
     DBuf<int64_t> d_tile_cut;
-    DBuf<int64_t> d_pterms;      // PullTerm = one int64
+    DBuf<PullTerm> d_pterms;
     DBuf<int> d_pwave_cut, d_ptile_cut;
     int64_t n_factor_pulled = 0, n_factor_terms = 0;
-    DBuf<int64_t> d_desc;        // FrontDesc = 8 x int64
-    DBuf<int64_t> d_sdesc;       // FrontDesc per row slice of the sliced panels
-    std::vector<int64_t> slice_kptr;              // per slice: its K scatter list in ksrc / kdst
-    std::vector<int> slice_nk;
+    DBuf<FrontDesc> d_desc;
+    DBuf<FrontDesc> d_sdesc;     // per row slice of the sliced panels
     DBuf<int> d_spos, d_sn_parent, top_flags;
     DBuf<int> d_tk_pos, d_tk_sl, d_tbase;      // tasks of k_top_solve_sliced (SolveArgs::tk_*); empty unless the set has tall fronts
     DBuf<double> xf;
@@ -1264,471 +1262,110 @@ private:
         t.ncolpar = d_ncolpar.p; t.front_off = d_front_off.p; t.upd_off = d_upd_off.p;
         t.child_ptr = d_child_ptr.p; t.child_idx = d_child_idx.p; t.kptr = d_kptr.p;
         t.ksrc = d_ksrc.p; t.kdst = d_kdst.p; t.sched = d_sched.p; t.psign = d_psign.p; t.perm = d_perm.p;
-        t.dense_off = d_dense_off.p; t.item_ptr = d_item_ptr.p; t.items = (const ExtItem*)d_items.p; t.gl_ptr = d_item_ptr.p; t.gl_src = d_gl_src.p; t.udst = d_udst.p;
+        t.dense_off = d_dense_off.p; t.item_ptr = d_item_ptr.p; t.items = d_items.p; t.gl_ptr = d_item_ptr.p; t.gl_src = d_gl_src.p; t.udst = d_udst.p;
         t.glm_ptr = d_glm_ptr.p; t.udst_m = d_udst_m.p; t.hp_col = d_hp_col.p; t.hp_row = d_hp_row.p; t.hp_lidx = d_hp_lidx.p; t.pr_ptr = d_pr_ptr.p; t.pr_slot = d_pr_slot.p;
         t.cut_ptr = d_cut_ptr.p; t.cuts = d_cuts.p; t.wave_cut = d_wave_cut.p; t.tinv_off = d_tinv_off.p;
-        t.sitems = (const SubItem*)d_sitems.p; t.tile_cut = d_tile_cut.p;
-        t.pterms = (const PullTerm*)d_pterms.p; t.pwave_cut = d_pwave_cut.p; t.ptile_cut = d_ptile_cut.p; t.desc = (const FrontDesc*)d_desc.p; t.sdesc = (const FrontDesc*)d_sdesc.p;
+        t.sitems = d_sitems.p; t.tile_cut = d_tile_cut.p;
+        t.pterms = d_pterms.p; t.pwave_cut = d_pwave_cut.p; t.ptile_cut = d_ptile_cut.p; t.desc = d_desc.p; t.sdesc = d_sdesc.p;
         t.spos = d_spos.p; t.sn_parent = d_sn_parent.p;
         return t;
     }
 
     int front_size(int s) const { return hipkkt::front_size(S, s); }
 
-    // The byte image of the packed sweep records, in the layout schedule.cpp decided (layout_records: Launch::rec,
-    // sch.rec_bytes; 0 = the legacy layout, nothing to build).
-    void build_records(const std::vector<int64_t>& glptr, const std::vector<int>& gsrc)
-    {
-        if (sch.rec_refused_bytes && knobs().verbose)
-            std::fprintf(stderr, "[hipkkt] packed sweep records would take %.0f MB: legacy layout\n", sch.rec_refused_bytes / 1048576.0);
-        const int64_t total = sch.rec_bytes;
-        if (total <= 0) return;
-        std::vector<int64_t> store((size_t)(total / 8) + 8, 0);
-        char* base = reinterpret_cast<char*>(store.data());
-        for (size_t q = 0; q < sch.launches.size(); ++q) {
-            const Launch& L = sch.launches[q];
-            const bool leaf = rec_no_slots(sch.launches, q);
-            RecClass classes[2];
-            const int nclasses = rec_classes(L, classes);
-            for (int ci = 0; ci < nclasses; ++ci) {
-                const RecClass& c = classes[ci];
-                const int fmax = L.rec.fmax[c.cls];
-                for (int k = 0; k < c.count; ++k) {
-                    const int sn = sch.sched[(size_t)(c.first + k)];
-                    char* rec = base + L.rec.off[c.cls] + (int64_t)k * L.rec.stride[c.cls];
-                    const int nc = S.sn_start[sn + 1] - S.sn_start[sn], nb = (int)(S.rowptr[sn + 1] - S.rowptr[sn]), f = nc + nb;
-                    if (f > fmax) throw std::runtime_error("packed record: front larger than its class");
-                    SolveHdr h{};
-                    h.mat_off = c.cls == 0 ? h_toff[(size_t)sn] : S.front_off[sn];
-                    h.rp = S.rowptr[sn];
-                    h.s = sn; h.c0 = S.sn_start[sn]; h.nc = nc; h.nb = nb;
-                    h.par = S.sn_parent[sn];
-                    h.nchild = sch.nch.empty() ? 0 : sch.nch[(size_t)sn];
-                    std::memcpy(rec, &h, sizeof(h));
-                    int* idx = reinterpret_cast<int*>(rec + sizeof(SolveHdr));
-                    for (int i = 0; i < nc; ++i) idx[i] = S.perm[(size_t)(h.c0 + i)];
-                    for (int i = nc; i < f; ++i) idx[i] = S.rows[(size_t)(h.rp + i - nc)];
-                    if (leaf) continue;
-                    int* slot = idx + fmax;
-                    const int64_t lc0 = (int64_t)h.c0 + h.rp;
-                    for (int i = 0; i < fmax; ++i) {
-                        int* g = slot + 8 * (int64_t)i;
-                        g[0] = 0;
-                        for (int q = 1; q <= 6; ++q) g[q] = -1;
-                        g[7] = 0;
-                        if (i >= f) continue;
-                        const int64_t g0 = glptr[(size_t)(lc0 + i)], g1 = glptr[(size_t)(lc0 + i + 1)];
-                        g[0] = (int)(g1 - g0);
-                        for (int q = 0; q < 6 && g0 + q < g1; ++q) g[1 + q] = gsrc[(size_t)(g0 + q)];
-                        g[7] = (int)(g0 + 6);
-                    }
-                }
-            }
-        }
-        d_recs.upload(store);
-        if (knobs().verbose) std::fprintf(stderr, "[hipkkt] packed sweep records: %.1f MB\n", total / 1048576.0);
-    }
-
+    // The device tables are built on the host (engine_tables.cpp, schedule.cpp); here they are uploaded, group by
+    // group, and the work buffers allocated and zeroed.
     void upload(const std::vector<int>& dsigns)
     {
+        const int verbose = knobs().verbose;
         // the factorisation's extend-add work lists and which leaves their parents pull (schedule.cpp)
         FactorLists fl = build_factor_lists(S, sch);
         n_factor_pulled = fl.n_pulled; n_factor_terms = fl.n_terms;
-        // leaves with one column and a short row list, pulled by their parents in the many-column sweeps (see the gather
-        // lists below; HIPKKT_PULL_LEAVES=0: none)
-        const bool pull_on = knobs().pull_leaves;
-        std::vector<char> pulled((size_t)S.nsuper, 0);
-        {
-            std::vector<char> in_small((size_t)S.nsuper, 0);       // (one-wave launches only: the block kernels do not know the flag)
-            for (const Launch& L : sch.launches)
-                if (L.small) for (int t = L.begin; t < L.begin + L.count; ++t) in_small[(size_t)sch.sched[(size_t)t]] = 1;
-            for (int s = 0; pull_on && s < S.nsuper; ++s) {
-                const int nb = (int)(S.rowptr[s + 1] - S.rowptr[s]);
-                pulled[(size_t)s] = in_small[(size_t)s] && S.child_ptr[s + 1] == S.child_ptr[s] && S.sn_start[s + 1] - S.sn_start[s] == 1 &&
-                                    S.sn_parent[s] >= 0 && nb >= 1 && nb <= 47;
-            }
-        }
+        EngineTables T = build_engine_tables(S, sch, fl, dsigns);
+        n_pull_rows = T.n_pull_rows;
         d_sn_start.upload(S.sn_start);
         d_rowptr.upload(S.rowptr);
         d_rows.upload(S.rows);
         d_rel.upload(S.rel);
-        std::vector<int> ncolpar(S.nsuper, 0);
-        for (int s = 0; s < S.nsuper; ++s) {
-            int p = S.sn_parent[s];
-            if (p < 0) continue;
-            int pnc = S.sn_start[p + 1] - S.sn_start[p], k = 0;
-            for (int64_t q = S.rowptr[s]; q < S.rowptr[s + 1] && S.rel[q] < pnc; ++q) ++k;
-            ncolpar[s] = k;
-        }
-        d_ncolpar.upload(ncolpar);
+        d_ncolpar.upload(T.ncolpar);
         d_front_off.upload(S.front_off);
         d_upd_off.upload(S.upd_off);
         d_child_ptr.upload(S.child_ptr);
         d_child_idx.upload(S.child_idx);
         d_kptr.upload(S.kptr);
-        std::vector<int> ks_all(S.ksrc);
-        slice_kptr.assign(sch.slice_list.size(), 0);
-        slice_nk.assign(sch.slice_list.size(), 0);
-        {
-            // the panel kernel keeps a block-class front as a trapezoid in LDS (factor_kernels.hip: pcol): its K
-            // entries get their packed position; one-wave fronts keep lrow + lcol*f
-            std::vector<int> kd(S.kdst);
-            for (const Launch& L : sch.launches) {
-                if (L.small) continue;
-                for (int q = L.begin; q < L.begin + L.count - L.nsliced; ++q) {      // (sliced fronts keep lrow + lcol*f)
-                    const int s = sch.sched[q];
-                    const int f = front_size(s);
-                    for (int64_t e = S.kptr[s]; e < S.kptr[s + 1]; ++e) {
-                        const int lcol = kd[e] / f, lrow = kd[e] - lcol * f;
-                        kd[e] = lrow + (int)(((int64_t)lcol * (2 * f - 1 - lcol)) >> 1);
-                    }
-                }
-            }
-            // A row slice of a sliced front gets a K list of its own, with the positions in ITS LDS image (top block +
-            // its rows, as a trapezoid): the panel kernel neither scans the other slices' entries nor divides per entry.
-            for (size_t q = 0; q < sch.slice_list.size(); ++q) {
-                const int s = sch.slice_list[q][0], sl = sch.slice_list[q][1], nsl = sch.slice_list[q][2];
-                const int ff = front_size(s), nc = S.sn_start[s + 1] - S.sn_start[s], nb = ff - nc;
-                const int rsmax = (nb + nsl - 1) / nsl, r_lo = nc + sl * rsmax;
-                const int rs = std::max(0, std::min(rsmax, ff - r_lo)), f = nc + rs;
-                slice_kptr[q] = (int64_t)ks_all.size();
-                for (int64_t e = S.kptr[s]; e < S.kptr[s + 1]; ++e) {
-                    const int lcol = S.kdst[e] / ff;
-                    int r = S.kdst[e] - lcol * ff;
-                    if (r >= nc) { if (r < r_lo || r >= r_lo + rs) continue; r = nc + (r - r_lo); }
-                    ks_all.push_back(S.ksrc[e]);
-                    kd.push_back(r + (int)(((int64_t)lcol * (2 * f - 1 - lcol)) >> 1));
-                }
-                slice_nk[q] = (int)((int64_t)ks_all.size() - slice_kptr[q]);
-            }
-            if (ks_all.size() >= ((size_t)1 << 31)) throw std::runtime_error("K scatter lists exceed int32 indexing");
-            d_kdst.upload(kd);
-            d_ksrc.upload(ks_all);
-        }
+        d_kdst.upload(T.kdst);
+        d_ksrc.upload(T.ksrc);
         d_sched.upload(sch.sched);
-        // (d_tiles is uploaded with the tile work lists below: the launch order of a level's tiles may be permuted there)
-        {
-            d_ov_started.alloc(std::max<size_t>(sch.launches.size(), 1));
-            HIP_CHECK(hipMemset(d_ov_started.p, 0, std::max<size_t>(sch.launches.size(), 1) * sizeof(int)));
-            std::vector<int> nt((size_t)S.nsuper, 0);
-            for (size_t q = sch.ov_first; q < sch.launches.size(); ++q) {
-                const Launch& L = sch.launches[q];
-                for (int t = L.begin; t < L.begin + L.count; ++t) {
-                    const int sn = sch.sched[(size_t)t];
-                    const int nb = front_size(sn) - (S.sn_start[sn + 1] - S.sn_start[sn]);
-                    const int k = (nb + 63) / 64;
-                    nt[(size_t)sn] = k * (k + 1) / 2;
-                }
-            }
-            d_ov_ntiles.upload(nt);
-            // fronts factorised in row slices publish their progress per slice
-            std::vector<int> sbase((size_t)std::max(S.nsuper, 1), -1);
-            for (size_t q = sch.slice_list.size(); q-- > 0;) sbase[(size_t)sch.slice_list[q][0]] = (int)q;      // (slices of a front are consecutive)
-            d_ov_sbase.upload(sbase);
-            d_ov_sprog.alloc(std::max<size_t>(sch.slice_list.size(), 1));
-            HIP_CHECK(hipMemset(d_ov_sprog.p, 0, std::max<size_t>(sch.slice_list.size(), 1) * sizeof(int)));
-            d_ov_prog.alloc((size_t)S.nsuper);
-            d_ov_done.alloc((size_t)S.nsuper);
-            HIP_CHECK(hipMemset(d_ov_prog.p, 0, (size_t)std::max(S.nsuper, 1) * sizeof(int)));
-            HIP_CHECK(hipMemset(d_ov_done.p, 0, (size_t)std::max(S.nsuper, 1) * sizeof(int)));
+        d_ov_started.alloc(std::max<size_t>(sch.launches.size(), 1));
+        HIP_CHECK(hipMemset(d_ov_started.p, 0, std::max<size_t>(sch.launches.size(), 1) * sizeof(int)));
+        d_ov_ntiles.upload(T.ov_ntiles);
+        d_ov_sbase.upload(T.ov_sbase);
+        d_ov_sprog.alloc(std::max<size_t>(sch.slice_list.size(), 1));
+        HIP_CHECK(hipMemset(d_ov_sprog.p, 0, std::max<size_t>(sch.slice_list.size(), 1) * sizeof(int)));
+        d_ov_prog.alloc((size_t)S.nsuper);
+        d_ov_done.alloc((size_t)S.nsuper);
+        HIP_CHECK(hipMemset(d_ov_prog.p, 0, (size_t)std::max(S.nsuper, 1) * sizeof(int)));
+        HIP_CHECK(hipMemset(d_ov_done.p, 0, (size_t)std::max(S.nsuper, 1) * sizeof(int)));
+        d_tinv_off.upload(T.toff);
+        d_desc.upload(T.desc);
+        d_sdesc.upload(T.sdesc);
+        d_spos.upload(sch.spos);
+        d_sn_parent.upload(S.sn_parent);
+        if (!sch.tp.empty()) {       // the set has sliced fronts: the tasks of k_top_solve_sliced
+            d_tk_pos.upload(sch.tp); d_tk_sl.upload(sch.ts); d_tbase.upload(sch.h_tbase);
+            xf.alloc((size_t)S.N * 2);
         }
-        {
-            std::vector<int64_t> toff(S.nsuper + 1, 0);
-            std::vector<char> in_list(S.nsuper, 0);
-            for (int s : sch.tinv_list) in_list[s] = 1;
-            // (level by level like the panel and update stores: symbolic.cpp, step 10)
-            {
-                int64_t wo = 0;
-                for (int t = 0; t < S.nsuper; ++t) {
-                    const int s = S.level_sn[t];
-                    int64_t nc = S.sn_start[s + 1] - S.sn_start[s];
-                    int64_t fs = nc + (S.rowptr[s + 1] - S.rowptr[s]);
-                    toff[s] = wo;
-                    wo += in_list[s] ? 2 * fs * nc : 0;
-                }
-                toff[S.nsuper] = wo;
-            }
-            d_tinv_off.upload(toff);
-            h_toff = toff;
-            static_assert(sizeof(FrontDesc) == 64, "FrontDesc layout");
-            std::vector<FrontDesc> desc(sch.sched.size());
-            for (size_t q = 0; q < sch.sched.size(); ++q) {
-                const int s = sch.sched[q];
-                FrontDesc d;
-                d.front_off = S.front_off[s]; d.upd_off = S.upd_off[s]; d.w_off = toff[s]; d.rp = S.rowptr[s];
-                d.kptr = S.kptr[s]; d.s = s; d.c0 = S.sn_start[s]; d.nc = S.sn_start[s + 1] - S.sn_start[s];
-                d.nb = (int)(S.rowptr[s + 1] - S.rowptr[s]); d.nk = (int)(S.kptr[s + 1] - S.kptr[s]);
-                d.pad = (pulled[(size_t)s] ? 1 : 0) | (fl.pulled[(size_t)s] ? 2 : 0);     // (launch records: bit 0 = a pulled leaf of the many-column sweeps, see below; bit 1 = of the factorisation)
-                desc[q] = d;
-            }
-            std::vector<int64_t> rawd(desc.size() * 8);
-            std::memcpy(rawd.data(), desc.data(), desc.size() * sizeof(FrontDesc));
-            d_desc.upload(rawd);
-            std::vector<int> pos_of(S.nsuper, -1);
-            for (size_t q = 0; q < sch.sched.size(); ++q) pos_of[sch.sched[q]] = (int)q;
-            std::vector<int64_t> raws(std::max<size_t>(sch.slice_list.size(), 1) * 8, 0);
-            for (size_t q = 0; q < sch.slice_list.size(); ++q) {
-                FrontDesc d = desc[(size_t)pos_of[sch.slice_list[q][0]]];
-                d.pad = (sch.slice_list[q][1] << 16) | sch.slice_list[q][2];
-                d.kptr = slice_kptr[q]; d.nk = slice_nk[q];             // (its own K list, positions in the slice's image)
-                std::memcpy(raws.data() + q * 8, &d, sizeof(FrontDesc));
-            }
-            d_sdesc.upload(raws);
-            d_spos.upload(sch.spos);
-            d_sn_parent.upload(S.sn_parent);
-            if (!sch.tp.empty()) {       // the set has sliced fronts: the tasks of k_top_solve_sliced
-                d_tk_pos.upload(sch.tp); d_tk_sl.upload(sch.ts); d_tbase.upload(sch.h_tbase);
-                xf.alloc((size_t)S.N * 2);
-            }
-            top_flags.alloc((size_t)2 * std::max(sch.top_nflag, 1) + 4);
-            HIP_CHECK(hipMemset(top_flags.p, 0, top_flags.n * sizeof(int)));
-            d_chain_nchild.upload(sch.nch);
-            d_chain.alloc((size_t)2 * std::max(S.nsuper, 1));
-            HIP_CHECK(hipMemset(d_chain.p, 0, d_chain.n * sizeof(int)));
-            tinv.alloc((size_t)toff[S.nsuper]);
-            HIP_CHECK(hipMemset(tinv.p, 0, std::max<size_t>(tinv.n, 1) * sizeof(double)));
-            d_tinv_list.upload(sch.tinv_list);
+        top_flags.alloc((size_t)2 * std::max(sch.top_nflag, 1) + 4);
+        HIP_CHECK(hipMemset(top_flags.p, 0, top_flags.n * sizeof(int)));
+        d_chain_nchild.upload(sch.nch);
+        d_chain.alloc((size_t)2 * std::max(S.nsuper, 1));
+        HIP_CHECK(hipMemset(d_chain.p, 0, d_chain.n * sizeof(int)));
+        tinv.alloc((size_t)T.toff[S.nsuper]);
+        HIP_CHECK(hipMemset(tinv.p, 0, std::max<size_t>(tinv.n, 1) * sizeof(double)));
+        d_tinv_list.upload(sch.tinv_list);
+        d_cut_ptr.upload(T.cut_ptr);
+        d_cuts.upload(T.cuts);
+        if (verbose >= 2 && sch.top_launches > 0) std::fputs(describe_gather_sources(S, sch, T).c_str(), stderr);
+        d_item_ptr.upload(T.item_ptr);
+        // extend-add items of the PANEL columns and Schur sub-items of the update-block columns: schedule.cpp
+        d_dense_off.upload(fl.dense_off);
+        if (verbose) {
+            std::fputs(describe_update_blocks(S, fl).c_str(), stderr);
+            if (verbose >= 2) std::fputs(describe_pieces(S, sch, fl).c_str(), stderr);      // the "[pieces]" lines of this handle's lists
+            std::fputs(describe_pulled_terms(fl).c_str(), stderr);
         }
-        {
-            std::vector<int64_t> cut_ptr(S.nsuper + 1, 0);
-            std::vector<int> cuts;
-            for (int c = 0; c < S.nsuper; ++c) {
-                cut_ptr[c] = (int64_t)cuts.size();
-                int p = S.sn_parent[c];
-                if (p < 0) continue;
-                int pnc = S.sn_start[p + 1] - S.sn_start[p];
-                int pnb = (int)(S.rowptr[p + 1] - S.rowptr[p]);
-                int nt = (pnb + 63) / 64;
-                const int* rb = S.rel.data() + S.rowptr[c];
-                int nbc = (int)(S.rowptr[c + 1] - S.rowptr[c]);
-                for (int t = 0; t <= nt; ++t)
-                    cuts.push_back((int)(std::lower_bound(rb, rb + nbc, pnc + 64 * t) - rb));
-            }
-            cut_ptr[S.nsuper] = (int64_t)cuts.size();
-            d_cut_ptr.upload(cut_ptr);
-            d_cuts.upload(cuts);
-        }
-        {
-            // extend-add items and forward-solve gather lists, both keyed by the parent's local index
-            const int64_t nloc = (int64_t)S.N + (int64_t)S.rows.size();
-            std::vector<int64_t> ptr((size_t)nloc + 1, 0);
-            auto lbase = [&](int s) { return (int64_t)S.sn_start[s] + S.rowptr[s]; };
-            for (int c = 0; c < S.nsuper; ++c) {
-                int p = S.sn_parent[c];
-                if (p < 0) continue;
-                for (int64_t q = S.rowptr[c]; q < S.rowptr[c + 1]; ++q) ptr[lbase(p) + S.rel[q] + 1]++;
-            }
-            for (int64_t i = 0; i < nloc; ++i) ptr[i + 1] += ptr[i];
-            // gather lists of the forward sweep: one entry per child row, keyed by the receiving local row
-            std::vector<int> gsrc((size_t)ptr[nloc]);
-            {
-                std::vector<int64_t> nxt(ptr.begin(), ptr.end() - 1);
-                for (int p = 0; p < S.nsuper; ++p)
-                    for (int e = S.child_ptr[p]; e < S.child_ptr[p + 1]; ++e) {     // children in fixed order
-                        int c = S.child_idx[e];
-                        for (int64_t q = S.rowptr[c]; q < S.rowptr[c + 1]; ++q) gsrc[nxt[lbase(p) + S.rel[q]]++] = (int)q;
-                    }
-            }
-            if (S.rows.size() >= ((size_t)1 << 31)) throw std::runtime_error("row structure exceeds int32 indexing");
-            if (knobs().verbose >= 2 && sch.top_launches > 0) {
-                // gather-list lengths of the rows of the persistent solve set (what k_top_solve's parked indices must cover)
-                long hist[6] = {0, 0, 0, 0, 0, 0};
-                long fronts_over8 = 0, fronts_over12 = 0, nf = 0;
-                int64_t gmax = 0;
-                for (size_t q = sch.launches.size() - sch.top_launches; q < sch.launches.size(); ++q)
-                    for (int t = sch.launches[q].begin; t < sch.launches[q].begin + sch.launches[q].count; ++t) {
-                        const int sn = sch.sched[(size_t)t];
-                        const int f = front_size(sn);
-                        int64_t fm = 0;
-                        for (int i = 0; i < f; ++i) {
-                            const int64_t n = ptr[lbase(sn) + i + 1] - ptr[lbase(sn) + i];
-                            hist[n == 0 ? 0 : n <= 4 ? 1 : n <= 8 ? 2 : n <= 12 ? 3 : n <= 16 ? 4 : 5]++;
-                            fm = std::max(fm, n);
-                        }
-                        gmax = std::max(gmax, fm);
-                        fronts_over8 += fm > 8; fronts_over12 += fm > 12; ++nf;
-                    }
-                std::fprintf(stderr, "[hipkkt] persistent solve set: gather sources per row: 0: %ld, 1-4: %ld, 5-8: %ld, 9-12: %ld, "
-                             "13-16: %ld, more: %ld (max %lld); fronts with a row over 8: %ld, over 12: %ld of %ld\n",
-                             hist[0], hist[1], hist[2], hist[3], hist[4], hist[5], (long long)gmax, fronts_over8, fronts_over12, nf);
-            }
-            d_item_ptr.upload(ptr);
-            // extend-add items of the PANEL columns and Schur sub-items of the update-block columns: schedule.cpp
-            static_assert(sizeof(ExtItem) == 32, "ExtItem layout");
-            const std::vector<ExtItem>& items = fl.items;
-            const std::vector<int64_t>& wcut = fl.wcut;
-            d_dense_off.upload(fl.dense_off);
-            if (knobs().verbose) {
-                int64_t n_dense = 0;
-                for (int c : fl.dense_child) n_dense += c >= 0;
-                std::fprintf(stderr, "[hipkkt] dense children: %lld\n", (long long)n_dense);
-                std::fprintf(stderr, "[hipkkt] update blocks: %d chains of panels (%d links) share two buffers each; %lld bytes kept, %lld without sharing\n",
-                             S.shared_chains, S.shared_links, (long long)(S.update_store * 8), (long long)(S.update_store_unshared * 8));
-                if (knobs().verbose >= 2) std::fputs(describe_pieces(S, sch, fl).c_str(), stderr);      // the "[pieces]" lines of this handle's lists
-                std::fprintf(stderr, "[hipkkt] pulled leaves' terms: %zu chunks of 64, deepest stack %d\n", fl.pterms.size() / 64, fl.max_depth);
-            }
-            std::vector<int64_t> raw(std::max<size_t>(items.size(), 1) * 4);
-            std::memcpy(raw.data(), items.data(), items.size() * sizeof(ExtItem));
-            d_items.upload(raw);
-            d_wave_cut.upload(wcut);
-            if (knobs().verbose) {
-                if (knobs().verbose >= 2) {            // the extend-add work of the last fronts of the schedule
-                    for (size_t q = sch.sched.size() > 12 ? sch.sched.size() - 12 : 0; q < sch.sched.size(); ++q) {
-                        const int sn = sch.sched[q];
-                        const int64_t* w = wcut.data() + (size_t)sn * 17;
-                        int64_t mx = 0, rows = 0;
-                        for (int k = 0; k < 16; ++k) mx = std::max(mx, w[k + 1] - w[k]);
-                        for (int64_t it = w[0]; it < w[16]; ++it) rows += items[(size_t)it].cnt;
-                        std::fprintf(stderr, "[hipkkt] front %d f %d nc %d kids %d: %lld panel items (%lld entries), largest wave slice %lld\n",
-                                     sn, front_size(sn), S.sn_start[sn + 1] - S.sn_start[sn], S.child_ptr[sn + 1] - S.child_ptr[sn],
-                                     (long long)(w[16] - w[0]), (long long)rows, (long long)mx);
-                    }
-                }
-            }
-            static_assert(sizeof(SubItem) == 16, "SubItem layout");
-            const std::vector<SubItem>& sit = fl.sit;
-            std::vector<int64_t>& tcut = fl.tcut;
-            std::vector<int>& ptcut = fl.ptcut;
-            std::vector<int64_t> tiles_up(sch.tiles);       // (the tiles in the order they are launched in)
-            {
-                // XCD-aware launch order of a wide level's tiles (HIPKKT_TILE_XCD=n: launches with at least n fronts;
-                // 0 = off): workgroup i of a launch runs on XCD i mod 8, each XCD has its own L2, and every tile of a front
-                // reads that front's L21 strips -- a front's tiles are dealt to ONE residue class (eight fronts interleaved,
-                // fronts in work order so that a group's fronts have similar tile counts), so its strips come from HBM
-                // once instead of once per XCD that happens to hold one of its tiles.
-                // Measured on cfg2 (rocprofv3 --pmc FETCH_SIZE, r03): k_schur's reads 838 -> 525 MB per factorisation with the
-                // wide levels (>= 150 fronts) permuted, factorisation 1.754 / 1.760 -> 1.743 / 1.751 ms; permuting the narrow
-                // levels as well costs time (>= 32: 1.766 / 1.770 -- a handful of fronts' tiles then crowd one XCD).
-                const int tile_xcd = knobs().tile_xcd;
-                int dealt_launches = 0;
-                int64_t dealt_tiles = 0;
-                std::string dealt_list;
-                if (tile_xcd > 0) {
-                    std::vector<int64_t> nc2(tcut);
-                    std::vector<int> pc2(ptcut);
-                    for (const Launch& L : sch.launches) {
-                        if (L.small || L.count < tile_xcd || L.ntiles <= 0) continue;
-                        ++dealt_launches;
-                        dealt_tiles += L.ntiles;
-                        dealt_list += " " + std::to_string(&L - sch.launches.data());
-                        // the launch's fronts and their (contiguous) logical tile ranges
-                        std::vector<std::pair<int64_t, int64_t>> rng;       // [first, last) per front, launch order
-                        for (int t = L.begin; t < L.begin + L.count; ++t) {
-                            const int sn = sch.sched[(size_t)t];
-                            if (sch.tile_base[sn] < 0) continue;
-                            const int nb = front_size(sn) - (S.sn_start[sn + 1] - S.sn_start[sn]);
-                            const int k = (nb + 63) / 64;
-                            if (k > 0) rng.push_back({sch.tile_base[sn], sch.tile_base[sn] + (int64_t)k * (k + 1) / 2});
-                        }
-                        int64_t pos = L.tile_begin;
-                        for (size_t g0 = 0; g0 < rng.size(); g0 += 8) {
-                            const size_t g1 = std::min(rng.size(), g0 + 8);
-                            int64_t longest = 0;
-                            for (size_t x = g0; x < g1; ++x) longest = std::max(longest, rng[x].second - rng[x].first);
-                            for (int64_t j = 0; j < longest; ++j)
-                                for (size_t x = g0; x < g1; ++x)
-                                    if (rng[x].first + j < rng[x].second) {
-                                        const int64_t from = rng[x].first + j;
-                                        tiles_up[(size_t)pos] = sch.tiles[(size_t)from];
-                                        for (int w = 0; w < 5; ++w) nc2[(size_t)pos * 5 + w] = tcut[(size_t)from * 5 + w];
-                                        for (int w = 0; w < 5; ++w) pc2[(size_t)pos * 5 + w] = ptcut[(size_t)from * 5 + w];
-                                        ++pos;
-                                    }
-                        }
-                        if (pos != (int64_t)L.tile_begin + L.ntiles) throw std::runtime_error("tile permutation lost a tile");
-                    }
-                    tcut.swap(nc2);
-                    ptcut.swap(pc2);
-                }
-                if (knobs().verbose)
-                    std::fprintf(stderr, "[hipkkt] tile order: %d launches dealt to XCD residue classes (%lld tiles):%s\n", dealt_launches,
-                                 (long long)dealt_tiles, dealt_launches ? dealt_list.c_str() : " none");
-            }
-            d_tiles.upload(tiles_up);
-            std::vector<int64_t> raw2(sit.size() * 2);
-            std::memcpy(raw2.data(), sit.data(), sit.size() * sizeof(SubItem));
-            d_sitems.upload(raw2);
-            d_tile_cut.upload(tcut);
+        d_items.upload(fl.items);
+        d_wave_cut.upload(fl.wcut);
+        if (verbose >= 2) std::fputs(describe_panel_items(S, sch, fl).c_str(), stderr);
+        if (verbose) std::fputs(describe_tile_order(T).c_str(), stderr);
+        d_tiles.upload(T.tiles);       // (the tiles in the order they are launched in; tcut / ptcut follow it)
+        d_sitems.upload(fl.sit);
+        d_tile_cut.upload(fl.tcut);
 #ifdef HIPKKT_EXPERIMENTS
-            // EXPERIMENT (timing only, WRONG RESULTS; never in the default build): the pulled leaves' items and sub-items are
-            // gone and their update blocks are not stored, but nobody forms their terms either -- what the factorisation
-            // would take if the leaves' extend-add cost nothing: the ceiling of HIPKKT_PULL_FACTOR_LEAVES
-            if (std::getenv("HIPKKT_EXPERIMENT_DROP_LEAF_UPDATES")) {
-                fl.pterms.clear();
-                std::fill(fl.pwcut.begin(), fl.pwcut.end(), 0);
-                std::fill(ptcut.begin(), ptcut.end(), 0);
-            }
+        // EXPERIMENT (timing only, WRONG RESULTS; never in the default build): the pulled leaves' items and sub-items are
+        // gone and their update blocks are not stored, but nobody forms their terms either -- what the factorisation
+        // would take if the leaves' extend-add cost nothing: the ceiling of HIPKKT_PULL_FACTOR_LEAVES
+        if (std::getenv("HIPKKT_EXPERIMENT_DROP_LEAF_UPDATES")) {
+            fl.pterms.assign(1, PullTerm{});
+            std::fill(fl.pwcut.begin(), fl.pwcut.end(), 0);
+            std::fill(fl.ptcut.begin(), fl.ptcut.end(), 0);
+        }
 #endif
-            {   // the pulled leaves' terms (PullTerm = one int64) and their chunk ranges per wave slice / tile wave
-                static_assert(sizeof(PullTerm) == 8, "PullTerm layout");
-                std::vector<int64_t> rawp(std::max<size_t>(fl.pterms.size(), 1), 0);
-                std::memcpy(rawp.data(), fl.pterms.data(), fl.pterms.size() * sizeof(PullTerm));
-                d_pterms.upload(rawp);
-                if (fl.pwcut.empty()) fl.pwcut.push_back(0);
-                d_pwave_cut.upload(fl.pwcut);
-                d_ptile_cut.upload(ptcut);
-            }
-            d_gl_src.upload(gsrc);
-            build_records(ptr, gsrc);
-            // where each contribution entry sits in its receiver's gather list (solve_multi's layout)
-            std::vector<int> ud(std::max<size_t>(S.rows.size(), 1), 0);
-            for (size_t g = 0; g < gsrc.size(); ++g) ud[(size_t)gsrc[g]] = (int)g;
-            d_udst.upload(ud);
-            // PULLED LEAVES (many-column sweeps only).  Half of a sparse KKT system's contribution rows come from leaves with
-            // ONE column (cfg2: 113 k of them, the slack rows of the linear cone): forward, such a leaf only forwards
-            // u_r = -L(r,0) b_c to its parent's rows -- 4 KB per row and 512 columns, written and read once.  In the
-            // many-column sweeps the PARENT computes those terms itself from the leaf's row of B (one row instead of nb, and
-            // shared by the parent's rows through L2), the leaf does nothing forward, and its backward step is a gather
-            // kernel of its own (k_bwd_leaf_m).  The parent's gather list is split: the stored contributions of its other
-            // children (contiguous rows of the receiver-ordered store, as before, without the pulled ones) and the pulled
-            // terms (leaf column, position of L(r,0) in the fronts).
-            {
-                std::vector<int> row_sn(std::max<size_t>(S.rows.size(), 1), -1);
-                for (int c = 0; c < S.nsuper; ++c)
-                    for (int64_t q = S.rowptr[c]; q < S.rowptr[c + 1]; ++q) row_sn[(size_t)q] = c;
-                std::vector<int64_t> mptr((size_t)nloc + 1, 0), prp(1, 0);
-                std::vector<int> udm(std::max<size_t>(S.rows.size(), 1), -1), hcol, prs;
-                std::vector<int64_t> hl;
-                int64_t slot = 0;
-                for (int64_t lc = 0; lc < nloc; ++lc) {
-                    mptr[(size_t)lc] = slot;
-                    bool any = false;
-                    for (int64_t g = ptr[(size_t)lc]; g < ptr[(size_t)lc + 1] && !any; ++g) any = pulled[(size_t)row_sn[(size_t)gsrc[(size_t)g]]] != 0;
-                    if (any) prs.push_back((int)slot++);                  // the sum of this row's pulled terms: first of its run
-                    for (int64_t g = ptr[(size_t)lc]; g < ptr[(size_t)lc + 1]; ++g) {
-                        const int q = gsrc[(size_t)g], c = row_sn[(size_t)q];
-                        if (pulled[(size_t)c]) {
-                            hcol.push_back(S.sn_start[c]);
-                            hl.push_back(S.front_off[c] + 1 + ((int64_t)q - S.rowptr[c]));     // L(r, 0): column-major, ld f, nc = 1
-                        } else {
-                            udm[(size_t)q] = (int)slot++;
-                        }
-                    }
-                    if (any) prp.push_back((int64_t)hcol.size());
-                }
-                mptr[(size_t)nloc] = slot;
-                n_pull_rows = (int)prs.size();
-                const size_t n_pull_terms = hcol.size();      // (before the padding entry of an empty list)
-                if (hcol.empty()) { hcol.push_back(0); hl.push_back(0); }
-                if (prs.empty()) prs.push_back(0);
-                std::vector<int> hrow(hcol.size());
-                for (size_t k = 0; k < hcol.size(); ++k) hrow[k] = S.perm[(size_t)hcol[k]];
-                d_glm_ptr.upload(mptr); d_udst_m.upload(udm); d_hp_col.upload(hcol); d_hp_row.upload(hrow); d_hp_lidx.upload(hl);
-                d_pr_ptr.upload(prp); d_pr_slot.upload(prs);
-                if (knobs().verbose)
-                    std::fprintf(stderr, "[hipkkt] many-column sweeps: %lld of %lld contribution rows pulled from one-column leaves into %d sums\n",
-                                 (long long)n_pull_terms, (long long)ptr[(size_t)nloc], n_pull_rows);
-            }
-        }
+        // the pulled leaves' terms and their chunk ranges per wave slice / tile wave
+        d_pterms.upload(fl.pterms);
+        d_pwave_cut.upload(fl.pwcut);
+        d_ptile_cut.upload(fl.ptcut);
+        d_gl_src.upload(T.gsrc);
+        if (!T.recs.empty()) d_recs.upload(T.recs);
+        if (verbose) std::fputs(describe_records(sch).c_str(), stderr);
+        d_udst.upload(T.udst);
+        // the many-column sweeps' split gather lists (engine_tables.hpp: PULLED LEAVES)
+        d_glm_ptr.upload(T.glm_ptr); d_udst_m.upload(T.udst_m); d_hp_col.upload(T.hp_col); d_hp_row.upload(T.hp_row); d_hp_lidx.upload(T.hp_lidx);
+        d_pr_ptr.upload(T.pr_ptr); d_pr_slot.upload(T.pr_slot);
+        if (verbose) std::fputs(describe_solve_pulled(T).c_str(), stderr);
         d_perm.upload(S.perm);
-        std::vector<signed char> ps(S.N);
-        for (int k = 0; k < S.N; ++k) ps[k] = (signed char)(dsigns[S.perm[k]] >= 0 ? 1 : -1);
-        d_psign.upload(ps);
-        {
-            size_t ws = 0;
-            for (const Launch& L : sch.launches) if (L.ntall > 0) ws = std::max(ws, tall_ws_doubles(S.N, L.ntall, L.fmax));
-            if (ws) { tall_ws.alloc(ws); tall_ws.zero(nullptr); HIP_CHECK(hipStreamSynchronize(nullptr)); }     // (its first N doubles: ticket words, zero between sweeps)
-        }
+        d_psign.upload(T.psign);
+        if (T.tall_ws) { tall_ws.alloc(T.tall_ws); tall_ws.zero(nullptr); HIP_CHECK(hipStreamSynchronize(nullptr)); }     // (its first N doubles: ticket words, zero between sweeps)
         fronts.alloc((size_t)S.front_store);
         upd.alloc((size_t)S.update_store);
         Dinv.alloc((size_t)S.N);
@@ -2455,52 +2092,16 @@ int hipkkt_kkt_create_ex2(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t
         h->mapD.upload(K.mapD);
         h->Pval.alloc(K.mapP.size());
         h->Aval.alloc(K.mapA.size());
-        // full symmetric CSR image of K for the residual
+        // full symmetric CSR image of K for the residual (kkt_assembly.cpp)
         {
-            const int N = K.N;
-            std::vector<int64_t> ptr((size_t)N + 1, 0);
-            for (int j = 0; j < N; ++j)
-                for (int64_t q = K.colptr[j]; q < K.colptr[j + 1]; ++q) {
-                    int i = K.rowval[q];
-                    ptr[i + 1]++;
-                    if (i != j) ptr[j + 1]++;
-                }
-            for (int i = 0; i < N; ++i) ptr[i + 1] += ptr[i];
-            std::vector<int> col((size_t)ptr[N]), vmap((size_t)ptr[N]);
-            std::vector<int64_t> nx(ptr.begin(), ptr.end() - 1);
-            // row i gets its upper-triangle partners (i, j>i) from column scans in ascending j and its
-            // lower partners from its own column; fill lower part first so columns ascend within a row
-            for (int j = 0; j < N; ++j) {            // entries (i<j) stored in column j: row j, col i
-                for (int64_t q = K.colptr[j]; q < K.colptr[j + 1]; ++q) {
-                    int i = K.rowval[q];
-                    int64_t d = nx[j]++;
-                    col[d] = i;
-                    vmap[d] = (int)q;
-                }
-            }
-            for (int j = 0; j < N; ++j)              // mirrored entries: row i, col j (j > i), ascending j
-                for (int64_t q = K.colptr[j]; q < K.colptr[j + 1]; ++q) {
-                    int i = K.rowval[q];
-                    if (i == j) continue;
-                    int64_t d = nx[i]++;
-                    col[d] = j;
-                    vmap[d] = (int)q;
-                }
-            h->fptr.upload(ptr);
-            h->fcol.upload(col);
-            h->fmap.upload(vmap);
-            {
-                // rows of the x block: where their P entries end (columns ascend, so those are a prefix of the row) -- the
-                // reduced-system layer's P x products stop there instead of walking the row's A' entries as well (cfg3:
-                // ~250 of them per row behind a handful of P entries)
-                std::vector<int64_t> pend((size_t)std::max<int64_t>(K.n, 1), 0);
-                for (int64_t i = 0; i < K.n; ++i)
-                    pend[(size_t)i] = std::lower_bound(col.begin() + ptr[(size_t)i], col.begin() + ptr[(size_t)i + 1], (int)K.n) - col.begin();
-                h->fpend.upload(pend);
-            }
+            const KKTImage I = build_kkt_image(K);
+            h->fptr.upload(I.ptr);
+            h->fcol.upload(I.col);
+            h->fmap.upload(I.vmap);
+            h->fpend.upload(I.pend);
             {
                 // ... and what hipkkt_kkt_system_residuals walks: whole x rows, the A prefix of the z rows
-                const IterateRows R = plan_iterate_rows(K.n, K.m, ptr.data(), col.data(), kLongRow, kLongChunk);
+                const IterateRows R = plan_iterate_rows(K.n, K.m, I.ptr.data(), I.col.data(), kLongRow, kLongChunk);
                 h->it_prefix_ok = R.prefix_ok;
                 h->it_rend.upload(R.rend);
                 h->it_nlong = (int)R.long_rows.size();
@@ -2513,41 +2114,19 @@ int hipkkt_kkt_create_ex2(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t
                     h->it_long_partial.alloc((size_t)2 * h->it_nchunks);
                 }
             }
-            h->fval.alloc(vmap.size());
-            {
-                std::vector<int> kp((size_t)2 * K.nnzK, -1);
-                for (size_t q = 0; q < vmap.size(); ++q) {
-                    const size_t e = (size_t)vmap[q];
-                    if (kp[2 * e] < 0) kp[2 * e] = (int)q; else kp[2 * e + 1] = (int)q;
-                }
-                h->kpos.upload(kp);
+            h->fval.alloc(I.vmap.size());
+            h->kpos.upload(I.kpos);
+            h->nlong = (int)I.long_rows.size();
+            h->long_rows_h = I.long_rows;
+            h->nchunks = (int)(I.chunk_q.size() / 2);
+            if (h->nlong) {
+                h->long_rows.upload(I.long_rows);
+                h->long_chunk_ptr.upload(I.long_chunk_ptr);
+                h->chunk_q.upload(I.chunk_q);
+                h->long_partial.alloc((size_t)h->nchunks * kMaxNR);
+                h->long_partial_cols = kMaxNR;
             }
-            {
-                std::vector<int> lrows;
-                std::vector<int64_t> lptr{0}, cq;
-                for (int i = 0; i < N; ++i) {
-                    const int64_t len = ptr[i + 1] - ptr[i];
-                    if (len <= kLongRow) continue;
-                    lrows.push_back(i);
-                    for (int64_t q = ptr[i]; q < ptr[i + 1]; q += kLongChunk) {
-                        cq.push_back(q);
-                        cq.push_back(std::min<int64_t>(q + kLongChunk, ptr[i + 1]));
-                    }
-                    lptr.push_back((int64_t)cq.size() / 2);
-                }
-                h->nlong = (int)lrows.size();
-                h->long_rows_h = lrows;
-                h->nchunks = (int)(cq.size() / 2);
-                if (h->nlong) {
-                    h->long_rows.upload(lrows);
-                    h->long_chunk_ptr.upload(lptr);
-                    h->chunk_q.upload(cq);
-                    h->long_partial.alloc((size_t)h->nchunks * kMaxNR);
-                    h->long_partial_cols = kMaxNR;
-                }
-            }
-            double avg = (double)ptr[N] / std::max(N, 1);
-            h->lanes_per_row = avg > 24.0 ? 64 : 8;
+            h->lanes_per_row = I.lanes_per_row;
         }
         const size_t N = (size_t)K.N;
         // right-hand side, solution, residual and candidate: up to kMaxNR columns share a sweep (kkt_solve_core)
@@ -2574,82 +2153,36 @@ int hipkkt_kkt_create_ex2(hipkkt_kkt_t* out, int64_t n, int64_t m, const int64_t
             h->sys_out_dev = h->ir_sticky + 8;          // {dtau, dkappa, tau_num, tau_den} of kkt_solve!: read back with the record in ONE copy
             h->ir_norms = h->sys_out_dev + 4;           // several columns: norme0[kMaxNR], normb[kMaxNR], cand[kMaxNR]
         }
-        // cones
+        // cones (kkt_assembly.cpp)
         {
-            size_t nc = K.cones.size();
-            std::vector<int> kind(nc), off(nc), numel(nc), sidx(nc), soff(nc), elem((size_t)K.m), soclist, soc_of;
-            std::vector<int64_t> boff(nc);
-            std::vector<int> explist, powlist, nsidx(nc, -1);
-            std::vector<double> param(nc, 0.0);
-            soc_of.assign((size_t)K.sparse_len, 0);
-            for (size_t c = 0; c < nc; ++c) {
-                const ConeInfo& ci = K.cones[c];
-                kind[c] = ci.kind; off[c] = ci.off; numel[c] = ci.numel; boff[c] = ci.boff;
-                sidx[c] = ci.sparse ? ci.sidx : -1;
-                soff[c] = ci.sparse ? ci.soff : -1;
-                for (int t = 0; t < ci.numel; ++t) elem[ci.off + t] = (int)c;
-                if (ci.kind == HIPKKT_CONE_SOC) soclist.push_back((int)c);
-                if (ci.kind == HIPKKT_CONE_EXP) explist.push_back((int)c);
-                if (ci.kind == HIPKKT_CONE_POW) powlist.push_back((int)c);
-                nsidx[c] = ci.nsidx; param[c] = ci.param;
-                if (ci.kind == HIPKKT_CONE_PSD) {
-                    h->has_psd = true;
-                    if (ci.dim > kPsdMaxDim) h->psd_too_big = true;
-                }
-                if (ci.sparse) for (int t = 0; t < ci.numel; ++t) soc_of[ci.soff + t] = ci.sidx;
-            }
-            h->nsoc = (int)soclist.size();
-            h->nexp = (int)explist.size(); h->npow = (int)powlist.size();
+            const ConeTables C = build_cone_tables(K);
+            const size_t nc = K.cones.size();
+            h->has_psd = C.has_psd; h->psd_too_big = C.psd_too_big;
+            h->nsoc = (int)C.soc_list.size();
+            h->nexp = (int)C.exp_list.size(); h->npow = (int)C.pow_list.size();
             if (K.nnonsym > 0) {
-                h->c_explist.upload(explist); h->c_powlist.upload(powlist); h->c_nsidx.upload(nsidx); h->c_param.upload(param);
+                h->c_explist.upload(C.exp_list); h->c_powlist.upload(C.pow_list); h->c_nsidx.upload(C.ns_index); h->c_param.upload(C.param);
                 h->ns_grad.alloc((size_t)3 * K.nnonsym); h->ns_H.alloc((size_t)9 * K.nnonsym);
                 HIP_CHECK(hipMemset(h->ns_grad.p, 0, (size_t)3 * K.nnonsym * sizeof(double)));
                 HIP_CHECK(hipMemset(h->ns_H.p, 0, (size_t)9 * K.nnonsym * sizeof(double)));
             }
             if (K.ngenpow > 0) {
-                std::vector<int> gcone, gdim1, goff, gsmall, gbig, mapQR((size_t)K.genpow_len);
-                std::vector<double> alpha((size_t)K.genpow_len, 0.0);
-                for (size_t c = 0; c < nc; ++c) {
-                    const ConeInfo& ci = K.cones[c];
-                    if (ci.kind != HIPKKT_CONE_GENPOW) continue;
-                    gcone.push_back((int)c); gdim1.push_back(ci.dim1); goff.push_back(ci.gpoff);
-                    (ci.numel <= kGenPowWaveMax ? gsmall : gbig).push_back(ci.gpidx);
-                    for (int t = 0; t < ci.dim1; ++t) {
-                        alpha[ci.gpoff + t] = K.gp_alpha[ci.gqoff + t];
-                        mapQR[ci.gpoff + t] = K.mapGP_q[ci.gqoff + t];
-                    }
-                    for (int t = ci.dim1; t < ci.numel; ++t) mapQR[ci.gpoff + t] = K.mapGP_r[ci.groff + t - ci.dim1];
-                }
-                h->ngp_small = (int)gsmall.size(); h->ngp_big = (int)gbig.size();
-                h->gp_cone.upload(gcone); h->gp_dim1.upload(gdim1); h->gp_off.upload(goff); h->gp_alpha.upload(alpha);
-                h->gp_small.upload(gsmall); h->gp_big.upload(gbig);
-                h->gp_mapP.upload(K.mapGP_p); h->gp_mapQR.upload(mapQR); h->gp_mapD.upload(K.mapGP_D);
+                h->ngp_small = (int)C.gp_small.size(); h->ngp_big = (int)C.gp_big.size();
+                h->gp_cone.upload(C.gp_cone); h->gp_dim1.upload(C.gp_dim1); h->gp_off.upload(C.gp_off); h->gp_alpha.upload(C.gp_alpha);
+                h->gp_small.upload(C.gp_small); h->gp_big.upload(C.gp_big);
+                h->gp_mapP.upload(K.mapGP_p); h->gp_mapQR.upload(C.gp_mapQR); h->gp_mapD.upload(K.mapGP_D);
                 const size_t gl = (size_t)K.genpow_len;
                 h->gp_grad.alloc(gl); h->gp_d.alloc(gl); h->gp_p.alloc(gl); h->gp_qr.alloc(gl);
                 for (double* q : {h->gp_grad.p, h->gp_d.p, h->gp_p.p, h->gp_qr.p}) HIP_CHECK(hipMemset(q, 0, gl * sizeof(double)));
             }
-            {
-                std::vector<int> plist, blist, pdim(nc, 0);
-                std::vector<int64_t> paoff(nc, 0);
-                int64_t ao = 0;
-                for (size_t c = 0; c < nc; ++c) {
-                    const ConeInfo& ci = K.cones[c];
-                    if (ci.kind != HIPKKT_CONE_PSD) continue;
-                    pdim[c] = ci.dim;
-                    paoff[c] = ao;
-                    ao += (int64_t)ci.dim * ci.dim;
-                    // two size classes, as gp_small / gp_big: the all-in-LDS kernels see sides <= kPsdMaxDim only
-                    if (ci.dim <= kPsdMaxDim) { plist.push_back((int)c); h->psd_kmax = std::max(h->psd_kmax, ci.dim); }
-                    else { blist.push_back((int)c); h->psdb_kmax = std::max(h->psdb_kmax, ci.dim); }
-                }
-                h->npsd = (int)plist.size(); h->npsdb = (int)blist.size();
-                h->c_psdlist.upload(plist); h->c_psddim.upload(pdim); h->c_psdaoff.upload(paoff);
-                h->c_psdblist.upload(blist);
-                h->psdA.alloc((size_t)ao); h->psdR.alloc((size_t)ao); h->psdRinv.alloc((size_t)ao);
-            }
-            h->c_kind.upload(kind); h->c_off.upload(off); h->c_numel.upload(numel); h->c_boff.upload(boff);
-            h->c_sidx.upload(sidx); h->c_soff.upload(soff); h->c_elem.upload(elem); h->c_soclist.upload(soclist);
-            h->soc_of_entry.upload(soc_of);
+            h->psd_kmax = C.psd_kmax; h->psdb_kmax = C.psdb_kmax;
+            h->npsd = (int)C.psd_list.size(); h->npsdb = (int)C.psdb_list.size();
+            h->c_psdlist.upload(C.psd_list); h->c_psddim.upload(C.psd_dim); h->c_psdaoff.upload(C.psd_aoff);
+            h->c_psdblist.upload(C.psdb_list);
+            h->psdA.alloc((size_t)C.psd_store); h->psdR.alloc((size_t)C.psd_store); h->psdRinv.alloc((size_t)C.psd_store);
+            h->c_kind.upload(C.kind); h->c_off.upload(C.off); h->c_numel.upload(C.numel); h->c_boff.upload(C.boff);
+            h->c_sidx.upload(C.sidx); h->c_soff.upload(C.soff); h->c_elem.upload(C.elem_cone); h->c_soclist.upload(C.soc_list);
+            h->soc_of_entry.upload(C.soc_of_entry);
             h->w.alloc((size_t)K.m); h->eta.alloc(nc); h->lam.alloc((size_t)K.m);
             h->soc_u.alloc((size_t)K.sparse_len); h->soc_v.alloc((size_t)K.sparse_len);
             h->soc_eta2.alloc((size_t)K.nsparse); h->Hs.alloc((size_t)K.nHs);

@@ -51,37 +51,7 @@ inline hipError_t set_max_lds(K kernel, int bytes)
 
 // (ExtItem, SubItem -- the extend-add work lists' records, built by schedule.cpp -- and PullTerm: launch_shapes.hpp)
 
-struct FrontDesc {               // everything a kernel needs to know about one front, in launch order; 64 bytes
-    int64_t front_off;           // panel store offset
-    int64_t upd_off;             // update store offset
-    int64_t w_off;               // solve-matrix store offset
-    int64_t rp;                  // rowptr[s]
-    int64_t kptr;                // first K entry
-    int s;                       // supernode id
-    int c0;                      // first column
-    int nc;                      // columns
-    int nb;                      // rows below
-    int nk;                      // K entries
-    int pad;                     // row-sliced panels (TreeDev::sdesc): slice << 16 | number of slices
-};
-
-// Packed sweep records (layout: schedule.cpp, layout_records; byte image: hipkkt.hip, build_records): what a sweep kernel needs to know about a front, laid out so that it
-// arrives in ONE round of loads.  The fronts of a launch and size class (block-class / one-wave / tiny) have records of one
-// size, so a record's address follows from the front's place in the launch alone: [SolveHdr (64 B)] [idx: fmax ints]
-// [gather slots: fmax x 32 B, absent on tree level 0] -- a thread fetches the header and its row's slots side by side,
-// and the values (b, the children's contributions, the matrix) in the second round.  The legacy layout (FrontDesc ->
-// gl_ptr / perm / rows -> gl_src -> values) took four.
-//   idx[i]   i < nc: the row of column c0 + i in the caller's order (perm); i >= nc: the permuted index of below-row i (rows)
-//   slot i   {count, six sources (indices into uvec, -1 beyond the count), index into gl_src of the seventh source}
-struct SolveHdr {
-    int64_t mat_off;             // block class: W = [T; M] in the solve-matrix store (W' behind it); one-wave / tiny: the panel in the front store
-    int64_t rp;                  // rowptr[s]: first of the nb rows below in rows[] / uvec
-    int s, c0, nc, nb;
-    int par;                     // parent supernode, -1 for a root
-    int nchild;                  // children swept by chained launches (ChainArgs::nchild)
-    int64_t pad[3];
-};
-static_assert(sizeof(SolveHdr) == kSolveHdrBytes, "SolveHdr layout");
+// (FrontDesc, the launch records, and SolveHdr, the header of the packed sweep records: launch_shapes.hpp)
 // (RecSeg, the records of one kernel launch's fronts by size class: launch_shapes.hpp)
 
 struct TreeDev {                 // device copies of the symbolic structure
@@ -112,7 +82,7 @@ struct TreeDev {                 // device copies of the symbolic structure
     // (used by the gather lists below).
     const int64_t* item_ptr;     // = gl_ptr
     const ExtItem* items;
-    // dense child (hipkkt.hip, upload): offset in upd of the child whose update block is this front's whole front
+    // dense child (schedule.cpp, build_factor_lists): offset in upd of the child whose update block is this front's whole front
     // (entry (r, j) -> entry (r, j), leading dimension = this front's size), or -1; block-class fronts only
     const int64_t* dense_off;
     // forward-solve gather lists: local row r of front s (same indexing) receives
@@ -289,7 +259,7 @@ void launch_fwd_multi(const SolveArgs& a, int begin, int count, bool small, int 
 // fronts too tall for the block kernels' LDS: their rows spread over workgroups (fmax: tallest of them; SolveArgs::tall_ws)
 void launch_fwd_tall(const SolveArgs& a, int begin, int count, int fmax, hipStream_t st);
 void launch_bwd_tall(const SolveArgs& a, int begin, int count, int fmax, int N, hipStream_t st);
-size_t tall_ws_doubles(int N, int ntall, int fmax);     // doubles SolveArgs::tall_ws needs for a launch with ntall such fronts
+// (the doubles SolveArgs::tall_ws needs for a launch with such fronts: launch_shapes.hpp, tall_ws_doubles)
 void launch_pull_leaves_multi(const SolveArgs& a, int nrows, int KP, hipStream_t st);
 void launch_bwd_multi(const SolveArgs& a, int begin, int count, bool small, int ncmax, int KP, hipStream_t st, bool leaves = false);
 
@@ -489,9 +459,7 @@ struct ConeDev {
     int npsdb = 0, psdb_kmax = 1;
     double* psd_work = nullptr;
 };
-// A generalized power cone of up to this many rows is scaled (and multiplied) by one wave, four cones to a workgroup: 8
-// rows per lane, all loads of a pass in flight at once.  A larger one takes a workgroup of 256 with an LDS stage.
-constexpr int kGenPowWaveMax = 512;
+// (kGenPowWaveMax, the rows of a generalized power cone that one wave takes: launch_shapes.hpp)
 struct ConeState {
     double* w;                   // m: NN: sqrt(s/z); SOC: normalised w
     double* lam;                 // m: scaled point lambda = W z (NN: sqrt(s z); SOC: coneops_socone.jl:113-123); may be null
@@ -519,7 +487,7 @@ struct ConeState {
     double* fval = nullptr;
     const int* kpos = nullptr;
 };
-constexpr int kPsdMaxDim = 48;   // largest PSD side handled by the in-LDS scaling kernel
+// (kPsdMaxDim, the largest PSD side handled by the in-LDS scaling kernel: launch_shapes.hpp)
 // Largest side of the big class.  Its scaling kernel keeps in LDS only the pair (M, V) that the one-sided Jacobi rotates,
 // 2 k^2 doubles: 147 456 B at k = 96, which leaves 16 KB of the CU's 160 KiB for the reduction arrays; at k = 100 the pair
 // takes 160 000 B and leaves 3 840 B.  96 is the last multiple of 16 that fits.  (= HIPKKT_PSD_MAX_SIDE_LARGE)

@@ -4,12 +4,14 @@
 // (directldl_kkt_assembly.jl:161-165).
 #include "kkt_assembly.hpp"
 
+#include <algorithm>
 #include <cmath>
 #include <limits>
 #include <stdexcept>
 #include <string>
 
 #include "../../include/hipkkt.h"
+#include "launch_shapes.hpp"
 
 namespace hipkkt {
 
@@ -221,6 +223,120 @@ void assemble_kkt(int64_t n64, int64_t m64, const int64_t* Pp, const int64_t* Pi
             K.dsigns[pcol + 2] = 1;
         }
     }
+}
+
+KKTImage build_kkt_image(const KKTAssembly& K)
+{
+    KKTImage I;
+    const int N = K.N;
+    std::vector<int64_t>& ptr = I.ptr;
+    ptr.assign((size_t)N + 1, 0);
+    for (int j = 0; j < N; ++j)
+        for (int64_t q = K.colptr[j]; q < K.colptr[j + 1]; ++q) {
+            int i = K.rowval[q];
+            ptr[i + 1]++;
+            if (i != j) ptr[j + 1]++;
+        }
+    for (int i = 0; i < N; ++i) ptr[i + 1] += ptr[i];
+    std::vector<int>&col = I.col, &vmap = I.vmap;
+    col.assign((size_t)ptr[N], 0);
+    vmap.assign((size_t)ptr[N], 0);
+    std::vector<int64_t> nx(ptr.begin(), ptr.end() - 1);
+    // row i gets its upper-triangle partners (i, j>i) from column scans in ascending j and its
+    // lower partners from its own column; fill lower part first so columns ascend within a row
+    for (int j = 0; j < N; ++j) {            // entries (i<j) stored in column j: row j, col i
+        for (int64_t q = K.colptr[j]; q < K.colptr[j + 1]; ++q) {
+            int i = K.rowval[q];
+            int64_t d = nx[j]++;
+            col[d] = i;
+            vmap[d] = (int)q;
+        }
+    }
+    for (int j = 0; j < N; ++j)              // mirrored entries: row i, col j (j > i), ascending j
+        for (int64_t q = K.colptr[j]; q < K.colptr[j + 1]; ++q) {
+            int i = K.rowval[q];
+            if (i == j) continue;
+            int64_t d = nx[i]++;
+            col[d] = j;
+            vmap[d] = (int)q;
+        }
+    I.pend.assign((size_t)std::max<int64_t>(K.n, 1), 0);
+    for (int64_t i = 0; i < K.n; ++i)
+        I.pend[(size_t)i] = std::lower_bound(col.begin() + ptr[(size_t)i], col.begin() + ptr[(size_t)i + 1], (int)K.n) - col.begin();
+    I.kpos.assign((size_t)2 * K.nnzK, -1);
+    for (size_t q = 0; q < vmap.size(); ++q) {
+        const size_t e = (size_t)vmap[q];
+        if (I.kpos[2 * e] < 0) I.kpos[2 * e] = (int)q; else I.kpos[2 * e + 1] = (int)q;
+    }
+    I.long_chunk_ptr.assign(1, 0);
+    for (int i = 0; i < N; ++i) {
+        const int64_t len = ptr[i + 1] - ptr[i];
+        if (len <= kLongRow) continue;
+        I.long_rows.push_back(i);
+        for (int64_t q = ptr[i]; q < ptr[i + 1]; q += kLongChunk) {
+            I.chunk_q.push_back(q);
+            I.chunk_q.push_back(std::min<int64_t>(q + kLongChunk, ptr[i + 1]));
+        }
+        I.long_chunk_ptr.push_back((int64_t)I.chunk_q.size() / 2);
+    }
+    double avg = (double)ptr[N] / std::max(N, 1);
+    I.lanes_per_row = avg > 24.0 ? 64 : 8;
+    return I;
+}
+
+ConeTables build_cone_tables(const KKTAssembly& K)
+{
+    ConeTables C;
+    const size_t nc = K.cones.size();
+    C.kind.resize(nc); C.off.resize(nc); C.numel.resize(nc); C.sidx.resize(nc); C.soff.resize(nc); C.boff.resize(nc);
+    C.elem_cone.assign((size_t)K.m, 0);
+    C.ns_index.assign(nc, -1);
+    C.param.assign(nc, 0.0);
+    C.soc_of_entry.assign((size_t)K.sparse_len, 0);
+    for (size_t c = 0; c < nc; ++c) {
+        const ConeInfo& ci = K.cones[c];
+        C.kind[c] = ci.kind; C.off[c] = ci.off; C.numel[c] = ci.numel; C.boff[c] = ci.boff;
+        C.sidx[c] = ci.sparse ? ci.sidx : -1;
+        C.soff[c] = ci.sparse ? ci.soff : -1;
+        for (int t = 0; t < ci.numel; ++t) C.elem_cone[ci.off + t] = (int)c;
+        if (ci.kind == HIPKKT_CONE_SOC) C.soc_list.push_back((int)c);
+        if (ci.kind == HIPKKT_CONE_EXP) C.exp_list.push_back((int)c);
+        if (ci.kind == HIPKKT_CONE_POW) C.pow_list.push_back((int)c);
+        C.ns_index[c] = ci.nsidx; C.param[c] = ci.param;
+        if (ci.kind == HIPKKT_CONE_PSD) {
+            C.has_psd = true;
+            if (ci.dim > kPsdMaxDim) C.psd_too_big = true;
+        }
+        if (ci.sparse) for (int t = 0; t < ci.numel; ++t) C.soc_of_entry[ci.soff + t] = ci.sidx;
+    }
+    if (K.ngenpow > 0) {
+        C.gp_mapQR.assign((size_t)K.genpow_len, 0);
+        C.gp_alpha.assign((size_t)K.genpow_len, 0.0);
+        for (size_t c = 0; c < nc; ++c) {
+            const ConeInfo& ci = K.cones[c];
+            if (ci.kind != HIPKKT_CONE_GENPOW) continue;
+            C.gp_cone.push_back((int)c); C.gp_dim1.push_back(ci.dim1); C.gp_off.push_back(ci.gpoff);
+            (ci.numel <= kGenPowWaveMax ? C.gp_small : C.gp_big).push_back(ci.gpidx);
+            for (int t = 0; t < ci.dim1; ++t) {
+                C.gp_alpha[ci.gpoff + t] = K.gp_alpha[ci.gqoff + t];
+                C.gp_mapQR[ci.gpoff + t] = K.mapGP_q[ci.gqoff + t];
+            }
+            for (int t = ci.dim1; t < ci.numel; ++t) C.gp_mapQR[ci.gpoff + t] = K.mapGP_r[ci.groff + t - ci.dim1];
+        }
+    }
+    C.psd_dim.assign(nc, 0);
+    C.psd_aoff.assign(nc, 0);
+    for (size_t c = 0; c < nc; ++c) {
+        const ConeInfo& ci = K.cones[c];
+        if (ci.kind != HIPKKT_CONE_PSD) continue;
+        C.psd_dim[c] = ci.dim;
+        C.psd_aoff[c] = C.psd_store;
+        C.psd_store += (int64_t)ci.dim * ci.dim;
+        // two size classes, as gp_small / gp_big: the all-in-LDS kernels see sides <= kPsdMaxDim only
+        if (ci.dim <= kPsdMaxDim) { C.psd_list.push_back((int)c); C.psd_kmax = std::max(C.psd_kmax, ci.dim); }
+        else { C.psdb_list.push_back((int)c); C.psdb_kmax = std::max(C.psdb_kmax, ci.dim); }
+    }
+    return C;
 }
 
 }  // namespace hipkkt

@@ -57,4 +57,41 @@ void assemble_kkt(int64_t n, int64_t m, const int64_t* Pp, const int64_t* Pi, co
                   const int32_t* kinds, const int64_t* dims, int base, KKTAssembly& K,
                   const int64_t* param_ptr = nullptr, const double* param_vals = nullptr);
 
+// ---- the device tables of a KKT handle (hipkkt_kkt_create uploads them as they are)
+
+// K's full-symmetric CSR image for the residual products: row i holds its lower partners (from its own column) and then
+// the mirrored upper ones, so columns ascend within a row; vmap[d] = the K entry behind position d.  pend (rows < n): where
+// the row's P entries end (columns ascend, so those are a prefix of the row) -- the reduced-system layer's P x products
+// stop there instead of walking the row's A' entries as well (cfg3: ~250 of them per row behind a handful of P entries).
+// kpos: the one (diagonal) or two positions of every K entry in the image, -1 for the second slot of a diagonal entry.
+// Rows longer than kLongRow entries (launch_shapes.hpp) are listed in long_rows and cut into chunks of kLongChunk:
+// chunk k of long row r is [chunk_q[2 k], chunk_q[2 k + 1]), k in [long_chunk_ptr[r], long_chunk_ptr[r + 1]).
+struct KKTImage {
+    std::vector<int64_t> ptr, pend;
+    std::vector<int> col, vmap, kpos;
+    std::vector<int> long_rows;
+    std::vector<int64_t> long_chunk_ptr, chunk_q;
+    int lanes_per_row = 8;         // lanes the residual kernel gives a row: 64 where rows average more than 24 entries
+};
+KKTImage build_kkt_image(const KKTAssembly& K);
+
+// The cone tables (kernels.hpp: ConeDev): per cone its kind, rows, Hs block and sparse expansion; per row its cone; the
+// lists by kind -- second-order, exponential, power, PSD by size class (side <= kPsdMaxDim: psd_list, the others:
+// psdb_list), generalized power by size class (numel <= kGenPowWaveMax: gp_small) -- and the generalized power cones'
+// per-row alphas and K positions (q, then r, concatenated per cone).
+struct ConeTables {
+    std::vector<int> kind, off, numel, sidx, soff, elem_cone, soc_list, soc_of_entry;
+    std::vector<int64_t> boff;
+    std::vector<int> exp_list, pow_list, ns_index;
+    std::vector<double> param;
+    std::vector<int> gp_cone, gp_dim1, gp_off, gp_small, gp_big, gp_mapQR;
+    std::vector<double> gp_alpha;
+    std::vector<int> psd_list, psdb_list, psd_dim;
+    std::vector<int64_t> psd_aoff;
+    int64_t psd_store = 0;         // doubles of all PSD cones' matrices (sum of side^2)
+    bool has_psd = false, psd_too_big = false;
+    int psd_kmax = 1, psdb_kmax = 1;
+};
+ConeTables build_cone_tables(const KKTAssembly& K);
+
 }  // namespace hipkkt

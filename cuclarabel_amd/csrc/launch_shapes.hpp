@@ -76,6 +76,8 @@ struct PullTerm {
     uint32_t tgt_ab;
 };
 constexpr uint32_t kPullNone = 0xffffffffu;
+static_assert(sizeof(ExtItem) == 32, "ExtItem layout");
+static_assert(sizeof(SubItem) == 16, "SubItem layout");
 static_assert(sizeof(PullTerm) == 8, "PullTerm layout");
 
 // most fronts the persistent top-of-tree kernel takes (every workgroup resident: solve_kernels.hip, k_top_solve)
@@ -111,8 +113,58 @@ inline MultiShape multi_shape(int KP, int multi_vec, int multi_ct)
     return m;
 }
 
-// packed sweep records (kernels.hpp: SolveHdr): bytes of a record's header
+// fronts too tall for the block sweep kernels' LDS (solve_kernels.hip: k_fwd_tall / k_bwd_tall): columns of a front the
+// kernels keep in LDS (panels have at most 144), rows of a front per workgroup (HIPKKT_TALL_BLOCK_ROWS, a multiple of 64
+// in 64..4096), and the doubles SolveArgs::tall_ws needs for a launch with ntall such fronts, the tallest of fmax rows
+constexpr int kBdColsSolveMax = 160;
+inline int tall_block_rows(int knob) { return knob < 64 ? 64 : (knob > 4096 ? 4096 : (knob & ~63)); }
+inline size_t tall_ws_doubles(int N, int ntall, int fmax, int block_rows)
+{
+    return (size_t)N + (size_t)ntall * (size_t)((fmax + block_rows - 1) / block_rows) * kBdColsSolveMax;
+}
+
+// the cone kernels' size classes (kernels.hip, psd_cone.hpp; the lists: kkt_assembly.cpp, build_cone_tables): the largest
+// PSD side handled by the in-LDS scaling kernel, and the rows of a generalized power cone that one wave scales (and
+// multiplies), four cones to a workgroup: 8 rows per lane, all loads of a pass in flight at once.  A larger one takes a
+// workgroup of 256 with an LDS stage.
+constexpr int kPsdMaxDim = 48;
+constexpr int kGenPowWaveMax = 512;
+
+struct FrontDesc {               // everything a kernel needs to know about one front, in launch order; 64 bytes
+    int64_t front_off;           // panel store offset
+    int64_t upd_off;             // update store offset
+    int64_t w_off;               // solve-matrix store offset
+    int64_t rp;                  // rowptr[s]
+    int64_t kptr;                // first K entry
+    int s;                       // supernode id
+    int c0;                      // first column
+    int nc;                      // columns
+    int nb;                      // rows below
+    int nk;                      // K entries
+    int pad;                     // row-sliced panels (TreeDev::sdesc): slice << 16 | number of slices
+};
+static_assert(sizeof(FrontDesc) == 64, "FrontDesc layout");
+
+// packed sweep records: bytes of a record's header
 constexpr int kSolveHdrBytes = 64;
+// Packed sweep records (layout: schedule.cpp, layout_records; byte image: engine_tables.cpp, build_engine_tables): what a
+// sweep kernel needs to know about a front, laid out so that it
+// arrives in ONE round of loads.  The fronts of a launch and size class (block-class / one-wave / tiny) have records of one
+// size, so a record's address follows from the front's place in the launch alone: [SolveHdr (64 B)] [idx: fmax ints]
+// [gather slots: fmax x 32 B, absent on tree level 0] -- a thread fetches the header and its row's slots side by side,
+// and the values (b, the children's contributions, the matrix) in the second round.  The legacy layout (FrontDesc ->
+// gl_ptr / perm / rows -> gl_src -> values) took four.
+//   idx[i]   i < nc: the row of column c0 + i in the caller's order (perm); i >= nc: the permuted index of below-row i (rows)
+//   slot i   {count, six sources (indices into uvec, -1 beyond the count), index into gl_src of the seventh source}
+struct SolveHdr {
+    int64_t mat_off;             // block class: W = [T; M] in the solve-matrix store (W' behind it); one-wave / tiny: the panel in the front store
+    int64_t rp;                  // rowptr[s]: first of the nb rows below in rows[] / uvec
+    int s, c0, nc, nb;
+    int par;                     // parent supernode, -1 for a root
+    int nchild;                  // children swept by chained launches (ChainArgs::nchild)
+    int64_t pad[3];
+};
+static_assert(sizeof(SolveHdr) == kSolveHdrBytes, "SolveHdr layout");
 struct RecSeg {                  // the records of one kernel launch's fronts, by size class: 0 block-class, 1 one-wave, 2 tiny
     int64_t off[3];              // byte offset in SolveArgs::recs of the class's first record
     int stride[3];               // bytes per record

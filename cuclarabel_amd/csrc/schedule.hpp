@@ -2,6 +2,7 @@
 // launches are overlapped, chained or persistent (build_schedule), where a launch's packed sweep records lie
 // (layout_records) and how one sweep is split (plan_sweep).  The device contributes one integer and three occupancy
 // answers (DeviceLimits); the engine (hipkkt.hip) executes what is decided here: it allocates, uploads and launches.
+// (The device tables that follow from these decisions: engine_tables.hpp.)
 #pragma once
 #include <array>
 #include <cstddef>

@@ -849,7 +849,7 @@ __global__ __launch_bounds__(BS, BS == 1024 ? 4 : 2) void k_top_solve(SolveArgs 
 // forward solution slice 0 left there) so that siblings may overwrite xp meanwhile.  The slices of a front never
 // exchange anything; a parent waits for all slices of a child, a child for all slices of its parent.  As in
 // k_top_solve everything static (matrix entries, gather indices, b, D^{-1}, row indices) is parked before the wait.
-constexpr int kBdColsSolveMax = 160;     // columns of a front the tall kernels keep in LDS (panels have at most 144)
+// (kBdColsSolveMax, the columns of a front the tall kernels keep in LDS: launch_shapes.hpp)
 constexpr int kSlPF = 2;         // forward items per wave parked (the kernel must fit 128 VGPRs)
 constexpr int kSlGP = 4;         // gather indices per row parked
 // (front, slice) tasks: wave 0 waits for every task of the children of s inside the set.  Lanes over children for each
@@ -1735,7 +1735,7 @@ static void init_solve_lds()
 // entries are gathered and solved against T = L11^{-1} in LDS, the rows below stream their row of M = L21 T from W
 // (coalesced over the rows) and are stored straight to the contribution vector; backward, a wave owns columns and
 // walks the rows with its lanes (the ancestors' x gathered on the way), one wave reduction per column.  Single column
-// only; a launch's tall fronts sit at its end (hipkkt.hip, Launch::ntall) and stay out of the persistent kernels.
+// only; a launch's tall fronts sit at its end (schedule.hpp, Launch::ntall) and stay out of the persistent kernels.
 // r04: a tall front's rows are spread over workgroups -- one workgroup walked 25 088 rows x 96 columns per hop of a
 // 261-panel chain (cfg2 with 0.1 % long-range couplings: 519 ms per sweep pair, 15 GB/s) -- and a direction is ONE
 // launch per panel: the sweep of such a chain is a launch per panel and kernel, ~10 us each whatever the work.
@@ -1826,16 +1826,7 @@ __global__ __launch_bounds__(1024) void k_bwd_tall(SolveArgs A, int begin, int B
         A.out[T.perm[c0 + j]] = v;
     }
 }
-static int tall_block_rows()
-{
-    const int br = knobs().tall_block_rows;
-    return br < 64 ? 64 : (br > 4096 ? 4096 : (br & ~63));
-}
-size_t tall_ws_doubles(int N, int ntall, int fmax)
-{
-    const int BR = tall_block_rows();
-    return (size_t)N + (size_t)ntall * (size_t)((fmax + BR - 1) / BR) * kBdColsSolveMax;
-}
+static int tall_block_rows() { return hipkkt::tall_block_rows(knobs().tall_block_rows); }
 void launch_fwd_tall(const SolveArgs& a, int begin, int count, int fmax, hipStream_t st)
 {
     if (count <= 0) return;

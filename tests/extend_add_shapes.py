@@ -268,7 +268,7 @@ def case(name, seed=1):
 
 
 # --------------------------------------------------------------------------- parents side by side (tests/test_gpu_factor_builds.py)
-# Ten designed parents in ONE launch for the XCD tile order (csrc/hipkkt.hip: HIPKKT_TILE_XCD permutes a launch's tiles together
+# Ten designed parents in ONE launch for the XCD tile order (csrc/engine_tables.cpp: HIPKKT_TILE_XCD permutes a launch's tiles together
 # with their pass-through ranges, tile_cut and ptile_cut): nine whose stored children bring tile pieces -- update blocks of 120
 # and of 128 rows, three tiles each, with very different lists -- and one of 60 rows, one tile, without any.  A group of eight
 # fronts and a last group of two; the roots above are two links each, so the forest is tall enough for the overlap mode.

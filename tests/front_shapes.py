@@ -604,7 +604,7 @@ def build_cases():
     return T
 
 
-# XCD tile order (csrc/hipkkt.hip: HIPKKT_TILE_XCD deals the tiles of a launch's fronts, eight fronts at a time, to the
+# XCD tile order (csrc/engine_tables.cpp: HIPKKT_TILE_XCD deals the tiles of a launch's fronts, eight fronts at a time, to the
 # residue classes of the workgroup index): ONE level with eleven fronts of 1, 1, 3, 3, 6 and 10 tiles -- a group of eight
 # with unequal tile counts and a last group of three -- and two block-class roots without tiles between them
 XCD_NB = (1, 193, 64, 129, 65, 128, 193, 1, 129, 65, 64)

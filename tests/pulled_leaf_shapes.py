@@ -164,7 +164,7 @@ def case(name, seed=1):
 
 
 # --------------------------------------------------------------------------- the many-column sweeps' pulled leaves
-# (csrc/hipkkt.hip, upload(): a leaf is pulled by the SOLVES when it has no children, one column, a parent, 1 <= nb <= 47
+# (csrc/engine_tables.cpp, mark_solve_pulled: a leaf is pulled by the SOLVES when it has no children, one column, a parent, 1 <= nb <= 47
 # rows and sits in a one-wave launch -- whatever its parent's class.)  Two things follow from the schedule and shape the
 # cases:
 #   * a one-column front of nb rows is one-wave only up to nb = 38 (f + nb^2 <= 1536), so nb = 39 .. 47 is a block-class

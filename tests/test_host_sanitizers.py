@@ -1,10 +1,10 @@
 """AddressSanitizer + UndefinedBehaviorSanitizer over the product's HOST code (csrc/kkt_assembly.cpp, csrc/ordering.cpp,
-csrc/symbolic.cpp, csrc/schedule.cpp: the set-up path of hipkkt_kkt_create / hipkkt_symbolic_analyse and the launch
-schedule and sweep plans the engine executes).  The GPU pool offers no sanitizer, so
+csrc/symbolic.cpp, csrc/schedule.cpp, csrc/engine_tables.cpp: the set-up path of hipkkt_kkt_create /
+hipkkt_symbolic_analyse, the launch schedule and sweep plans the engine executes and the device tables it uploads).  The GPU pool offers no sanitizer, so
 the kernels rest on the parity suite and the host code on this: tests/sanitize/host_driver.cpp is built from the same
 sources with g++ -fsanitize=address,undefined, fed the small BASELINE configurations and the small structure zoo, and
-checks the assembly maps, the permutation, the supernode partition, the level lists, the launch schedule and every
-sweep plan for consistency on the way."""
+checks the assembly maps, the permutation, the supernode partition, the level lists, the launch schedule, every
+sweep plan and the device tables of the engine and of the KKT handle for consistency on the way."""
 import os
 import subprocess
 
@@ -18,7 +18,8 @@ from cuclarabel_amd.cones import cone_kinds_dims
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "cuclarabel_amd", "csrc")
 SOURCES = [os.path.join(ROOT, "tests", "sanitize", "host_driver.cpp")] + [os.path.join(CSRC, f) for f in
-                                                                          ("kkt_assembly.cpp", "symbolic.cpp", "ordering.cpp", "schedule.cpp")]
+                                                                          ("kkt_assembly.cpp", "symbolic.cpp", "ordering.cpp", "schedule.cpp",
+                                                                           "engine_tables.cpp")]
 
 
 @pytest.fixture(scope="module")

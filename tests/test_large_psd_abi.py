@@ -41,7 +41,11 @@ def test_the_library_exports_it():
 def test_the_kernels_limit_is_the_headers():
     hpp = _read("cuclarabel_amd", "csrc", "kernels.hpp")
     assert re.search(r"constexpr\s+int\s+kPsdBigMaxDim\s*=\s*96\s*;", hpp)
-    assert re.search(r"constexpr\s+int\s+kPsdMaxDim\s*=\s*48\s*;", hpp), "the all-in-LDS class keeps its limit"
+    # (the small class's limit lives where host-only code sees it too; kernels.hpp includes that header)
+    shapes = _read("cuclarabel_amd", "csrc", "launch_shapes.hpp")
+    assert re.search(r'#include\s+"launch_shapes.hpp"', hpp)
+    assert re.search(r"constexpr\s+int\s+kPsdMaxDim\s*=\s*48\s*;", shapes), "the all-in-LDS class keeps its limit"
+    assert len(re.findall(r"constexpr\s+int\s+kPsdMaxDim\b", hpp + shapes)) == 1
 
 
 def test_the_python_layer_has_the_switch_and_defaults_to_off():

@@ -7,7 +7,9 @@
   * The new trees (front_shapes.multi_forests, pulled_leaf_shapes.solve_cases): host_driver --launches prints every
     supernode and launch of the real schedule; the designed fronts are there with their shapes and classes, the leaves the
     solves pull are the ones the construction names, and the three numbers of the engine's "contribution rows pulled" line
-    follow from the construction.  Every childless front sits in a level-0 launch (the driver's check_schedule).
+    follow from the construction.  Every childless front sits in a level-0 launch (the driver's check_schedule).  The
+    driver also reports what the PRODUCT's tables hold (csrc/engine_tables.cpp: the pulled flags and the three numbers);
+    they equal the restatement here, by default and under HIPKKT_PULL_LEAVES=0.
   * The references of the new cases are exact, calibrated and discriminating, as in test_front_shapes_host.py.
   * A numpy restatement of the many-column sweeps with three simulated faults: each one fails the bounds or the
     duplicate-column equality, the fault-free restatement does not."""
@@ -101,7 +103,7 @@ def _launches(exe, d, names, extra_env=None):
     assert r.returncode == 0, r.stderr[-3000:]
     out = {}
     for name, chunk in zip(names, r.stdout.split("@@case ")[1:]):
-        L, S = {}, {}
+        L, S, product = {}, {}, dict(pulled=[], numbers=None)
         for line in chunk.split("\n")[1:]:
             w = line.split()
             if w and w[0] == "L":
@@ -109,7 +111,11 @@ def _launches(exe, d, names, extra_env=None):
             elif w and w[0] == "S":
                 v = list(map(int, w[1:]))
                 S[v[0]] = dict(c0=v[1], nc=v[2], nb=v[3], parent=v[4], nchild=v[5], launch=v[6], rel=v[7:])
-        out[name] = (L, S)
+            elif w and w[0] == "P" and w[2] == "1":        # the product's own flag (EngineTables::solve_pulled)
+                product["pulled"].append(int(w[1]))
+            elif w and w[0] == "M":                        # ... and the numbers of its "contribution rows pulled" line
+                product["numbers"] = tuple(int(x) for x in w[1:])
+        out[name] = (L, S, product)
     return out
 
 
@@ -119,20 +125,38 @@ def launches(driver):
     return _launches(exe, d, list(NEW))
 
 
-def solve_pulled(L, S):
-    """The fronts the many-column sweeps pull, by the rule of LDLEngine::upload() (csrc/hipkkt.hip), and the three
-    numbers of its verbose line."""
-    got = sorted(s for s, d in S.items() if L[d["launch"]]["small"] and d["nchild"] == 0 and d["nc"] == 1 and d["parent"] >= 0
-                 and 1 <= d["nb"] <= 47)
+def solve_pulled(L, S, pull_on=True):
+    """The fronts the many-column sweeps pull, by the rule of build_engine_tables (csrc/engine_tables.cpp) restated here,
+    and the three numbers of the engine's verbose line."""
+    got = sorted(s for s, d in S.items() if pull_on and L[d["launch"]]["small"] and d["nchild"] == 0 and d["nc"] == 1
+                 and d["parent"] >= 0 and 1 <= d["nb"] <= 47)
     a = sum(S[s]["nb"] for s in got)
     b = sum(d["nb"] for d in S.values())
     c = len({(S[s]["parent"], r) for s in got for r in S[s]["rel"]})
     return got, (a, b, c)
 
 
+_PRODUCT_RUNS = {}
+
+
+@pytest.mark.parametrize("env_id", ["default", "pull_off"])
+@pytest.mark.parametrize("name", list(NEW))
+def test_the_product_pulls_what_the_rule_says(driver, launches, name, env_id):
+    """What the product's tables hold -- the pulled set and the three numbers -- equals the restatement solve_pulled, for
+    every new case, by default and with the pulling switched off."""
+    if env_id not in _PRODUCT_RUNS:
+        _PRODUCT_RUNS[env_id] = launches if env_id == "default" else _launches(*driver, list(NEW), ENVS[env_id])
+    L, S, product = _PRODUCT_RUNS[env_id][name]
+    got, abc = solve_pulled(L, S, pull_on=env_id == "default")
+    assert product["pulled"] == got, (product["pulled"], got)
+    assert product["numbers"] == abc, (product["numbers"], abc)
+    if env_id == "pull_off":
+        assert got == [] and abc[0] == 0 and abc[2] == 0 and abc[1] == launches[name][2]["numbers"][1]
+
+
 @pytest.mark.parametrize("name", list(NEW))
 def test_the_schedule_holds_the_designed_fronts(launches, name):
-    L, S = launches[name]
+    L, S, _ = launches[name]
     exp = NEW[name][1]
     for d in S.values():           # (check_schedule requires it too, for every pattern the driver sees)
         assert d["nchild"] > 0 or L[d["launch"]]["level"] == 0, "a childless front outside level 0"
