@@ -134,6 +134,8 @@ SYMBOLS = {
     "hipkkt_kkt_system_update_data_b": (C.c_int, [_P, _P, _P, C.c_int64]),
     "hipkkt_kkt_system_data_norms": (C.c_int, [_P, _P]),
     "hipkkt_kkt_system_set_problems": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "hipkkt_kkt_system_set_equilibration_batch": (C.c_int, [_P, _P, _P, _P]),
+    "hipkkt_kkt_system_data_norms_batch": (C.c_int, [_P, _P]),
     "hipkkt_kkt_system_set_member_refinement": (C.c_int, [_P, C.c_int]),
     "hipkkt_kkt_system_member_refinement_info": (C.c_int, [_P, _P]),
     "hipkkt_kkt_system_set_member_status": (C.c_int, [_P, C.c_int]),

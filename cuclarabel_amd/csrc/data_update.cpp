@@ -2,6 +2,7 @@
 #include "data_update.hpp"
 
 #include <algorithm>
+#include <cmath>
 
 namespace hipkkt {
 
@@ -68,6 +69,41 @@ EntryTables build_entry_tables(int n, int m, int N, const int64_t* colptr, const
         T.Acol[(size_t)t] = r;
     }
     return T;
+}
+
+int64_t check_member_costs(const double* c, int64_t nb)
+{
+    for (int64_t b = 0; b < nb; ++b)
+        if (!(c[b] > 0.0) || !std::isfinite(c[b])) return b;
+    return -1;
+}
+
+EntryMembers build_entry_members(const int* Prow, const int* Pcol, int64_t nP, const int* xmem, int n, int nb)
+{
+    EntryMembers E;
+    E.Pmem.resize((size_t)nP);
+    for (int64_t t = 0; t < nP; ++t) {
+        const int r = Prow[t], c = Pcol[t];
+        if (r < 0 || r >= n || c < 0 || c >= n) { E.ok = false; E.bad = t; return E; }
+        const int b = xmem[r];
+        if (b < 0 || b >= nb || xmem[c] != b) { E.ok = false; E.bad = t; return E; }
+        E.Pmem[(size_t)t] = b;
+    }
+    return E;
+}
+
+std::vector<int> build_norm_slots(const int* xmem, int n, const int* zmem, int m, int nb)
+{
+    std::vector<int> slot((size_t)n + (size_t)m);
+    for (int i = 0; i < n; ++i) {
+        if (xmem[i] < 0 || xmem[i] >= nb) return {};
+        slot[(size_t)i] = 2 * xmem[i];
+    }
+    for (int i = 0; i < m; ++i) {
+        if (zmem[i] < 0 || zmem[i] >= nb) return {};
+        slot[(size_t)n + (size_t)i] = 2 * zmem[i] + 1;
+    }
+    return slot;
 }
 
 }  // namespace hipkkt

@@ -30,4 +30,27 @@ struct EntryTables {
 EntryTables build_entry_tables(int n, int m, int N, const int64_t* colptr, const int* rowval, const int* mapP, int64_t nP,
                                const int* mapA, int64_t nA);
 
+// ---- member cost scalings (hipkkt_kkt_system_set_equilibration_batch, hipkkt_kkt_system_data_norms_batch): on a stack
+// of independent problems every member b has its own cost scaling c[b] (the reference computes c per problem:
+// problemdata.jl:133-221).
+
+// The first member whose c is not positive and finite (0, negative, inf, NaN), or -1 where all nb are fine.
+int64_t check_member_costs(const double* c, int64_t nb);
+
+// The member of every stored entry of P in the matrix's own numbering: Pmem[t] = xmem[Prow[t]], which the partition
+// guarantees to equal xmem[Pcol[t]].  ok = false (and `bad` = the first offender) where a row or column lies outside
+// [0, n), a member outside [0, nb), or an entry's row and column belong to different members -- the update kernel reads
+// c through the ROW, and this is the check that the row's member is the entry's.
+struct EntryMembers {
+    std::vector<int> Pmem;
+    bool ok = true;
+    int64_t bad = -1;
+};
+EntryMembers build_entry_members(const int* Prow, const int* Pcol, int64_t nP, const int* xmem, int n, int nb);
+
+// The word of the segmented norms a row's product is folded into, for the n x rows followed by the m z rows: x row i of
+// member b -> 2 b (max |q dinv|), z row i of member b -> 2 b + 1 (max |b einv|).  A member's x rows and z rows are
+// contiguous runs, so nearly every wave of 64 rows holds one word.  Empty where a member lies outside [0, nb).
+std::vector<int> build_norm_slots(const int* xmem, int n, const int* zmem, int m, int nb);
+
 }  // namespace hipkkt

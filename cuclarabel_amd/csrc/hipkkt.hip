@@ -1623,6 +1623,14 @@ struct hipkkt_kkt_s {
     bool eq_ready = false;
     DBuf<int> du_Prow, du_Pcol, du_Arow, du_Acol;
     DBuf<int64_t> du_idx;
+    // hipkkt_kkt_system_set_equilibration_batch: one cost scaling per member of the partition (eqb_on), on the host and the
+    // device, and nothing derived from them; eq_c is left as it was.  hipkkt_kkt_system_data_norms_batch: every combined
+    // row's word (data_update.hpp: build_norm_slots), built for the current partition on first use, and the 2 nb words.
+    bool eqb_on = false;
+    std::vector<double> eqb_c_h;
+    DBuf<double> eqb_c, eqb_norms;
+    DBuf<int> eqb_slot;
+    bool eqb_slot_ready = false;
     bool data_factor_stale = false;  // P or A changed since the last factorisation
     bool data_const_stale = false;   // P, A, q or b changed since (x2, z2) and the cached constant terms were formed
     DBuf<double> hst;                // staging of the *_host entry points of level C: 3 x (n + 2 m) doubles (rhs, variables, lhs)
@@ -3731,6 +3739,53 @@ int hipkkt_kkt_system_set_equilibration(hipkkt_kkt_t h, const double* d, const d
         }
         HIP_CHECK(hipStreamSynchronize(st));             // the caller's (and this call's) host arrays may go away
         h->eq_c = c;
+        h->eqb_on = false;                               // (one joint c again: the members' cost scalings are dropped)
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_set_equilibration_batch(hipkkt_kkt_t h, const double* d, const double* e, const double* c)
+{
+    return guarded([&]() {
+        const char* who = "hipkkt_kkt_system_set_equilibration_batch";
+        if (!h) throw ArgError("null handle");
+        if (h->deferred) throw ArgError("hipkkt_kkt_system_*: level C reads its scalars back (deferred status is for level B)");
+        if (h->bat_nb <= 0) throw ArgError(std::string(who) + ": the handle has no partition (hipkkt_kkt_system_set_problems)");
+        const int n = h->K.n, m = h->K.m, nb = h->bat_nb;
+        const bool ones = !d && !e;
+        if (!ones && ((n > 0 && !d) || (m > 0 && !e))) throw ArgError(std::string(who) + ": d and e are both given or both NULL");
+        if (!c) throw ArgError(std::string(who) + ": c is NULL");
+        const int64_t badc = check_member_costs(c, nb);
+        if (badc >= 0)
+            throw ArgError(std::string(who) + ": c[" + std::to_string(badc) + "] must be positive and finite (member " +
+                           std::to_string(badc) + ")");
+        HIP_CHECK(hipSetDevice(h->device));
+        data_ensure(h);
+        {
+            // the update kernels read c through an entry's ROW: every stored entry of P has its column in the row's member
+            const KKTAssembly& K = h->K;
+            const EntryTables T = build_entry_tables(K.n, K.m, K.N, K.colptr.data(), K.rowval.data(), K.mapP.data(),
+                                                     (int64_t)K.mapP.size(), K.mapA.data(), (int64_t)K.mapA.size());
+            const EntryMembers E = build_entry_members(T.Prow.data(), T.Pcol.data(), (int64_t)T.Prow.size(), h->bat_plan.xmem.data(), n, nb);
+            if (!T.ok || !E.ok) throw std::runtime_error(std::string(who) + ": a stored entry of P couples two members of the partition");
+        }
+        hipStream_t st = h->stream;
+        if (h->eqb_c.n != (size_t)nb) h->eqb_c.alloc((size_t)nb);
+        if (ones) {
+            const std::vector<double> one((size_t)std::max(n, m), 1.0);
+            for (DBuf<double>* v : {&h->eq_d, &h->eq_dinv, &h->eq_e, &h->eq_einv})
+                if (v->n) HIP_CHECK(hipMemcpyAsync(v->p, one.data(), v->n * sizeof(double), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipMemcpyAsync(h->eqb_c.p, c, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipStreamSynchronize(st));
+        } else {
+            if (n) HIP_CHECK(hipMemcpyAsync(h->eq_d.p, d, (size_t)n * sizeof(double), hipMemcpyHostToDevice, st));
+            if (m) HIP_CHECK(hipMemcpyAsync(h->eq_e.p, e, (size_t)m * sizeof(double), hipMemcpyHostToDevice, st));
+            launch_reciprocals(h->eq_dinv.p, h->eq_d.p, n, h->eq_einv.p, h->eq_e.p, m, st);
+            HIP_CHECK(hipMemcpyAsync(h->eqb_c.p, c, (size_t)nb * sizeof(double), hipMemcpyHostToDevice, st));
+            HIP_CHECK(hipStreamSynchronize(st));         // the caller's host arrays may go away
+        }
+        h->eqb_c_h.assign(c, c + nb);
+        h->eqb_on = true;
         return HIPKKT_OK;
     });
 }
@@ -3797,7 +3852,9 @@ static int data_update_matrix(hipkkt_kkt_t h, const char* who, bool isP, const d
         M.L = isP ? h->eq_d.p : h->eq_e.p;
         M.R = h->eq_d.p;
         M.c = isP ? h->eq_c : 1.0;                       // (a product by 1.0 is exact: A's fl(v * fl(e d)))
-        launch_data_update_matrix(M, d_values, d_index, k, h->stream);
+        // (member cost scalings: P's c is that of the entry's row's member; uniform over the launch, decided here)
+        if (isP && h->eqb_on) launch_data_update_matrix_member(M, h->bat_xmem.p, h->eqb_c.p, d_values, d_index, k, h->stream);
+        else launch_data_update_matrix(M, d_values, d_index, k, h->stream);
         HIP_CHECK(hipGetLastError());
         h->data_factor_stale = true;
         h->data_const_stale = true;
@@ -3822,7 +3879,9 @@ static int data_update_vector(hipkkt_kkt_t h, const char* who, bool isq, const d
         const int64_t len = h ? (isq ? h->K.n : h->K.m) : 0;
         const int64_t* d_index = nullptr;
         if (!data_update_begin(h, who, d_values, index, k, len, true, &d_index)) return HIPKKT_OK;
-        if (isq) launch_data_update_vector(h->sq.p, h->snegq.p, h->eq_d.p, h->eq_c, d_values, d_index, k, h->stream);
+        if (isq && h->eqb_on)
+            launch_data_update_vector_member(h->sq.p, h->snegq.p, h->eq_d.p, h->bat_xmem.p, h->eqb_c.p, d_values, d_index, k, h->stream);
+        else if (isq) launch_data_update_vector(h->sq.p, h->snegq.p, h->eq_d.p, h->eq_c, d_values, d_index, k, h->stream);
         else launch_data_update_vector(h->sb.p, nullptr, h->eq_e.p, 1.0, d_values, d_index, k, h->stream);
         HIP_CHECK(hipGetLastError());
         h->data_const_stale = true;
@@ -3855,6 +3914,39 @@ int hipkkt_kkt_system_data_norms(hipkkt_kkt_t h, double out[2])
         HIP_CHECK(hipStreamSynchronize(st));
         out[0] = h->pin->h[52] / h->eq_c;                // data_get_normq!: the unscaled norm, cinv applied (problemdata.jl:91-100)
         out[1] = h->pin->h[53];
+        return HIPKKT_OK;
+    });
+}
+
+int hipkkt_kkt_system_data_norms_batch(hipkkt_kkt_t h, double* out)
+{
+    return guarded([&]() {
+        iterate_guard(h);
+        if (!out) throw ArgError("hipkkt_kkt_system_data_norms_batch: bad argument");
+        if (h->bat_nb <= 0)
+            throw ArgError("hipkkt_kkt_system_data_norms_batch: the handle has no partition (hipkkt_kkt_system_set_problems)");
+        data_ensure(h);
+        const int n = h->K.n, m = h->K.m;
+        const size_t nb = (size_t)h->bat_nb;
+        if (!h->eqb_slot_ready) {                        // every combined row's word, once per partition
+            const std::vector<int> slot = build_norm_slots(h->bat_plan.xmem.data(), n, h->bat_plan.zmem.data(), m, h->bat_nb);
+            if (slot.size() != (size_t)n + (size_t)m) throw std::runtime_error("hipkkt_kkt_system_data_norms_batch: a row's member is out of range");
+            h->eqb_slot.upload(slot);
+            h->eqb_norms.alloc(2 * nb);
+            h->eqb_slot_ready = true;
+        }
+        hipStream_t st = h->stream;
+        h->eqb_norms.zero(st);
+        launch_data_norms_member(h->sq.p, h->eq_dinv.p, n, h->sb.p, h->eq_einv.p, m, h->eqb_slot.p, h->eqb_norms.p, st);
+        HIP_CHECK(hipGetLastError());
+        double* stage = h->bat_pin + 4 * nb;             // (the results' part of the page-locked staging: 2 nb of its 12 nb)
+        HIP_CHECK(hipMemcpyAsync(stage, h->eqb_norms.p, 2 * nb * sizeof(double), hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        for (size_t b = 0; b < nb; ++b) {
+            // data_get_normq! per member: the unscaled norm, the member's cinv applied (problemdata.jl:91-100)
+            out[2 * b] = stage[2 * b] / (h->eqb_on ? h->eqb_c_h[b] : h->eq_c);
+            out[2 * b + 1] = stage[2 * b + 1];
+        }
         return HIPKKT_OK;
     });
 }
@@ -3894,8 +3986,13 @@ int hipkkt_kkt_system_set_problems(hipkkt_kkt_t h, int64_t nb, const int64_t* x_
         if (!h) throw ArgError("null handle");
         if (!h->sys_ready) throw ArgError("hipkkt_kkt_system_*: call hipkkt_kkt_system_init first");
         if (h->deferred) throw ArgError("hipkkt_kkt_system_*: level C reads its scalars back (deferred status is for level B)");
+        if (h->eqb_on)
+            throw ArgError("hipkkt_kkt_system_set_problems: the handle holds member cost scalings "
+                           "(hipkkt_kkt_system_set_equilibration_batch) that belong to its partition; clear them first with "
+                           "hipkkt_kkt_system_set_equilibration");
         HIP_CHECK(hipSetDevice(h->device));
         if (nb == 0) {                                   // (the tables stay allocated until the next partition or the handle's end)
+            h->eqb_slot_ready = false;
             h->bat_nb = 0;
             h->mr_on = h->mr_valid = false;             // (the member refinement rule goes with its partition)
             h->ms_on = h->ms_valid = false;             // (... and so does the member status)
@@ -3918,6 +4015,7 @@ int hipkkt_kkt_system_set_problems(hipkkt_kkt_t h, int64_t nb, const int64_t* x_
         h->bat_nb = 0;
         h->mr_on = h->mr_valid = false;
         h->ms_on = h->ms_valid = false;
+        h->eqb_slot_ready = false;                       // (the norms' words go with their partition)
         h->bat_xoff.upload(P.x_off); h->bat_zoff.upload(P.z_off); h->bat_xmem.upload(P.xmem); h->bat_zmem.upload(P.zmem);
         h->bat_cmem.upload(P.cone_mem); h->bat_socptr.upload(P.soc_ptr); h->bat_psdptr.upload(P.psd_ptr);
         h->bat_degree.upload(P.degree);

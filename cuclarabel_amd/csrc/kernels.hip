@@ -123,6 +123,45 @@ void launch_data_update_vector(double* y, double* yneg, const double* scale, dou
     if (k <= 0) return;
     hipLaunchKernelGGL(k_data_update_vector, dim3(grid_for(k, 256, kDataUpdateGridCap)), dim3(256), 0, st, y, yneg, scale, c, v, idx, k);
 }
+// The same two updates on a stack whose members carry their own cost scaling (hipkkt_kkt_system_set_equilibration_batch;
+// the reference computes c per problem, problemdata.jl:133-221): c is cmem[xmem[row]], the entry's row's member through
+// the partition's row -> member table -- for a stored entry of P the column's member is the same.  Same order of
+// operations; kernels of their own, so that the launches with one scalar c run the code they always ran.
+__global__ void k_data_update_matrix_member(DataMatDev M, const int* __restrict__ xmem, const double* __restrict__ cmem,
+                                            const double* __restrict__ v, const int64_t* __restrict__ idx, int64_t k)
+{
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < k; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t j = idx ? idx[t] : t;
+        const int r = M.row[j];
+        const double s = v[t] * (M.L[r] * M.R[M.col[j]]) * cmem[xmem[r]];
+        M.val[j] = s;
+        put_k(M.K, M.fval, M.kpos, M.map[j], s);
+    }
+}
+void launch_data_update_matrix_member(const DataMatDev& M, const int* xmem, const double* cmem, const double* v, const int64_t* idx,
+                                      int64_t k, hipStream_t st)
+{
+    if (k <= 0) return;
+    hipLaunchKernelGGL(k_data_update_matrix_member, dim3(grid_for(k, 256, kDataUpdateGridCap)), dim3(256), 0, st, M, xmem, cmem, v, idx, k);
+}
+__global__ void k_data_update_vector_member(double* __restrict__ y, double* __restrict__ yneg, const double* __restrict__ scale,
+                                            const int* __restrict__ xmem, const double* __restrict__ cmem,
+                                            const double* __restrict__ v, const int64_t* __restrict__ idx, int64_t k)
+{
+    for (int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; t < k; t += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t j = idx ? idx[t] : t;
+        const double s = v[t] * scale[j] * cmem[xmem[j]];
+        y[j] = s;
+        if (yneg) yneg[j] = -s;
+    }
+}
+void launch_data_update_vector_member(double* y, double* yneg, const double* scale, const int* xmem, const double* cmem,
+                                      const double* v, const int64_t* idx, int64_t k, hipStream_t st)
+{
+    if (k <= 0) return;
+    hipLaunchKernelGGL(k_data_update_vector_member, dim3(grid_for(k, 256, kDataUpdateGridCap)), dim3(256), 0, st, y, yneg, scale, xmem,
+                       cmem, v, idx, k);
+}
 // scalings on the handle: dinv = 1 / d, einv = 1 / e (IEEE quotients) in one launch over n + m items
 __global__ void k_reciprocals(double* __restrict__ dinv, const double* __restrict__ d, int64_t n, double* __restrict__ einv,
                               const double* __restrict__ e, int64_t m)
@@ -181,6 +220,50 @@ void launch_data_norms(const double* q, const double* dinv, int64_t n, const dou
     if (n + m <= 0) return;
     hipLaunchKernelGGL(k_data_norms, dim3(grid_for(n + m, 256, kDataNormsGridCap)), dim3(256), 0, st, q, dinv, n, b, einv, m,
                        (unsigned long long*)out2);
+}
+
+// The same maxima per member of a stack (hipkkt_kkt_system_data_norms_batch): out[2 b] = max over member b's x rows of
+// |q_i dinv_i|, out[2 b + 1] = max over its z rows of |b_i einv_i|, the products formed as k_data_norms forms them and
+// folded on their bit patterns.  slot[i] (data_update.hpp: build_norm_slots) names the word of combined row i (the x rows,
+// then the z rows).  A member's rows are contiguous runs, so nearly every wave holds ONE word: it folds its 64 patterns
+// and sends one integer atomicMax, k_member_diag_max's way; a wave that straddles a boundary (between two members, or
+// between the x and the z rows) sends its lanes' patterns one by one.  out (2 nb words) must hold zeros at the start.
+__global__ __launch_bounds__(256) void k_data_norms_member(const double* __restrict__ q, const double* __restrict__ dinv, int64_t n,
+                                                           const double* __restrict__ b, const double* __restrict__ einv, int64_t m,
+                                                           const int* __restrict__ slot, unsigned long long* __restrict__ out)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t len = n + m;
+    for (int64_t base = (int64_t)blockIdx.x * 256; base < len; base += (int64_t)gridDim.x * 256) {      // (uniform over the workgroup)
+        if (base + wave * 64 >= len) continue;                                       // (the wave has no row: uniform over the wave)
+        const int64_t i = base + (int64_t)threadIdx.x;
+        const bool valid = i < len;
+        int word = -1;
+        unsigned long long p = 0ull;
+        if (valid) {
+            word = slot[i];
+            p = i < n ? (unsigned long long)__double_as_longlong(fabs(q[i] * dinv[i]))
+                      : (unsigned long long)__double_as_longlong(fabs(b[i - n] * einv[i - n]));
+        }
+        const int lead = __builtin_amdgcn_readfirstlane(word);                       // (lane 0's row is valid: the rows are a prefix)
+        if (__all(!valid || word == lead)) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const unsigned long long r = (unsigned long long)__double_as_longlong(__shfl_xor(__longlong_as_double((long long)p), o, 64));
+                p = r > p ? r : p;
+            }
+            if (lane == 0 && p) atomicMax(out + lead, p);
+        } else if (valid && p) {
+            atomicMax(out + word, p);
+        }
+    }
+}
+void launch_data_norms_member(const double* q, const double* dinv, int64_t n, const double* b, const double* einv, int64_t m,
+                              const int* slot, double* out, hipStream_t st)
+{
+    if (n + m <= 0) return;
+    hipLaunchKernelGGL(k_data_norms_member, dim3(grid_for(n + m, 256, kDataNormsGridCap)), dim3(256), 0, st, q, dinv, n, b, einv, m,
+                       slot, (unsigned long long*)out);
 }
 
 // ---- reductions: block max -> partial[], then one small block finishes

@@ -311,6 +311,16 @@ void launch_reciprocals(double* dinv, const double* d, int64_t n, double* einv, 
 // out2[0] = max |q dinv|, out2[1] = max |b einv|; out2 (two doubles) must hold zeros when the kernel starts
 void launch_data_norms(const double* q, const double* dinv, int64_t n, const double* b, const double* einv, int64_t m,
                        double* out2, hipStream_t st);
+// the two updates that carry c, and the norms, on a stack whose members have their own cost scaling: c = cmem[xmem[row]]
+// (xmem: the partition's x row -> member table; cmem: nb doubles), same order of operations.  slot: n + m words' indices
+// (data_update.hpp: build_norm_slots); out: 2 nb doubles that hold zeros when the kernel starts -> out[2 b] = member b's
+// max |q dinv| (NOT yet divided by its c), out[2 b + 1] = its max |b einv|
+void launch_data_update_matrix_member(const DataMatDev& M, const int* xmem, const double* cmem, const double* v, const int64_t* idx,
+                                      int64_t k, hipStream_t st);
+void launch_data_update_vector_member(double* y, double* yneg, const double* scale, const int* xmem, const double* cmem,
+                                      const double* v, const int64_t* idx, int64_t k, hipStream_t st);
+void launch_data_norms_member(const double* q, const double* dinv, int64_t n, const double* b, const double* einv, int64_t m,
+                              const int* slot, double* out, hipStream_t st);
 void launch_scale(double* Kval, const int* idx, double scale, int64_t n, hipStream_t st);
 // eps = c0 + c1 * max_i |Kval[diag[i]]|  (kktsolver_directldl.jl:297-310) -> *eps_out
 void launch_regularizer(const double* Kval, const int* diag, int N, double c0, double c1,

@@ -196,9 +196,21 @@ def solve_device_batch_isolated(problems, settings=None, inspect=None, member_re
     return _solve_batch("solve_device_batch_isolated", problems, settings, inspect, bool(member_refinement), True)
 
 
-def _solve_batch(who, problems, settings, inspect, member_refinement, isolate=False):
-    """The loop of solve_device_batch, solve_device_batch_refined and solve_device_batch_isolated."""
-    import torch
+def _solve_batch(who, problems, settings, inspect, member_refinement, isolate=False, equilibrations=None):
+    """What solve_device_batch, solve_device_batch_refined and solve_device_batch_isolated share: the set-up, then the loop
+    from the default start.  equilibrations: see _setup_batch."""
+    return _loop_batch(_setup_batch(who, problems, settings, member_refinement, isolate, equilibrations), inspect)
+
+
+class _BatchSetup:
+    """Everything a batch solve needs that does not depend on the iterate: the stacked handle with its partition and
+    member modes, the loop's device tensors, the members' offsets and degrees.  Built once by _setup_batch; _loop_batch runs
+    on it any number of times (solver_device.DeviceBatchSolver)."""
+
+
+def _check_batch(who, problems, isolate):
+    """The batch entry points' argument check -> the members as (triu P, q, A, b, cone list); refusals are ValueError,
+    raised before a handle is built."""
     problems = list(problems)
     if not problems:
         raise ValueError(f"{who} needs at least one problem")
@@ -214,45 +226,106 @@ def _solve_batch(who, problems, settings, inspect, member_refinement, isolate=Fa
             for name, values in (("P", Pt.data), ("q", members[-1][1]), ("A", members[-1][2].data), ("b", members[-1][3])):
                 if not np.all(np.isfinite(values)):
                     raise ValueError(f"{who}: member {len(members) - 1} has a non-finite entry in {name}")
-    st = settings or IPMSettings()
-    nb = len(members)
+    return members
+
+
+def _setup_batch(who, problems, settings, member_refinement, isolate=False, equilibrations=None):
+    """equilibrations: None -- the stack is built from the members' data as given and the loop knows no equilibration, as
+    it always did; or a list of `equilibrate.Equilibration`, one per member (solver_device.DeviceBatchSolver) -- the
+    handle is built from every member's data scaled by its own (d, e, c_b) in the update kernels' order
+    (solver_device.scale_data), the scalings go onto the handle (hipkkt_kkt_system_set_equilibration_batch) and the loop
+    takes the equilibrated path of _loop per member."""
+    import torch
+    members = _check_batch(who, problems, isolate)
+    c = _BatchSetup()
+    c.st = settings or IPMSettings()
+    c.member_refinement, c.isolate = member_refinement, isolate
+    c.members = members
+    c.nb = nb = len(members)
+    if equilibrations is not None:
+        from .solver_device import scale_data
+        equilibrations = list(equilibrations)
+        if len(equilibrations) != nb:
+            raise ValueError(f"{who}: one Equilibration per member ({nb}), got {len(equilibrations)}")
+        members = [scale_data(mb[0], mb[1], mb[2], mb[3], eq) + (mb[4],) for mb, eq in zip(members, equilibrations)]
     P = sp.block_diag([mb[0] for mb in members], format="csc")
     A = sp.block_diag([mb[2] for mb in members], format="csc")
     q = np.concatenate([mb[1] for mb in members])
     b = np.concatenate([mb[3] for mb in members])
-    cone_specs = [c for mb in members for c in mb[4]]
+    cone_specs = [k for mb in members for k in mb[4]]
     blocks = [(mb[0].shape[0], mb[2].shape[0]) for mb in members]
     x_off = np.concatenate([[0], np.cumsum([bl[0] for bl in blocks])]).astype(int)
     z_off = np.concatenate([[0], np.cumsum([bl[1] for bl in blocks])]).astype(int)
     n, m = int(x_off[-1]), int(z_off[-1])
-    degree = np.array([sum(c.dim if isinstance(c, (NonnegativeConeT, PSDTriangleConeT)) else 1 if isinstance(c, SecondOrderConeT)
-                           else 0 for c in mb[4]) for mb in members], float)
-    normq = np.array([np.abs(mb[1]).max() if mb[1].size else 0.0 for mb in members])
-    normb = np.array([np.abs(mb[3]).max() if mb[3].size else 0.0 for mb in members])
+    c.x_off, c.z_off, c.n, c.m = x_off, z_off, n, m
+    c.degree = np.array([sum(k.dim if isinstance(k, (NonnegativeConeT, PSDTriangleConeT)) else 1 if isinstance(k, SecondOrderConeT)
+                             else 0 for k in mb[4]) for mb in members], float)
+    # (no equilibration: the norms of q and b from the host data; equilibrated: from the handle, once per solve)
+    c.normq = np.array([np.abs(mb[1]).max() if mb[1].size else 0.0 for mb in members])
+    c.normb = np.array([np.abs(mb[3]).max() if mb[3].size else 0.0 for mb in members])
 
-    backend = HipSystemBackend(P, A, cone_specs)
+    c.backend = backend = HipSystemBackend(P, A, cone_specs)
     ks, system = backend.ks, backend.system
-    dev = system._devstr
+    c.dev = dev = system._devstr
     ks.set_stream(torch.cuda.current_stream(torch.device(dev)).cuda_stream)
     up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
     new = lambda k: torch.zeros(max(k, 1), dtype=torch.float64, device=dev)[:k]
-    qd, bd = up(q), up(b)
-    p = lambda t: t.data_ptr()
-    ir_total = 0
+    c.qd, c.bd = up(q), up(b)
 
-    # ---- default start (solver.jl:383-404), the shifts per member
-    x, s, z = new(n), new(m), new(m)
-    dx, ds, dz = new(n), new(m), new(m)
-    aff_s, rhs_s = new(m), new(m)
-    rx, rx_inf, Px, rhs_x = new(n), new(n), new(n), new(n)
-    rz, rz_inf, rhs_z = new(m), new(m), new(m)
-    aff_x, aff_z = new(n), new(m)                        # the affine right-hand side with the frozen members' rows zeroed
+    c.x, c.s, c.z = new(n), new(m), new(m)
+    c.dx, c.ds, c.dz = new(n), new(m), new(m)
+    c.aff_s, c.rhs_s = new(m), new(m)
+    c.rx, c.rx_inf, c.Px, c.rhs_x = new(n), new(n), new(n), new(n)
+    c.rz, c.rz_inf, c.rhs_z = new(m), new(m), new(m)
+    c.aff_x, c.aff_z = new(n), new(m)                    # the affine right-hand side with the frozen members' rows zeroed
     system.init(q, b)
     system.set_problems(blocks)
     if member_refinement:
         system.set_member_refinement(True)
     if isolate:
         system.set_member_status(True)
+    c.equil = None
+    if equilibrations is not None:
+        # the members' scalings onto the handle; what the loop reads of them (as solver_device._Equil for one problem)
+        system.set_equilibration_batch(equilibrations)
+        c.equil = eq = _BatchSetup()
+        eq.ptrs = system.equilibration_dev()
+        eq.c = np.array([float(e_.c) for e_ in equilibrations])
+        eq.cinv = 1.0 / eq.c
+        eq.d = np.concatenate([np.asarray(e_.d, float).ravel() for e_ in equilibrations])
+        eq.e = np.concatenate([np.asarray(e_.e, float).ravel() for e_ in equilibrations])
+        eq.einv = 1.0 / eq.e
+        eq.fx, eq.fz, eq.fs = new(n), new(m), new(m)     # variables_unscale!'s factors per row, filled at the end of a solve
+    return c
+
+
+def _loop_batch(c, inspect=None):
+    """The loop of solve_device_batch, solve_device_batch_refined and solve_device_batch_isolated, from the default start,
+    on a _BatchSetup.  c.equil set (solver_device.DeviceBatchSolver): the handle was built from data equilibrated member by
+    member -- the residual pass takes the handle's (d, dinv, e, einv), every member's cost scaling c_b is backed out of
+    its own scalars (cinv, info.jl:19-51), the norms of its unscaled q and b come from the handle once per solve
+    (hipkkt_kkt_system_data_norms_batch), variables_unscale! (variables.jl:247-275) is applied per member before the one
+    copy to the host, and the objectives are those of the residual pass's scalars (the host keeps no current copy of the
+    data).  None: the loop as it always was."""
+    import torch
+    st, member_refinement, isolate, members, nb = c.st, c.member_refinement, c.isolate, c.members, c.nb
+    x_off, z_off, n, m, degree = c.x_off, c.z_off, c.n, c.m, c.degree
+    backend = c.backend
+    system, dev = backend.system, c.dev
+    qd, bd = c.qd, c.bd
+    equil = c.equil
+    d_equil = None if equil is None else equil.ptrs
+    normq, normb = (c.normq, c.normb) if equil is None else system.data_norms_batch().T.copy()
+    p = lambda t: t.data_ptr()
+    ir_total = 0
+
+    # ---- default start (solver.jl:383-404), the shifts per member
+    x, s, z = c.x, c.s, c.z
+    dx, ds, dz = c.dx, c.ds, c.dz
+    aff_s, rhs_s = c.aff_s, c.rhs_s
+    rx, rx_inf, Px, rhs_x = c.rx, c.rx_inf, c.Px, c.rhs_x
+    rz, rz_inf, rhs_z = c.rz, c.rz_inf, c.rhs_z
+    aff_x, aff_z = c.aff_x, c.aff_z
     ir_member = np.zeros(nb, dtype=np.int64)             # (member rule: every member's own rounds)
     backend.update_identity()
     system.solve_constant_rhs()
@@ -269,6 +342,7 @@ def _solve_batch(who, problems, settings, inspect, member_refinement, isolate=Fa
     iterations = [0] * nb
     prev = [None] * nb
     hist = [[] for _ in range(nb)]
+    restored = [False] * nb                              # (the member ended on the iterate before its last history row)
     prev_vars = None
     tiny = 100 * np.finfo(float).eps
 
@@ -284,7 +358,7 @@ def _solve_batch(who, problems, settings, inspect, member_refinement, isolate=Fa
         while True:
             active = [k for k in range(nb) if status[k] == UNSOLVED]
             # ---- residuals (residuals.jl:1-37); every member's twelve scalars in ONE read-back
-            R = system.residuals_batch_dev(p(x), p(s), p(z), tau, p(rx), p(rz), p(rx_inf), p(rz_inf), p(Px))
+            R = system.residuals_batch_dev(p(x), p(s), p(z), tau, p(rx), p(rz), p(rx_inf), p(rz_inf), p(Px), d_equil)
             qx, bz, sz, xPx = R[:, 0], R[:, 1], R[:, 2], R[:, 3]
             rtau = qx + bz + kappa + xPx / tau
             mu = (sz + tau * kappa) / (degree + 1)
@@ -292,16 +366,21 @@ def _solve_batch(who, problems, settings, inspect, member_refinement, isolate=Fa
                 inspect(dict(x=x, s=s, z=z, dx=dx, ds=ds, dz=dz, aff_s=aff_s, rhs_s=rhs_s, rx=rx, rz=rz, rx_inf=rx_inf,
                              rz_inf=rz_inf, Px=Px, q=qd, b=bd), backend)
             for k in active:
-                # ---- info_update! (info.jl:1-63), no equilibration
+                # ---- info_update! (info.jl:1-63); equilibrated: the norms came scaled by d, e and their inverses out of
+                #      the residual pass, and the member's cost scaling c_b is backed out here (cinv, info.jl:19-51)
                 nx, nz, ns, n_rxi, n_Px, n_rzi, n_rz, n_rx = (float(v) for v in R[k, 4:12])
                 tinv = 1.0 / tau[k]
                 cost_p = qx[k] * tinv + xPx[k] * tinv * tinv / 2
                 cost_d = -bz[k] * tinv - xPx[k] * tinv * tinv / 2
+                if equil is not None:
+                    cinv = equil.cinv[k]
+                    cost_p, cost_d, nz = cost_p * cinv, cost_d * cinv, nz * cinv          # info.jl:27-28, :34
+                    n_rxi = n_rxi * cinv                                                  # :38
                 res_pinf = n_rxi / max(1.0, nz)
                 res_dinf = max(n_Px / max(1.0, nx), n_rzi / max(1.0, nx + ns))
                 nx, nz, ns = nx * tinv, nz * tinv, ns * tinv
                 res_p = n_rz * tinv / max(1.0, normb[k] + nx + ns)
-                res_d = n_rx * tinv / max(1.0, normq[k] + nx + nz)
+                res_d = (n_rx * tinv if equil is None else n_rx * tinv * cinv) / max(1.0, normq[k] + nx + nz)      # :51
                 gap_abs = abs(cost_p - cost_d)
                 gap_rel = gap_abs / max(1.0, min(abs(cost_p), abs(cost_d)))
                 kt = kappa[k] * tinv
@@ -334,6 +413,7 @@ def _solve_batch(who, problems, settings, inspect, member_refinement, isolate=Fa
                         s[z_off[k]:z_off[k + 1]] = ps[z_off[k]:z_off[k + 1]]
                         z[z_off[k]:z_off[k + 1]] = pz[z_off[k]:z_off[k + 1]]
                         tau[k], kappa[k] = ptau[k], pkappa[k]
+                        restored[k] = True
             active = [k for k in range(nb) if status[k] == UNSOLVED]
             if not active:
                 break
@@ -433,12 +513,15 @@ def _solve_batch(who, problems, settings, inspect, member_refinement, isolate=Fa
         #      tolerances is ALMOST_SOLVED
         late = [k for k in range(nb) if status[k] in (NUMERICAL_ERROR, INSUFFICIENT_PROGRESS, MAX_ITERATIONS)]
         if late:
-            R = system.residuals_batch_dev(p(x), p(s), p(z), tau, p(rx), p(rz), p(rx_inf), p(rz_inf), p(Px))
+            R = system.residuals_batch_dev(p(x), p(s), p(z), tau, p(rx), p(rz), p(rx_inf), p(rz_inf), p(Px), d_equil)
             for k in late:
                 qx, bz, xPx, nx, nz, ns, n_rz, n_rx = (float(R[k, i]) for i in (0, 1, 3, 4, 5, 6, 10, 11))
                 tinv = 1.0 / tau[k]
                 cp = qx * tinv + xPx * tinv * tinv / 2
                 cd = -bz * tinv - xPx * tinv * tinv / 2
+                if equil is not None:
+                    cinv = equil.cinv[k]
+                    cp, cd, nz, n_rx = cp * cinv, cd * cinv, nz * cinv, n_rx * cinv
                 nx, nz, ns = nx * tinv, nz * tinv, ns * tinv
                 rp = n_rz * tinv / max(1.0, normb[k] + nx + ns)
                 rd = n_rx * tinv / max(1.0, normq[k] + nx + nz)
@@ -449,6 +532,25 @@ def _solve_batch(who, problems, settings, inspect, member_refinement, isolate=Fa
                     status[k] = ALMOST_SOLVED
     # ---- solution_post_process! per member: unscale by the member's tau (kappa for certificates); one copy to the host
     torch.cuda.synchronize()
+    if equil is not None:
+        # variables_unscale! (variables.jl:247-275) per member: x *= d / scale, z *= e / (scale c_b), s *= einv / scale, on
+        # the device, then the one copy; the objectives are the costs of the residual pass over the iterate the member
+        # ended on (its last history row; the one before where the previous iterate was restored)
+        scale = np.array([1.0 / (kappa[k] if status[k] in (PRIMAL_INFEASIBLE, DUAL_INFEASIBLE) else tau[k]) for k in range(nb)])
+        equil.fx.copy_(torch.from_numpy(equil.d * np.repeat(scale, np.diff(x_off))))
+        equil.fz.copy_(torch.from_numpy(equil.e * np.repeat(scale * equil.cinv, np.diff(z_off))))
+        equil.fs.copy_(torch.from_numpy(equil.einv * np.repeat(scale, np.diff(z_off))))
+        xh, zh, sh = (x * equil.fx).cpu().numpy(), (z * equil.fz).cpu().numpy(), (s * equil.fs).cpu().numpy()
+        out = []
+        for k in range(nb):
+            row = hist[k][-2 if restored[k] else -1]
+            objp, objd = row["pcost"], row["dcost"]
+            if status[k] in (PRIMAL_INFEASIBLE, DUAL_INFEASIBLE):
+                objp = objd = float("nan")
+            out.append(IPMResult(status[k], xh[x_off[k]:x_off[k + 1]].copy(), zh[z_off[k]:z_off[k + 1]].copy(),
+                                 sh[z_off[k]:z_off[k + 1]].copy(), objp, objd, iterations[k],
+                                 int(ir_member[k]) if member_refinement else ir_total, hist[k]))
+        return out
     xh, zh, sh = x.cpu().numpy(), z.cpu().numpy(), s.cpu().numpy()
     out = []
     for k, (Pt, qk, _, bk, _) in enumerate(members):

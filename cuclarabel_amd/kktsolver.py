@@ -555,6 +555,28 @@ class HipKKTSystem:
               "hipkkt_kkt_system_set_problems")
         self.nb = len(blocks)
 
+    def set_equilibration_batch(self, equilibrations):
+        """set_equilibration with the cost scaling per member: a list of `equilibrate.Equilibration`, one per member in
+        stacking order; their d and e are concatenated, their c form the array of nb.  Raises HipKKTError where the library
+        refuses (no partition, a c that is not positive and finite -- the member is named)."""
+        eqs = list(equilibrations)
+        if self.nb and len(eqs) != self.nb:
+            raise ValueError(f"one Equilibration per member ({self.nb}), got {len(eqs)}")
+        d = f64(np.concatenate([np.asarray(q.d, float).ravel() for q in eqs])) if eqs else f64([])
+        e = f64(np.concatenate([np.asarray(q.e, float).ravel() for q in eqs])) if eqs else f64([])
+        c = f64([float(q.c) for q in eqs])
+        if d.size != self.ks.n or e.size != self.ks.m:
+            raise ValueError("the members' d must have n entries together and their e m entries")
+        check(_lib.lib().hipkkt_kkt_system_set_equilibration_batch(self.ks._h, ptr(d), ptr(e), ptr(c)),
+              "hipkkt_kkt_system_set_equilibration_batch")
+
+    def data_norms_batch(self):
+        """numpy array (nb, 2): row b = (max |q dinv| over member b's x rows / c_b, max |b einv| over its z rows) -- the
+        norms of member b's unscaled q and b (data_get_normq!, data_get_normb! per member)."""
+        out = np.zeros((max(self.nb, 1), 2))
+        check(_lib.lib().hipkkt_kkt_system_data_norms_batch(self.ks._h, ptr(out)), "hipkkt_kkt_system_data_norms_batch")
+        return out[:self.nb]
+
     def set_member_refinement(self, enable):
         """The refinement's accept / stop rule per member of the partition instead of over the stack, for every
         single-column solve of the handle.  Replacing or clearing the partition switches it off again.  Raises

@@ -563,8 +563,12 @@ int hipkkt_kkt_system_equilibration_dev(hipkkt_kkt_t h, const double **d_d, cons
  * enqueue nothing.  hipkkt_kkt_update_P / _A of level B keep their behaviour and set no such mark.
  * One launch per call on the handle's stream, behind the upload of index where there is one; no synchronisation beyond
  * what that upload needs, and the number of launches does not depend on k.  The q and b calls need
- * hipkkt_kkt_system_init; all four are refused on a deferred-status handle (HIPKKT_ERR_ARG) and work unchanged on a
- * handle partitioned by hipkkt_kkt_system_set_problems (they carry no per-member scalar). */
+ * hipkkt_kkt_system_init; all four are refused on a deferred-status handle (HIPKKT_ERR_ARG).  On a handle partitioned
+ * by hipkkt_kkt_system_set_problems they work unchanged with the handle's one c, until
+ * hipkkt_kkt_system_set_equilibration_batch has given every member its own cost scaling: from then on the c of the P and
+ * q formulas is c[b] of the member b that owns the entry's row (P: row and column lie in one member; q: row i) -- same
+ * rounding order, still one launch whatever k and nb, the indexed and the vector form still bit for bit equal, the
+ * write-through, the staleness marks and the refusals unchanged; _A and _b carry no c and do not change. */
 int hipkkt_kkt_system_update_data_P(hipkkt_kkt_t h, const double *d_values, const int64_t *index, int64_t k);
 int hipkkt_kkt_system_update_data_A(hipkkt_kkt_t h, const double *d_values, const int64_t *index, int64_t k);
 int hipkkt_kkt_system_update_data_q(hipkkt_kkt_t h, const double *d_values, const int64_t *index, int64_t k);
@@ -611,8 +615,37 @@ int hipkkt_kkt_system_data_norms(hipkkt_kkt_t h, double out[2]);
  * <= 48 only: a handle that holds an exponential, power or generalized power cone or a PSD cone of side > 48, or that
  * has called hipkkt_kkt_enable_large_psd, is refused with HIPKKT_ERR_ARG, and so is a deferred-status handle.  The
  * tables (row -> member, cone -> member, workgroup -> (member, chunk)) and all work space are sized by nb; nb is bounded
- * by n only.  Synchronises with the handle's stream once (tables in use are replaced); enqueues no kernel. */
+ * by n only.  Synchronises with the handle's stream once (tables in use are replaced); enqueues no kernel.  A handle that
+ * holds member cost scalings (hipkkt_kkt_system_set_equilibration_batch, below) refuses to replace or clear its partition
+ * (HIPKKT_ERR_ARG, nothing changed): the caller clears them first with hipkkt_kkt_system_set_equilibration. */
 int hipkkt_kkt_system_set_problems(hipkkt_kkt_t h, int64_t nb, const int64_t *x_off, const int64_t *z_off);
+
+/* hipkkt_kkt_system_set_equilibration with the cost scaling given per member: data_equilibrate! (problemdata.jl:133-221)
+ * computes c for ONE problem, from that problem's q and P; a stack of independent problems equilibrated as the problems
+ * it consists of has one c per member, where a joint c would be the cost scaling of the member with the largest q.
+ * d (n) and e (m): HOST vectors, handled exactly as in the scalar call (copied once, dinv = 1 / d and einv = 1 / e as
+ * IEEE quotients, both NULL: all ones; the same tables built on first use); c: a HOST array of nb cost scalings.  Needs a
+ * partition (HIPKKT_ERR_ARG without one).  c[b] must be finite and > 0, else HIPKKT_ERR_ARG with member b named by
+ * hipkkt_last_error and the handle untouched.  The handle keeps the c[b] and nothing derived from them; the scalar c that
+ * hipkkt_kkt_system_set_equilibration stored is left alone, so no scalar call except the two data updates that carry c
+ * (hipkkt_kkt_system_update_data_P / _q, above) and hipkkt_kkt_system_data_norms_batch can observe this mode.  The scalar
+ * hipkkt_kkt_system_set_equilibration (also with NULLs) afterwards returns the handle to one joint c.  While the handle
+ * holds member cost scalings hipkkt_kkt_system_set_problems is refused, so that a partition that no longer matches them
+ * cannot be reached.  P, A, q and b on the handle are NOT touched.  Refused on a deferred-status handle.  Synchronises
+ * (the host arrays may be reused when it returns).  The check of c[] and the tables are host-only code
+ * (csrc/data_update.cpp). */
+int hipkkt_kkt_system_set_equilibration_batch(hipkkt_kkt_t h, const double *d, const double *e, const double *c);
+
+/* hipkkt_kkt_system_data_norms per member -- data_get_normq! / data_get_normb! (problemdata.jl:91-109) on each member's
+ * rows: out (HOST, 2 nb doubles) gets out[2 b] = the maximum over member b's x rows of |q_i dinv_i|, divided by c[b] (by
+ * the handle's c on a handle without member cost scalings), and out[2 b + 1] = the maximum over its z rows of
+ * |b_i einv_i|, 0 for a member without z rows.  Products and quotient are formed as the scalar call forms them; the
+ * maxima are taken with an integer atomicMax on the bit patterns of the non-negative products (no floating-point
+ * atomic): exact, and the same whatever the order.  A NaN in member b's q makes out[2 b] non-finite and leaves every
+ * other member's values as they are.  One launch and one read-back whatever nb (synchronises).  Needs
+ * hipkkt_kkt_system_init and a partition; refused on a deferred-status handle.  With nb = 1 and c[0] equal to the
+ * handle's c the two values equal the scalar call's. */
+int hipkkt_kkt_system_data_norms_batch(hipkkt_kkt_t h, double *out);
 
 /* The iterative refinement's accept / stop rule (kktsolver_directldl.jl:389-449) per member instead of over the stack.
  * enable != 0: from now on every single-column solve of this handle -- hipkkt_kkt_solve, hipkkt_kkt_solve_dev,

@@ -17,7 +17,14 @@ update (cone scaling, scatter, regulariser) and factorisation (with --isolate: t
 timed loop is slower with the events in it, so take problems/s from a run without.  One JSON line per run.  --root: the tree whose cuclarabel_amd is imported (another build of the library for an
 A/B comparison in one session: run this script with the other tree's root and --mode stacked).
 
+--resident (mode batch): a parameter sweep on one structure, two ways in alternation, one JSON line per round with both
+times: `seconds_resident` -- a solver_device.DeviceBatchSolver set up ONCE before the rounds, per round
+`.update_data_stack(q=..., b=...)` (device tensors, by pointer) plus `.solve()`; `seconds_fresh` -- the batch built anew
+from the round's data (a new DeviceBatchSolver with the same equilibrations, then `.solve()`), which is what a user
+without the resident solver pays every round.  --member-refinement / --isolate choose the member modes of both.
+
     python scripts/bench_batch_loop.py --mode batch --members 64 --n 10000 --runs 3
+    python scripts/bench_batch_loop.py --mode batch --members 64 --n 10000 --runs 3 --resident --member-refinement --isolate
 """
 import argparse
 import json
@@ -35,17 +42,22 @@ def main():
     ap.add_argument("--member-refinement", action="store_true")
     ap.add_argument("--isolate", action="store_true")
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--resident", action="store_true")
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     args = ap.parse_args()
     if args.member_refinement and args.mode != "batch":
         ap.error("--member-refinement goes with --mode batch")
-    if (args.isolate or args.profile) and args.mode != "batch":
-        ap.error("--isolate and --profile go with --mode batch")
+    if (args.isolate or args.profile or args.resident) and args.mode != "batch":
+        ap.error("--isolate, --profile and --resident go with --mode batch")
+    if args.resident and args.profile:
+        ap.error("--resident times whole rounds; --profile goes with the plain batch loop")
     sys.path.insert(0, args.root)
     import torch
     from cuclarabel_amd import ipm_device, problems
 
     pbs = [problems.config4(j, n=args.n) for j in range(args.members)]
+    if args.resident:
+        return resident_rounds(args, pbs, torch)
     # the loops call `inspect` once per iteration, right behind the residual call's read-back: the time between the first
     # and the last call is the loop's own, without the handle's set-up (symbolic analysis) and the final copy
     stamps, seen = [], {}
@@ -97,6 +109,43 @@ def main():
             out["ms_per_iteration"] = round(1e3 * (stamps[-1] - stamps[0]) / (len(stamps) - 1), 4)
         out.update(extra(res))
         print(json.dumps(out), flush=True)
+
+
+def resident_rounds(args, pbs, torch):
+    """set-up once, then per round new q and b for every member: resident update + solve against a batch built anew"""
+    import numpy as np
+    from cuclarabel_amd.solver_device import DeviceBatchSolver
+    modes = dict(member_refinement=bool(args.member_refinement), isolate=bool(args.isolate))
+    data = [(pb.P, np.asarray(pb.q, float), pb.A, np.asarray(pb.b, float), pb.cones) for pb in pbs]
+    t0 = time.perf_counter()
+    S = DeviceBatchSolver(data, **modes)
+    S.solve()                                            # warm-up: kernels loaded, allocator primed
+    torch.cuda.synchronize()
+    setup = time.perf_counter() - t0
+    dev = S._c.dev
+    for k in range(args.runs):
+        fq, fb = 1.0 + 0.05 * (k + 1), 1.0 + 0.01 * (k + 1)
+        new = [(P, fq * q, A, fb * b, cones) for (P, q, A, b, cones) in data]
+        qd = torch.from_numpy(np.concatenate([mb[1] for mb in new])).to(dev)
+        bd = torch.from_numpy(np.concatenate([mb[3] for mb in new])).to(dev)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        S.update_data_stack(q=qd, b=bd)
+        res = S.solve()
+        torch.cuda.synchronize()
+        t_res = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        ref = DeviceBatchSolver(new, equilibrations=S.equilibrations, **modes).solve()
+        torch.cuda.synchronize()
+        t_fresh = time.perf_counter() - t0
+        same = all(a.x.tobytes() == b.x.tobytes() and a.status == b.status for a, b in zip(res, ref))
+        print(json.dumps(dict(mode="batch-resident", members=args.members, n=args.n, run=k, setup_seconds=round(setup, 6),
+                              seconds_resident=round(t_res, 6), seconds_fresh=round(t_fresh, 6),
+                              problems_per_s_resident=round(args.members / t_res, 2),
+                              problems_per_s_fresh=round(args.members / t_fresh, 2),
+                              loop_iterations=max(r.iterations for r in res), statuses=sorted(set(r.status for r in res)),
+                              resident_equals_fresh=bool(same), root=os.path.basename(os.path.abspath(args.root)), **modes)),
+              flush=True)
 
 
 if __name__ == "__main__":
